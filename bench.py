@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: top-level PCG build + Fiedler solve (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path over one synthetic input by the protocol of
 SURVEY.md 8d / BASELINE.md 3.3: the flattened tree tables go host -> HBM
 (``scs_tables_upload`` from page-locked memory), ``scs_pcg_build`` (W rows of this
 rank), ``scs_fiedler`` (degrees + LOBPCG) and the V x 2 embedding comes back to the
-host.  The same pass on tables already resident in HBM is reported beside it as
+host.  The same pass on tables already resident in HBM is reported beside it (--full) as
 ``value_tables_resident``.  N = 1 runs BASELINE.json
 configs[2] (10 000 taxa / 500 trees / branch), the largest configuration
 BASELINE.json assigns to a single MI355X; N > 1 runs configs[3] (50 000 taxa /
@@ -19,18 +19,28 @@ host-side rendezvous (unique-id broadcast, barrier, max over ranks) is the
 package's own TCP star (hoststore.py), no torch import anywhere; every number
 is produced by libscs_hip.so through its C-ABI.
 
+A plain run sets up, warms up, times the K steps and prints the line: nothing else touches the
+device.  ``--dump-outputs DIR`` then writes what the last timed step returned to its caller --
+``embedding.npy`` (the V x 2 embedding, float64) and ``eigenvalues.npy`` (the three largest
+eigenvalues of S = D^-1/2 W D^-1/2 as scs_fiedler reports them, float64) -- for output-for-output
+comparisons of two builds (inputs are seeded: the same arguments give the same input).
+Everything else runs only under ``--full``.
+
 Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
   roofline            the kernel with the most device time per step (HIP-event-timed on the
                       library's stream inside the timed region), `roofline_other` the other one
                       of the two that matter (k_accumulate_mono, k_symm), `roofline_path` the
                       path-level figure (B_A + B_C) / t of SURVEY.md 8d;
+and, with --full only,
   value_tables_resident  the same step without the tables' upload (`value` includes it);
   parity              the gates of SURVEY.md 8d at FULL size: rows of W vs the C oracle, the
                       embedding vs scikit-learn on both scales, labels;
   cpu_baseline        the CPU path timed on this box: all-core C restatement of the build +
                       scikit-learn's eigen-solve on the full matrix, and a bounded sample of
                       the reference's literal dict-based build (oracle/scs_oracle.build_pcg);
-  seeds / planted     seeds 0, 1, 2 (median) and the planted input, with lambda2 / lambda3.
+  seeds / planted     seeds 0, 1, 2 (median) and the planted input, with lambda2 / lambda3;
+  all_double, other_workloads, recursion, the measured copy rate, and -- N > 1 -- the other
+  layout (other_modes) and the same workload on one GPU.
 """
 
 from __future__ import annotations
@@ -97,7 +107,24 @@ def parse_args():
     ap.add_argument("--quick-reference-leg", action="store_true",
                     help="cpu_baseline.reference_style_build on 300 taxa / 30 trees (seconds) instead of the "
                          "full configs[1] (a minute or two)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: parity gates, cpu_baseline, tables-resident step, copy "
+                         "rate, all-double / seeds / planted / other workloads / recursion legs, the other multi-rank "
+                         "layout and the one-GPU comparison (--no-parity / --no-cpu-baseline / --no-extra trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """DIR/<name>.npy, float64.  The embedding is V x 2 (16 bytes a taxon): whole up to 4 M taxa, far
+    beyond any W that fits on a device, so no sampling is needed under the 64 MB the dumps may take."""
+    os.makedirs(out_dir, exist_ok=True)
+    for key, arr in outputs.items():
+        np.save(os.path.join(out_dir, f"{key}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def even_splits(n: int, world: int, upper: bool = False) -> list[int]:
@@ -477,6 +504,10 @@ def run_workload(name, args, dev, dist, rank, world, steps, warmup, full, seed=N
         },
     }
     report["_maps"] = maps
+    # what the last timed step handed its caller (--dump-outputs): the embedding and the three largest eigenvalues of
+    # S = D^-1/2 W D^-1/2 (lambda[0], lambda[1], lambda_next of include/scs_hip.h)
+    report["_outputs"] = {"embedding": maps,
+                          "eigenvalues": np.array([stats["lambda"][0], stats["lambda"][1], stats["lambda_next"]])}
     if world > 1:
         report["stages"]["build_exchange_bytes_received"] = bstats.get("exchange_bytes", 0.0)
         # the one collective of an iteration: device time (HIP events around every fourth, scaled)
@@ -530,7 +561,7 @@ def run_workload(name, args, dev, dist, rank, world, steps, warmup, full, seed=N
         report["stages"]["tables_bytes"] = int(16 * tables.n_leaves + 16 * m + 8)
         report["stages"]["tables_in_pinned_host_memory"] = bool(getattr(tables, "pinned", False))
 
-    if rank == 0 and world == 1 and not args.no_parity:
+    if rank == 0 and world == 1 and args.full and not args.no_parity:
         from oracle import tables_oracle as to
 
         graph, maps2, stats2, _ = one_step(keep=True)
@@ -588,7 +619,7 @@ def run_workload(name, args, dev, dist, rank, world, steps, warmup, full, seed=N
             }
         graph.free()
     if world > 1:
-        if rank == 0 and not args.no_parity:
+        if rank == 0 and args.full and not args.no_parity:
             from oracle import tables_oracle as to
 
             rows = (rb + np.unique(np.random.RandomState(1).randint(0, re_ - rb, size=4))).astype(np.int32)
@@ -691,21 +722,26 @@ def main() -> int:
 
     name = args.workload or ("cfg2" if world == 1 else "cfg3")
     # the box's own copy rate beside the nominal 8 TB/s (SURVEY.md 8d "Peak to quote")
-    try:
-        copy_gbs = dev.copy_bandwidth() if rank == 0 else None
-    except Exception as exc:  # noqa: BLE001 - a report field, never fatal
-        copy_gbs = None
-        print(f"bench.py: copy bandwidth not measured: {exc}", file=sys.stderr)
-    main_rep = run_workload(name, args, dev, dist, rank, world, args.steps, args.warmup, full=True,
+    copy_gbs = None
+    if args.full:
+        try:
+            copy_gbs = dev.copy_bandwidth() if rank == 0 else None
+        except Exception as exc:  # noqa: BLE001 - a report field, never fatal
+            print(f"bench.py: copy bandwidth not measured: {exc}", file=sys.stderr)
+    main_rep = run_workload(name, args, dev, dist, rank, world, args.steps, args.warmup, full=args.full,
                             planted=args.planted)
+    outputs = main_rep.pop("_outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     maps_by_mode = {main_rep["stages"].get("multi_rank_mode", "single"): main_rep.pop("_maps", None)}
     other_modes = {}
-    if world > 1 and not args.no_extra and args.multi_rank_mode in ("shared", "upper"):
+    if world > 1 and args.full and not args.no_extra and args.multi_rank_mode in ("shared", "upper"):
         # the other layout in the same invocation (a first real multi-GPU run then decides between
         # them): timed, rows of W against the oracle, embedding against the one-GPU run below
         alt = "upper" if args.multi_rank_mode == "shared" else "shared"
         try:
             rep = run_workload(name, args, dev, dist, rank, world, min(args.steps, 3), 1, full=False, mode=alt)
+            rep.pop("_outputs", None)
             maps_by_mode[alt] = rep.pop("_maps", None)
             other_modes[alt] = {k: rep[k] for k in ("value", "ms_per_step", "steps", "config", "roofline",
                                                     "roofline_other", "stages", "parity") if k in rep}
@@ -725,7 +761,7 @@ def main() -> int:
         "scaling_note": "N > 1 runs BASELINE.json configs[3] in the row-partitioned layout north_star names "
                         "(--multi-rank-mode shared; the upper-triangle job is other_modes.upper of the same "
                         "line); its one-GPU time, the strong-scaling baseline, is other_workloads.cfg3.value "
-                        "of the N = 1 line and same_workload_on_one_gpu.value of every N > 1 line",
+                        "of the N = 1 line and same_workload_on_one_gpu.value of every N > 1 line (--full)",
         "vs_baseline": None,
         "dtype": ("f64 (loop operator: fp32 image of W; fp64 renewal + confirmation)"
                   if main_rep.get("config", {}).get("precision", "").startswith("fp64 arithmetic;") else "f64"),
@@ -733,14 +769,15 @@ def main() -> int:
         "value_definition": "SURVEY.md 8d / BASELINE.md 3.3 protocol: tables host -> HBM (page-locked source; "
                             "the chunks behind the first tree batch overlap the build's first kernels, all of "
                             "them inside the timed region), scs_pcg_build, scs_fiedler, V x 2 embedding to the "
-                            "host; the same step on HBM-resident tables is value_tables_resident",
+                            "host; the same step on HBM-resident tables is value_tables_resident (--full)",
     }
-    try:
-        from spectralclustersupertree_amd import kmeans2
+    if args.full:
+        try:
+            from spectralclustersupertree_amd import kmeans2
 
-        result["kmeans2_fast_path_active"] = bool(kmeans2.fast_path_active())
-    except Exception as exc:  # noqa: BLE001 - a report field, never fatal
-        result["kmeans2_fast_path_active"] = f"error: {exc}"
+            result["kmeans2_fast_path_active"] = bool(kmeans2.fast_path_active())
+        except Exception as exc:  # noqa: BLE001 - a report field, never fatal
+            result["kmeans2_fast_path_active"] = f"error: {exc}"
     for key in ("config", "roofline", "roofline_other", "roofline_path", "value_tables_resident", "stages",
                 "parity", "cpu_baseline"):
         if key in main_rep:
@@ -766,7 +803,7 @@ def main() -> int:
 
     t_bench0 = time.perf_counter()
     budget_s = float(os.environ.get("SCS_BENCH_BUDGET_S", "400"))  # wall clock the extra legs below may use in all
-    if world == 1 and not args.no_extra and "fp32 image" in result.get("dtype", ""):
+    if world == 1 and args.full and not args.no_extra and "fp32 image" in result.get("dtype", ""):
         # the same workload with the loop in double precision throughout (SCS_LOWP=0): the price of NOT using the
         # image, in the same line as the headline
         old_lowp = os.environ.get("SCS_LOWP")
@@ -786,7 +823,7 @@ def main() -> int:
                 del os.environ["SCS_LOWP"]
             else:
                 os.environ["SCS_LOWP"] = old_lowp
-    if world == 1 and args.workload is None and not args.no_extra:
+    if world == 1 and args.full and args.workload is None and not args.no_extra:
         # seeds 0, 1, 2 (median) and one planted input, lambda2 / lambda3 printed
         seeds = {str(args.seed): {"value": main_rep["value"], "lambda2": main_rep["stages"]["lambda2"],
                                   "lambda3": main_rep["stages"]["lambda3"],
@@ -883,7 +920,7 @@ def main() -> int:
     # N > 1: rank 0 also times the SAME workload alone on its GPU (one warm-up + one pass,
     # single-rank context, the other ranks wait), so that every multi-GPU line carries the
     # one-device time it is to be compared with
-    if world > 1 and rank == 0 and not args.no_extra:
+    if world > 1 and rank == 0 and args.full and not args.no_extra:
         from spectralclustersupertree_amd.backend import Device
 
         try:

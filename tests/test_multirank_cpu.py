@@ -170,11 +170,32 @@ def test_group_aligned_splits():
         group_splits([0, 3, 10], [0, 5, 10])
 
 
-def test_two_rank_gloo_rendezvous_and_gather(tmp_path):
-    import torch.multiprocessing as mp
+def _spawn(fn, args: tuple, nprocs: int, timeout_s: float = 600.0) -> None:
+    """fn(rank, *args) in `nprocs` fresh processes (the standard library's spawn start method); the first
+    rank that fails stops the others.  Only the workers import torch: the test process may hold the
+    package's HIP runtime, and torch brings a ROCm build of its own."""
+    import multiprocessing
 
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(r, *args)) for r in range(nprocs)]
+    for p in procs:
+        p.start()
+    deadline = time.monotonic() + timeout_s
+    while any(p.is_alive() for p in procs) and time.monotonic() < deadline:
+        if any(p.exitcode not in (None, 0) for p in procs):
+            break
+        time.sleep(0.05)
+    for p in procs:
+        if p.is_alive():
+            p.kill()
+        p.join()
+    codes = [p.exitcode for p in procs]
+    assert codes == [0] * nprocs, f"worker exit codes {codes}"
+
+
+def test_two_rank_gloo_rendezvous_and_gather(tmp_path):
     port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_worker, (2, port, str(tmp_path)), 2)
     assert (tmp_path / "ok0").exists() and (tmp_path / "ok1").exists()
 
 
@@ -189,10 +210,11 @@ def _bench_worker(rank: int, world: int, port: int, out_dir: str) -> None:
     import contextlib
     import io
     import json
+    import warnings
 
     from oracle import scs_oracle as so
     from oracle import tables_oracle as to
-    from spectralclustersupertree_amd import backend
+    from spectralclustersupertree_amd import backend, synthetic
 
     class FakeGraph:
         def __init__(self, dev, tables, rb, re_, shared):
@@ -206,8 +228,12 @@ def _bench_worker(rank: int, world: int, port: int, out_dir: str) -> None:
                 "bytes_w": 8.0 * (re_ - rb) * n, "bytes_tables": 16.0 * tables.n_taxa * m,
                 "exchange_bytes": 1e6 if shared else 0.0}
 
+        solves = 0
+
         def fiedler(self, v0, tol=1e-13, max_iter=2000, block=0):
             import warnings
+
+            FakeGraph.solves += 1
 
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
@@ -267,7 +293,8 @@ def _bench_worker(rank: int, world: int, port: int, out_dir: str) -> None:
 
     # the upper-triangle job (the job keeps the upper triangle only) ...
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--workload", "custom",
-                "--taxa", "600", "--trees", "4", "--strategy", "depth", "--no-extra", "--multi-rank-mode", "upper"]
+                "--taxa", "600", "--trees", "4", "--strategy", "depth", "--no-extra", "--multi-rank-mode", "upper",
+                "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main()
@@ -279,7 +306,7 @@ def _bench_worker(rank: int, world: int, port: int, out_dir: str) -> None:
     # ... and the DEFAULT, the row-partitioned one with the tile exchange -- which also times the other
     # layout (other_modes.upper) and holds both embeddings against the one-GPU run of the same input
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "custom",
-                "--taxa", "600", "--trees", "5", "--strategy", "depth"]
+                "--taxa", "600", "--trees", "5", "--strategy", "depth", "--full"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main()
@@ -304,14 +331,40 @@ def _bench_worker(rank: int, world: int, port: int, out_dir: str) -> None:
             assert rep["parity"]["embedding_vs_one_gpu_max_abs"] == 0.0
     else:
         assert buf.getvalue().strip() == ""
+    # a plain run (no --full): the warm-up and the timed steps are the only solves, the line carries the
+    # headline and what those steps measured, and --dump-outputs writes the last step's embedding
+    dump = Path(out_dir, "dump")
+    FakeGraph.solves = 0
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--workload", "custom",
+                "--taxa", "600", "--trees", "5", "--strategy", "depth", "--dump-outputs", str(dump)]
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        rc = bench.main()
+    assert rc == 0 and FakeGraph.solves == 1 + 3
+    if rank == 0:
+        line = json.loads(buf.getvalue().strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "s"
+        for key in ("metric", "value", "higher_is_better", "dtype", "roofline", "stages"):
+            assert key in line, key
+        for key in ("parity", "other_modes", "same_workload_on_one_gpu", "cpu_baseline", "hbm_copy_measured_gbs"):
+            assert key not in line, key
+        emb = np.load(dump / "embedding.npy")
+        assert emb.dtype == np.float64 and emb.shape == (600, 2)
+        tables = synthetic.make_tables(0, 600, 5, "depth")
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            want = to.sign_flip_columns(so.spectral_maps(to.pcg_dense(tables)[0], np.random.RandomState(0)))
+        assert np.array_equal(emb, want)
+        eig = np.load(dump / "eigenvalues.npy")
+        assert eig.dtype == np.float64 and eig.tolist() == [1.0, 0.5, 0.4]
+    else:
+        assert buf.getvalue().strip() == ""
     Path(out_dir, f"bench_ok{rank}").write_text("ok")
 
 
 def test_bench_two_rank_control_flow(tmp_path):
-    import torch.multiprocessing as mp
-
     port = _free_port()
-    mp.spawn(_bench_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    _spawn(_bench_worker, (2, port, str(tmp_path)), 2)
     assert (tmp_path / "bench_ok0").exists() and (tmp_path / "bench_ok1").exists()
 
 

@@ -7,7 +7,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/kstats
 rm -rf $out && mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py --steps 5 --no-cpu-baseline --no-extra --no-parity "$@" > $out/bench.json 2> $out/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py --full --steps 5 --no-cpu-baseline --no-extra --no-parity "$@" > $out/bench.json 2> $out/kt.err
 f=$(find $out/kt -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'P'
 import csv, sys

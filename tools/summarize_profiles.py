@@ -88,13 +88,13 @@ alg = {k_symm: (symm_alg, "bytes of W tiles streamed + block in/out"),
        key_of(fetch, "k_degrees"): (8.0 * n * n, "8 V^2 read (+ 2 V^2 written when the pass leaves the single-precision image)"),
        k_acc: (acc_alg, "per tree batch: W tile sums written once + tables read once")}
 
-lines = [f"# Round-{tag[1:]} profile: `python3 bench.py --steps 5 --no-cpu-baseline --no-extra --no-parity` "
+lines = [f"# Round-{tag[1:]} profile: `python3 bench.py --full --steps 5 --no-cpu-baseline --no-extra --no-parity` "
          f"(BASELINE.json configs[2]: {n} taxa / {m} trees / {bench['config']['pcg_weighting']}), one MI355X", "",
          "Collected by `tools/collect_profiles.sh` with `rocprofv3 --kernel-trace --stats --output-format csv` (kernel times) and, in "
          "separate runs with `--kernel-trace` only, `--pmc FETCH_SIZE`, `--pmc WRITE_SIZE` and three SQ counter passes (bench with "
          "--steps 2 --warmup 0); summarised by `tools/summarize_profiles.py`.  Files: "
          f"`{tag}_bench_cfg2_kernel_stats.csv` (raw stats), `{tag}_bench_cfg2_under_rocprof.json` (bench line printed under the "
-         f"profiler), `{tag}_bench_default_run.json` (un-profiled default `python bench.py` line incl. parity gates, cpu_baseline, "
+         f"profiler), `{tag}_bench_default_run.json` (un-profiled `python bench.py --full` line incl. parity gates, cpu_baseline, "
          f"seeds, planted input and the configs[1]/configs[3] reference passes), `{tag}_accumulate_phase_stamps.txt`, "
          f"`{tag}_accumulate_sq_counters_*.txt` (SQ counters of the accumulate kernel: round-1 structure, with the hand-scheduled "
          f"cell loop, final structure), `{tag}_bench_cfg4_single_gpu.json` (configs[4] on ONE device).", "",
