@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 105.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 106.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -306,6 +306,25 @@ int scs_tables_upload(scs_ctx *ctx, int32_t n_taxa, int32_t n_trees, const int64
                       const int32_t *leaf_taxon, const int32_t *adj_depth, const double *adj_val,
                       const double *tree_w, scs_tables **out);
 int scs_tables_free(scs_ctx *ctx, scs_tables *tables);
+
+/* ---- scoring a supertree against its sources ------ */
+
+/* Robinson-Foulds terms per source tree and clade support per supertree node -- neither the reference nor the
+ * recursion computes them.  `sources` are flattened trees (scs_tables_upload / scs_tables_from_forest; adj_val and
+ * tree_w are not read: every count is unweighted) over the taxon ids 0 .. n_taxa - 1; the supertree S comes as
+ * preorder arrays of n_nodes: parent[v] < v (-1 for node 0, the root), taxon[v] = id of a tip (each id at most
+ * once; ids >= the sources' n_taxa are taxa no source has), -1 for an inner node.  Clusters are leaf sets; a
+ * cluster of a tree on leaf set L is nontrivial when 2 <= size < |L|; C(S|T) = the nontrivial sets C ∩ L(T) over
+ * the clades C of S, C(T) = T's own nontrivial clusters.  Per source tree t (n_trees entries):
+ *   n_super[t] = |C(S|T)|, n_source[t] = |C(T)|, shared[t] = |C(S|T) ∩ C(T)|  (RF = n_super + n_source - 2 shared)
+ * Per node C of S (n_nodes entries, S's preorder, unary nodes included):
+ *   informative[C] = #{T : 2 <= |C ∩ L(T)| < |L(T)|},  supported[C] = those T with C ∩ L(T) in C(T).
+ * max_batch_trees > 0 caps the trees of one device batch (tests); 0: sized by workspace.  Output pointers may be
+ * null.  SCS_EINVAL: malformed supertree arrays, or (checked on the device) a source taxon out of range, missing
+ * from S or twice in one tree. */
+int scs_score_supertree(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                        const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super, int64_t *n_source,
+                        int64_t *shared, int64_t *informative, int64_t *supported);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

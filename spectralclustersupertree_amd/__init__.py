@@ -1,11 +1,13 @@
 """MI355X-native spectral-clustering core for Spectral Cluster Supertree.
 
 Public API mirrors the reference package (reference: src/sc_supertree/__init__.py:6-9):
-``construct_supertree`` and ``load_trees``.
+``construct_supertree`` and ``load_trees``; ``score_supertree`` (RF distances to the sources, clade
+support) is this package's own.
 """
 
 from spectralclustersupertree_amd.load import load_trees
 from spectralclustersupertree_amd.scs import construct_supertree
+from spectralclustersupertree_amd.score import SupertreeScore, score_supertree
 
-__all__ = ["construct_supertree", "load_trees"]
+__all__ = ["SupertreeScore", "construct_supertree", "load_trees", "score_supertree"]
 __version__ = "0.1.0"

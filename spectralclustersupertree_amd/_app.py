@@ -1,6 +1,6 @@
 """cogent3 app plug-ins (reference: src/sc_supertree/_app.py:34-96, entry points
 pyproject.toml:54-57): ``load_trees``, ``sc_supertree`` and ``outgroup_root`` over this package's
-``construct_supertree``.  With cogent3 installed they are ``define_app`` composables as in the
+``construct_supertree``, and ``score_supertree`` (this package's own).  With cogent3 installed they are ``define_app`` composables as in the
 reference; without it (this build's image) they are plain callables with the same arguments and
 error behaviour, so pipelines written against the reference's apps read the same."""
 
@@ -13,6 +13,7 @@ import numpy as np
 
 from spectralclustersupertree_amd.load import load_trees as _load_trees
 from spectralclustersupertree_amd.scs import construct_supertree as _construct
+from spectralclustersupertree_amd.score import score_supertree as _score
 
 try:  # pragma: no cover - cogent3 is not installable in the build image
     from cogent3.app.composable import define_app as _define_app  # type: ignore[import-not-found]
@@ -41,6 +42,12 @@ def sc_supertree(
 ):
     return _construct(trees, weights, pcg_weighting, contract_edges=contract_edges,
                       random_state=random_state)
+
+
+@_define_app
+def score_supertree(supertree, trees):
+    """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support."""
+    return _score(supertree, trees)
 
 
 @_define_app

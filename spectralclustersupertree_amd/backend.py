@@ -126,6 +126,34 @@ class Device:
         out._source = tables  # (page-locked arrays may still be read until the first build returns)
         return out
 
+    # -- scoring a supertree ----------------------------------------------------
+    def score(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
+        """``scs_score_supertree``: RF terms per source tree and clade support per supertree node.
+
+        ``sources`` are the flattened source trees (``TreeTables``, uploaded here, or ``DeviceTables``) over
+        the supertree's taxon ids; ``parent`` / ``taxon`` the supertree in preorder (parent -1 at the root,
+        taxon -1 at inner nodes).  ``batch_trees`` > 0 caps the trees of one device batch.  Returns int64
+        arrays ``n_super``, ``n_source``, ``shared`` (per tree) and ``informative``, ``supported`` (per node).
+        """
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        n_nodes, m = len(parent), tabs.n_trees
+        if taxon.shape != (n_nodes,):
+            msg = "parent and taxon must have one entry per supertree node"
+            raise ValueError(msg)
+        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_super", "n_source", "shared")}
+        out.update({k: np.zeros(n_nodes, dtype=np.int64) for k in ("informative", "supported")})
+        rc = self._lib.scs_score_supertree(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                           int(batch_trees), nv.lptr(out["n_super"]), nv.lptr(out["n_source"]),
+                                           nv.lptr(out["shared"]), nv.lptr(out["informative"]),
+                                           nv.lptr(out["supported"]))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_supertree: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

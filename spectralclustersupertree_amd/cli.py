@@ -5,6 +5,8 @@ arrays by the C Newick loader -- no tree object is built for the input."""
 
 from __future__ import annotations
 
+from pathlib import Path
+
 import click
 
 from spectralclustersupertree_amd import __version__
@@ -27,7 +29,14 @@ from spectralclustersupertree_amd import __version__
     default=False,
     is_flag=True,
 )
-def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool) -> None:
+@click.option("--scores-out", default=None,
+              help="Also score the supertree against the sources: a TSV with one row per source tree "
+                   "(index, n_leaves, n_super, n_source, shared, rf).")
+@click.option("--support-out", default=None,
+              help="Also write the supertree with each clade's support (supported / informative sources) as its "
+                   "node name (Newick).")
+def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
+        scores_out: str | None = None, support_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
@@ -42,6 +51,14 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     team = default_team()
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
+        if scores_out or support_out:
+            from spectralclustersupertree_amd.score import score_supertree
+
+            result = score_supertree(supertree, load_tree_arrays(in_file))
+            if scores_out:
+                Path(scores_out).write_text(result.table())
+            if support_out:
+                Path(support_out).write_text(result.annotate().get_newick(with_node_names=True) + "\n")
 
 
 if __name__ == "__main__":

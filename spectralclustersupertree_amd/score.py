@@ -1,0 +1,226 @@
+"""How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
+supertree node.  Neither the reference nor ``construct_supertree`` computes them.
+
+For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
+2 <= size < |L|.  C(S|T) = the nontrivial sets C ∩ L(T) over the clades C of the supertree S; C(T) = T's own.
+
+* per source tree: ``n_super = |C(S|T)|``, ``n_source = |C(T)|``, ``shared = |C(S|T) ∩ C(T)|`` and
+  ``rf = n_super + n_source - 2 shared`` (zeros for trees of fewer than 3 leaves);
+* per node C of S (preorder, ``TreeNode.to_flat`` order, unary nodes included): ``informative`` = the trees
+  with 2 <= |C ∩ L(T)| < |L(T)|, ``supported`` = those of them with C ∩ L(T) in C(T).  Tips and the root are 0.
+
+Every count comes from the HIP kernels behind ``scs_score_supertree``; the host only validates and lays out.
+"""
+
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from spectralclustersupertree_amd.flatten import flatten_trees
+from spectralclustersupertree_amd.tree import TreeNode, is_not_completed
+from spectralclustersupertree_amd.treearrays import TreeArrays
+
+# trees per device batch; None: sized by the workspace (a test sets a small value to reach the batch loop)
+BATCH_TREES: int | None = None
+
+
+@dataclass
+class SupertreeScore:
+    """Scores of ``supertree`` against its sources; int64 arrays."""
+
+    supertree: TreeNode
+    n_leaves: np.ndarray  # per source tree
+    n_super: np.ndarray
+    n_source: np.ndarray
+    shared: np.ndarray
+    informative: np.ndarray  # per supertree node, preorder
+    supported: np.ndarray
+    # wall seconds: "prepare" (host: supertree arrays, checks, flattening objects), "tables" (a TreeArrays forest
+    # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels)
+    timings: dict = field(default_factory=dict)
+
+    @property
+    def rf(self) -> np.ndarray:
+        return self.n_super + self.n_source - 2 * self.shared
+
+    @property
+    def total_rf(self) -> int:
+        """The RF supertree score: the RF distances to the sources, summed."""
+        return int(self.rf.sum())
+
+    def support(self) -> np.ndarray:
+        """``supported / informative`` per node (NaN where no source is informative)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.informative > 0, self.supported / np.maximum(self.informative, 1), np.nan)
+
+    def annotate(self) -> TreeNode:
+        """A copy of the supertree whose internal non-root nodes carry ``support`` = supported / informative
+        (None where no source is informative) and the same value as their name, so that
+        ``get_newick(with_node_names=True)`` writes it."""
+        out = self.supertree.copy()
+        values = self.support()
+        for i, node in enumerate(_preorder(out)):
+            if node.is_tip() or i == 0:
+                continue
+            v = values[i]
+            node.support = None if np.isnan(v) else float(v)
+            node.name = None if np.isnan(v) else repr(float(v))
+        return out
+
+    def table(self) -> str:
+        """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf."""
+        rows = ["index\tn_leaves\tn_super\tn_source\tshared\trf"]
+        rf = self.rf
+        for t in range(len(rf)):
+            rows.append(f"{t}\t{self.n_leaves[t]}\t{self.n_super[t]}\t{self.n_source[t]}\t{self.shared[t]}\t{rf[t]}")
+        return "\n".join(rows) + "\n"
+
+
+def _preorder(tree: TreeNode) -> list[TreeNode]:
+    """Nodes in the order of ``TreeNode.to_flat``."""
+    out: list[TreeNode] = []
+    stack = [tree]
+    while stack:
+        node = stack.pop()
+        out.append(node)
+        stack.extend(reversed(node.children))
+    return out
+
+
+def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[str]]:
+    """``(parent, taxon, tips)``: the supertree's preorder arrays over taxon ids = positions in ``tips``
+    (its tip names in preorder).  ``ValueError`` for a nameless or repeated tip."""
+    parents, names, _, _ = supertree.to_flat()
+    parent = np.asarray(parents, dtype=np.int32)
+    n = len(parent)
+    has_child = np.zeros(n, dtype=bool)
+    has_child[parent[1:]] = True
+    taxon = np.full(n, -1, dtype=np.int32)
+    tips: list[str] = []
+    for v in np.flatnonzero(~has_child):
+        name = names[v]
+        if name is None or name == "":
+            msg = "every tip of the supertree needs a name"
+            raise ValueError(msg)
+        taxon[v] = len(tips)
+        tips.append(name)
+    if len(set(tips)) != len(tips):
+        msg = "the supertree holds a taxon more than once"
+        raise ValueError(msg)
+    return parent, taxon, tips
+
+
+def score_supertree(supertree: TreeNode, trees, *, device=None) -> SupertreeScore:
+    """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring).
+
+    ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
+    ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
+    by those inputs and ignored: every count is unweighted.  The supertree must hold every taxon of every source
+    tree exactly once (``ValueError`` otherwise); it may hold taxa no source has.  ``device``: a
+    ``backend.Device``; default the process's device (in a launched multi-rank job the caller's own: scoring is
+    not spread over ranks).
+    """
+    t0 = time.perf_counter()
+    parent, taxon, tips = supertree_arrays(supertree)
+    index = {name: i for i, name in enumerate(tips)}
+    if isinstance(trees, TreeArrays):
+        if trees.n_trees == 0:
+            msg = "There must be at least one tree to score against."
+            raise ValueError(msg)
+        present = trees.present_taxa()
+        new_id = np.full(max(trees.n_taxa, 1), -1, dtype=np.int32)
+        for x in present:
+            name = trees.name(int(x))
+            if name not in index:
+                msg = f"taxon {name!r} of a source tree is not in the supertree"
+                raise ValueError(msg)
+            new_id[int(x)] = index[name]
+        dev = device if device is not None else _default_device()
+        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id)
+        out.timings["prepare"] = time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
+        return out
+
+    trees = [t for t in trees if not is_not_completed(t)]
+    if len(trees) == 0:
+        msg = "There must be at least one tree to score against."
+        raise ValueError(msg)
+    for tree in trees:
+        for name in tree.get_tip_names():
+            if name not in index:
+                msg = f"taxon {name!r} of a source tree is not in the supertree"
+                raise ValueError(msg)
+    tables = flatten_trees(trees, [1.0] * len(trees), "one", taxa=tips)
+    dev = device if device is not None else _default_device()
+    t1 = time.perf_counter()
+    tabs = dev.upload(tables)
+    t2 = time.perf_counter()
+    try:
+        res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
+    finally:
+        tabs.free()
+    t3 = time.perf_counter()
+    return SupertreeScore(supertree, np.diff(tables.tree_off), res["n_super"], res["n_source"], res["shared"],
+                          res["informative"], res["supported"],
+                          {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2})
+
+
+def _default_device():
+    from spectralclustersupertree_amd.scs import default_device
+
+    return default_device()
+
+
+def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id) -> SupertreeScore:
+    """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
+    (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
+    import ctypes as C
+
+    from spectralclustersupertree_amd import _native as nv
+    from spectralclustersupertree_amd.backend import DeviceForest, DeviceTables
+
+    t0 = time.perf_counter()
+    m = arrays.n_trees
+    n_leaves = arrays.leaf_counts().astype(np.int64)
+    n_nodes = len(parent)
+    zeros = {k: np.zeros(m, dtype=np.int64) for k in ("n_super", "n_source", "shared")}
+    node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in ("informative", "supported")}
+    # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
+    universe = max(arrays.n_taxa, n_taxa, 1)
+    new_id = np.concatenate([new_id, np.full(universe - len(new_id), -1, dtype=np.int32)])
+    forest = DeviceForest.upload(
+        dev, universe, np.ascontiguousarray(arrays.node_off, dtype=np.int64),
+        np.ascontiguousarray(arrays.parent, dtype=np.int32), np.ascontiguousarray(arrays.taxon, dtype=np.int32),
+        np.ascontiguousarray(arrays.length, dtype=np.float64), np.ascontiguousarray(arrays.support, dtype=np.float64),
+        np.ones(m, dtype=np.float64), int(n_leaves.sum()))
+    try:
+        part_of = np.where(new_id >= 0, 0, -1).astype(np.int32)
+        (child,) = forest.split(part_of, new_id, [n_taxa], 0)
+    finally:
+        forest.free()
+    try:
+        t1 = t2 = time.perf_counter()
+        if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
+            res = {**zeros, **node0}
+        else:
+            handle = C.c_void_p()
+            nv.check(dev._lib.scs_tables_from_forest(dev._ctx, child._h, None, int(n_taxa), C.byref(handle)))
+            tabs = DeviceTables(dev, handle, int(n_taxa), child.n_trees)
+            t1 = time.perf_counter()
+            try:
+                res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
+            finally:
+                tabs.free()
+            t2 = time.perf_counter()
+            tree_index = np.array(child.tables()[4], dtype=np.int64)
+            for k in ("n_super", "n_source", "shared"):
+                full = zeros[k]
+                full[tree_index] = res[k]
+                res[k] = full
+    finally:
+        child.free()
+    return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
+                          res["informative"], res["supported"],
+                          {"tables": t1 - t0, "score": t2 - t1})
