@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 106.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 107.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -325,6 +325,17 @@ int scs_tables_free(scs_ctx *ctx, scs_tables *tables);
 int scs_score_supertree(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
                         const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super, int64_t *n_source,
                         int64_t *shared, int64_t *informative, int64_t *supported);
+
+/* Rooted triplet terms per source tree, same inputs and SCS_EINVAL cases as
+ * scs_score_supertree.  For a source tree T on the leaf set L and S' = S|L, a triple {a, b, c} of L is resolved
+ * ab|c in a tree when one of its clusters holds a and b but not c, and a fan when no cluster separates one pair:
+ *   t_super[t]  = triples S' resolves,  t_source[t] = triples T resolves,
+ *   t_shared[t] = triples resolved alike in both  (triplet distance = t_super + t_source - 2 t_shared).
+ * Trees of fewer than 3 leaves give zeros; counts are unweighted.  The pair kernel holds two bitsets over a tree's
+ * leaves in LDS: SCS_EINVAL as well for a source tree of more than 327 679 leaves. */
+int scs_score_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                       const int32_t *taxon, int32_t max_batch_trees, int64_t *t_super, int64_t *t_source,
+                       int64_t *t_shared);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

@@ -45,9 +45,10 @@ def sc_supertree(
 
 
 @_define_app
-def score_supertree(supertree, trees):
-    """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support."""
-    return _score(supertree, trees)
+def score_supertree(supertree, trees, *, triplets: bool = False):
+    """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, and with
+    ``triplets=True`` the rooted triplet terms."""
+    return _score(supertree, trees, triplets=triplets)
 
 
 @_define_app

@@ -35,9 +35,14 @@ from spectralclustersupertree_amd import __version__
 @click.option("--support-out", default=None,
               help="Also write the supertree with each clade's support (supported / informative sources) as its "
                    "node name (Newick).")
+@click.option("--triplets", default=False, is_flag=True,
+              help="Add the rooted triplet terms to --scores-out (t_super, t_source, t_shared, triplet_distance).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
-        scores_out: str | None = None, support_out: str | None = None) -> None:
+        scores_out: str | None = None, support_out: str | None = None, triplets: bool = False) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
+    if triplets and not scores_out:
+        msg = "--triplets needs --scores-out"
+        raise click.UsageError(msg)
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
 
@@ -54,7 +59,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         if scores_out or support_out:
             from spectralclustersupertree_amd.score import score_supertree
 
-            result = score_supertree(supertree, load_tree_arrays(in_file))
+            result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets)
             if scores_out:
                 Path(scores_out).write_text(result.table())
             if support_out:

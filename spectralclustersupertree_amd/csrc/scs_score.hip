@@ -69,6 +69,54 @@ __device__ __forceinline__ void sc_count(unsigned long long *__restrict__ ctr, i
     }
 }
 
+// first index in [l, r) with sp[i] >= v, r if none (sp ascending)
+__device__ __forceinline__ int64_t sc_first_ge(const int32_t *__restrict__ sp, int64_t l, int64_t r, int32_t v) {
+    while (l < r) {
+        const int64_t m = (l + r) >> 1;
+        if (sp[m] >= v) r = m; else l = m + 1;
+    }
+    return l;
+}
+
+// last index in [l, r] with sp[i] <= v (sp ascending, sp[l] <= v)
+__device__ __forceinline__ int64_t sc_last_le(const int32_t *__restrict__ sp, int64_t l, int64_t r, int32_t v) {
+    while (l < r) {
+        const int64_t m = (l + r + 1) >> 1;
+        if (sp[m] <= v) l = m; else r = m - 1;
+    }
+    return l;
+}
+
+// binary descents on T's min table of adj (level 0 = adj, level j >= 1 at amin[(j - 1) * Lb]), gaps of the tree at
+// batch-relative base: the start of the stretch [p, pos) of gaps whose depth is > d (>= d when `ge`) ...
+__device__ __forceinline__ int64_t sc_stretch_left(const int32_t *__restrict__ adj, const int32_t *__restrict__ amin,
+                                                   int64_t Lb, int levels, int64_t base, int64_t pos, int32_t d,
+                                                   bool ge) {
+    for (int j = levels - 1; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos >= w) {
+            const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+            const int32_t x = lev[base + pos - w];
+            if (ge ? x >= d : x > d) pos -= w;
+        }
+    }
+    return pos;
+}
+
+// ... and the end of the stretch [pos, p) of gaps whose depth is >= d, p <= last
+__device__ __forceinline__ int64_t sc_stretch_right(const int32_t *__restrict__ adj, const int32_t *__restrict__ amin,
+                                                    int64_t Lb, int levels, int64_t base, int64_t pos, int64_t last,
+                                                    int32_t d) {
+    for (int j = levels - 1; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos + w <= last) {
+            const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+            if (lev[base + pos] >= d) pos += w;
+        }
+    }
+    return pos;
+}
+
 // level j of a packed (uint64) or int32 min table / an int2 min-max table from level j - 1 (entries that would
 // reach past the array keep level j - 1: no query of a tree reads them)
 __global__ void k_score_level_u64(const uint64_t *__restrict__ prev, uint64_t *__restrict__ cur, int64_t n,
@@ -208,32 +256,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_score_nodes(sc_nodes_args a) {
     if (gap) {
         // T's own first gap: nearest gap to the left with depth <= adj[k] is missing or shallower
         const int32_t d = a.adj[q];
-        int64_t pos = k;  // exclusive end of the stretch of deeper gaps
-        for (int j = a.levels - 1; j >= 0; --j) {
-            const int64_t w = (int64_t)1 << j;
-            if (pos >= w) {
-                const int32_t *lev = j == 0 ? a.adj : a.amin + (int64_t)(j - 1) * a.Lb;
-                if (lev[base + pos - w] > d) pos -= w;
-            }
-        }
+        const int64_t pos = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
         t_first = pos == 0 || a.adj[base + pos - 1] < d;
 
         const int32_t u = a.node[q], du = a.dep[q];
         const int32_t sl = a.s_lo[u], sr = a.s_hi[u];
         const int32_t *sp = a.sp + base;
         // lo: first k' with sp[k'] >= sl (<= k), hi: last with sp[k'] <= sr (>= k + 1)
-        int64_t l0 = 0, l1 = k;
-        while (l0 < l1) {
-            const int64_t m = (l0 + l1) >> 1;
-            if (sp[m] >= sl) l1 = m; else l0 = m + 1;
-        }
-        const int64_t lo = l0;
-        int64_t h0 = k + 1, h1 = n - 1;
-        while (h0 < h1) {
-            const int64_t m = (h0 + h1 + 1) >> 1;
-            if (sp[m] <= sr) h0 = m; else h1 = m - 1;
-        }
-        const int64_t hi = h0;
+        const int64_t lo = sc_first_ge(sp, 0, k, sl);
+        const int64_t hi = sc_last_le(sp, k + 1, n - 1, sr);
         s_first = lo == k || (int32_t)(sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[lo], (int64_t)sp[k] - 1) >> 32) > du;
         if (s_first && (lo > 0 || hi < n - 1)) {
             // restricted parent: the deeper of the bounding gaps
@@ -317,6 +348,215 @@ __global__ void k_score_subtree(const int64_t *__restrict__ p0, const int64_t *_
     sup[x] = p1[e] - p1[x];
 }
 
+// ---- rooted triplets (scs_score_triplets) ----
+//
+// A tree on the leaf set L is given as its leaves in some order and the depths of the n - 1 adjacent LCAs (its
+// gaps): T as adj_depth in T order, S' = S|L(T) as D in S order.  Gap k starts an internal node when it is the
+// node's first gap; the node's leaves lie between the nearest strictly shallower gaps on either side, and its
+// parent is the node of the deeper of those two gaps.  With y over T's non-root internal nodes, z over S''s,
+// py / pz their parents and I(y, z) = |cl(y) ∩ cl(z)|:
+//   t_source = sum_y C(|y|, 2) (|py| - |y|),  t_super likewise over S',
+//   t_shared = sum_y sum_z C(I(y,z), 2) (I(py,pz) - I(y,pz) - I(py,z) + I(y,z))
+// (a triple ab|c resolved alike in both is counted once: at the children y, z of the two LCAs that hold a and b).
+//   k_trip_nodes: one thread per gap lists both trees' nodes as int4 {lo, hi + 1, parent lo, parent hi + 1} --
+//     T ranges in T positions, S' ranges in S order -- and sums t_source / t_super.
+//   k_trip_pairs: one workgroup per (tree, block of up to TP_ZMAX S' nodes z).  cl(z) and cl(pz) become bitsets
+//     over T positions in LDS, each 32-bit word paired with the count of set bits before it, so a count over a
+//     range of T positions is two ds_read_b64; the workgroup then sweeps T's node list once for all its z.
+
+constexpr int TP_ZMAX = 8;                // S' nodes per workgroup
+constexpr int TP_LDS_BUDGET = 40 << 10;   // LDS bytes a workgroup aims at (4 workgroups per CU) ...
+constexpr int TP_LDS_MAX = 160 << 10;     // ... and may take for one S' node: trees of up to 327 679 leaves
+
+struct sc_trip_args {
+    const int64_t *off;                     // tree_off + t0
+    int nb;
+    const int32_t *sp, *dep, *node;         // [Lb] S positions in S order, D and U of S'
+    const int32_t *adj, *amin;              // T's min table of adj_depth (as in sc_nodes_args)
+    int levels;
+    int64_t Lb;
+    const uint64_t *s_tab;                  // S's packed gap table
+    int64_t s_stride;
+    const int32_t *s_lo, *s_hi;             // leaf range of every S node
+    int4 *ylist, *zlist;                    // [Lb]: the nodes of a tree from its first leaf on
+    int32_t *ycnt, *zcnt;                   // [nb] list lengths
+    unsigned long long *c_super, *c_source; // [nb] of the batch
+};
+
+// slot of a `hit` lane in tree t's list (wave-aggregated when the wave works on one tree), -1 for the others
+__device__ __forceinline__ int sc_append(int32_t *__restrict__ cnt, int t, bool hit) {
+    const int t0 = __shfl(t, 0, 64);
+    if (__all(t == t0)) {
+        const unsigned long long mask = __ballot(hit);
+        int first = 0;
+        if ((threadIdx.x & 63) == 0 && mask) first = atomicAdd(cnt + t0, (int)__popcll(mask));
+        first = __shfl(first, 0, 64);
+        const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
+                                                         __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+        return hit ? first + below : -1;
+    }
+    return hit ? atomicAdd(cnt + t, 1) : -1;
+}
+
+// per-tree 64-bit sums, wave-aggregated as in sc_count
+__device__ __forceinline__ void sc_add64(unsigned long long *__restrict__ ctr, int t, unsigned long long v) {
+    const int t0 = __shfl(t, 0, 64);
+    if (__all(t == t0)) {
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(ctr + t0, v);
+    } else if (v) {
+        atomicAdd(ctr + t, v);
+    }
+}
+
+__device__ __forceinline__ unsigned long long sc_pairs_out(int64_t lo, int64_t hi, int64_t plo, int64_t phi) {
+    const int64_t s = hi - lo + 1;
+    return (unsigned long long)(s * (s - 1) / 2 * (phi - plo + 1 - s));
+}
+
+// one thread per gap: T's and S''s non-root internal nodes into their lists, t_source / t_super
+__global__ void __launch_bounds__(SC_THREADS) k_trip_nodes(sc_trip_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    int4 ny = make_int4(0, 0, 0, 0), nz = ny;
+    bool t_node = false, s_node = false;
+    unsigned long long vt = 0, vs = 0;
+    if (in && k + 1 < n) {
+        // T: the first gap of its node (the nearest gap to the left with depth <= d is missing or shallower)
+        const int32_t d = a.adj[q];
+        const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+        if (lo == 0 || a.adj[base + lo - 1] < d) {
+            const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+            if (lo > 0 || hi < n - 1) {  // (not the root)
+                const int64_t g = lo == 0 ? hi
+                                  : hi == n - 1 ? lo - 1
+                                  : (a.adj[base + lo - 1] >= a.adj[base + hi] ? lo - 1 : hi);
+                const int32_t dg = a.adj[base + g];
+                const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+                const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+                t_node = true;
+                ny = make_int4((int)lo, (int)hi + 1, (int)plo, (int)phi + 1);
+                vt = sc_pairs_out(lo, hi, plo, phi);
+            }
+        }
+        // S': the node u = U[k] restricted, first gap and parent as in k_score_nodes
+        const int32_t u = a.node[q], du = a.dep[q];
+        const int32_t *sp = a.sp + base;
+        const int64_t lo_s = sc_first_ge(sp, 0, k, a.s_lo[u]);
+        const int64_t hi_s = sc_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+        const bool first = lo_s == k ||
+                           (int32_t)(sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[lo_s], (int64_t)sp[k] - 1) >> 32) > du;
+        if (first && (lo_s > 0 || hi_s < n - 1)) {
+            const int64_t g = lo_s == 0 ? hi_s
+                              : hi_s == n - 1 ? lo_s - 1
+                              : (a.dep[base + lo_s - 1] >= a.dep[base + hi_s] ? lo_s - 1 : hi_s);
+            const int32_t w = a.node[base + g];
+            const int64_t plo = sc_first_ge(sp, 0, lo_s, a.s_lo[w]);
+            const int64_t phi = sc_last_le(sp, hi_s, n - 1, a.s_hi[w]);
+            s_node = true;
+            nz = make_int4((int)lo_s, (int)hi_s + 1, (int)plo, (int)phi + 1);
+            vs = sc_pairs_out(lo_s, hi_s, plo, phi);
+        }
+    }
+    const int iy = sc_append(a.ycnt, t, t_node);
+    if (iy >= 0) a.ylist[base + iy] = ny;
+    const int iz = sc_append(a.zcnt, t, s_node);
+    if (iz >= 0) a.zlist[base + iz] = nz;
+    sc_add64(a.c_source, t, vt);
+    sc_add64(a.c_super, t, vs);
+}
+
+// set bits of a bitset row below T position x: (word x / 32, mask of the bits below x % 32)
+__device__ __forceinline__ int tp_count(const int2 *row, int w, unsigned m) {
+    const int2 r = row[w];
+    return r.y + __popc((unsigned)r.x & m);
+}
+
+// the hot path: one workgroup per (tree t, block of zb of t's S' nodes); blk[i] = first workgroup of the batch's
+// tree i (cumulative over the trees, blk[0] = the batch's own start); W = words of a row (> largest n / 32)
+__global__ void __launch_bounds__(SC_THREADS) k_trip_pairs(const int64_t *__restrict__ blk, int nb,
+                                                           const int64_t *__restrict__ off,
+                                                           const int4 *__restrict__ ylist,
+                                                           const int4 *__restrict__ zlist,
+                                                           const int32_t *__restrict__ ycnt,
+                                                           const int32_t *__restrict__ zcnt,
+                                                           const int2 *__restrict__ tp, int zb, int W,
+                                                           unsigned long long *__restrict__ t_shared) {
+    extern __shared__ __attribute__((aligned(16))) int2 rows[];  // [2 zb][W]: rows 2j / 2j + 1 = cl(z_j) / cl(pz_j)
+    const int64_t g = blk[0] + blockIdx.x;
+    const int t = sc_tree_of(blk, nb, g);
+    const int j0 = (int)(g - blk[t]) * zb;
+    const int nz = min(zb, zcnt[t] - j0);
+    if (nz <= 0) return;  // (the grid counts n - 2 nodes per tree: an upper bound)
+    const int64_t base = off[t] - off[0];
+    const int nrow = 2 * nz;
+    for (int i = threadIdx.x; i < nrow * W; i += SC_THREADS) rows[i] = make_int2(0, 0);
+    __syncthreads();
+    unsigned *bits = reinterpret_cast<unsigned *>(rows);  // (word i of the image: .x of entry i / 2)
+    for (int j = 0; j < nz; ++j) {
+        const int4 z = zlist[base + j0 + j];
+        for (int k = z.x + threadIdx.x; k < z.y; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j) * W + (x >> 5)), 1u << (x & 31));
+        }
+        for (int k = z.z + threadIdx.x; k < z.w; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j + 1) * W + (x >> 5)), 1u << (x & 31));
+        }
+    }
+    __syncthreads();
+    // every word's .y = set bits in the words before it: one wave per row, wave64 scans of 64 words
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < nrow; r += SC_THREADS / 64) {
+        int2 *row = rows + r * W;
+        int run = 0;
+        for (int c = 0; c < W; c += 64) {
+            const int i = c + lane;
+            const int v = i < W ? __popc((unsigned)row[i].x) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    __syncthreads();
+    unsigned long long acc = 0;
+    const int ny = ycnt[t];
+    for (int i = threadIdx.x; i < ny; i += SC_THREADS) {
+        const int4 y = ylist[base + i];  // T positions [y.x, y.y) of y, [y.z, y.w) of py
+        const int wa = y.x >> 5, wb = y.y >> 5, wc = y.z >> 5, wd = y.w >> 5;
+        const unsigned ma = (1u << (y.x & 31)) - 1u, mb = (1u << (y.y & 31)) - 1u;
+        const unsigned mc = (1u << (y.z & 31)) - 1u, md = (1u << (y.w & 31)) - 1u;
+        for (int j = 0; j < nz; ++j) {
+            const int2 *rz = rows + 2 * j * W, *rp = rz + W;
+            const int iyz = tp_count(rz, wb, mb) - tp_count(rz, wa, ma);
+            if (iyz < 2) continue;
+            const int ipyz = tp_count(rz, wd, md) - tp_count(rz, wc, mc);
+            const int iypz = tp_count(rp, wb, mb) - tp_count(rp, wa, ma);
+            const int ipp = tp_count(rp, wd, md) - tp_count(rp, wc, mc);
+            acc += (unsigned long long)((int64_t)iyz * (iyz - 1) / 2 * (int64_t)(ipp - iypz - ipyz + iyz));
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    __syncthreads();  // (the rows are read no more: their first 32 bytes take the wave sums)
+    unsigned long long *ws = reinterpret_cast<unsigned long long *>(rows);
+    if (lane == 0) ws[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long tot = 0;
+        for (int w = 0; w < SC_THREADS / 64; ++w) tot += ws[w];
+        if (tot) atomicAdd(t_shared + t, tot);
+    }
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -326,44 +566,75 @@ int sc_levels_host(int64_t n) {
 
 int grid_of(int64_t n) { return (int)std::max<int64_t>((n + SC_THREADS - 1) / SC_THREADS, 1); }
 
-}  // namespace
+size_t sc_up256(size_t b) { return (b + 255) / 256 * 256; }
 
-extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
-                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super,
-                                   int64_t *n_source, int64_t *shared, int64_t *informative, int64_t *supported) {
-    SCS_REQUIRE(ctx && src && parent && taxon, "scs_score_supertree: null argument");
-    SCS_REQUIRE(n_nodes >= 1, "scs_score_supertree: the supertree has no node");
-    SCS_REQUIRE(parent[0] == -1, "scs_score_supertree: node 0 must be the root (parent -1)");
-    const int32_t n_taxa = src->n_taxa;
+bool sc_launched(hipError_t &e) {
+    if (e == hipSuccess) e = hipGetLastError();
+    return e == hipSuccess;
+}
+
+// what both exports share: the supertree's host layout, the batches and the device block with S's arrays, the rows and
+// the per-batch tables of steps 1 - 2.  The caller's own arrays: extra_bytes once (d_extra) and extra_per_leaf /
+// extra_per_tree bytes per leaf / tree of the largest batch (d_extra_batch), both counted in the batch budget.
+struct sc_call {
+    const char *who = nullptr;
+    int32_t n_taxa = 0, n_leaves = 0, M = 0;
+    int64_t n_gaps = 0, row_stride = 0, max_lb = 0;
+    int levels = 0;
+    std::vector<int32_t> s_lo, s_hi, sub_end, s_pos, s_gap_node, bstart;
+    std::vector<uint64_t> s_gap;
+    void *block = nullptr;
+    int32_t *d_spos = nullptr, *d_gnode = nullptr, *d_slo = nullptr, *d_shi = nullptr, *d_end = nullptr;
+    int32_t *d_rows = nullptr, *d_sp = nullptr, *d_dep = nullptr, *d_node = nullptr, *d_amin = nullptr;
+    uint64_t *d_stab = nullptr;
+    int2 *d_mm = nullptr;
+    unsigned *d_flag = nullptr;
+    char *d_extra = nullptr, *d_extra_batch = nullptr;
+};
+
+// checks, host layout, block, uploads (their errors in e); SCS_OK or the code of a failure before the block exists
+int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nodes, const int32_t *parent,
+             const int32_t *taxon, int32_t max_batch_trees, size_t extra_bytes, uint64_t extra_per_leaf,
+             uint64_t extra_per_tree, sc_call &c, hipError_t &e) {
+    c.who = who;
+    SCS_REQUIRE(ctx && src && parent && taxon, "%s: null argument", who);
+    SCS_REQUIRE(n_nodes >= 1, "%s: the supertree has no node", who);
+    SCS_REQUIRE(parent[0] == -1, "%s: node 0 must be the root (parent -1)", who);
+    const int32_t n_taxa = c.n_taxa = src->n_taxa;
     // ---- the supertree's preorder arrays on the host: leaf ranges, subtree ends, gap table (O(nodes)) ----
-    std::vector<int32_t> s_lo(n_nodes), s_hi(n_nodes), sub_end(n_nodes), depth(n_nodes), n_kids(n_nodes, 0);
+    std::vector<int32_t> &s_lo = c.s_lo, &s_hi = c.s_hi, &sub_end = c.sub_end;
+    s_lo.resize(n_nodes);
+    s_hi.resize(n_nodes);
+    sub_end.resize(n_nodes);
+    std::vector<int32_t> depth(n_nodes), n_kids(n_nodes, 0);
     for (int32_t v = 1; v < n_nodes; ++v) {
-        SCS_REQUIRE(parent[v] >= 0 && parent[v] < v, "scs_score_supertree: parent[%d] = %d is not an earlier node", v,
-                    parent[v]);
+        SCS_REQUIRE(parent[v] >= 0 && parent[v] < v, "%s: parent[%d] = %d is not an earlier node", who, v, parent[v]);
         n_kids[parent[v]]++;
     }
-    std::vector<int32_t> s_pos(std::max(n_taxa, 1), -1);
+    std::vector<int32_t> &s_pos = c.s_pos;
+    s_pos.assign(std::max(n_taxa, 1), -1);
     int32_t n_leaves = 0;
     depth[0] = 0;
     for (int32_t v = 0; v < n_nodes; ++v) {
         if (v) depth[v] = depth[parent[v]] + 1;
         if (n_kids[v] == 0) {
             const int32_t x = taxon[v];
-            SCS_REQUIRE(x >= 0, "scs_score_supertree: tip %d has no taxon", v);
+            SCS_REQUIRE(x >= 0, "%s: tip %d has no taxon", who, v);
             if (x < n_taxa) {
-                SCS_REQUIRE(s_pos[x] < 0, "scs_score_supertree: taxon %d occurs twice in the supertree", x);
+                SCS_REQUIRE(s_pos[x] < 0, "%s: taxon %d occurs twice in the supertree", who, x);
                 s_pos[x] = n_leaves;
             }
             s_lo[v] = n_leaves;
             s_hi[v] = n_leaves;
             ++n_leaves;
         } else {
-            SCS_REQUIRE(taxon[v] < 0, "scs_score_supertree: inner node %d carries a taxon", v);
+            SCS_REQUIRE(taxon[v] < 0, "%s: inner node %d carries a taxon", who, v);
             s_lo[v] = INT32_MAX;
             s_hi[v] = -1;
         }
         sub_end[v] = v + 1;
     }
+    c.n_leaves = n_leaves;
     for (int32_t v = n_nodes - 1; v >= 1; --v) {  // (preorder: children after parents)
         const int32_t u = parent[v];
         s_lo[u] = std::min(s_lo[u], s_lo[v]);
@@ -371,31 +642,33 @@ extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t 
         sub_end[u] = std::max(sub_end[u], sub_end[v]);
     }
     // gap g (between S leaves g and g + 1) belongs to the node whose consecutive children it separates
-    const int64_t n_gaps = std::max<int64_t>(n_leaves - 1, 1);
-    std::vector<uint64_t> s_gap(n_gaps, 0);
-    std::vector<int32_t> s_gap_node(n_gaps, 0);
+    const int64_t n_gaps = c.n_gaps = std::max<int64_t>(n_leaves - 1, 1);
+    c.s_gap.assign(n_gaps, 0);
+    c.s_gap_node.assign(n_gaps, 0);
     for (int32_t v = 1; v < n_nodes; ++v) {
         const int32_t u = parent[v];
         if (s_hi[v] < s_hi[u]) {  // v is not u's last child
             const int32_t g = s_hi[v];
-            s_gap[g] = ((uint64_t)depth[u] << 32) | (uint32_t)g;
-            s_gap_node[g] = u;
+            c.s_gap[g] = ((uint64_t)depth[u] << 32) | (uint32_t)g;
+            c.s_gap_node[g] = u;
         }
     }
-    const int32_t M = src->n_trees;
+    const int32_t M = c.M = src->n_trees;
     const std::vector<int64_t> &off = src->h_tree_off;
     SCS_HIP_CHECK(hipSetDevice(ctx->device));
     SCS_TRY(scs_tables_finish(ctx, src));  // (late chunks of a page-locked upload: all of them are read)
     hipStream_t s = ctx->stream;
 
     // ---- batches: rows (V per tree) + per-leaf arrays and tables (levels of the batch's largest tree) ----
-    const int64_t row_stride = scs_round_up(std::max<int64_t>(n_leaves, 1), SC_ROW_ALIGN);
-    const int levels = sc_levels_host(std::max<int64_t>(src->max_leaves, 1));
+    const int64_t row_stride = c.row_stride = scs_round_up(std::max<int64_t>(n_leaves, 1), SC_ROW_ALIGN);
+    const int levels = c.levels = sc_levels_host(std::max<int64_t>(src->max_leaves, 1));
     const auto per_tree = [&](int32_t t) {
         const int64_t n = off[t + 1] - off[t];
-        return (uint64_t)row_stride * 4 + (uint64_t)n * (4 * 3 + 8 * levels + 4 * (levels - 1));
+        return (uint64_t)row_stride * 4 + (uint64_t)n * (4 * 3 + 8 * levels + 4 * (levels - 1) + extra_per_leaf) +
+               extra_per_tree;
     };
-    std::vector<int32_t> bstart{0};
+    std::vector<int32_t> &bstart = c.bstart;
+    bstart.assign(1, 0);
     {
         uint64_t acc = 0;
         for (int32_t t = 0; t < M; ++t) {
@@ -413,152 +686,269 @@ extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t 
         max_rows = std::max<int64_t>(max_rows, bstart[b + 1] - bstart[b]);
         max_lb = std::max<int64_t>(max_lb, off[bstart[b + 1]] - off[bstart[b]]);
     }
-    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    c.max_lb = max_lb;
     const int s_levels = sc_levels_host(n_gaps);
-    // persistent part: S arrays, marks, prefix sums, counters, flags
+    // persistent part: S arrays, flags, the caller's arrays
     size_t o = 0;
-    const size_t o_spos = o; o += up256((size_t)std::max(n_taxa, 1) * 4);
-    const size_t o_gnode = o; o += up256((size_t)n_gaps * 4);
-    const size_t o_stab = o; o += up256((size_t)n_gaps * 8 * s_levels);
-    const size_t o_slo = o; o += up256((size_t)n_nodes * 4);
-    const size_t o_shi = o; o += up256((size_t)n_nodes * 4);
-    const size_t o_end = o; o += up256((size_t)n_nodes * 4);
-    const size_t o_mark = o; o += up256((size_t)n_nodes * 8);
-    const size_t o_pref = o; o += up256(((size_t)n_nodes + 1) * 16);
-    const size_t o_out = o; o += up256((size_t)n_nodes * 16);
-    const size_t o_cnt = o; o += up256((size_t)M * 24);
+    const size_t o_spos = o; o += sc_up256((size_t)std::max(n_taxa, 1) * 4);
+    const size_t o_gnode = o; o += sc_up256((size_t)n_gaps * 4);
+    const size_t o_stab = o; o += sc_up256((size_t)n_gaps * 8 * s_levels);
+    const size_t o_slo = o; o += sc_up256((size_t)n_nodes * 4);
+    const size_t o_shi = o; o += sc_up256((size_t)n_nodes * 4);
+    const size_t o_end = o; o += sc_up256((size_t)n_nodes * 4);
     const size_t o_flag = o; o += 256;
+    const size_t o_extra = o; o += sc_up256(extra_bytes);
     // batch part
-    const size_t o_rows = o; o += up256((size_t)max_rows * row_stride * 4);
-    const size_t o_sp = o; o += up256((size_t)max_lb * 4);
-    const size_t o_dep = o; o += up256((size_t)max_lb * 4);
-    const size_t o_node = o; o += up256((size_t)max_lb * 4);
-    const size_t o_mm = o; o += up256((size_t)max_lb * 8 * levels);
-    const size_t o_amin = o; o += up256((size_t)max_lb * 4 * std::max(levels - 1, 1));
-    void *block = nullptr;
-    SCS_TRY(scs_block_alloc(ctx, o, &block));
-    char *bp = (char *)block;
-    auto *d_spos = (int32_t *)(bp + o_spos);
-    auto *d_gnode = (int32_t *)(bp + o_gnode);
-    auto *d_stab = (uint64_t *)(bp + o_stab);
-    auto *d_slo = (int32_t *)(bp + o_slo);
-    auto *d_shi = (int32_t *)(bp + o_shi);
-    auto *d_end = (int32_t *)(bp + o_end);
-    auto *d_mark = (int32_t *)(bp + o_mark);
-    auto *d_pref = (int64_t *)(bp + o_pref);
-    auto *d_out = (int64_t *)(bp + o_out);
-    auto *d_cnt = (unsigned long long *)(bp + o_cnt);
-    auto *d_flag = (unsigned *)(bp + o_flag);
-    auto *d_rows = (int32_t *)(bp + o_rows);
-    auto *d_sp = (int32_t *)(bp + o_sp);
-    auto *d_dep = (int32_t *)(bp + o_dep);
-    auto *d_node = (int32_t *)(bp + o_node);
-    auto *d_mm = (int2 *)(bp + o_mm);
-    auto *d_amin = (int32_t *)(bp + o_amin);
+    const size_t o_rows = o; o += sc_up256((size_t)max_rows * row_stride * 4);
+    const size_t o_sp = o; o += sc_up256((size_t)max_lb * 4);
+    const size_t o_dep = o; o += sc_up256((size_t)max_lb * 4);
+    const size_t o_node = o; o += sc_up256((size_t)max_lb * 4);
+    const size_t o_mm = o; o += sc_up256((size_t)max_lb * 8 * levels);
+    const size_t o_amin = o; o += sc_up256((size_t)max_lb * 4 * std::max(levels - 1, 1));
+    const size_t o_xb = o; o += sc_up256((size_t)(max_lb * extra_per_leaf + max_rows * extra_per_tree));
+    SCS_TRY(scs_block_alloc(ctx, o, &c.block));
+    char *bp = (char *)c.block;
+    c.d_spos = (int32_t *)(bp + o_spos);
+    c.d_gnode = (int32_t *)(bp + o_gnode);
+    c.d_stab = (uint64_t *)(bp + o_stab);
+    c.d_slo = (int32_t *)(bp + o_slo);
+    c.d_shi = (int32_t *)(bp + o_shi);
+    c.d_end = (int32_t *)(bp + o_end);
+    c.d_flag = (unsigned *)(bp + o_flag);
+    c.d_extra = bp + o_extra;
+    c.d_rows = (int32_t *)(bp + o_rows);
+    c.d_sp = (int32_t *)(bp + o_sp);
+    c.d_dep = (int32_t *)(bp + o_dep);
+    c.d_node = (int32_t *)(bp + o_node);
+    c.d_mm = (int2 *)(bp + o_mm);
+    c.d_amin = (int32_t *)(bp + o_amin);
+    c.d_extra_batch = bp + o_xb;
 
-    hipError_t e = hipSuccess;
-    unsigned bad = 0;
-    auto launch_ok = [&]() {
-        if (e == hipSuccess) e = hipGetLastError();
-        return e == hipSuccess;
-    };
-    e = hipMemcpyAsync(d_spos, s_pos.data(), (size_t)std::max(n_taxa, 1) * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gnode, s_gap_node.data(), (size_t)n_gaps * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_stab, s_gap.data(), (size_t)n_gaps * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_slo, s_lo.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_shi, s_hi.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_end, sub_end.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, (size_t)n_nodes * 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, s);
+    e = hipMemcpyAsync(c.d_spos, s_pos.data(), (size_t)std::max(n_taxa, 1) * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c.d_gnode, c.s_gap_node.data(), (size_t)n_gaps * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.d_stab, c.s_gap.data(), (size_t)n_gaps * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.d_slo, s_lo.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.d_shi, s_hi.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.d_end, sub_end.data(), (size_t)n_nodes * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(c.d_flag, 0, 4, s);
     for (int j = 1; j < s_levels && e == hipSuccess; ++j) {
-        k_score_level_u64<<<grid_of(n_gaps), SC_THREADS, 0, s>>>(d_stab + (j - 1) * n_gaps, d_stab + j * n_gaps, n_gaps,
-                                                                 (int64_t)1 << (j - 1));
-        launch_ok();
+        k_score_level_u64<<<grid_of(n_gaps), SC_THREADS, 0, s>>>(c.d_stab + (j - 1) * n_gaps, c.d_stab + j * n_gaps,
+                                                                 n_gaps, (int64_t)1 << (j - 1));
+        sc_launched(e);
     }
-    for (size_t b = 0; b + 1 < bstart.size() && e == hipSuccess; ++b) {
-        const int32_t t0 = bstart[b], nb = bstart[b + 1] - t0;
-        const int64_t *d_off = src->d_tree_off + t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
-        e = hipMemsetAsync(d_rows, 0xff, (size_t)nb * row_stride * 4, s);
-        if (e != hipSuccess) break;
-        k_score_scatter<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, src->d_leaf_taxon, n_taxa, d_spos, d_rows,
-                                                           row_stride, d_flag);
-        if (!launch_ok()) break;
-        // (a bad taxon leaves a row short: nothing below may read the arrays it did not fill -- stop here)
-        e = hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess || bad) break;
-        k_score_compact<<<nb, SC_THREADS, 0, s>>>(d_off, d_rows, row_stride, d_sp, d_mm);
-        if (!launch_ok()) break;
-        const int32_t *adj = src->d_adj_depth + L0;
-        for (int j = 1; j < levels && e == hipSuccess; ++j) {
-            k_score_level_tree<<<grid_of(Lb), SC_THREADS, 0, s>>>(j == 1 ? adj : d_amin + (int64_t)(j - 2) * Lb,
-                                                                   d_amin + (int64_t)(j - 1) * Lb, d_mm + (j - 1) * Lb,
-                                                                   d_mm + j * Lb, Lb, (int64_t)1 << (j - 1));
-            launch_ok();
-        }
-        if (e != hipSuccess) break;
-        k_score_restrict<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, d_sp, d_stab, n_gaps, d_gnode, d_dep, d_node);
-        if (!launch_ok()) break;
+    return SCS_OK;
+}
+
+// steps 1 - 2 for batch b: sp, the tp min-max table, T's min table of adj, D and U.  False (stop) on an error or on a
+// bad source taxon (`bad`): a row left short must not be read
+bool sc_prepare_batch(const scs_tables *src, hipStream_t s, sc_call &c, size_t b, hipError_t &e, unsigned &bad) {
+    const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+    const int64_t *d_off = src->d_tree_off + t0;
+    const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
+    e = hipMemsetAsync(c.d_rows, 0xff, (size_t)nb * c.row_stride * 4, s);
+    if (e != hipSuccess) return false;
+    k_score_scatter<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, src->d_leaf_taxon, c.n_taxa, c.d_spos, c.d_rows,
+                                                       c.row_stride, c.d_flag);
+    if (!sc_launched(e)) return false;
+    e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess || bad) return false;
+    k_score_compact<<<nb, SC_THREADS, 0, s>>>(d_off, c.d_rows, c.row_stride, c.d_sp, c.d_mm);
+    if (!sc_launched(e)) return false;
+    const int32_t *adj = src->d_adj_depth + L0;
+    for (int j = 1; j < c.levels && e == hipSuccess; ++j) {
+        k_score_level_tree<<<grid_of(Lb), SC_THREADS, 0, s>>>(j == 1 ? adj : c.d_amin + (int64_t)(j - 2) * Lb,
+                                                               c.d_amin + (int64_t)(j - 1) * Lb, c.d_mm + (j - 1) * Lb,
+                                                               c.d_mm + j * Lb, Lb, (int64_t)1 << (j - 1));
+        sc_launched(e);
+    }
+    if (e != hipSuccess) return false;
+    k_score_restrict<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, c.d_sp, c.d_stab, c.n_gaps, c.d_gnode, c.d_dep,
+                                                        c.d_node);
+    return sc_launched(e);
+}
+
+// waits for the stream (after the caller's copies), releases the block, reports
+int sc_end(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad) {
+    hipStream_t s = ctx->stream;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);  // (nothing may still write into the block)
+    scs_block_release(ctx, c.block);
+    if (e != hipSuccess) {
+        scs_set_error("%s: %s", c.who, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? SCS_ENOMEM : SCS_EHIP;
+    }
+    if (bad) {
+        scs_set_error("%s: %s", c.who, (bad & 1u)   ? "a leaf_taxon entry is out of range [0, n_taxa)"
+                                       : (bad & 2u) ? "a source tree has a taxon the supertree lacks"
+                                                    : "a source tree has a taxon twice");
+        return SCS_EINVAL;
+    }
+    return SCS_OK;
+}
+
+}  // namespace
+
+extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super,
+                                   int64_t *n_source, int64_t *shared, int64_t *informative, int64_t *supported) {
+    // own arrays: marks, prefix sums, outputs per S node; three counters per tree
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
+    const size_t o_mark = 0, o_pref = o_mark + sc_up256(nn * 8), o_out = o_pref + sc_up256((nn + 1) * 16),
+                 o_cnt = o_out + sc_up256(nn * 16), own = o_cnt + sc_up256(mt * 24);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_supertree", n_nodes, parent, taxon, max_batch_trees, own, 0, 0, c, e));
+    const int32_t M = c.M;
+    hipStream_t s = ctx->stream;
+    auto *d_mark = (int32_t *)(c.d_extra + o_mark);
+    auto *d_pref = (int64_t *)(c.d_extra + o_pref);
+    auto *d_out = (int64_t *)(c.d_extra + o_out);
+    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, nn * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
         sc_nodes_args a;
-        a.off = d_off;
+        a.off = src->d_tree_off + t0;
         a.nb = nb;
-        a.sp = d_sp;
-        a.dep = d_dep;
-        a.node = d_node;
-        a.mm = d_mm;
-        a.adj = adj;
-        a.amin = d_amin;
-        a.levels = levels;
+        a.sp = c.d_sp;
+        a.dep = c.d_dep;
+        a.node = c.d_node;
+        a.mm = c.d_mm;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
         a.Lb = Lb;
-        a.s_tab = d_stab;
-        a.s_stride = n_gaps;
-        a.s_lo = d_slo;
-        a.s_hi = d_shi;
+        a.s_tab = c.d_stab;
+        a.s_stride = c.n_gaps;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
         a.mark_inf = d_mark;
         a.mark_sup = d_mark + n_nodes;
         a.c_super = d_cnt + t0;
         a.c_source = d_cnt + M + t0;
         a.c_shared = d_cnt + 2 * (int64_t)M + t0;
         k_score_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
-        if (!launch_ok()) break;
+        if (!sc_launched(e)) break;
     }
     if (e == hipSuccess && !bad) {
         k_score_prefix<<<1, 1024, 0, s>>>(d_mark, d_mark + n_nodes, n_nodes, d_pref, d_pref + n_nodes + 1);
-        launch_ok();
+        sc_launched(e);
     }
     if (e == hipSuccess && !bad) {
-        k_score_subtree<<<grid_of(n_nodes), SC_THREADS, 0, s>>>(d_pref, d_pref + n_nodes + 1, d_end, n_nodes, d_out,
+        k_score_subtree<<<grid_of(n_nodes), SC_THREADS, 0, s>>>(d_pref, d_pref + n_nodes + 1, c.d_end, n_nodes, d_out,
                                                                 d_out + n_nodes);
-        launch_ok();
+        sc_launched(e);
     }
     std::vector<unsigned long long> cnt((size_t)M * 3);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && informative)
         e = hipMemcpyAsync(informative, d_out, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && supported)
         e = hipMemcpyAsync(supported, d_out + n_nodes, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);  // (nothing may still write into the block)
-    scs_block_release(ctx, block);
-    if (e != hipSuccess) {
-        scs_set_error("scs_score_supertree: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? SCS_ENOMEM : SCS_EHIP;
-    }
-    if (bad) {
-        scs_set_error("scs_score_supertree: %s", (bad & 1u)   ? "a leaf_taxon entry is out of range [0, n_taxa)"
-                                                 : (bad & 2u) ? "a source tree has a taxon the supertree lacks"
-                                                              : "a source tree has a taxon twice");
-        return SCS_EINVAL;
-    }
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    const std::vector<int64_t> &off = src->h_tree_off;
     for (int32_t t = 0; t < M; ++t) {
         const int64_t n = off[t + 1] - off[t];
         const int64_t ns = (int64_t)cnt[t], nt = n >= 2 ? (int64_t)cnt[M + t] - 1 : 0, sh = (int64_t)cnt[2 * M + t];
         if (n_super) n_super[t] = ns;
         if (n_source) n_source[t] = nt;
         if (shared) shared[t] = sh;
+    }
+    return SCS_OK;
+}
+
+extern "C" int scs_score_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                  const int32_t *taxon, int32_t max_batch_trees, int64_t *t_super, int64_t *t_source,
+                                  int64_t *t_shared) {
+    // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "scs_score_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS",
+                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    // own arrays: three counters and the first pair workgroup per tree (+ 1); per batch two node lists (int4 per
+    // leaf) and their two lengths per tree
+    const size_t mt = src ? (size_t)src->n_trees : 0;
+    const size_t o_cnt = 0, o_blk = sc_up256(mt * 24), own = o_blk + sc_up256((mt + 1) * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_triplets", n_nodes, parent, taxon, max_batch_trees, own, 32, 8, c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    auto *d_ylist = (int4 *)c.d_extra_batch;
+    auto *d_zlist = d_ylist + c.max_lb;
+    auto *d_ycnt = (int32_t *)(d_zlist + c.max_lb);
+    // per batch: W words per bitset row (largest tree of the batch), zb S' nodes per workgroup; blk: the first pair
+    // workgroup of every tree, ceil((n - 2) / zb) of them (n - 2 bounds the non-root internal nodes)
+    const size_t n_batches = c.bstart.size() - 1;
+    std::vector<int> words(n_batches), zbs(n_batches);
+    std::vector<int64_t> blk((size_t)M + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        zbs[b] = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (16 * words[b])));
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
+            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_trip_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
+        if (e != hipSuccess) break;
+        sc_trip_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.dep = c.d_dep;
+        a.node = c.d_node;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_tab = c.d_stab;
+        a.s_stride = c.n_gaps;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.ylist = d_ylist;
+        a.zlist = d_zlist;
+        a.ycnt = d_ycnt;
+        a.zcnt = d_ycnt + nb;
+        a.c_super = d_cnt + t0;
+        a.c_source = d_cnt + M + t0;
+        k_trip_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        if (n_wg == 0) continue;
+        const size_t lds = std::max<size_t>((size_t)zbs[b] * 16 * words[b], 32);
+        k_trip_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_zlist, a.ycnt, a.zcnt,
+                                                             c.d_mm, zbs[b], words[b], d_cnt + 2 * (int64_t)M + t0);
+        if (!sc_launched(e)) break;
+    }
+    std::vector<unsigned long long> cnt((size_t)M * 3);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    for (int32_t t = 0; t < M; ++t) {
+        if (t_super) t_super[t] = (int64_t)cnt[t];
+        if (t_source) t_source[t] = (int64_t)cnt[M + t];
+        if (t_shared) t_shared[t] = (int64_t)cnt[2 * M + t];
     }
     return SCS_OK;
 }

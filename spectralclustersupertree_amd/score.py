@@ -1,5 +1,6 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
-supertree node.  Neither the reference nor ``construct_supertree`` computes them.
+supertree node, and on request rooted triplet terms per source tree (section 15).  Neither
+the reference nor ``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
 2 <= size < |L|.  C(S|T) = the nontrivial sets C ∩ L(T) over the clades C of the supertree S; C(T) = T's own.
@@ -9,7 +10,22 @@ For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of 
 * per node C of S (preorder, ``TreeNode.to_flat`` order, unary nodes included): ``informative`` = the trees
   with 2 <= |C ∩ L(T)| < |L(T)|, ``supported`` = those of them with C ∩ L(T) in C(T).  Tips and the root are 0.
 
-Every count comes from the HIP kernels behind ``scs_score_supertree``; the host only validates and lays out.
+Rooted triplets (``triplets=True``).  With L = L(T), m = |L| and S' = S|L, a triple {a, b, c} ⊆ L is *resolved ab|c*
+in a tree when some cluster of that tree holds a and b but not c; when no cluster does this for any pair, the triple
+is a *fan*.  Per source tree:
+
+* ``t_source`` = the triples T resolves, ``t_super`` = the triples S' resolves, ``t_shared`` = the triples resolved
+  the same way in both;
+* ``triplet_distance = t_super + t_source - 2 t_shared``: the triples whose topology differs (resolved differently,
+  or resolved in one tree and a fan in the other).  Trees of m < 3 leaves give zeros.
+
+With y over T's non-root nodes, z over S''s, py / pz their parents and I(y, z) = |cl(y) ∩ cl(z)| (clusters restricted
+to L): ``t_shared`` = Σ_y Σ_z C(I(y,z), 2) (I(py,pz) - I(y,pz) - I(py,z) + I(y,z)) and ``t_source`` =
+Σ_y C(|y|, 2) (|py| - |y|), ``t_super`` likewise over S'.  A shared triple ab|c is counted once, at the children of
+the two LCAs of a, b, c that hold a and b; the second factor counts the c in (cl(py) ∖ cl(y)) ∩ (cl(pz) ∖ cl(z)).
+
+Every count comes from the HIP kernels behind ``scs_score_supertree`` and ``scs_score_triplets``; the host only
+validates and lays out.
 """
 
 from __future__ import annotations
@@ -39,8 +55,13 @@ class SupertreeScore:
     informative: np.ndarray  # per supertree node, preorder
     supported: np.ndarray
     # wall seconds: "prepare" (host: supertree arrays, checks, flattening objects), "tables" (a TreeArrays forest
-    # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels)
+    # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
+    # "triplets" (scs_score_triplets, when requested)
     timings: dict = field(default_factory=dict)
+    # rooted triplet terms per source tree (``triplets=True``; None otherwise)
+    t_super: np.ndarray | None = None
+    t_source: np.ndarray | None = None
+    t_shared: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -50,6 +71,30 @@ class SupertreeScore:
     def total_rf(self) -> int:
         """The RF supertree score: the RF distances to the sources, summed."""
         return int(self.rf.sum())
+
+    @property
+    def triplet_distance(self) -> np.ndarray:
+        """Per source tree: the triples whose topology differs between S|L(T) and T."""
+        self._need_triplets()
+        return self.t_super + self.t_source - 2 * self.t_shared
+
+    @property
+    def total_triplet_distance(self) -> int:
+        self._need_triplets()
+        return int(self.triplet_distance.sum())
+
+    @property
+    def triplet_fit(self) -> float:
+        """Σ t_shared / Σ t_source: the share of the sources' resolved triples the supertree resolves alike (NaN when
+        no source resolves a triple)."""
+        self._need_triplets()
+        total = int(self.t_source.sum())
+        return float(int(self.t_shared.sum()) / total) if total > 0 else float("nan")
+
+    def _need_triplets(self) -> None:
+        if self.t_shared is None:
+            msg = "triplet terms were not computed: score_supertree(..., triplets=True)"
+            raise ValueError(msg)
 
     def support(self) -> np.ndarray:
         """``supported / informative`` per node (NaN where no source is informative)."""
@@ -71,11 +116,18 @@ class SupertreeScore:
         return out
 
     def table(self) -> str:
-        """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf."""
-        rows = ["index\tn_leaves\tn_super\tn_source\tshared\trf"]
+        """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, and when the triplet terms
+        were computed t_super, t_source, t_shared, triplet_distance."""
+        trip = self.t_shared is not None
+        head = "index\tn_leaves\tn_super\tn_source\tshared\trf"
+        rows = [head + "\tt_super\tt_source\tt_shared\ttriplet_distance" if trip else head]
         rf = self.rf
+        td = self.triplet_distance if trip else None
         for t in range(len(rf)):
-            rows.append(f"{t}\t{self.n_leaves[t]}\t{self.n_super[t]}\t{self.n_source[t]}\t{self.shared[t]}\t{rf[t]}")
+            row = f"{t}\t{self.n_leaves[t]}\t{self.n_super[t]}\t{self.n_source[t]}\t{self.shared[t]}\t{rf[t]}"
+            if trip:
+                row += f"\t{self.t_super[t]}\t{self.t_source[t]}\t{self.t_shared[t]}\t{td[t]}"
+            rows.append(row)
         return "\n".join(rows) + "\n"
 
 
@@ -113,8 +165,10 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
     return parent, taxon, tips
 
 
-def score_supertree(supertree: TreeNode, trees, *, device=None) -> SupertreeScore:
-    """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring).
+def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, device=None) -> SupertreeScore:
+    """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
+    ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``), counted on the same
+    device tables as the RF terms.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -139,8 +193,9 @@ def score_supertree(supertree: TreeNode, trees, *, device=None) -> SupertreeScor
                 raise ValueError(msg)
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
-        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id)
-        out.timings["prepare"] = time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
+        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets)
+        out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
+                                  - out.timings.get("triplets", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -159,12 +214,18 @@ def score_supertree(supertree: TreeNode, trees, *, device=None) -> SupertreeScor
     t2 = time.perf_counter()
     try:
         res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
+        t3 = t4 = time.perf_counter()
+        if triplets:
+            res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+            t4 = time.perf_counter()
     finally:
         tabs.free()
-    t3 = time.perf_counter()
+    timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
+    if triplets:
+        timings["triplets"] = t4 - t3
     return SupertreeScore(supertree, np.diff(tables.tree_off), res["n_super"], res["n_source"], res["shared"],
-                          res["informative"], res["supported"],
-                          {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2})
+                          res["informative"], res["supported"], timings,
+                          res.get("t_super"), res.get("t_source"), res.get("t_shared"))
 
 
 def _default_device():
@@ -173,7 +234,7 @@ def _default_device():
     return default_device()
 
 
-def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id) -> SupertreeScore:
+def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -185,7 +246,8 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     m = arrays.n_trees
     n_leaves = arrays.leaf_counts().astype(np.int64)
     n_nodes = len(parent)
-    zeros = {k: np.zeros(m, dtype=np.int64) for k in ("n_super", "n_source", "shared")}
+    per_tree = ("n_super", "n_source", "shared") + (("t_super", "t_source", "t_shared") if triplets else ())
+    zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
     node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in ("informative", "supported")}
     # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
     universe = max(arrays.n_taxa, n_taxa, 1)
@@ -201,7 +263,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = time.perf_counter()
+        t1 = t2 = t3 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
         else:
@@ -211,16 +273,22 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
             t1 = time.perf_counter()
             try:
                 res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
+                t2 = t3 = time.perf_counter()
+                if triplets:
+                    res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+                    t3 = time.perf_counter()
             finally:
                 tabs.free()
-            t2 = time.perf_counter()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
-            for k in ("n_super", "n_source", "shared"):
+            for k in per_tree:
                 full = zeros[k]
                 full[tree_index] = res[k]
                 res[k] = full
     finally:
         child.free()
+    timings = {"tables": t1 - t0, "score": t2 - t1}
+    if triplets:
+        timings["triplets"] = t3 - t2
     return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
-                          res["informative"], res["supported"],
-                          {"tables": t1 - t0, "score": t2 - t1})
+                          res["informative"], res["supported"], timings,
+                          res.get("t_super"), res.get("t_source"), res.get("t_shared"))
