@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 107.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 108.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -336,6 +336,20 @@ int scs_score_supertree(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes
 int scs_score_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
                        const int32_t *taxon, int32_t max_batch_trees, int64_t *t_super, int64_t *t_source,
                        int64_t *t_shared);
+
+/* Clade conflicts, same inputs and SCS_EINVAL cases as scs_score_supertree.  Two sets A and
+ * B conflict when A ∩ B is not empty and neither holds the other; a set conflicts with a tree when it conflicts with
+ * one of the tree's clusters (a cluster the tree displays never does).  For a source tree T on the leaf set L and
+ * S' = S|L, with C(S|T) and C(T) as for scs_score_supertree:
+ *   n_super_conflict[t]  = the clusters of C(S|T) that conflict with T,
+ *   n_source_conflict[t] = the clusters of C(T) that conflict with S'.
+ * Per node C of S (n_nodes entries, S's preorder):
+ *   conflicting[C] = #{T : C ∩ L(T) is nontrivial and conflicts with T}  (supported + conflicting <= informative;
+ *   the rest are the sources that are compatible with C without resolving it).
+ * Trees of fewer than 3 leaves give zeros; counts are unweighted.  Output pointers may be null. */
+int scs_score_conflicts(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                        const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super_conflict,
+                        int64_t *n_source_conflict, int64_t *conflicting);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

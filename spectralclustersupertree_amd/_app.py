@@ -45,10 +45,10 @@ def sc_supertree(
 
 
 @_define_app
-def score_supertree(supertree, trees, *, triplets: bool = False):
-    """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, and with
-    ``triplets=True`` the rooted triplet terms."""
-    return _score(supertree, trees, triplets=triplets)
+def score_supertree(supertree, trees, *, triplets: bool = False, conflicts: bool = False):
+    """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, with
+    ``triplets=True`` the rooted triplet terms and with ``conflicts=True`` the clade conflict counts."""
+    return _score(supertree, trees, triplets=triplets, conflicts=conflicts)
 
 
 @_define_app

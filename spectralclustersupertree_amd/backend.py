@@ -174,6 +174,27 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_conflicts(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
+        """``scs_score_conflicts``: clade conflict counts, with the inputs of ``score``.  Returns int64 arrays
+        ``n_super_conflict``, ``n_source_conflict`` (per tree) and ``conflicting`` (per node)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        n_nodes, m = len(parent), tabs.n_trees
+        if taxon.shape != (n_nodes,):
+            msg = "parent and taxon must have one entry per supertree node"
+            raise ValueError(msg)
+        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_super_conflict", "n_source_conflict")}
+        out["conflicting"] = np.zeros(n_nodes, dtype=np.int64)
+        rc = self._lib.scs_score_conflicts(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                           int(batch_trees), nv.lptr(out["n_super_conflict"]),
+                                           nv.lptr(out["n_source_conflict"]), nv.lptr(out["conflicting"]))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_conflicts: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

@@ -37,11 +37,20 @@ from spectralclustersupertree_amd import __version__
                    "node name (Newick).")
 @click.option("--triplets", default=False, is_flag=True,
               help="Add the rooted triplet terms to --scores-out (t_super, t_source, t_shared, triplet_distance).")
+@click.option("--conflicts", default=False, is_flag=True,
+              help="Add the clade conflict counts to --scores-out (n_super_conflict, n_source_conflict).")
+@click.option("--conflict-out", default=None,
+              help="Also write the supertree with each clade's supported/conflicting/informative source counts as "
+                   "its node name (Newick).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
-        scores_out: str | None = None, support_out: str | None = None, triplets: bool = False) -> None:
+        scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
+        conflicts: bool = False, conflict_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
+        raise click.UsageError(msg)
+    if conflicts and not scores_out:
+        msg = "--conflicts needs --scores-out"
         raise click.UsageError(msg)
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
@@ -56,14 +65,24 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     team = default_team()
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
-        if scores_out or support_out:
+        if scores_out or support_out or conflict_out:
             from spectralclustersupertree_amd.score import score_supertree
 
-            result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets)
+            result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
+                                     conflicts=conflicts or conflict_out is not None)
             if scores_out:
-                Path(scores_out).write_text(result.table())
+                Path(scores_out).write_text(result.table() if conflicts else _without_conflicts(result).table())
             if support_out:
                 Path(support_out).write_text(result.annotate().get_newick(with_node_names=True) + "\n")
+            if conflict_out:
+                Path(conflict_out).write_text(result.annotate_counts().get_newick(with_node_names=True) + "\n")
+
+
+def _without_conflicts(result):
+    """``result`` whose table leaves the conflict columns out (--conflict-out without --conflicts)."""
+    import dataclasses
+
+    return dataclasses.replace(result, n_super_conflict=None, n_source_conflict=None, conflicting=None)
 
 
 if __name__ == "__main__":

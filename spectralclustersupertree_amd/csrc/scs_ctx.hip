@@ -39,7 +39,8 @@ extern "C" const char *scs_last_error(void) { return g_last_error.c_str(); }
 // 102 (round 5): scs_stats grew by the mixed-precision loop's fields
 // 103: ... and by event_pair_ms
 // 107: scs_score_triplets added
-extern "C" int scs_version(void) { return 107; }
+// 108: scs_score_conflicts added
+extern "C" int scs_version(void) { return 108; }
 
 extern "C" int scs_device_count(void) {
     int n = 0;

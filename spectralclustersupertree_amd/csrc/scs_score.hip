@@ -557,6 +557,328 @@ __global__ void __launch_bounds__(SC_THREADS) k_trip_pairs(const int64_t *__rest
     }
 }
 
+// ---- clade conflicts (scs_score_conflicts) ----
+//
+// Two sets conflict when they overlap and neither holds the other.  A cluster z of one tree (S' or T) conflicts with
+// the other tree iff some gap p of the other tree's leaf order has exactly one of its leaves in z and lies strictly
+// below lca(z) there.  Fix a gap p, x one of its two leaves, x' the other and K the leaves of lca(x, x'): the clusters
+// it flags through x are the ancestors of x that miss x' and are not inside K -- a path from z*, the lowest ancestor
+// of x with a leaf outside K (the deeper LCA of x with the nearest leaf outside K on either side of x, in z's own leaf
+// order), up to A = lca(x, x'), A excluded.  +1 at a gap of z*, -1 at a gap of A: the marks on a node's gaps (its
+// subtree) sum to the paths through it, and it conflicts iff the sum is positive.
+//   k_conf_ip / k_conf_level: ip[T position] = S' index (the inverse of tp) and its min-max table.
+//   k_conf_marks, one thread per gap, for both trees: T's gap marks S''s gaps (descents on tp's table, LCAs on S's
+//     gap table), S''s gap marks T's gaps (descents on ip's table, LCAs on T's min table of adj).
+//   k_conf_scan: one workgroup per tree, inclusive prefix sums of both mark rows.
+//   k_conf_nodes, one thread per gap: every non-root node at its first gap reads its sum; a flagged S' node marks the
+//     S path [u, w) of its cluster for `conflicting`, as k_score_nodes does for `supported`.
+
+struct sc_conf_args {
+    const int64_t *off;          // tree_off + t0
+    int nb;
+    const int32_t *sp, *dep, *node;  // [Lb] S positions in S order, D and U of S'
+    const int2 *mm;              // min-max table of tp (S' order): level j at mm[j * Lb]
+    const int2 *im;              // min-max table of ip (T order): level j at im[j * Lb]
+    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
+    int levels;
+    int64_t Lb;
+    const uint64_t *s_tab;       // S's packed gap table
+    int64_t s_stride;
+    const int32_t *s_lo, *s_hi;  // leaf range of every S node
+    int32_t *mark_s, *mark_t;    // [Lb] marks on S''s / T's gaps, then their per-tree inclusive prefix sums
+    int32_t *mark_node;          // [S nodes]
+    unsigned long long *c_super, *c_source;  // [nb] of the batch
+};
+
+// The searches of k_conf_marks gallop: blocks of 1, 2, 4, ... entries while the condition holds, then the binary
+// descent from the last level that failed -- O(log of the distance found), as most answers lie a few leaves away.
+
+// nearest index left of x / right of x (tree-relative, the tree at base, n leaves) whose entry in a min-max table lies
+// outside [lo, hi]: -1 / n when there is none
+__device__ __forceinline__ int64_t sc_outside_left(const int2 *__restrict__ tab, int64_t Lb, int levels, int64_t base,
+                                                   int64_t x, int32_t lo, int32_t hi) {
+    int64_t pos = x;
+    int j = 0;
+    for (; j < levels; ++j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos < w) break;
+        const int2 v = tab[j * Lb + base + pos - w];
+        if (v.x < lo || v.y > hi) break;
+        pos -= w;
+    }
+    for (--j; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos >= w) {
+            const int2 v = tab[j * Lb + base + pos - w];
+            if (v.x >= lo && v.y <= hi) pos -= w;
+        }
+    }
+    return pos - 1;
+}
+
+__device__ __forceinline__ int64_t sc_outside_right(const int2 *__restrict__ tab, int64_t Lb, int levels, int64_t base,
+                                                    int64_t x, int64_t n, int32_t lo, int32_t hi) {
+    int64_t pos = x + 1;
+    int j = 0;
+    for (; j < levels; ++j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos + w > n) break;
+        const int2 v = tab[j * Lb + base + pos];
+        if (v.x < lo || v.y > hi) break;
+        pos += w;
+    }
+    for (--j; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos + w <= n) {
+            const int2 v = tab[j * Lb + base + pos];
+            if (v.x >= lo && v.y <= hi) pos += w;
+        }
+    }
+    return pos;
+}
+
+// sc_stretch_left (ge) / sc_stretch_right, galloping: the start of the stretch [p, pos) of T gaps with depth >= d ...
+__device__ __forceinline__ int64_t sc_gallop_left(const int32_t *__restrict__ adj, const int32_t *__restrict__ amin,
+                                                  int64_t Lb, int levels, int64_t base, int64_t pos, int32_t d) {
+    int j = 0;
+    for (; j < levels; ++j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos < w) break;
+        const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+        if (lev[base + pos - w] < d) break;
+        pos -= w;
+    }
+    for (--j; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos >= w) {
+            const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+            if (lev[base + pos - w] >= d) pos -= w;
+        }
+    }
+    return pos;
+}
+
+// ... and the end of the stretch [pos, p) of gaps with depth >= d, p <= last
+__device__ __forceinline__ int64_t sc_gallop_right(const int32_t *__restrict__ adj, const int32_t *__restrict__ amin,
+                                                   int64_t Lb, int levels, int64_t base, int64_t pos, int64_t last,
+                                                   int32_t d) {
+    int j = 0;
+    for (; j < levels; ++j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos + w > last) break;
+        const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+        if (lev[base + pos] < d) break;
+        pos += w;
+    }
+    for (--j; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos + w <= last) {
+            const int32_t *lev = j == 0 ? adj : amin + (int64_t)(j - 1) * Lb;
+            if (lev[base + pos] >= d) pos += w;
+        }
+    }
+    return pos;
+}
+
+// sc_first_ge over [0, k] given sp[k] >= v, and sc_last_le over [k, last] given sp[k] <= v, galloping from k
+__device__ __forceinline__ int64_t sc_gallop_first_ge(const int32_t *__restrict__ sp, int64_t k, int32_t v) {
+    int64_t w = 1;
+    while (k - w >= 0 && sp[k - w] >= v) {
+        k -= w;
+        w <<= 1;
+    }
+    return sc_first_ge(sp, std::max<int64_t>(k - w + 1, 0), k, v);
+}
+
+__device__ __forceinline__ int64_t sc_gallop_last_le(const int32_t *__restrict__ sp, int64_t k, int64_t last,
+                                                     int32_t v) {
+    int64_t w = 1;
+    while (k + w <= last && sp[k + w] <= v) {
+        k += w;
+        w <<= 1;
+    }
+    return sc_last_le(sp, k, std::min<int64_t>(k + w - 1, last), v);
+}
+
+// min of adj over the batch-relative range [l, r] (r >= l)
+__device__ __forceinline__ int32_t sc_conf_adj_min(const sc_conf_args &a, int64_t l, int64_t r) {
+    const int j = sc_log2(r - l + 1);
+    const int32_t *lev = j == 0 ? a.adj : a.amin + (int64_t)(j - 1) * a.Lb;
+    return min(lev[l], lev[r - ((int64_t)1 << j) + 1]);
+}
+
+// level 0 of ip's min-max table: im[T position] = (k, k) for the tree's S' index k
+__global__ void k_conf_ip(const int64_t *__restrict__ off, int nb, const int2 *__restrict__ mm0,
+                          int2 *__restrict__ im0) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = off[0] + q;
+    if (p >= off[nb]) return;
+    const int64_t base = off[sc_tree_of(off, nb, p)] - off[0];
+    const int32_t k = (int32_t)(q - base);
+    im0[base + mm0[q].x] = make_int2(k, k);
+}
+
+__global__ void k_conf_level(const int2 *__restrict__ prev, int2 *__restrict__ cur, int64_t n, int64_t half) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int2 m = prev[i];
+    if (i + half < n) {
+        const int2 m2 = prev[i + half];
+        cur[i] = make_int2(min(m.x, m2.x), max(m.y, m2.y));
+    } else {
+        cur[i] = m;
+    }
+}
+
+// one thread per gap k of a tree: as T's gap it marks the paths of S' nodes it flags, as S''s gap those of T's nodes
+__global__ void __launch_bounds__(SC_THREADS) k_conf_marks(sc_conf_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    if (p >= a.off[a.nb]) return;
+    const int t = sc_tree_of(a.off, a.nb, p);
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    if (k + 1 >= n) return;
+    const int32_t *sp = a.sp + base;
+    {
+        // T's gap k: K = the T positions [klo, khi] of lca_T(k, k + 1); x, x' = their S' indices
+        const int32_t d = a.adj[q];
+        const int32_t klo = (int32_t)sc_gallop_left(a.adj, a.amin, a.Lb, a.levels, base, k, d);
+        const int32_t khi = (int32_t)sc_gallop_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+        if (klo > 0 || khi < n - 1) {  // (K = L leaves nothing outside)
+            const int32_t i0 = a.im[q].x, i1 = a.im[q + 1].x;
+            const int64_t lo = min(i0, i1), hi = max(i0, i1);
+            const uint64_t pa = sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[lo], (int64_t)sp[hi] - 1);
+            const int32_t da = (int32_t)(pa >> 32);
+            int64_t ga = -1;
+            for (int s = 0; s < 2; ++s) {
+                const int64_t x = s ? hi : lo;
+                const int64_t l = sc_outside_left(a.mm, a.Lb, a.levels, base, x, klo, khi);
+                const int64_t r = sc_outside_right(a.mm, a.Lb, a.levels, base, x, n, klo, khi);
+                const uint64_t pl = l >= 0 ? sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[l], (int64_t)sp[x] - 1) : 0;
+                const uint64_t pr = r < n ? sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[x], (int64_t)sp[r] - 1) : 0;
+                const int32_t dl = l >= 0 ? (int32_t)(pl >> 32) : -1, dr = r < n ? (int32_t)(pr >> 32) : -1;
+                if (max(dl, dr) <= da) continue;  // (z* is A or above it: no path)
+                const int64_t gz = dl >= dr ? sc_last_le(sp, l, x - 1, (int32_t)(uint32_t)pl)
+                                            : sc_last_le(sp, x, r - 1, (int32_t)(uint32_t)pr);
+                if (ga < 0) ga = sc_last_le(sp, lo, hi - 1, (int32_t)(uint32_t)pa);
+                atomicAdd(a.mark_s + base + gz, 1);
+                atomicAdd(a.mark_s + base + ga, -1);
+            }
+        }
+    }
+    {
+        // S''s gap k: K' = the S' indices [klo, khi] of its node U[k]; x, x' = the T positions of S' leaves k, k + 1
+        const int32_t u = a.node[q];
+        const int32_t klo = (int32_t)sc_gallop_first_ge(sp, k, a.s_lo[u]);
+        const int32_t khi = (int32_t)sc_gallop_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+        if (klo > 0 || khi < n - 1) {
+            const int32_t i0 = a.mm[q].x, i1 = a.mm[q + 1].x;
+            const int64_t lo = min(i0, i1), hi = max(i0, i1);
+            const int32_t da = sc_conf_adj_min(a, base + lo, base + hi - 1);
+            int64_t ga = -1;
+            for (int s = 0; s < 2; ++s) {
+                const int64_t x = s ? hi : lo;
+                const int64_t l = sc_outside_left(a.im, a.Lb, a.levels, base, x, klo, khi);
+                const int64_t r = sc_outside_right(a.im, a.Lb, a.levels, base, x, n, klo, khi);
+                const int32_t dl = l >= 0 ? sc_conf_adj_min(a, base + l, base + x - 1) : -1;
+                const int32_t dr = r < n ? sc_conf_adj_min(a, base + x, base + r - 1) : -1;
+                if (max(dl, dr) <= da) continue;
+                // a gap of the LCA: the first gap of the range no deeper than its minimum
+                const int64_t gz = dl >= dr ? sc_gallop_right(a.adj, a.amin, a.Lb, a.levels, base, l, x - 1, dl + 1)
+                                            : sc_gallop_right(a.adj, a.amin, a.Lb, a.levels, base, x, r - 1, dr + 1);
+                if (ga < 0) ga = sc_gallop_right(a.adj, a.amin, a.Lb, a.levels, base, lo, hi - 1, da + 1);
+                atomicAdd(a.mark_t + base + gz, 1);
+                atomicAdd(a.mark_t + base + ga, -1);
+            }
+        }
+    }
+}
+
+// inclusive prefix sums of both mark rows over every tree's own entries, one workgroup per tree
+__global__ void __launch_bounds__(SC_THREADS) k_conf_scan(const int64_t *__restrict__ off, int32_t *__restrict__ m0,
+                                                          int32_t *__restrict__ m1) {
+    __shared__ int ws[2][SC_THREADS / 64];
+    const int t = blockIdx.x;
+    const int64_t base = off[t] - off[0], n = off[t + 1] - off[t];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int run0 = 0, run1 = 0;
+    for (int64_t c = 0; c < n; c += SC_THREADS) {
+        const int64_t i = c + threadIdx.x;
+        int x0 = i < n ? m0[base + i] : 0, x1 = i < n ? m1[base + i] : 0;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int y0 = __shfl_up(x0, d, 64), y1 = __shfl_up(x1, d, 64);
+            if (lane >= d) {
+                x0 += y0;
+                x1 += y1;
+            }
+        }
+        if (lane == 63) {
+            ws[0][wave] = x0;
+            ws[1][wave] = x1;
+        }
+        __syncthreads();
+        int b0 = run0, b1 = run1;
+        for (int w = 0; w < SC_THREADS / 64; ++w) {
+            if (w < wave) {
+                b0 += ws[0][w];
+                b1 += ws[1][w];
+            }
+            run0 += ws[0][w];
+            run1 += ws[1][w];
+        }
+        if (i < n) {
+            m0[base + i] = b0 + x0;
+            m1[base + i] = b1 + x1;
+        }
+        __syncthreads();
+    }
+}
+
+// marks on the gaps [lo, hi) of the tree at base, from the inclusive prefix sums
+__device__ __forceinline__ int32_t sc_conf_sum(const int32_t *__restrict__ pre, int64_t base, int64_t lo, int64_t hi) {
+    return pre[base + hi - 1] - (lo > 0 ? pre[base + lo - 1] : 0);
+}
+
+// one thread per gap: the non-root nodes of both trees at their first gaps read their sums
+__global__ void __launch_bounds__(SC_THREADS) k_conf_nodes(sc_conf_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    bool t_hit = false, s_hit = false;
+    if (in && k + 1 < n) {
+        // T: the first gap of its node, the node's leaves [lo, hi]
+        const int32_t d = a.adj[q];
+        const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+        if (lo == 0 || a.adj[base + lo - 1] < d) {
+            const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+            if (lo > 0 || hi < n - 1) t_hit = sc_conf_sum(a.mark_t, base, lo, hi) > 0;
+        }
+        // S': the restricted node u = U[k], first gap and parent as in k_score_nodes
+        const int32_t u = a.node[q], du = a.dep[q];
+        const int32_t *sp = a.sp + base;
+        const int64_t lo_s = sc_first_ge(sp, 0, k, a.s_lo[u]);
+        const int64_t hi_s = sc_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+        const bool first = lo_s == k ||
+                           (int32_t)(sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[lo_s], (int64_t)sp[k] - 1) >> 32) > du;
+        if (first && (lo_s > 0 || hi_s < n - 1) && sc_conf_sum(a.mark_s, base, lo_s, hi_s) > 0) {
+            s_hit = true;
+            const int64_t g = lo_s == 0 ? hi_s
+                              : hi_s == n - 1 ? lo_s - 1
+                              : (a.dep[base + lo_s - 1] >= a.dep[base + hi_s] ? lo_s - 1 : hi_s);
+            atomicAdd(a.mark_node + u, 1);
+            atomicAdd(a.mark_node + a.node[base + g], -1);
+        }
+    }
+    sc_count(a.c_source, t, t_hit);
+    sc_count(a.c_super, t, s_hit);
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -949,6 +1271,96 @@ extern "C" int scs_score_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n
         if (t_super) t_super[t] = (int64_t)cnt[t];
         if (t_source) t_source[t] = (int64_t)cnt[M + t];
         if (t_shared) t_shared[t] = (int64_t)cnt[2 * M + t];
+    }
+    return SCS_OK;
+}
+
+extern "C" int scs_score_conflicts(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super_conflict,
+                                   int64_t *n_source_conflict, int64_t *conflicting) {
+    // own arrays: marks (two rows: k_score_prefix sums two; the second stays 0), prefix sums and outputs per S node,
+    // two counters per tree; per batch leaf ip's min-max table (the levels sc_begin gives the batch) and two mark rows
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
+    const int levels = sc_levels_host(std::max<int64_t>(src ? src->max_leaves : 1, 1));
+    const size_t o_mark = 0, o_pref = o_mark + sc_up256(nn * 8), o_out = o_pref + sc_up256((nn + 1) * 16),
+                 o_cnt = o_out + sc_up256(nn * 16), own = o_cnt + sc_up256(mt * 16);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_conflicts", n_nodes, parent, taxon, max_batch_trees, own,
+                     8 * (uint64_t)levels + 8, 0, c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_mark = (int32_t *)(c.d_extra + o_mark);
+    auto *d_pref = (int64_t *)(c.d_extra + o_pref);
+    auto *d_out = (int64_t *)(c.d_extra + o_out);
+    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
+    auto *d_im = (int2 *)c.d_extra_batch;
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, nn * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 16, s);
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const int64_t *d_off = src->d_tree_off + t0;
+        int32_t *d_ms = (int32_t *)(d_im + (int64_t)c.levels * Lb), *d_mt = d_ms + Lb;
+        e = hipMemsetAsync(d_ms, 0, (size_t)Lb * 8, s);
+        if (e != hipSuccess) break;
+        k_conf_ip<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, c.d_mm, d_im);
+        if (!sc_launched(e)) break;
+        for (int j = 1; j < c.levels && e == hipSuccess; ++j) {
+            k_conf_level<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_im + (j - 1) * Lb, d_im + j * Lb, Lb,
+                                                            (int64_t)1 << (j - 1));
+            sc_launched(e);
+        }
+        if (e != hipSuccess) break;
+        sc_conf_args a;
+        a.off = d_off;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.dep = c.d_dep;
+        a.node = c.d_node;
+        a.mm = c.d_mm;
+        a.im = d_im;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_tab = c.d_stab;
+        a.s_stride = c.n_gaps;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.mark_s = d_ms;
+        a.mark_t = d_mt;
+        a.mark_node = d_mark;
+        a.c_super = d_cnt + t0;
+        a.c_source = d_cnt + M + t0;
+        k_conf_marks<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        k_conf_scan<<<nb, SC_THREADS, 0, s>>>(d_off, d_ms, d_mt);
+        if (!sc_launched(e)) break;
+        k_conf_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+    }
+    if (e == hipSuccess && !bad) {
+        k_score_prefix<<<1, 1024, 0, s>>>(d_mark, d_mark + n_nodes, n_nodes, d_pref, d_pref + n_nodes + 1);
+        sc_launched(e);
+    }
+    if (e == hipSuccess && !bad) {
+        k_score_subtree<<<grid_of(n_nodes), SC_THREADS, 0, s>>>(d_pref, d_pref + n_nodes + 1, c.d_end, n_nodes, d_out,
+                                                                d_out + n_nodes);
+        sc_launched(e);
+    }
+    std::vector<unsigned long long> cnt((size_t)M * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && conflicting)
+        e = hipMemcpyAsync(conflicting, d_out, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    for (int32_t t = 0; t < M; ++t) {
+        if (n_super_conflict) n_super_conflict[t] = (int64_t)cnt[t];
+        if (n_source_conflict) n_source_conflict[t] = (int64_t)cnt[M + t];
     }
     return SCS_OK;
 }

@@ -1,6 +1,6 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
-supertree node, and on request rooted triplet terms per source tree (section 15).  Neither
-the reference nor ``construct_supertree`` computes them.
+supertree node, and on request rooted triplet terms per source tree (section 15) and clade
+conflict counts (section 16).  Neither the reference nor ``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
 2 <= size < |L|.  C(S|T) = the nontrivial sets C ∩ L(T) over the clades C of the supertree S; C(T) = T's own.
@@ -24,8 +24,18 @@ to L): ``t_shared`` = Σ_y Σ_z C(I(y,z), 2) (I(py,pz) - I(y,pz) - I(py,z) + I(y
 Σ_y C(|y|, 2) (|py| - |y|), ``t_super`` likewise over S'.  A shared triple ab|c is counted once, at the children of
 the two LCAs of a, b, c that hold a and b; the second factor counts the c in (cl(py) ∖ cl(y)) ∩ (cl(pz) ∖ cl(z)).
 
-Every count comes from the HIP kernels behind ``scs_score_supertree`` and ``scs_score_triplets``; the host only
-validates and lays out.
+Clade conflicts (``conflicts=True``).  Two sets A and B *conflict* when A ∩ B ≠ ∅, A ⊄ B and B ⊄ A; a set conflicts
+with a tree when it conflicts with one of the tree's clusters.  A cluster the tree displays never conflicts with it,
+and a fully resolved tree conflicts with every set it does not display.  With L = L(T) and S' = S|L:
+
+* per source tree: ``n_super_conflict`` = the clusters of C(S|T) that conflict with T, ``n_source_conflict`` = the
+  clusters of C(T) that conflict with S' (zeros for trees of fewer than 3 leaves);
+* per node C of S: ``conflicting`` = the trees for which C ∩ L(T) is nontrivial and conflicts with T.  So
+  ``supported + conflicting <= informative``, and ``informative - supported - conflicting`` counts the sources that
+  are compatible with C but do not resolve it (a polytomy there, say): no evidence against C.
+
+Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets`` and
+``scs_score_conflicts``; the host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -56,12 +66,16 @@ class SupertreeScore:
     supported: np.ndarray
     # wall seconds: "prepare" (host: supertree arrays, checks, flattening objects), "tables" (a TreeArrays forest
     # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
-    # "triplets" (scs_score_triplets, when requested)
+    # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
     t_source: np.ndarray | None = None
     t_shared: np.ndarray | None = None
+    # clade conflicts (``conflicts=True``; None otherwise): per source tree, and per supertree node (preorder)
+    n_super_conflict: np.ndarray | None = None
+    n_source_conflict: np.ndarray | None = None
+    conflicting: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -115,18 +129,41 @@ class SupertreeScore:
             node.name = None if np.isnan(v) else repr(float(v))
         return out
 
+    def annotate_counts(self) -> TreeNode:
+        """A copy of the supertree whose internal non-root nodes are named ``supported/conflicting/informative``
+        (no name where no source is informative), so that ``get_newick(with_node_names=True)`` writes the counts.
+        ``ValueError`` unless the conflicts were computed."""
+        if self.conflicting is None:
+            msg = "conflict counts were not computed: score_supertree(..., conflicts=True)"
+            raise ValueError(msg)
+        out = self.supertree.copy()
+        for i, node in enumerate(_preorder(out)):
+            if node.is_tip() or i == 0:
+                continue
+            inf = int(self.informative[i])
+            node.name = f"{int(self.supported[i])}/{int(self.conflicting[i])}/{inf}" if inf > 0 else None
+        return out
+
     def table(self) -> str:
-        """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, and when the triplet terms
-        were computed t_super, t_source, t_shared, triplet_distance."""
+        """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, then t_super, t_source,
+        t_shared, triplet_distance when the triplet terms were computed and n_super_conflict, n_source_conflict
+        when the conflicts were."""
         trip = self.t_shared is not None
+        conf = self.n_super_conflict is not None
         head = "index\tn_leaves\tn_super\tn_source\tshared\trf"
-        rows = [head + "\tt_super\tt_source\tt_shared\ttriplet_distance" if trip else head]
+        if trip:
+            head += "\tt_super\tt_source\tt_shared\ttriplet_distance"
+        if conf:
+            head += "\tn_super_conflict\tn_source_conflict"
+        rows = [head]
         rf = self.rf
         td = self.triplet_distance if trip else None
         for t in range(len(rf)):
             row = f"{t}\t{self.n_leaves[t]}\t{self.n_super[t]}\t{self.n_source[t]}\t{self.shared[t]}\t{rf[t]}"
             if trip:
                 row += f"\t{self.t_super[t]}\t{self.t_source[t]}\t{self.t_shared[t]}\t{td[t]}"
+            if conf:
+                row += f"\t{self.n_super_conflict[t]}\t{self.n_source_conflict[t]}"
             rows.append(row)
         return "\n".join(rows) + "\n"
 
@@ -165,10 +202,12 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
     return parent, taxon, tips
 
 
-def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, device=None) -> SupertreeScore:
+def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
+                    device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
-    ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``), counted on the same
-    device tables as the RF terms.
+    ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
+    ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``),
+    both counted on the same device tables as the RF terms.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -193,9 +232,9 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, devic
                 raise ValueError(msg)
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
-        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets)
+        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
-                                  - out.timings.get("triplets", 0.0))
+                                  - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -214,18 +253,28 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, devic
     t2 = time.perf_counter()
     try:
         res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-        t3 = t4 = time.perf_counter()
+        t3 = t4 = t5 = time.perf_counter()
         if triplets:
             res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t4 = time.perf_counter()
+            t4 = t5 = time.perf_counter()
+        if conflicts:
+            res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+            t5 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
     if triplets:
         timings["triplets"] = t4 - t3
-    return SupertreeScore(supertree, np.diff(tables.tree_off), res["n_super"], res["n_source"], res["shared"],
+    if conflicts:
+        timings["conflicts"] = t5 - t4
+    return _result(supertree, np.diff(tables.tree_off), res, timings)
+
+
+def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
+    return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
                           res["informative"], res["supported"], timings,
-                          res.get("t_super"), res.get("t_source"), res.get("t_shared"))
+                          res.get("t_super"), res.get("t_source"), res.get("t_shared"),
+                          res.get("n_super_conflict"), res.get("n_source_conflict"), res.get("conflicting"))
 
 
 def _default_device():
@@ -234,7 +283,8 @@ def _default_device():
     return default_device()
 
 
-def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets) -> SupertreeScore:
+def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
+                  conflicts) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -247,8 +297,10 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     n_leaves = arrays.leaf_counts().astype(np.int64)
     n_nodes = len(parent)
     per_tree = ("n_super", "n_source", "shared") + (("t_super", "t_source", "t_shared") if triplets else ())
+    per_tree += ("n_super_conflict", "n_source_conflict") if conflicts else ()
+    per_node = ("informative", "supported") + (("conflicting",) if conflicts else ())
     zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
-    node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in ("informative", "supported")}
+    node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in per_node}
     # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
     universe = max(arrays.n_taxa, n_taxa, 1)
     new_id = np.concatenate([new_id, np.full(universe - len(new_id), -1, dtype=np.int32)])
@@ -263,7 +315,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = time.perf_counter()
+        t1 = t2 = t3 = t4 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
         else:
@@ -273,10 +325,13 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
             t1 = time.perf_counter()
             try:
                 res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-                t2 = t3 = time.perf_counter()
+                t2 = t3 = t4 = time.perf_counter()
                 if triplets:
                     res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t3 = time.perf_counter()
+                    t3 = t4 = time.perf_counter()
+                if conflicts:
+                    res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+                    t4 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -289,6 +344,6 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     timings = {"tables": t1 - t0, "score": t2 - t1}
     if triplets:
         timings["triplets"] = t3 - t2
-    return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
-                          res["informative"], res["supported"], timings,
-                          res.get("t_super"), res.get("t_source"), res.get("t_shared"))
+    if conflicts:
+        timings["conflicts"] = t4 - t3
+    return _result(supertree, n_leaves, res, timings)

@@ -4,6 +4,8 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py                      # the three sizes below
     python tools/score_bench.py --size 10000x500     # one size; NxM or NxMxK (K leaves per tree)
     python tools/score_bench.py --triplets           # also the rooted triplet terms
+    python tools/score_bench.py --conflicts          # also the clade conflict counts
+    python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
 """
 
 from __future__ import annotations
@@ -21,6 +23,7 @@ import numpy as np  # noqa: E402
 from spectralclustersupertree_amd import score_supertree, synthetic  # noqa: E402
 from spectralclustersupertree_amd.backend import Device  # noqa: E402
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
+from spectralclustersupertree_amd.treearrays import TreeArrays  # noqa: E402
 
 SIZES = ("10000x500", "100000x5000", "20000x2000x500")
 
@@ -39,22 +42,50 @@ def random_binary_tree(seed: int, n_taxa: int) -> TreeNode:
     return parts[0]
 
 
-def run(dev: Device, size: str, repeats: int, triplets: bool = False) -> dict:
+def caterpillar(order) -> TreeNode:
+    """(((x0, x1), x2), ...) over the taxon ids ``order``, O(n)."""
+    node = TreeNode(synthetic.taxon_name(int(order[0])))
+    for x in order[1:]:
+        node = TreeNode(None, [node, TreeNode(synthetic.taxon_name(int(x)))])
+    return node
+
+
+def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeArrays:
+    """``n_trees`` caterpillars on the first ``per_tree`` taxa (all by default) in reverse taxon order, as preorder
+    node arrays: the inner nodes root first, then the leaves (the first two hang from the deepest inner node)."""
+    k = n_taxa if per_tree is None else per_tree
+    order = np.arange(k - 1, -1, -1, dtype=np.int32)
+    parent = np.concatenate([np.arange(-1, k - 2, dtype=np.int32), [k - 2, k - 2],
+                             np.arange(k - 3, -1, -1, dtype=np.int32)])
+    taxon = np.concatenate([np.full(k - 1, -1, dtype=np.int32), order])
+    nn = 2 * k - 1
+    return TreeArrays(n_taxa=n_taxa, node_off=np.arange(n_trees + 1, dtype=np.int64) * nn,
+                      parent=np.tile(parent, n_trees), taxon=np.tile(taxon, n_trees),
+                      length=np.full(n_trees * nn, np.nan), support=np.full(n_trees * nn, np.nan),
+                      weights=np.ones(n_trees), taxa=[synthetic.taxon_name(i) for i in range(n_taxa)])
+
+
+def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
+        cat: bool = False) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
     t0 = time.perf_counter()
-    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
-    sup = random_binary_tree(2, n_taxa)
+    if cat:
+        arrays = caterpillar_arrays(n_taxa, n_trees, per_tree)
+        sup = caterpillar(np.arange(n_taxa))
+    else:
+        arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+        sup = random_binary_tree(2, n_taxa)
     gen_s = time.perf_counter() - t0
     runs = []
     for _ in range(repeats):
         t0 = time.perf_counter()
-        res = score_supertree(sup, arrays, triplets=triplets, device=dev)
+        res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, device=dev)
         runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
-        "size": size, "n_taxa": n_taxa, "n_trees": n_trees, "leaves": int(arrays.leaf_counts().sum()),
+        "size": size, "input": "caterpillar" if cat else "random", "n_taxa": n_taxa, "n_trees": n_trees, "leaves": int(arrays.leaf_counts().sum()),
         "supertree_nodes": len(res.informative), "repeats": repeats, "input_generation_s": round(gen_s, 3),
         "wall_s": round(wall, 4), "host_prepare_s": round(tim["prepare"], 4),
         "device_tables_s": round(tim["tables"], 4), "score_call_s": round(tim["score"], 4),
@@ -63,6 +94,14 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False) -> dict:
     if triplets:
         out.update({"triplets_call_s": round(tim["triplets"], 4), "total_triplet_distance": res.total_triplet_distance,
                     "triplet_fit": res.triplet_fit})
+    if conflicts:
+        leaves = int(arrays.leaf_counts().sum())
+        out.update({"conflicts_call_s": round(tim["conflicts"], 4),
+                    "conflicts_ns_per_leaf": round(tim["conflicts"] / max(leaves, 1) * 1e9, 3),
+                    "total_n_super_conflict": int(res.n_super_conflict.sum()),
+                    "total_n_source_conflict": int(res.n_source_conflict.sum()),
+                    "total_conflicting": int(res.conflicting.sum()), "total_supported": int(res.supported.sum()),
+                    "total_informative": int(res.informative.sum())})
     return out
 
 
@@ -71,13 +110,16 @@ def main() -> None:
     ap.add_argument("--size", action="append", help="NxM or NxMxK; repeatable (default: the three sizes)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--triplets", action="store_true", help="also count the rooted triplet terms")
+    ap.add_argument("--conflicts", action="store_true", help="also count the clade conflicts")
+    ap.add_argument("--caterpillar", action="store_true",
+                    help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
-                        device=dev)  # warm-up
+                        conflicts=args.conflicts, device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
-            print(json.dumps(run(dev, size, reps, args.triplets)), flush=True)
+            print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar)), flush=True)
 
 
 if __name__ == "__main__":
