@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 108.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -350,6 +350,25 @@ int scs_score_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes,
 int scs_score_conflicts(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
                         const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super_conflict,
                         int64_t *n_source_conflict, int64_t *conflicting);
+
+/* Branch concordance, same inputs and SCS_EINVAL cases as scs_score_supertree.  A node C of S
+ * is a quartet branch when it is not the root, has exactly two children A (the first in preorder) and B, and its
+ * parent has exactly two children, C and its sibling D.  A source tree T on the leaf set L is decisive for C when
+ * A ∩ L, B ∩ L and D ∩ L are all non-empty; a decisive T is concordant when (A ∪ B) ∩ L is a cluster of T, alt1 when
+ * (A ∪ D) ∩ L is, alt2 when (B ∪ D) ∩ L is (at most one of the three holds) and `other` when none is.
+ * Per source tree:
+ *   n_decisive[t]    = the quartet branches t is decisive for,
+ *   n_concordant[t]  = those it is concordant with,
+ *   n_alternative[t] = those where it displays alt1 or alt2.
+ * Per node C of S (n_nodes entries, S's preorder; zeros where C is not a quartet branch):
+ *   decisive[C], concordant[C], alt1[C], alt2[C] = the sources of each kind
+ *   (decisive <= informative, concordant <= supported, alt1 + alt2 <= conflicting,
+ *   other = decisive - concordant - alt1 - alt2 >= 0).
+ * Trees of fewer than 3 leaves give zeros; counts are unweighted.  Output pointers may be null. */
+int scs_score_concordance(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                          const int32_t *taxon, int32_t max_batch_trees, int64_t *n_decisive, int64_t *n_concordant,
+                          int64_t *n_alternative, int64_t *decisive, int64_t *concordant, int64_t *alt1,
+                          int64_t *alt2);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

@@ -45,10 +45,12 @@ def sc_supertree(
 
 
 @_define_app
-def score_supertree(supertree, trees, *, triplets: bool = False, conflicts: bool = False):
+def score_supertree(supertree, trees, *, triplets: bool = False, conflicts: bool = False,
+                    concordance: bool = False):
     """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, with
-    ``triplets=True`` the rooted triplet terms and with ``conflicts=True`` the clade conflict counts."""
-    return _score(supertree, trees, triplets=triplets, conflicts=conflicts)
+    ``triplets=True`` the rooted triplet terms, with ``conflicts=True`` the clade conflict counts and with
+    ``concordance=True`` the branch concordance counts."""
+    return _score(supertree, trees, triplets=triplets, conflicts=conflicts, concordance=concordance)
 
 
 @_define_app

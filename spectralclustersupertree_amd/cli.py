@@ -42,15 +42,27 @@ from spectralclustersupertree_amd import __version__
 @click.option("--conflict-out", default=None,
               help="Also write the supertree with each clade's supported/conflicting/informative source counts as "
                    "its node name (Newick).")
+@click.option("--concordance", default=False, is_flag=True,
+              help="Add the branch concordance counts to --scores-out (n_decisive, n_concordant, n_alternative).")
+@click.option("--concordance-out", default=None,
+              help="Also write the supertree with each quartet branch's concordant/alt1/alt2/decisive source counts "
+                   "as its node name (Newick).")
+@click.option("--branches-out", default=None,
+              help="Also write a TSV with one row per quartet branch (node, clade_size, informative, supported, "
+                   "decisive, concordant, alt1, alt2, other).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
-        conflicts: bool = False, conflict_out: str | None = None) -> None:
+        conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
+        concordance_out: str | None = None, branches_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
         raise click.UsageError(msg)
     if conflicts and not scores_out:
         msg = "--conflicts needs --scores-out"
+        raise click.UsageError(msg)
+    if concordance and not scores_out:
+        msg = "--concordance needs --scores-out"
         raise click.UsageError(msg)
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
@@ -65,17 +77,33 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     team = default_team()
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
-        if scores_out or support_out or conflict_out:
+        if scores_out or support_out or conflict_out or concordance_out or branches_out:
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
-                                     conflicts=conflicts or conflict_out is not None)
+                                     conflicts=conflicts or conflict_out is not None,
+                                     concordance=concordance or concordance_out is not None
+                                     or branches_out is not None)
             if scores_out:
-                Path(scores_out).write_text(result.table() if conflicts else _without_conflicts(result).table())
+                shown = result if conflicts else _without_conflicts(result)
+                Path(scores_out).write_text((shown if concordance else _without_concordance(shown)).table())
             if support_out:
                 Path(support_out).write_text(result.annotate().get_newick(with_node_names=True) + "\n")
             if conflict_out:
                 Path(conflict_out).write_text(result.annotate_counts().get_newick(with_node_names=True) + "\n")
+            if concordance_out:
+                Path(concordance_out).write_text(
+                    result.annotate_concordance().get_newick(with_node_names=True) + "\n")
+            if branches_out:
+                Path(branches_out).write_text(result.branch_table())
+
+
+def _without_concordance(result):
+    """``result`` whose table leaves the concordance columns out (--concordance-out or --branches-out without
+    --concordance)."""
+    import dataclasses
+
+    return dataclasses.replace(result, n_decisive=None, n_concordant=None, n_alternative=None)
 
 
 def _without_conflicts(result):

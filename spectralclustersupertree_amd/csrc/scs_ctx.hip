@@ -40,7 +40,8 @@ extern "C" const char *scs_last_error(void) { return g_last_error.c_str(); }
 // 103: ... and by event_pair_ms
 // 107: scs_score_triplets added
 // 108: scs_score_conflicts added
-extern "C" int scs_version(void) { return 108; }
+// 109: scs_score_concordance added
+extern "C" int scs_version(void) { return 109; }
 
 extern "C" int scs_device_count(void) {
     int n = 0;

@@ -879,6 +879,99 @@ __global__ void __launch_bounds__(SC_THREADS) k_conf_nodes(sc_conf_args a) {
     sc_count(a.c_super, t, s_hit);
 }
 
+// ---- branch concordance (scs_score_concordance) ----
+//
+// A node C of S is a quartet branch when it is not the root, has exactly two children A (first in preorder) and B, and
+// its parent has exactly two children, C and its sibling D.  A source tree T on L is decisive for C when A ∩ L, B ∩ L
+// and D ∩ L are all non-empty; it is then concordant when (A ∪ B) ∩ L is a cluster of T, alt1 when (A ∪ D) ∩ L is,
+// alt2 when (B ∪ D) ∩ L is (the three conflict pairwise: at most one holds), and `other` when none is.
+// With A ∩ L and B ∩ L non-empty, C is the S node of LCA_S(C ∩ L): U[k] at the gap k between the last leaf of A ∩ L and
+// the first of B ∩ L in S order, and as C has two children no other gap of the tree has U = C.  So one thread per gap
+// finds every decisive (C, T) once: [lo, hi] = C ∩ L by two searches in sp, A ∩ L = [lo, k], B ∩ L = [k + 1, hi], and
+// D ∩ L is the stretch of sp inside the parent's leaf range on the other side of [lo, hi].  A union of two of the
+// three ranges is a cluster of T iff the T positions of its leaves (min / max over each range from tp's table) span
+// exactly its size and the LCA of that span has no further leaf (step 4 of section 14).  Every result belongs to C
+// alone: the counts go straight onto per-node counters, no path marks and no prefix pass.
+
+struct sc_conc_args {
+    const int64_t *off;          // tree_off + t0
+    int nb;
+    const int32_t *sp, *node;    // [Lb] S positions in S order, U of S'
+    const int2 *mm;              // min-max table of tp: level j at mm[j * Lb]
+    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
+    int64_t Lb;
+    const int32_t *s_lo, *s_hi;  // leaf range of every S node
+    const int32_t *q_parent;     // [S nodes] the parent of a quartet branch, -1 for every other node
+    unsigned long long *n_dec, *n_con, *n_alt1, *n_alt2;  // [S nodes]
+    unsigned long long *c_dec, *c_con, *c_alt;            // [nb] of the batch
+};
+
+// are the `size` (>= 2) leaves of the tree at base (n leaves) whose T positions span [ab.x, ab.y] a cluster of T
+__device__ __forceinline__ bool sc_conc_cluster(const sc_conc_args &a, int64_t base, int64_t n, int2 ab,
+                                                int64_t size) {
+    if (ab.y - ab.x + 1 != size) return false;
+    const int64_t l = base + ab.x, r = base + ab.y - 1;
+    const int j = sc_log2(r - l + 1);
+    const int32_t *lev = j == 0 ? a.adj : a.amin + (int64_t)(j - 1) * a.Lb;
+    const int32_t dT = min(lev[l], lev[r - ((int64_t)1 << j) + 1]);
+    return (ab.x == 0 || a.adj[l - 1] < dT) && (ab.y == n - 1 || a.adj[r + 1] < dT);
+}
+
+__device__ __forceinline__ int2 sc_join(int2 x, int2 y) { return make_int2(min(x.x, y.x), max(x.y, y.y)); }
+
+// one thread per gap: the quartet branch u = U[k] the tree is decisive for, classified
+__global__ void __launch_bounds__(SC_THREADS) k_conc_branches(sc_conc_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    bool dec = false, con = false, alt = false;
+    if (in && k + 1 < n) {
+        const int32_t u = a.node[q];
+        const int32_t pu = a.q_parent[u];
+        if (pu >= 0) {
+            const int32_t *sp = a.sp + base;
+            const int32_t sl = a.s_lo[u], pl = a.s_lo[pu];
+            const int64_t lo = sc_gallop_first_ge(sp, k, sl);
+            const int64_t hi = sc_gallop_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+            // D ∩ L = [dlo, dhi]: after [lo, hi] when u is the parent's first child, before it otherwise
+            int64_t dlo = 0, dhi = -1;
+            if (pl == sl) {
+                const int32_t pr = a.s_hi[pu];
+                if (hi + 1 < n && sp[hi + 1] <= pr) {
+                    dlo = hi + 1;
+                    dhi = sc_gallop_last_le(sp, hi + 1, n - 1, pr);
+                }
+            } else if (lo > 0 && sp[lo - 1] >= pl) {
+                dhi = lo - 1;
+                dlo = sc_gallop_first_ge(sp, lo - 1, pl);
+            }
+            if (dhi >= dlo) {
+                dec = true;
+                const int2 ma = sc_rmq_minmax(a.mm, a.Lb, base + lo, base + k);
+                const int2 mb = sc_rmq_minmax(a.mm, a.Lb, base + k + 1, base + hi);
+                const int2 md = sc_rmq_minmax(a.mm, a.Lb, base + dlo, base + dhi);
+                const int64_t za = k - lo + 1, zb = hi - k, zd = dhi - dlo + 1;
+                con = sc_conc_cluster(a, base, n, sc_join(ma, mb), za + zb);
+                bool alt1 = false, alt2 = false;
+                if (!con) alt1 = sc_conc_cluster(a, base, n, sc_join(ma, md), za + zd);
+                if (!con && !alt1) alt2 = sc_conc_cluster(a, base, n, sc_join(mb, md), zb + zd);
+                alt = alt1 || alt2;
+                atomicAdd(a.n_dec + u, 1ull);
+                if (con) atomicAdd(a.n_con + u, 1ull);
+                if (alt1) atomicAdd(a.n_alt1 + u, 1ull);
+                if (alt2) atomicAdd(a.n_alt2 + u, 1ull);
+            }
+        }
+    }
+    sc_count(a.c_dec, t, dec);
+    sc_count(a.c_con, t, con);
+    sc_count(a.c_alt, t, alt);
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -1361,6 +1454,72 @@ extern "C" int scs_score_conflicts(scs_ctx *ctx, const scs_tables *src, int32_t 
     for (int32_t t = 0; t < M; ++t) {
         if (n_super_conflict) n_super_conflict[t] = (int64_t)cnt[t];
         if (n_source_conflict) n_source_conflict[t] = (int64_t)cnt[M + t];
+    }
+    return SCS_OK;
+}
+
+extern "C" int scs_score_concordance(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                     const int32_t *taxon, int32_t max_batch_trees, int64_t *n_decisive,
+                                     int64_t *n_concordant, int64_t *n_alternative, int64_t *decisive,
+                                     int64_t *concordant, int64_t *alt1, int64_t *alt2) {
+    // own arrays: four counters and the quartet-branch record per S node, three counters per tree; nothing per leaf
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
+    const size_t o_node = 0, o_qp = o_node + sc_up256(nn * 32), o_cnt = o_qp + sc_up256(nn * 4),
+                 own = o_cnt + sc_up256(mt * 24);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_concordance", n_nodes, parent, taxon, max_batch_trees, own, 0, 0, c, e));
+    const int32_t M = c.M;
+    hipStream_t s = ctx->stream;
+    auto *d_node = (unsigned long long *)(c.d_extra + o_node);
+    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
+    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
+    // quartet branches: two children, below a parent of two children (sc_begin has checked `parent`)
+    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
+    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
+    for (int32_t v = 1; v < n_nodes; ++v)
+        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_node, 0, nn * 32, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
+        sc_conc_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.node = c.d_node;
+        a.mm = c.d_mm;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.Lb = Lb;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.q_parent = d_qp;
+        a.n_dec = d_node;
+        a.n_con = d_node + nn;
+        a.n_alt1 = d_node + 2 * nn;
+        a.n_alt2 = d_node + 3 * nn;
+        a.c_dec = d_cnt + t0;
+        a.c_con = d_cnt + M + t0;
+        a.c_alt = d_cnt + 2 * (int64_t)M + t0;
+        k_conc_branches<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+    }
+    std::vector<unsigned long long> cnt((size_t)M * 3);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
+    int64_t *const outs[4] = {decisive, concordant, alt1, alt2};
+    for (int i = 0; i < 4 && e == hipSuccess; ++i)
+        if (outs[i]) e = hipMemcpyAsync(outs[i], d_node + i * nn, nn * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    for (int32_t t = 0; t < M; ++t) {
+        if (n_decisive) n_decisive[t] = (int64_t)cnt[t];
+        if (n_concordant) n_concordant[t] = (int64_t)cnt[M + t];
+        if (n_alternative) n_alternative[t] = (int64_t)cnt[2 * M + t];
     }
     return SCS_OK;
 }

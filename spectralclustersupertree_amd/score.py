@@ -1,6 +1,7 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
-supertree node, and on request rooted triplet terms per source tree (section 15) and clade
-conflict counts (section 16).  Neither the reference nor ``construct_supertree`` computes them.
+supertree node, and on request rooted triplet terms per source tree (section 15), clade
+conflict counts (section 16) and branch concordance factors (section 17).  Neither the reference nor
+``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
 2 <= size < |L|.  C(S|T) = the nontrivial sets C ∩ L(T) over the clades C of the supertree S; C(T) = T's own.
@@ -34,8 +35,22 @@ and a fully resolved tree conflicts with every set it does not display.  With L 
   ``supported + conflicting <= informative``, and ``informative - supported - conflicting`` counts the sources that
   are compatible with C but do not resolve it (a polytomy there, say): no evidence against C.
 
-Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets`` and
-``scs_score_conflicts``; the host only validates and lays out.
+Branch concordance (``concordance=True``).  A node C of S is a *quartet branch* when it is not the root, has exactly
+two children A (the first in preorder) and B, and its parent has exactly two children, C and its sibling D: the branch
+above C then has three nearest-neighbour arrangements, AB|D (the supertree's), AD|B and BD|A.  A source tree T on L is
+*decisive* for C when A ∩ L, B ∩ L and D ∩ L are all non-empty; a decisive T is *concordant* when (A ∪ B) ∩ L is a
+cluster of T, *alt1* when (A ∪ D) ∩ L is, *alt2* when (B ∪ D) ∩ L is (the three sets conflict pairwise, so at most one
+holds) and *other* when none is.  These are the gene concordance and discordance factors of IQ-TREE (gCF, gDF1, gDF2,
+gDFP) with the source trees as the genes.
+
+* per node C of S: ``decisive``, ``concordant``, ``alt1``, ``alt2`` (zeros where C is not a quartet branch), so
+  ``decisive <= informative``, ``concordant <= supported``, ``alt1 + alt2 <= conflicting`` and
+  ``other = decisive - concordant - alt1 - alt2 >= 0``;
+* per source tree: ``n_decisive`` = the quartet branches it is decisive for, ``n_concordant`` = those it is concordant
+  with, ``n_alternative`` = those where it displays alt1 or alt2.
+
+Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
+``scs_score_conflicts`` and ``scs_score_concordance``; the host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -66,7 +81,8 @@ class SupertreeScore:
     supported: np.ndarray
     # wall seconds: "prepare" (host: supertree arrays, checks, flattening objects), "tables" (a TreeArrays forest
     # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
-    # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested)
+    # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
+    # "concordance" (scs_score_concordance, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -76,6 +92,14 @@ class SupertreeScore:
     n_super_conflict: np.ndarray | None = None
     n_source_conflict: np.ndarray | None = None
     conflicting: np.ndarray | None = None
+    # branch concordance (``concordance=True``; None otherwise): per source tree, and per supertree node (preorder)
+    n_decisive: np.ndarray | None = None
+    n_concordant: np.ndarray | None = None
+    n_alternative: np.ndarray | None = None
+    decisive: np.ndarray | None = None
+    concordant: np.ndarray | None = None
+    alt1: np.ndarray | None = None
+    alt2: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -144,17 +168,109 @@ class SupertreeScore:
             node.name = f"{int(self.supported[i])}/{int(self.conflicting[i])}/{inf}" if inf > 0 else None
         return out
 
+    @property
+    def quartet_branch(self) -> np.ndarray:
+        """Bool mask per node (preorder): not the root, exactly two children, and a parent with exactly two."""
+        return quartet_branches(np.asarray(self.supertree.to_flat()[0], dtype=np.int64))
+
+    def _need_concordance(self) -> None:
+        if self.decisive is None:
+            msg = "concordance counts were not computed: score_supertree(..., concordance=True)"
+            raise ValueError(msg)
+
+    @property
+    def other(self) -> np.ndarray:
+        """Per node: the decisive sources that display none of the three arrangements (IQ-TREE's gDFP count)."""
+        self._need_concordance()
+        return self.decisive - self.concordant - self.alt1 - self.alt2
+
+    def _percent(self, counts: np.ndarray) -> np.ndarray:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.decisive > 0, 100.0 * counts / np.maximum(self.decisive, 1), np.nan)
+
+    @property
+    def gcf(self) -> np.ndarray:
+        """``concordant`` in percent of ``decisive`` (NaN where no source is decisive)."""
+        self._need_concordance()
+        return self._percent(self.concordant)
+
+    @property
+    def gdf1(self) -> np.ndarray:
+        """``alt1`` in percent of ``decisive``."""
+        self._need_concordance()
+        return self._percent(self.alt1)
+
+    @property
+    def gdf2(self) -> np.ndarray:
+        """``alt2`` in percent of ``decisive``."""
+        self._need_concordance()
+        return self._percent(self.alt2)
+
+    @property
+    def gdfp(self) -> np.ndarray:
+        """``other`` in percent of ``decisive``."""
+        return self._percent(self.other)
+
+    def annotate_concordance(self) -> TreeNode:
+        """A copy of the supertree whose quartet branches are named ``concordant/alt1/alt2/decisive`` and whose other
+        internal nodes carry no name, so that ``get_newick(with_node_names=True)`` writes the counts.
+        ``ValueError`` unless the concordance was computed."""
+        self._need_concordance()
+        out = self.supertree.copy()
+        mask = self.quartet_branch
+        for i, node in enumerate(_preorder(out)):
+            if node.is_tip():
+                continue
+            node.name = (f"{int(self.concordant[i])}/{int(self.alt1[i])}/{int(self.alt2[i])}/{int(self.decisive[i])}"
+                         if mask[i] else None)
+        return out
+
+    def nni_candidates(self) -> list[dict]:
+        """The quartet branches where an alternative arrangement has more sources than the branch itself: one dict
+        per branch with ``node`` (preorder index), ``alternative`` (``"alt1"`` or ``"alt2"``, the larger; alt1 on
+        a tie), ``decisive``, ``concordant``, ``alt1``, ``alt2`` and ``margin`` = that alternative's count minus
+        ``concordant``; largest margin first, then by node."""
+        self._need_concordance()
+        best = np.maximum(self.alt1, self.alt2)
+        out = []
+        for i in np.flatnonzero(best > self.concordant):
+            out.append({"node": int(i), "alternative": "alt1" if self.alt1[i] >= self.alt2[i] else "alt2",
+                        "decisive": int(self.decisive[i]), "concordant": int(self.concordant[i]),
+                        "alt1": int(self.alt1[i]), "alt2": int(self.alt2[i]),
+                        "margin": int(best[i] - self.concordant[i])})
+        out.sort(key=lambda r: (-r["margin"], r["node"]))
+        return out
+
+    def branch_table(self) -> str:
+        """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
+        concordant, alt1, alt2, other.  ``ValueError`` unless the concordance was computed."""
+        self._need_concordance()
+        nodes = _preorder(self.supertree)
+        size = np.array([1 if v.is_tip() else 0 for v in nodes], dtype=np.int64)
+        parent = self.supertree.to_flat()[0]
+        for i in range(len(nodes) - 1, 0, -1):
+            size[parent[i]] += size[i]
+        other = self.other
+        rows = ["node\tclade_size\tinformative\tsupported\tdecisive\tconcordant\talt1\talt2\tother"]
+        for i in np.flatnonzero(self.quartet_branch):
+            rows.append(f"{i}\t{size[i]}\t{self.informative[i]}\t{self.supported[i]}\t{self.decisive[i]}"
+                        f"\t{self.concordant[i]}\t{self.alt1[i]}\t{self.alt2[i]}\t{other[i]}")
+        return "\n".join(rows) + "\n"
+
     def table(self) -> str:
         """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, then t_super, t_source,
-        t_shared, triplet_distance when the triplet terms were computed and n_super_conflict, n_source_conflict
-        when the conflicts were."""
+        t_shared, triplet_distance when the triplet terms were computed, n_super_conflict, n_source_conflict
+        when the conflicts were and n_decisive, n_concordant, n_alternative when the concordance was."""
         trip = self.t_shared is not None
         conf = self.n_super_conflict is not None
+        conc = self.n_decisive is not None
         head = "index\tn_leaves\tn_super\tn_source\tshared\trf"
         if trip:
             head += "\tt_super\tt_source\tt_shared\ttriplet_distance"
         if conf:
             head += "\tn_super_conflict\tn_source_conflict"
+        if conc:
+            head += "\tn_decisive\tn_concordant\tn_alternative"
         rows = [head]
         rf = self.rf
         td = self.triplet_distance if trip else None
@@ -164,6 +280,8 @@ class SupertreeScore:
                 row += f"\t{self.t_super[t]}\t{self.t_source[t]}\t{self.t_shared[t]}\t{td[t]}"
             if conf:
                 row += f"\t{self.n_super_conflict[t]}\t{self.n_source_conflict[t]}"
+            if conc:
+                row += f"\t{self.n_decisive[t]}\t{self.n_concordant[t]}\t{self.n_alternative[t]}"
             rows.append(row)
         return "\n".join(rows) + "\n"
 
@@ -177,6 +295,16 @@ def _preorder(tree: TreeNode) -> list[TreeNode]:
         out.append(node)
         stack.extend(reversed(node.children))
     return out
+
+
+def quartet_branches(parent: np.ndarray) -> np.ndarray:
+    """Bool mask over preorder nodes given their ``parent`` array (root -1): the nodes with exactly two children
+    whose parent has exactly two children."""
+    parent = np.asarray(parent, dtype=np.int64)
+    kids = np.bincount(parent[1:], minlength=len(parent))
+    mask = np.zeros(len(parent), dtype=bool)
+    mask[1:] = (kids[1:] == 2) & (kids[parent[1:]] == 2)
+    return mask
 
 
 def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[str]]:
@@ -203,11 +331,13 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
-                    device=None) -> SupertreeScore:
+                    concordance: bool = False, device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
-    ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``),
-    both counted on the same device tables as the RF terms.
+    ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
+    ``concordance=True`` the branch concordance counts (``n_decisive``, ``n_concordant``, ``n_alternative`` per
+    tree, ``decisive``, ``concordant``, ``alt1``, ``alt2`` per node), all counted on the same device tables as the
+    RF terms.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -232,9 +362,11 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
                 raise ValueError(msg)
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
-        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts)
+        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
+                            concordance)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
-                                  - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0))
+                                  - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
+                                  - out.timings.get("concordance", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -253,13 +385,16 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     t2 = time.perf_counter()
     try:
         res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-        t3 = t4 = t5 = time.perf_counter()
+        t3 = t4 = t5 = t6 = time.perf_counter()
         if triplets:
             res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t4 = t5 = time.perf_counter()
+            t4 = t5 = t6 = time.perf_counter()
         if conflicts:
             res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t5 = time.perf_counter()
+            t5 = t6 = time.perf_counter()
+        if concordance:
+            res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+            t6 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
@@ -267,6 +402,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         timings["triplets"] = t4 - t3
     if conflicts:
         timings["conflicts"] = t5 - t4
+    if concordance:
+        timings["concordance"] = t6 - t5
     return _result(supertree, np.diff(tables.tree_off), res, timings)
 
 
@@ -274,7 +411,9 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
     return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
                           res["informative"], res["supported"], timings,
                           res.get("t_super"), res.get("t_source"), res.get("t_shared"),
-                          res.get("n_super_conflict"), res.get("n_source_conflict"), res.get("conflicting"))
+                          res.get("n_super_conflict"), res.get("n_source_conflict"), res.get("conflicting"),
+                          res.get("n_decisive"), res.get("n_concordant"), res.get("n_alternative"),
+                          res.get("decisive"), res.get("concordant"), res.get("alt1"), res.get("alt2"))
 
 
 def _default_device():
@@ -284,7 +423,7 @@ def _default_device():
 
 
 def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
-                  conflicts) -> SupertreeScore:
+                  conflicts, concordance) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -298,7 +437,9 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     n_nodes = len(parent)
     per_tree = ("n_super", "n_source", "shared") + (("t_super", "t_source", "t_shared") if triplets else ())
     per_tree += ("n_super_conflict", "n_source_conflict") if conflicts else ()
+    per_tree += ("n_decisive", "n_concordant", "n_alternative") if concordance else ()
     per_node = ("informative", "supported") + (("conflicting",) if conflicts else ())
+    per_node += ("decisive", "concordant", "alt1", "alt2") if concordance else ()
     zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
     node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in per_node}
     # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
@@ -315,7 +456,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = t4 = time.perf_counter()
+        t1 = t2 = t3 = t4 = t5 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
         else:
@@ -325,13 +466,16 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
             t1 = time.perf_counter()
             try:
                 res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-                t2 = t3 = t4 = time.perf_counter()
+                t2 = t3 = t4 = t5 = time.perf_counter()
                 if triplets:
                     res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t3 = t4 = time.perf_counter()
+                    t3 = t4 = t5 = time.perf_counter()
                 if conflicts:
                     res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t4 = time.perf_counter()
+                    t4 = t5 = time.perf_counter()
+                if concordance:
+                    res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+                    t5 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -346,4 +490,6 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
         timings["triplets"] = t3 - t2
     if conflicts:
         timings["conflicts"] = t4 - t3
+    if concordance:
+        timings["concordance"] = t5 - t4
     return _result(supertree, n_leaves, res, timings)

@@ -5,6 +5,7 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --size 10000x500     # one size; NxM or NxMxK (K leaves per tree)
     python tools/score_bench.py --triplets           # also the rooted triplet terms
     python tools/score_bench.py --conflicts          # also the clade conflict counts
+    python tools/score_bench.py --concordance        # also the branch concordance counts
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
 """
 
@@ -66,7 +67,7 @@ def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeA
 
 
 def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
-        cat: bool = False) -> dict:
+        cat: bool = False, concordance: bool = False) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
@@ -81,7 +82,8 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
     runs = []
     for _ in range(repeats):
         t0 = time.perf_counter()
-        res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, device=dev)
+        res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, concordance=concordance,
+                              device=dev)
         runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
@@ -102,7 +104,22 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
                     "total_n_source_conflict": int(res.n_source_conflict.sum()),
                     "total_conflicting": int(res.conflicting.sum()), "total_supported": int(res.supported.sum()),
                     "total_informative": int(res.informative.sum())})
+    if concordance:
+        leaves = int(arrays.leaf_counts().sum())
+        out.update({"concordance_call_s": round(tim["concordance"], 5),
+                    "concordance_call_s_min_median_max": [round(x, 5)
+                                                          for x in _spread([r[1]["concordance"] for r in runs])],
+                    "concordance_ns_per_leaf": round(tim["concordance"] / max(leaves, 1) * 1e9, 3),
+                    "score_call_s_min_median_max": [round(x, 5) for x in _spread([r[1]["score"] for r in runs])],
+                    "total_decisive": int(res.decisive.sum()), "total_concordant": int(res.concordant.sum()),
+                    "total_alt1": int(res.alt1.sum()), "total_alt2": int(res.alt2.sum()),
+                    "total_other": int(res.other.sum()), "quartet_branches": int(res.quartet_branch.sum())})
     return out
+
+
+def _spread(values) -> tuple[float, float, float]:
+    v = sorted(values)
+    return v[0], v[len(v) // 2], v[-1]
 
 
 def main() -> None:
@@ -111,15 +128,17 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--triplets", action="store_true", help="also count the rooted triplet terms")
     ap.add_argument("--conflicts", action="store_true", help="also count the clade conflicts")
+    ap.add_argument("--concordance", action="store_true", help="also count the branch concordance factors")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
-                        conflicts=args.conflicts, device=dev)  # warm-up
+                        conflicts=args.conflicts, concordance=args.concordance, device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
-            print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar)), flush=True)
+            print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar,
+                                 args.concordance)), flush=True)
 
 
 if __name__ == "__main__":
