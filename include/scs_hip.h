@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_score_branch_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -369,6 +369,25 @@ int scs_score_concordance(scs_ctx *ctx, const scs_tables *sources, int32_t n_nod
                           const int32_t *taxon, int32_t max_batch_trees, int64_t *n_decisive, int64_t *n_concordant,
                           int64_t *n_alternative, int64_t *decisive, int64_t *concordant, int64_t *alt1,
                           int64_t *alt2);
+
+/* Per-branch triplet support, same inputs and SCS_EINVAL cases as scs_score_supertree: the
+ * graded form of scs_score_concordance.  For a quartet branch C of S (children A and B, sibling D) and a source tree T
+ * on the leaf set L that is decisive for it (A' = A ∩ L, B' = B ∩ L, D' = D ∩ L all non-empty), each of the
+ * |A'| |B'| |D'| triples (a in A', b in B', d in D') is resolved ab|d by T (some cluster of T holds a and b but not
+ * d), ad|b, bd|a, or left a fan.
+ * Per node C of S (n_nodes entries, S's preorder; zeros where C is not a quartet branch), summed over the sources:
+ *   bt_total[C] = the triples, bt_concordant[C] / bt_alt1[C] / bt_alt2[C] = those resolved ab|d / ad|b / bd|a
+ *   (bt_concordant + bt_alt1 + bt_alt2 <= bt_total, the rest are fans; bt_total[C] > 0 iff decisive[C] > 0).
+ * Per source tree, the same sums over its branches:
+ *   n_bt_total[t], n_bt_concordant[t], n_bt_alternative[t] (alt1 + alt2)
+ *   (a triple belongs to at most one branch: n_bt_total <= t_super, n_bt_concordant <= t_shared).
+ * Counts are unweighted and exact; output pointers may be null.  The pair kernel holds three bitsets over a tree's
+ * leaves in LDS: SCS_EINVAL as well for a source tree of more than 218 431 leaves, and when the sum over the trees of
+ * (leaves / 3)^3, the bound of a node's count, does not fit int64. */
+int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                              const int32_t *taxon, int32_t max_batch_trees, int64_t *n_bt_total,
+                              int64_t *n_bt_concordant, int64_t *n_bt_alternative, int64_t *bt_total,
+                              int64_t *bt_concordant, int64_t *bt_alt1, int64_t *bt_alt2);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

@@ -46,11 +46,13 @@ def sc_supertree(
 
 @_define_app
 def score_supertree(supertree, trees, *, triplets: bool = False, conflicts: bool = False,
-                    concordance: bool = False):
+                    concordance: bool = False, branch_triplets: bool = False):
     """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, with
-    ``triplets=True`` the rooted triplet terms, with ``conflicts=True`` the clade conflict counts and with
-    ``concordance=True`` the branch concordance counts."""
-    return _score(supertree, trees, triplets=triplets, conflicts=conflicts, concordance=concordance)
+    ``triplets=True`` the rooted triplet terms, with ``conflicts=True`` the clade conflict counts, with
+    ``concordance=True`` the branch concordance counts and with ``branch_triplets=True`` the per-branch triplet
+    support."""
+    return _score(supertree, trees, triplets=triplets, conflicts=conflicts, concordance=concordance,
+                  branch_triplets=branch_triplets)
 
 
 @_define_app

@@ -125,7 +125,7 @@ _I32 = C.c_int32
 # per argument (``data_as``) costs more than the call itself for the tiny nodes of a deep recursion;
 # dptr / iptr / lptr below check the dtype instead
 _DP = _IP = _LP = C.c_void_p
-ABI_VERSION = 109  # scs_version() of the header these bindings were written against
+ABI_VERSION = 109  # scs_version() of the header these bindings were written against (symbols added since keep it)
 
 SIGNATURES = {
     "scs_version": (C.c_int, []),
@@ -164,6 +164,7 @@ SIGNATURES = {
     "scs_score_triplets": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _LP, _LP, _LP]),
     "scs_score_conflicts": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _LP, _LP, _LP]),
     "scs_score_concordance": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _LP, _LP, _LP, _LP, _LP, _LP, _LP]),
+    "scs_score_branch_triplets": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _LP, _LP, _LP, _LP, _LP, _LP, _LP]),
     "scs_pcg_build": (C.c_int, [_P, _P, _I32, _I32, _I32, _PP, C.POINTER(BuildStats)]),
     "scs_graph_contract": (C.c_int, [_P, _P, _IP, _I32, _PP]),
     "scs_graph_matrix_free": (C.c_int, [_P, _P, _I32, _PP]),

@@ -216,6 +216,28 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_branch_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
+        """``scs_score_branch_triplets``: per-branch triplet support, with the inputs of ``score``.  Returns int64
+        arrays ``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative`` (per tree) and ``bt_total``,
+        ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` (per node)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        n_nodes, m = len(parent), tabs.n_trees
+        if taxon.shape != (n_nodes,):
+            msg = "parent and taxon must have one entry per supertree node"
+            raise ValueError(msg)
+        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_bt_total", "n_bt_concordant", "n_bt_alternative")}
+        out.update({k: np.zeros(n_nodes, dtype=np.int64)
+                    for k in ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2")})
+        rc = self._lib.scs_score_branch_triplets(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                                 int(batch_trees), *(nv.lptr(v) for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_branch_triplets: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

@@ -50,10 +50,17 @@ from spectralclustersupertree_amd import __version__
 @click.option("--branches-out", default=None,
               help="Also write a TSV with one row per quartet branch (node, clade_size, informative, supported, "
                    "decisive, concordant, alt1, alt2, other).")
+@click.option("--branch-triplets", default=False, is_flag=True,
+              help="Add the per-branch triplet support to --scores-out (n_bt_total, n_bt_concordant, "
+                   "n_bt_alternative) and to --branches-out (bt_total, bt_concordant, bt_alt1, bt_alt2).")
+@click.option("--branch-triplets-out", default=None,
+              help="Also write the supertree with each quartet branch's concordant/alt1/alt2/total triple counts as "
+                   "its node name (Newick).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
-        concordance_out: str | None = None, branches_out: str | None = None) -> None:
+        concordance_out: str | None = None, branches_out: str | None = None, branch_triplets: bool = False,
+        branch_triplets_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
@@ -63,6 +70,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         raise click.UsageError(msg)
     if concordance and not scores_out:
         msg = "--concordance needs --scores-out"
+        raise click.UsageError(msg)
+    if branch_triplets and not (scores_out or branches_out):
+        msg = "--branch-triplets needs --scores-out or --branches-out"
         raise click.UsageError(msg)
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
@@ -77,13 +87,19 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     team = default_team()
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
-        if scores_out or support_out or conflict_out or concordance_out or branches_out:
+        if scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out:
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
                                      conflicts=conflicts or conflict_out is not None,
                                      concordance=concordance or concordance_out is not None
-                                     or branches_out is not None)
+                                     or branches_out is not None,
+                                     branch_triplets=branch_triplets or branch_triplets_out is not None)
+            if branch_triplets_out:
+                Path(branch_triplets_out).write_text(
+                    result.annotate_branch_triplets().get_newick(with_node_names=True) + "\n")
+            if not branch_triplets:
+                result = _without_branch_triplets(result)  # (the tables keep their columns of before)
             if scores_out:
                 shown = result if conflicts else _without_conflicts(result)
                 Path(scores_out).write_text((shown if concordance else _without_concordance(shown)).table())
@@ -96,6 +112,15 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                     result.annotate_concordance().get_newick(with_node_names=True) + "\n")
             if branches_out:
                 Path(branches_out).write_text(result.branch_table())
+
+
+def _without_branch_triplets(result):
+    """``result`` whose tables leave the branch triplet columns out (--branch-triplets-out without
+    --branch-triplets)."""
+    import dataclasses
+
+    return dataclasses.replace(result, n_bt_total=None, n_bt_concordant=None, n_bt_alternative=None, bt_total=None,
+                               bt_concordant=None, bt_alt1=None, bt_alt2=None)
 
 
 def _without_concordance(result):

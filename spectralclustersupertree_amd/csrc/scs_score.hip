@@ -972,6 +972,223 @@ __global__ void __launch_bounds__(SC_THREADS) k_conc_branches(sc_conc_args a) {
     sc_count(a.c_alt, t, alt);
 }
 
+// ---- per-branch triplet support (scs_score_branch_triplets) ----
+//
+// The graded form of the branch concordance: for a quartet branch C of S (children A and B, sibling D) and a source T
+// on L that is decisive for it (A' = A ∩ L, B' = B ∩ L, D' = D ∩ L all non-empty), the |A'||B'||D'| triples (a, b, d)
+// with a in A', b in B', d in D' are resolved ab|d (concordant), ad|b (alt1), bd|a (alt2) or left a fan by T.  With y
+// over T's non-root nodes, py the parent and I(y, X) = |cl(y) ∩ X|, a triple resolved ab|d has exactly one y with
+// a, b in y and d in py \ y:
+//   bt_concordant = sum_y I(y,A') I(y,B') (I(py,D') - I(y,D')),  alt1 with (A', D', B'),  alt2 with (B', D', A').
+//   k_bt_records: one thread per gap lists T's nodes (as k_trip_nodes does) and, by steps 1 - 3 of k_conc_branches,
+//     the decisive branch of the gap as a record {u, lo, k, hi, dlo, dhi} (S' indices); bt_total on the way.
+//   k_bt_pairs: one workgroup per (tree, block of zb records).  A', A' ∪ B' and A' ∪ B' ∪ D' become bitset rows over T
+//     positions in LDS in the {bits, prefix} layout of k_trip_pairs (the B' and D' counts are differences of two
+//     rows); the workgroup sweeps T's node list once for all its records.
+
+constexpr int BT_ZMAX = 8;       // records per workgroup
+constexpr int BT_ROW_BYTES = 24; // LDS bytes per 32 T positions of one record: three rows of int2
+
+struct sc_bt_rec {
+    int32_t u;             // the quartet branch (S node)
+    int32_t lo, k, hi;     // A' = S' indices [lo, k], B' = [k + 1, hi]
+    int32_t dlo, dhi;      // D' = [dlo, dhi]
+};
+
+struct sc_bt_args {
+    const int64_t *off;          // tree_off + t0
+    int nb;
+    const int32_t *sp, *node;    // [Lb] S positions in S order, U of S'
+    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
+    int levels;
+    int64_t Lb;
+    const int32_t *s_lo, *s_hi;  // leaf range of every S node
+    const int32_t *q_parent;     // [S nodes] the parent of a quartet branch, -1 for every other node
+    int4 *ylist;                 // [Lb] T's nodes of a tree from its first leaf on
+    sc_bt_rec *recs;             // [Lb] the tree's records likewise
+    int32_t *ycnt, *rcnt;        // [nb] list lengths
+    unsigned long long *n_tot;   // [S nodes] bt_total
+    unsigned long long *c_tot;   // [nb] n_bt_total of the batch
+};
+
+// one thread per gap: T's non-root internal node that starts here, and the quartet branch the tree is decisive for
+__global__ void __launch_bounds__(SC_THREADS) k_bt_records(sc_bt_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    int4 ny = make_int4(0, 0, 0, 0);
+    sc_bt_rec r = {0, 0, 0, 0, 0, 0};
+    bool t_node = false, dec = false;
+    unsigned long long vt = 0;
+    if (in && k + 1 < n) {
+        // T: the first gap of its node, the node's and its parent's leaves (as k_trip_nodes)
+        const int32_t d = a.adj[q];
+        const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+        if (lo == 0 || a.adj[base + lo - 1] < d) {
+            const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+            if (lo > 0 || hi < n - 1) {  // (not the root)
+                const int64_t g = lo == 0 ? hi
+                                  : hi == n - 1 ? lo - 1
+                                  : (a.adj[base + lo - 1] >= a.adj[base + hi] ? lo - 1 : hi);
+                const int32_t dg = a.adj[base + g];
+                const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+                const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+                t_node = true;
+                ny = make_int4((int)lo, (int)hi + 1, (int)plo, (int)phi + 1);
+            }
+        }
+        // S: u = U[k] a quartet branch, [lo, hi] and the D' stretch (steps 1 - 3 of k_conc_branches)
+        const int32_t u = a.node[q];
+        const int32_t pu = a.q_parent[u];
+        if (pu >= 0) {
+            const int32_t *sp = a.sp + base;
+            const int32_t sl = a.s_lo[u], pl = a.s_lo[pu];
+            const int64_t lo_s = sc_gallop_first_ge(sp, k, sl);
+            const int64_t hi_s = sc_gallop_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+            int64_t dlo = 0, dhi = -1;
+            if (pl == sl) {
+                const int32_t pr = a.s_hi[pu];
+                if (hi_s + 1 < n && sp[hi_s + 1] <= pr) {
+                    dlo = hi_s + 1;
+                    dhi = sc_gallop_last_le(sp, hi_s + 1, n - 1, pr);
+                }
+            } else if (lo_s > 0 && sp[lo_s - 1] >= pl) {
+                dhi = lo_s - 1;
+                dlo = sc_gallop_first_ge(sp, lo_s - 1, pl);
+            }
+            if (dhi >= dlo) {
+                dec = true;
+                r = {u, (int32_t)lo_s, (int32_t)k, (int32_t)hi_s, (int32_t)dlo, (int32_t)dhi};
+                vt = (unsigned long long)((k - lo_s + 1) * (hi_s - k) * (dhi - dlo + 1));
+                atomicAdd(a.n_tot + u, vt);
+            }
+        }
+    }
+    const int iy = sc_append(a.ycnt, t, t_node);
+    if (iy >= 0) a.ylist[base + iy] = ny;
+    const int ir = sc_append(a.rcnt, t, dec);
+    if (ir >= 0) a.recs[base + ir] = r;
+    sc_add64(a.c_tot, t, vt);
+}
+
+// the hot path: one workgroup per (tree t, block of zb of t's records); blk and W as in k_trip_pairs.  node_ctr holds
+// bt_concordant, bt_alt1, bt_alt2 as three arrays of nn entries; c_con / c_alt are the batch's per-tree counters
+__global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restrict__ blk, int nb,
+                                                         const int64_t *__restrict__ off,
+                                                         const int4 *__restrict__ ylist,
+                                                         const sc_bt_rec *__restrict__ recs,
+                                                         const int32_t *__restrict__ ycnt,
+                                                         const int32_t *__restrict__ rcnt,
+                                                         const int2 *__restrict__ tp, int zb, int W,
+                                                         unsigned long long *__restrict__ node_ctr, int64_t nn,
+                                                         unsigned long long *__restrict__ c_con,
+                                                         unsigned long long *__restrict__ c_alt) {
+    // [3 zb][W]: rows 3j, 3j + 1, 3j + 2 = A', A' ∪ B', A' ∪ B' ∪ D' of record j
+    extern __shared__ __attribute__((aligned(16))) int2 rows[];
+    const int64_t g = blk[0] + blockIdx.x;
+    const int t = sc_tree_of(blk, nb, g);
+    const int j0 = (int)(g - blk[t]) * zb;
+    const int nz = min(zb, rcnt[t] - j0);
+    if (nz <= 0) return;  // (the grid counts n - 2 records per tree: an upper bound)
+    const int64_t base = off[t] - off[0];
+    const int nrow = 3 * nz;
+    for (int i = threadIdx.x; i < nrow * W; i += SC_THREADS) rows[i] = make_int2(0, 0);
+    __syncthreads();
+    unsigned *bits = reinterpret_cast<unsigned *>(rows);  // (word i of the image: .x of entry i / 2)
+    for (int j = 0; j < nz; ++j) {
+        const sc_bt_rec r = recs[base + j0 + j];
+        for (int k = r.lo + threadIdx.x; k <= r.hi; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            const unsigned bit = 1u << (x & 31);
+            if (k <= r.k) atomicOr(bits + 2 * ((3 * j) * W + (x >> 5)), bit);
+            atomicOr(bits + 2 * ((3 * j + 1) * W + (x >> 5)), bit);
+            atomicOr(bits + 2 * ((3 * j + 2) * W + (x >> 5)), bit);
+        }
+        for (int k = r.dlo + threadIdx.x; k <= r.dhi; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            atomicOr(bits + 2 * ((3 * j + 2) * W + (x >> 5)), 1u << (x & 31));
+        }
+    }
+    __syncthreads();
+    // every word's .y = set bits in the words before it: one wave per row, wave64 scans of 64 words
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < nrow; r += SC_THREADS / 64) {
+        int2 *row = rows + r * W;
+        int run = 0;
+        for (int c = 0; c < W; c += 64) {
+            const int i = c + lane;
+            const int v = i < W ? __popc((unsigned)row[i].x) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    __syncthreads();
+    unsigned long long acc[BT_ZMAX][3];
+#pragma unroll
+    for (int j = 0; j < BT_ZMAX; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 0;
+    const int ny = ycnt[t];
+    for (int i = threadIdx.x; i < ny; i += SC_THREADS) {
+        const int4 y = ylist[base + i];  // T positions [y.x, y.y) of y, [y.z, y.w) of py
+        const int wa = y.x >> 5, wb = y.y >> 5, wc = y.z >> 5, wd = y.w >> 5;
+        const unsigned ma = (1u << (y.x & 31)) - 1u, mb = (1u << (y.y & 31)) - 1u;
+        const unsigned mc = (1u << (y.z & 31)) - 1u, md = (1u << (y.w & 31)) - 1u;
+#pragma unroll
+        for (int j = 0; j < BT_ZMAX; ++j) {
+            if (j >= nz) break;
+            const int2 *ra = rows + 3 * j * W, *rab = ra + W, *rabd = rab + W;
+            const int yab = tp_count(rab, wb, mb) - tp_count(rab, wa, ma);
+            if (yab == 0) continue;  // (every term has a factor I(y, A') or I(y, B'))
+            const int ya = tp_count(ra, wb, mb) - tp_count(ra, wa, ma);
+            const int yabd = tp_count(rabd, wb, mb) - tp_count(rabd, wa, ma);
+            const int pa = tp_count(ra, wd, md) - tp_count(ra, wc, mc);
+            const int pab = tp_count(rab, wd, md) - tp_count(rab, wc, mc);
+            const int pabd = tp_count(rabd, wd, md) - tp_count(rabd, wc, mc);
+            const int64_t ia = ya, ib = yab - ya, id = yabd - yab;         // I(y, A'), I(y, B'), I(y, D')
+            const int64_t oa = pa - ya, ob = (pab - pa) - ib, od = (pabd - pab) - id;  // the same of py \ y
+            acc[j][0] += (unsigned long long)(ia * ib * od);
+            acc[j][1] += (unsigned long long)(ia * id * ob);
+            acc[j][2] += (unsigned long long)(ib * id * oa);
+        }
+    }
+    __syncthreads();  // (the rows are read no more: their first 768 bytes take the wave sums)
+    unsigned long long *ws = reinterpret_cast<unsigned long long *>(rows);  // [waves][BT_ZMAX][3]
+#pragma unroll
+    for (int j = 0; j < BT_ZMAX; ++j) {
+        if (j >= nz) break;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            unsigned long long v = acc[j][c];
+            for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+            if (lane == 0) ws[(wave * BT_ZMAX + j) * 3 + c] = v;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        // lane 3 j + c: counter c of record j over the waves, one atomic where it is not zero; then the tree's two sums
+        unsigned long long tot = 0;
+        if (lane < 3 * nz)
+            for (int w = 0; w < SC_THREADS / 64; ++w) tot += ws[w * BT_ZMAX * 3 + lane];
+        const int c = lane % 3;
+        if (tot) atomicAdd(node_ctr + c * nn + recs[base + j0 + lane / 3].u, tot);
+        unsigned long long con = c == 0 ? tot : 0, alt = c == 0 ? 0 : tot;
+        for (int d = 32; d >= 1; d >>= 1) {
+            con += __shfl_xor(con, d, 64);
+            alt += __shfl_xor(alt, d, 64);
+        }
+        if (lane == 0 && con) atomicAdd(c_con + t, con);
+        if (lane == 0 && alt) atomicAdd(c_alt + t, alt);
+    }
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -1520,6 +1737,121 @@ extern "C" int scs_score_concordance(scs_ctx *ctx, const scs_tables *src, int32_
         if (n_decisive) n_decisive[t] = (int64_t)cnt[t];
         if (n_concordant) n_concordant[t] = (int64_t)cnt[M + t];
         if (n_alternative) n_alternative[t] = (int64_t)cnt[2 * M + t];
+    }
+    return SCS_OK;
+}
+
+extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                         const int32_t *taxon, int32_t max_batch_trees, int64_t *n_bt_total,
+                                         int64_t *n_bt_concordant, int64_t *n_bt_alternative, int64_t *bt_total,
+                                         int64_t *bt_concordant, int64_t *bt_alt1, int64_t *bt_alt2) {
+    // the three rows of one record of the largest tree must fit one workgroup's LDS
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(BT_ROW_BYTES * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "scs_score_branch_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in "
+                "LDS", (long long)m_max, TP_LDS_MAX / BT_ROW_BYTES * 32 - 1);
+    // a node's sum is at most sum_t (m_t / 3)^3: it must fit int64
+    if (src) {
+        unsigned __int128 cubes = 0;
+        for (int32_t t = 0; t < src->n_trees; ++t) {
+            const unsigned __int128 m = (unsigned __int128)(src->h_tree_off[t + 1] - src->h_tree_off[t]);
+            cubes += m * m * m;
+        }
+        SCS_REQUIRE(cubes / 27 <= (unsigned __int128)INT64_MAX,
+                    "scs_score_branch_triplets: the triple counts of %d source trees may not fit 64 bits",
+                    src->n_trees);
+    }
+    // own arrays: four counters and the quartet-branch record per S node, three counters and the first pair workgroup
+    // per tree (+ 1); per batch T's node list (int4) and the record list per leaf, their two lengths per tree
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
+    const size_t o_node = 0, o_qp = o_node + sc_up256(nn * 32), o_cnt = o_qp + sc_up256(nn * 4),
+                 o_blk = o_cnt + sc_up256(mt * 24), own = o_blk + sc_up256((mt + 1) * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_branch_triplets", n_nodes, parent, taxon, max_batch_trees, own,
+                     16 + sizeof(sc_bt_rec), 8, c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_node = (unsigned long long *)(c.d_extra + o_node);
+    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
+    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    auto *d_ylist = (int4 *)c.d_extra_batch;
+    auto *d_recs = (sc_bt_rec *)(d_ylist + c.max_lb);
+    auto *d_ycnt = (int32_t *)(d_recs + c.max_lb);
+    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
+    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
+    for (int32_t v = 1; v < n_nodes; ++v)
+        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    // per batch: W words per bitset row (largest tree of the batch), zb records per workgroup; blk: the first pair
+    // workgroup of every tree, ceil((n - 2) / zb) of them (a tree is decisive for at most n - 2 branches)
+    const size_t n_batches = c.bstart.size() - 1;
+    std::vector<int> words(n_batches), zbs(n_batches);
+    std::vector<int64_t> blk((size_t)M + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
+            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_node, 0, nn * 32, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_bt_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
+        if (e != hipSuccess) break;
+        sc_bt_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.node = c.d_node;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.q_parent = d_qp;
+        a.ylist = d_ylist;
+        a.recs = d_recs;
+        a.ycnt = d_ycnt;
+        a.rcnt = d_ycnt + nb;
+        a.n_tot = d_node;
+        a.c_tot = d_cnt + t0;
+        k_bt_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        if (n_wg == 0) continue;
+        // (at least the 768 bytes of the workgroup's wave sums)
+        const size_t lds = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b],
+                                            (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
+        k_bt_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
+                                                           c.d_mm, zbs[b], words[b], d_node + nn, (int64_t)nn,
+                                                           d_cnt + M + t0, d_cnt + 2 * (int64_t)M + t0);
+        if (!sc_launched(e)) break;
+    }
+    std::vector<unsigned long long> cnt((size_t)M * 3);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
+    int64_t *const outs[4] = {bt_total, bt_concordant, bt_alt1, bt_alt2};
+    for (int i = 0; i < 4 && e == hipSuccess; ++i)
+        if (outs[i]) e = hipMemcpyAsync(outs[i], d_node + i * nn, nn * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    for (int32_t t = 0; t < M; ++t) {
+        if (n_bt_total) n_bt_total[t] = (int64_t)cnt[t];
+        if (n_bt_concordant) n_bt_concordant[t] = (int64_t)cnt[M + t];
+        if (n_bt_alternative) n_bt_alternative[t] = (int64_t)cnt[2 * M + t];
     }
     return SCS_OK;
 }

@@ -1,7 +1,7 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
 supertree node, and on request rooted triplet terms per source tree (section 15), clade
-conflict counts (section 16) and branch concordance factors (section 17).  Neither the reference nor
-``construct_supertree`` computes them.
+conflict counts (section 16), branch concordance factors (section 17) and per-branch triplet support (section 18).
+Neither the reference nor ``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
 2 <= size < |L|.  C(S|T) = the nontrivial sets C ∩ L(T) over the clades C of the supertree S; C(T) = T's own.
@@ -49,8 +49,27 @@ gDFP) with the source trees as the genes.
 * per source tree: ``n_decisive`` = the quartet branches it is decisive for, ``n_concordant`` = those it is concordant
   with, ``n_alternative`` = those where it displays alt1 or alt2.
 
+Per-branch triplet support (``branch_triplets=True``): the graded form of the concordance, which is all-or-nothing
+per source (one misplaced taxon inside A moves a source to *other*).  For a quartet branch C and a source T on L that is
+decisive for it, with A' = A ∩ L, B' = B ∩ L, D' = D ∩ L, each of the |A'| |B'| |D'| triples (a ∈ A', b ∈ B', d ∈ D')
+is resolved ab|d by T (concordant), ad|b (alt1), bd|a (alt2) or left a fan.  ASTRAL's local quartet support and
+IQ-TREE's sCF are the unrooted relatives.
+
+* per node C of S, summed over the sources: ``bt_total``, ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` (zeros where C
+  is not a quartet branch) and ``bt_fan = bt_total - bt_concordant - bt_alt1 - bt_alt2 >= 0``; ``bt_total > 0``
+  exactly where ``decisive > 0``, and a source that is concordant (alt1, alt2) at C gives all of its triples there to
+  ``bt_concordant`` (``bt_alt1``, ``bt_alt2``);
+* per source tree, the same sums over its branches: ``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative``
+  (alt1 + alt2).  A triple of L belongs to at most one branch, so ``n_bt_total <= t_super`` and
+  ``n_bt_concordant <= t_shared``.
+
+With y over T's non-root nodes, py the parent and I(y, X) = |cl(y) ∩ X|: ``bt_concordant`` =
+Σ_y I(y,A') I(y,B') (I(py,D') - I(y,D')), ``bt_alt1`` with (A', D', B') and ``bt_alt2`` with (B', D', A') in those
+places: a triple resolved ab|d has exactly one y with a, b ∈ y and d ∈ py ∖ y.
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
-``scs_score_conflicts`` and ``scs_score_concordance``; the host only validates and lays out.
+``scs_score_conflicts``, ``scs_score_concordance`` and ``scs_score_branch_triplets``; the host only validates and lays
+out.
 """
 
 from __future__ import annotations
@@ -82,7 +101,8 @@ class SupertreeScore:
     # wall seconds: "prepare" (host: supertree arrays, checks, flattening objects), "tables" (a TreeArrays forest
     # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
     # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
-    # "concordance" (scs_score_concordance, when requested)
+    # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
+    # requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -100,6 +120,14 @@ class SupertreeScore:
     concordant: np.ndarray | None = None
     alt1: np.ndarray | None = None
     alt2: np.ndarray | None = None
+    # per-branch triplet support (``branch_triplets=True``; None otherwise): per source tree, and per supertree node
+    n_bt_total: np.ndarray | None = None
+    n_bt_concordant: np.ndarray | None = None
+    n_bt_alternative: np.ndarray | None = None
+    bt_total: np.ndarray | None = None
+    bt_concordant: np.ndarray | None = None
+    bt_alt1: np.ndarray | None = None
+    bt_alt2: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -225,43 +253,112 @@ class SupertreeScore:
                          if mask[i] else None)
         return out
 
-    def nni_candidates(self) -> list[dict]:
+    def nni_candidates(self, by: str = "sources") -> list[dict]:
         """The quartet branches where an alternative arrangement has more sources than the branch itself: one dict
         per branch with ``node`` (preorder index), ``alternative`` (``"alt1"`` or ``"alt2"``, the larger; alt1 on
         a tie), ``decisive``, ``concordant``, ``alt1``, ``alt2`` and ``margin`` = that alternative's count minus
-        ``concordant``; largest margin first, then by node."""
-        self._need_concordance()
-        best = np.maximum(self.alt1, self.alt2)
+        ``concordant``; largest margin first, then by node.  ``by="triplets"`` compares the per-branch triple
+        counts instead (``branch_triplets=True``): the same keys, holding ``bt_total``, ``bt_concordant``,
+        ``bt_alt1`` and ``bt_alt2``."""
+        if by == "sources":
+            self._need_concordance()
+            dec, con, alt1, alt2 = self.decisive, self.concordant, self.alt1, self.alt2
+        elif by == "triplets":
+            self._need_branch_triplets()
+            dec, con, alt1, alt2 = self.bt_total, self.bt_concordant, self.bt_alt1, self.bt_alt2
+        else:
+            msg = f"by must be 'sources' or 'triplets', not {by!r}"
+            raise ValueError(msg)
+        best = np.maximum(alt1, alt2)
         out = []
-        for i in np.flatnonzero(best > self.concordant):
-            out.append({"node": int(i), "alternative": "alt1" if self.alt1[i] >= self.alt2[i] else "alt2",
-                        "decisive": int(self.decisive[i]), "concordant": int(self.concordant[i]),
-                        "alt1": int(self.alt1[i]), "alt2": int(self.alt2[i]),
-                        "margin": int(best[i] - self.concordant[i])})
+        for i in np.flatnonzero(best > con):
+            out.append({"node": int(i), "alternative": "alt1" if alt1[i] >= alt2[i] else "alt2",
+                        "decisive": int(dec[i]), "concordant": int(con[i]),
+                        "alt1": int(alt1[i]), "alt2": int(alt2[i]),
+                        "margin": int(best[i] - con[i])})
         out.sort(key=lambda r: (-r["margin"], r["node"]))
+        return out
+
+    def _need_branch_triplets(self) -> None:
+        if self.bt_total is None:
+            msg = "branch triplet counts were not computed: score_supertree(..., branch_triplets=True)"
+            raise ValueError(msg)
+
+    @property
+    def bt_fan(self) -> np.ndarray:
+        """Per node: the triples around the branch that their source leaves unresolved."""
+        self._need_branch_triplets()
+        return self.bt_total - self.bt_concordant - self.bt_alt1 - self.bt_alt2
+
+    def _bt_percent(self, counts: np.ndarray) -> np.ndarray:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.bt_total > 0, 100.0 * counts / np.maximum(self.bt_total, 1), np.nan)
+
+    @property
+    def tcf(self) -> np.ndarray:
+        """``bt_concordant`` in percent of ``bt_total`` (NaN where it is zero)."""
+        self._need_branch_triplets()
+        return self._bt_percent(self.bt_concordant)
+
+    @property
+    def tdf1(self) -> np.ndarray:
+        """``bt_alt1`` in percent of ``bt_total``."""
+        self._need_branch_triplets()
+        return self._bt_percent(self.bt_alt1)
+
+    @property
+    def tdf2(self) -> np.ndarray:
+        """``bt_alt2`` in percent of ``bt_total``."""
+        self._need_branch_triplets()
+        return self._bt_percent(self.bt_alt2)
+
+    @property
+    def tdfu(self) -> np.ndarray:
+        """``bt_fan`` in percent of ``bt_total``."""
+        return self._bt_percent(self.bt_fan)
+
+    def annotate_branch_triplets(self) -> TreeNode:
+        """A copy of the supertree whose branches with ``bt_total > 0`` are named
+        ``bt_concordant/bt_alt1/bt_alt2/bt_total`` and whose other internal nodes carry no name, so that
+        ``get_newick(with_node_names=True)`` writes the counts.  ``ValueError`` unless they were computed."""
+        self._need_branch_triplets()
+        out = self.supertree.copy()
+        for i, node in enumerate(_preorder(out)):
+            if node.is_tip():
+                continue
+            node.name = (f"{int(self.bt_concordant[i])}/{int(self.bt_alt1[i])}/{int(self.bt_alt2[i])}"
+                         f"/{int(self.bt_total[i])}" if self.bt_total[i] > 0 else None)
         return out
 
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
-        concordant, alt1, alt2, other.  ``ValueError`` unless the concordance was computed."""
+        concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
+        were computed.  ``ValueError`` unless the concordance was computed."""
         self._need_concordance()
+        bt = self.bt_total is not None
         nodes = _preorder(self.supertree)
         size = np.array([1 if v.is_tip() else 0 for v in nodes], dtype=np.int64)
         parent = self.supertree.to_flat()[0]
         for i in range(len(nodes) - 1, 0, -1):
             size[parent[i]] += size[i]
         other = self.other
-        rows = ["node\tclade_size\tinformative\tsupported\tdecisive\tconcordant\talt1\talt2\tother"]
+        rows = ["node\tclade_size\tinformative\tsupported\tdecisive\tconcordant\talt1\talt2\tother"
+                + ("\tbt_total\tbt_concordant\tbt_alt1\tbt_alt2" if bt else "")]
         for i in np.flatnonzero(self.quartet_branch):
-            rows.append(f"{i}\t{size[i]}\t{self.informative[i]}\t{self.supported[i]}\t{self.decisive[i]}"
-                        f"\t{self.concordant[i]}\t{self.alt1[i]}\t{self.alt2[i]}\t{other[i]}")
+            row = (f"{i}\t{size[i]}\t{self.informative[i]}\t{self.supported[i]}\t{self.decisive[i]}"
+                   f"\t{self.concordant[i]}\t{self.alt1[i]}\t{self.alt2[i]}\t{other[i]}")
+            if bt:
+                row += f"\t{self.bt_total[i]}\t{self.bt_concordant[i]}\t{self.bt_alt1[i]}\t{self.bt_alt2[i]}"
+            rows.append(row)
         return "\n".join(rows) + "\n"
 
     def table(self) -> str:
         """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, then t_super, t_source,
         t_shared, triplet_distance when the triplet terms were computed, n_super_conflict, n_source_conflict
-        when the conflicts were and n_decisive, n_concordant, n_alternative when the concordance was."""
+        when the conflicts were, n_decisive, n_concordant, n_alternative when the concordance was and n_bt_total,
+        n_bt_concordant, n_bt_alternative when the branch triplet counts were."""
         trip = self.t_shared is not None
+        bt = self.n_bt_total is not None
         conf = self.n_super_conflict is not None
         conc = self.n_decisive is not None
         head = "index\tn_leaves\tn_super\tn_source\tshared\trf"
@@ -271,6 +368,8 @@ class SupertreeScore:
             head += "\tn_super_conflict\tn_source_conflict"
         if conc:
             head += "\tn_decisive\tn_concordant\tn_alternative"
+        if bt:
+            head += "\tn_bt_total\tn_bt_concordant\tn_bt_alternative"
         rows = [head]
         rf = self.rf
         td = self.triplet_distance if trip else None
@@ -282,6 +381,8 @@ class SupertreeScore:
                 row += f"\t{self.n_super_conflict[t]}\t{self.n_source_conflict[t]}"
             if conc:
                 row += f"\t{self.n_decisive[t]}\t{self.n_concordant[t]}\t{self.n_alternative[t]}"
+            if bt:
+                row += f"\t{self.n_bt_total[t]}\t{self.n_bt_concordant[t]}\t{self.n_bt_alternative[t]}"
             rows.append(row)
         return "\n".join(rows) + "\n"
 
@@ -331,13 +432,14 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
-                    concordance: bool = False, device=None) -> SupertreeScore:
+                    concordance: bool = False, branch_triplets: bool = False, device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
     ``concordance=True`` the branch concordance counts (``n_decisive``, ``n_concordant``, ``n_alternative`` per
-    tree, ``decisive``, ``concordant``, ``alt1``, ``alt2`` per node), all counted on the same device tables as the
-    RF terms.
+    tree, ``decisive``, ``concordant``, ``alt1``, ``alt2`` per node) and ``branch_triplets=True`` the per-branch
+    triplet support (``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative`` per tree, ``bt_total``,
+    ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` per node), all counted on the same device tables as the RF terms.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -363,10 +465,10 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
         out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
-                            concordance)
+                            concordance, branch_triplets)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
                                   - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
-                                  - out.timings.get("concordance", 0.0))
+                                  - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -385,16 +487,19 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     t2 = time.perf_counter()
     try:
         res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-        t3 = t4 = t5 = t6 = time.perf_counter()
+        t3 = t4 = t5 = t6 = t7 = time.perf_counter()
         if triplets:
             res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t4 = t5 = t6 = time.perf_counter()
+            t4 = t5 = t6 = t7 = time.perf_counter()
         if conflicts:
             res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t5 = t6 = time.perf_counter()
+            t5 = t6 = t7 = time.perf_counter()
         if concordance:
             res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t6 = time.perf_counter()
+            t6 = t7 = time.perf_counter()
+        if branch_triplets:
+            res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+            t7 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
@@ -404,6 +509,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         timings["conflicts"] = t5 - t4
     if concordance:
         timings["concordance"] = t6 - t5
+    if branch_triplets:
+        timings["branch_triplets"] = t7 - t6
     return _result(supertree, np.diff(tables.tree_off), res, timings)
 
 
@@ -413,7 +520,9 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
                           res.get("t_super"), res.get("t_source"), res.get("t_shared"),
                           res.get("n_super_conflict"), res.get("n_source_conflict"), res.get("conflicting"),
                           res.get("n_decisive"), res.get("n_concordant"), res.get("n_alternative"),
-                          res.get("decisive"), res.get("concordant"), res.get("alt1"), res.get("alt2"))
+                          res.get("decisive"), res.get("concordant"), res.get("alt1"), res.get("alt2"),
+                          res.get("n_bt_total"), res.get("n_bt_concordant"), res.get("n_bt_alternative"),
+                          res.get("bt_total"), res.get("bt_concordant"), res.get("bt_alt1"), res.get("bt_alt2"))
 
 
 def _default_device():
@@ -423,7 +532,7 @@ def _default_device():
 
 
 def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
-                  conflicts, concordance) -> SupertreeScore:
+                  conflicts, concordance, branch_triplets=False) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -440,6 +549,8 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     per_tree += ("n_decisive", "n_concordant", "n_alternative") if concordance else ()
     per_node = ("informative", "supported") + (("conflicting",) if conflicts else ())
     per_node += ("decisive", "concordant", "alt1", "alt2") if concordance else ()
+    per_tree += ("n_bt_total", "n_bt_concordant", "n_bt_alternative") if branch_triplets else ()
+    per_node += ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2") if branch_triplets else ()
     zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
     node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in per_node}
     # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
@@ -456,7 +567,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = t4 = t5 = time.perf_counter()
+        t1 = t2 = t3 = t4 = t5 = t6 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
         else:
@@ -466,16 +577,19 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
             t1 = time.perf_counter()
             try:
                 res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-                t2 = t3 = t4 = t5 = time.perf_counter()
+                t2 = t3 = t4 = t5 = t6 = time.perf_counter()
                 if triplets:
                     res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t3 = t4 = t5 = time.perf_counter()
+                    t3 = t4 = t5 = t6 = time.perf_counter()
                 if conflicts:
                     res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t4 = t5 = time.perf_counter()
+                    t4 = t5 = t6 = time.perf_counter()
                 if concordance:
                     res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t5 = time.perf_counter()
+                    t5 = t6 = time.perf_counter()
+                if branch_triplets:
+                    res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
+                    t6 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -492,4 +606,6 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
         timings["conflicts"] = t4 - t3
     if concordance:
         timings["concordance"] = t5 - t4
+    if branch_triplets:
+        timings["branch_triplets"] = t6 - t5
     return _result(supertree, n_leaves, res, timings)

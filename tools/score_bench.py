@@ -6,6 +6,7 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --triplets           # also the rooted triplet terms
     python tools/score_bench.py --conflicts          # also the clade conflict counts
     python tools/score_bench.py --concordance        # also the branch concordance counts
+    python tools/score_bench.py --branch-triplets    # also the per-branch triplet support
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
 """
 
@@ -67,7 +68,7 @@ def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeA
 
 
 def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
-        cat: bool = False, concordance: bool = False) -> dict:
+        cat: bool = False, concordance: bool = False, branch_triplets: bool = False) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
@@ -83,7 +84,7 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
     for _ in range(repeats):
         t0 = time.perf_counter()
         res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, concordance=concordance,
-                              device=dev)
+                              branch_triplets=branch_triplets, device=dev)
         runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
@@ -114,6 +115,16 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
                     "total_decisive": int(res.decisive.sum()), "total_concordant": int(res.concordant.sum()),
                     "total_alt1": int(res.alt1.sum()), "total_alt2": int(res.alt2.sum()),
                     "total_other": int(res.other.sum()), "quartet_branches": int(res.quartet_branch.sum())})
+    if branch_triplets:
+        out.update({"branch_triplets_call_s": round(tim["branch_triplets"], 5),
+                    "branch_triplets_call_s_min_median_max":
+                        [round(x, 5) for x in _spread([r[1]["branch_triplets"] for r in runs])],
+                    "total_bt_total": int(res.bt_total.sum()), "total_bt_concordant": int(res.bt_concordant.sum()),
+                    "total_bt_alt1": int(res.bt_alt1.sum()), "total_bt_alt2": int(res.bt_alt2.sum()),
+                    "total_bt_fan": int(res.bt_fan.sum()), "branches_with_triples": int((res.bt_total > 0).sum())})
+        if triplets:
+            out["triplets_call_s_min_median_max"] = [round(x, 5) for x in _spread([r[1]["triplets"] for r in runs])]
+            out["branch_triplets_over_triplets"] = round(tim["branch_triplets"] / tim["triplets"], 3)
     return out
 
 
@@ -129,16 +140,18 @@ def main() -> None:
     ap.add_argument("--triplets", action="store_true", help="also count the rooted triplet terms")
     ap.add_argument("--conflicts", action="store_true", help="also count the clade conflicts")
     ap.add_argument("--concordance", action="store_true", help="also count the branch concordance factors")
+    ap.add_argument("--branch-triplets", action="store_true", help="also count the per-branch triplet support")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
-                        conflicts=args.conflicts, concordance=args.concordance, device=dev)  # warm-up
+                        conflicts=args.conflicts, concordance=args.concordance, branch_triplets=args.branch_triplets,
+                        device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
             print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar,
-                                 args.concordance)), flush=True)
+                                 args.concordance, args.branch_triplets)), flush=True)
 
 
 if __name__ == "__main__":
