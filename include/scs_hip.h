@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_score_branch_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -578,6 +578,37 @@ int scs_debug_gram(scs_ctx *ctx, const double *a, const double *b, int32_t n, in
 /* y (rows x b) = S[row block] * x for a host x (V x b): one launch of the
  * SYMM kernel with the graph's degree scaling. */
 int scs_debug_apply(scs_ctx *ctx, scs_graph *graph, const double *x, int32_t b, double *y);
+
+/* scs_debug_apply through ONE solver object for `reps` consecutive applications, so that the symmetric
+ * schedule's tile list runs forwards, backwards, forwards, ... as it does in scs_fiedler's loop: y_out
+ * (reps x rows x b) receives every application's product.  image != 0: the single-precision image of W is
+ * made if the graph has none and the products come from it (b = 4 only); a graph whose shape keeps
+ * scs_fiedler from streaming an image (matrix-free, SCS_BUILD_UPPER, fewer than 4096 vertices, no memory) is
+ * refused with an error, never served from W (the loop's own switches, SCS_LOWP and the legacy loop, are
+ * not looked at).  info_out[8] reports what ran: [0] symmetric schedule
+ * (k_symm_tri) or not (k_symm), [1] image, [2] tiles per application (0 for k_symm), [3] column
+ * segments, [4] tile width in columns (0 for k_symm), [5] applications that streamed the image,
+ * [6] SCS_BUILD_UPPER partial products, [7] matrix-free.  The partial-sum buffers are filled with NaN
+ * patterns before every application: a partial sum no tile wrote shows in the product. */
+int scs_debug_apply_ex(scs_ctx *ctx, scs_graph *graph, const double *x, int32_t b, int32_t image,
+                       int32_t reps, double *y_out, int32_t *info_out);
+
+/* scs_debug_gram on column blocks of wider panels, as the solver calls it: out (ka x kb) = A^T B with
+ * A = columns [a_col0, a_col0 + ka) of the host panel a (n x lda, row-major), B likewise; a == b with
+ * lda == ldb is ONE device panel (two blocks of Q).  gram_blocks (1 ... 1024) caps the number of
+ * per-workgroup partials, scs_fiedler's `gram_blocks`. */
+int scs_debug_gram_ex(scs_ctx *ctx, const double *a, int32_t lda, int32_t a_col0, int32_t ka,
+                      const double *b, int32_t ldb, int32_t b_col0, int32_t kb, int32_t n,
+                      int32_t use_mfma, int32_t gram_blocks, double *out);
+
+/* One launch of the panel update kernel on host operands: Y = alpha * Y + sign * A C with Y = columns
+ * [y_col0, y_col0 + kc) of the panel y (n x ldy), A = columns [a_col0, a_col0 + ka) of a (n x lda), C
+ * (ka x kc, leading dimension ldc); kc <= 16, ka <= 48.  The whole panel y comes back, so that the
+ * columns beside the block can be checked.  a == y with lda == ldy is ONE device panel (in place, or two
+ * blocks of Q). */
+int scs_debug_update(scs_ctx *ctx, double *y, int32_t ldy, int32_t y_col0, int32_t kc, double alpha,
+                     const double *a, int32_t lda, int32_t a_col0, int32_t ka, const double *c,
+                     int32_t ldc, double sign, int32_t n);
 
 /* One grouped round of ncclSend + ncclRecv from this rank to itself through the wrapper the
  * shared build's tile exchange uses (ncclGroupStart ... ncclGroupEnd, ncclFloat64, the

@@ -363,6 +363,30 @@ class Device:
                                           b.shape[1], int(use_mfma), nv.dptr(out)))
         return out
 
+    def debug_gram_ex(self, a: np.ndarray, a_col0: int, ka: int, b: np.ndarray, b_col0: int, kb: int,
+                      use_mfma: bool, gram_blocks: int = 256) -> np.ndarray:
+        """``A^T B`` for column blocks of the row-major panels ``a`` and ``b`` (``scs_debug_gram_ex``);
+        passing the same array twice makes it one device panel."""
+        assert a.dtype == np.float64 and a.flags.c_contiguous and a.ndim == 2
+        assert b.dtype == np.float64 and b.flags.c_contiguous and b.ndim == 2 and b.shape[0] == a.shape[0]
+        out = np.empty((ka, kb))
+        nv.check(self._lib.scs_debug_gram_ex(self._ctx, nv.dptr(a), a.shape[1], a_col0, ka, nv.dptr(b),
+                                             b.shape[1], b_col0, kb, a.shape[0], int(use_mfma),
+                                             int(gram_blocks), nv.dptr(out)))
+        return out
+
+    def debug_update(self, y: np.ndarray, y_col0: int, kc: int, alpha: float, a: np.ndarray, a_col0: int,
+                     ka: int, c: np.ndarray, sign: float) -> None:
+        """``y[:, y_col0:+kc] = alpha * y[:, y_col0:+kc] + sign * a[:, a_col0:+ka] @ c[:, :kc]`` in place on
+        the host panel ``y`` through one launch of the update kernel (``scs_debug_update``); ``a is y``
+        makes them one device panel."""
+        for m in (y, a, c):
+            assert m.dtype == np.float64 and m.flags.c_contiguous and m.ndim == 2
+        assert a.shape[0] == y.shape[0] and c.shape[0] == ka
+        nv.check(self._lib.scs_debug_update(self._ctx, nv.dptr(y), y.shape[1], y_col0, kc, float(alpha),
+                                            nv.dptr(a), a.shape[1], a_col0, ka, nv.dptr(c), c.shape[1],
+                                            float(sign), y.shape[0]))
+
 
 class DeviceForest:
     """A source forest resident in HBM (``scs_forest``): preorder node arrays, and -- for the
@@ -734,6 +758,19 @@ class DeviceGraph:
         nv.check(self.dev._lib.scs_debug_apply(self.dev._ctx, self._h, nv.dptr(x), x.shape[1],
                                                nv.dptr(y)))
         return y
+
+    APPLY_INFO = ("symmetric", "image", "tiles", "segments", "tile_width", "n_apply32", "partial", "matrix_free")
+
+    def apply_ex(self, x: np.ndarray, image: bool = False, reps: int = 1):
+        """``reps`` consecutive SYMM applications by one solver object (``scs_debug_apply_ex``): the
+        products (reps x rows x b) and a dict of what ran (``APPLY_INFO``)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        n, rb, re_ = self.shape
+        y = np.empty((reps, re_ - rb, x.shape[1]))
+        info = np.zeros(8, dtype=np.int32)
+        nv.check(self.dev._lib.scs_debug_apply_ex(self.dev._ctx, self._h, nv.dptr(x), x.shape[1], int(image),
+                                                  int(reps), nv.dptr(y), nv.iptr(info)))
+        return y, dict(zip(self.APPLY_INFO, (int(v) for v in info)))
 
     def fiedler(self, x_init: np.ndarray | None = None, tol: float = DEFAULT_TOL,
                 max_iter: int = DEFAULT_MAX_ITER, block: int = 0):

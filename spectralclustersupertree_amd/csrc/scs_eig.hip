@@ -971,9 +971,29 @@ __device__ __forceinline__ void sum_partials(const double *__restrict__ partial,
 __global__ __launch_bounds__(256) void k_small_eig(const double *__restrict__ a, int n,
                                                     double *__restrict__ w, double *__restrict__ v) {
     __shared__ jacobi_lds s;
+    // The sweeps are written for matrices of order one (the solver's: S and its Rayleigh-Ritz projections):
+    // jacobi_rot leaves a pair alone when dl^2 + a_pq^2 is outside 1e-290 ... 1e290, the convergence test squares the entries, and
+    // -1e30 on the diagonal marks a dead direction.  A matrix far from that range is solved as a power of
+    // two times one of order one -- exact up to the underflow of entries that are negligible beside the
+    // largest; one within 2^-256 ... 2^256 is not touched at all.
+    double big = 0.0;
     for (int e = threadIdx.x; e < n * n; e += 256) {
         const int i = e / n, j = e - i * n;
-        s.a[i][j] = 0.5 * (a[i * n + j] + a[j * n + i]);
+        big = fmax(big, fabs(0.5 * a[i * n + j] + 0.5 * a[j * n + i]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) big = fmax(big, __shfl_xor(big, o, 64));
+    if ((threadIdx.x & 63) == 0) s.red[threadIdx.x >> 6] = big;
+    __syncthreads();
+    big = fmax(fmax(s.red[0], s.red[1]), fmax(s.red[2], s.red[3]));
+    const int ex = (big > 0.0 && big < INFINITY) ? ilogb(big) : 0;
+    const int sh = (ex >= 256 || ex <= -256) ? -ex : 0;
+    __syncthreads();
+    for (int e = threadIdx.x; e < n * n; e += 256) {
+        const int i = e / n, j = e - i * n;
+        const double x = 0.5 * (a[i * n + j] + a[j * n + i]);
+        // (halved before they are added where the sum itself would overflow)
+        s.a[i][j] = sh ? ldexp(0.5 * a[i * n + j], sh) + ldexp(0.5 * a[j * n + i], sh) : x;
     }
     __syncthreads();
     jacobi_eig(s, n);
@@ -981,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_small_eig(const double *__restrict__ a,
         const int i = e / n, k = e - i * n;
         v[i * n + k] = s.e[i][s.perm[k]];
     }
-    if (threadIdx.x < n) w[threadIdx.x] = s.w[threadIdx.x];
+    if (threadIdx.x < n) w[threadIdx.x] = sh ? ldexp(s.w[threadIdx.x], -sh) : s.w[threadIdx.x];
 }
 
 // ---------------------------------------------------------------------------
@@ -3901,6 +3921,138 @@ extern "C" int scs_debug_apply(scs_ctx *ctx, scs_graph *g, const double *x, int3
     SCS_TRY(sv.launch_symm(sv.z.d(), sv.yloc.d()));
     SCS_HIP_CHECK(hipMemcpyAsync(y, sv.yloc.d() + (g->upper ? (size_t)g->row_begin * b : 0),
                                  (size_t)sv.rows * b * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SCS_OK;
+}
+
+// scs_debug_apply with ONE solver object for `reps` applications (the tile lists alternate as in the loop),
+// optionally on the single-precision image, and a report of what ran
+extern "C" int scs_debug_apply_ex(scs_ctx *ctx, scs_graph *g, const double *x, int32_t b, int32_t image,
+                                  int32_t reps, double *y_out, int32_t *info_out) {
+    SCS_REQUIRE(ctx && g && x && y_out && info_out, "scs_debug_apply_ex: null argument");
+    SCS_REQUIRE(b == 4 || b == 8 || b == 12 || b == 16, "scs_debug_apply_ex: b must be 4, 8, 12 or 16");
+    SCS_REQUIRE(reps >= 1 && reps <= 64, "scs_debug_apply_ex: reps must be in [1, 64]");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    if (image) {
+        SCS_REQUIRE(!g->mf, "scs_debug_apply_ex: a matrix-free graph has no image");
+        SCS_REQUIRE(b == 4, "scs_debug_apply_ex: the image is streamed at block width 4 (asked: %d)", b);
+        SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, true));
+    }
+    SCS_TRY(scs_graph_prepare_degrees(ctx, g));
+    solver sv;
+    sv.ctx = ctx;
+    sv.g = g;
+    sv.s = ctx->stream;
+    sv.n = g->n;
+    sv.b = b;
+    sv.rows = g->row_end - g->row_begin;
+    sv.world = ctx->comm.world;
+    const int n = g->n;
+    dbuf dx;
+    SCS_TRY(dx.alloc((size_t)n * b * 8));
+    SCS_TRY(sv.alloc_symm_buffers());
+    if (image) {
+        // scs_fiedler's own condition for streaming the image: nothing else is ever run on it
+        const bool usable = g->have_w32 && n >= 4096 &&
+                            (sv.tri ? sv.tri_ct == 2 : (sv.world > 1 && !g->upper && !sv.part_mode));
+        if (!usable) {
+            scs_set_error("scs_debug_apply_ex: no image for this graph (%s)",
+                          !g->have_w32 ? "it could not be made" : "the solver does not stream one at this size");
+            return SCS_EUNSUP;
+        }
+        sv.use32 = true;
+    }
+    const size_t out_rows = (size_t)(g->upper ? n : sv.rows);
+    SCS_TRY(sv.yloc.alloc(out_rows * b * 8));
+    SCS_HIP_CHECK(hipMemcpyAsync(dx.p, x, (size_t)n * b * 8, hipMemcpyHostToDevice, ctx->stream));
+    k_scale_rows<<<(n * b + 255) / 256, 256, 0, ctx->stream>>>(dx.d(), b, 0, b, n, g->d_dinv, sv.z.d(), sv.ldz);
+    int tiles = 0;
+    for (int r = 0; r < reps; ++r) {
+        // every application has to write every partial sum it adds up: what an earlier one left must not
+        // stand in for a tile that was dropped
+        if (sv.tri) {  // (the sizes alloc_symm_buffers gave them)
+            const size_t slab = (size_t)n * b * 8;
+            const size_t n_rb = g->upper ? (size_t)(sv.tri_rb_hi - sv.tri_rb_lo) : (size_t)((n + TRI_TH - 1) / TRI_TH);
+            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_pdir.p, 0xFF, (size_t)std::max(sv.tri_nct, sv.tri32_nct) * slab,
+                                         ctx->stream));
+            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_ptr.p, 0xFF, n_rb * slab, ctx->stream));
+        }
+        if (!g->mf) SCS_HIP_CHECK(hipMemsetAsync(sv.ypart.p, 0xFF, sv.ypart_cap * 8, ctx->stream));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0xFF, out_rows * b * 8, ctx->stream));
+        SCS_TRY(sv.launch_symm(sv.z.d(), sv.yloc.d()));
+        SCS_HIP_CHECK(hipMemcpyAsync(y_out + (size_t)r * sv.rows * b,
+                                     sv.yloc.d() + (g->upper ? (size_t)g->row_begin * b : 0),
+                                     (size_t)sv.rows * b * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (sv.tri) tiles = sv.use32 ? sv.tri32_ntiles : sv.tri_ntiles;
+    info_out[0] = sv.tri ? 1 : 0;
+    info_out[1] = sv.use32 ? 1 : 0;
+    info_out[2] = tiles;
+    info_out[3] = sv.last_nseg;
+    info_out[4] = sv.tri ? (sv.use32 ? 512 : sv.tri_ct * 128) : 0;
+    info_out[5] = sv.n_apply32;
+    info_out[6] = sv.part_mode ? 1 : 0;
+    info_out[7] = g->mf ? 1 : 0;
+    return SCS_OK;
+}
+
+// scs_debug_gram on column sub-blocks of wider host panels, with the caller's count of partials
+extern "C" int scs_debug_gram_ex(scs_ctx *ctx, const double *a, int32_t lda, int32_t a_col0, int32_t ka,
+                                 const double *b, int32_t ldb, int32_t b_col0, int32_t kb, int32_t n,
+                                 int32_t use_mfma, int32_t gram_blocks, double *out) {
+    SCS_REQUIRE(ctx && a && b && out, "scs_debug_gram_ex: null argument");
+    SCS_REQUIRE(n >= 1 && ka >= 1 && ka <= 48 && kb >= 1 && kb <= 48, "scs_debug_gram_ex: bad shape");
+    SCS_REQUIRE(a_col0 >= 0 && a_col0 + ka <= lda && b_col0 >= 0 && b_col0 + kb <= ldb,
+                "scs_debug_gram_ex: the column block leaves the panel");
+    SCS_REQUIRE(gram_blocks >= 1 && gram_blocks <= 1024, "scs_debug_gram_ex: gram_blocks must be in [1, 1024]");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    solver sv;
+    sv.ctx = ctx;
+    sv.s = ctx->stream;
+    sv.n = n;
+    sv.gram_blocks = gram_blocks;
+    const bool same = a == b && lda == ldb;  // two blocks of one panel, as gram(Q, 3b, 2b, R, 3b, b)
+    dbuf da, db, dout;
+    SCS_TRY(da.alloc((size_t)n * lda * 8));
+    if (!same) SCS_TRY(db.alloc((size_t)n * ldb * 8));
+    SCS_TRY(dout.alloc((size_t)ka * kb * 8));
+    SCS_TRY(sv.part.alloc((size_t)1024 * 48 * 48 * 8));
+    SCS_HIP_CHECK(hipMemsetAsync(sv.part.p, 0xFF, (size_t)1024 * 48 * 48 * 8, ctx->stream));
+    SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * lda * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!same) SCS_HIP_CHECK(hipMemcpyAsync(db.p, b, (size_t)n * ldb * 8, hipMemcpyHostToDevice, ctx->stream));
+    SCS_TRY(sv.gram(da.d() + a_col0, lda, ka, (same ? da.d() : db.d()) + b_col0, ldb, kb, dout.d(), use_mfma != 0));
+    SCS_HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)ka * kb * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SCS_OK;
+}
+
+// one k_update launch on host operands; the whole y panel travels both ways
+extern "C" int scs_debug_update(scs_ctx *ctx, double *y, int32_t ldy, int32_t y_col0, int32_t kc, double alpha,
+                                const double *a, int32_t lda, int32_t a_col0, int32_t ka, const double *c,
+                                int32_t ldc, double sign, int32_t n) {
+    SCS_REQUIRE(ctx && y && a && c, "scs_debug_update: null argument");
+    SCS_REQUIRE(n >= 1 && kc >= 1 && kc <= MAXB && ka >= 1 && ka <= 3 * MAXB, "scs_debug_update: bad shape");
+    SCS_REQUIRE(y_col0 >= 0 && y_col0 + kc <= ldy && a_col0 >= 0 && a_col0 + ka <= lda && ldc >= kc,
+                "scs_debug_update: the column block leaves the panel");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    solver sv;
+    sv.ctx = ctx;
+    sv.s = ctx->stream;
+    sv.n = n;
+    const bool same = a == y && lda == ldy;  // in place, or two blocks of one panel
+    dbuf dy, da, dc;
+    SCS_TRY(dy.alloc((size_t)n * ldy * 8));
+    if (!same) SCS_TRY(da.alloc((size_t)n * lda * 8));
+    SCS_TRY(dc.alloc((size_t)ka * ldc * 8));
+    SCS_HIP_CHECK(hipMemcpyAsync(dy.p, y, (size_t)n * ldy * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (!same) SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * lda * 8, hipMemcpyHostToDevice, ctx->stream));
+    SCS_HIP_CHECK(hipMemcpyAsync(dc.p, c, (size_t)ka * ldc * 8, hipMemcpyHostToDevice, ctx->stream));
+    SCS_TRY(sv.update(dy.d() + y_col0, ldy, kc, alpha, (same ? dy.d() : da.d()) + a_col0, lda, ka, dc.d(), ldc, sign));
+    SCS_HIP_CHECK(hipMemcpyAsync(y, dy.p, (size_t)n * ldy * 8, hipMemcpyDeviceToHost, ctx->stream));
     SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return SCS_OK;
 }
