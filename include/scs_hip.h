@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets and scs_score_taxon_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -388,6 +388,24 @@ int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n
                               const int32_t *taxon, int32_t max_batch_trees, int64_t *n_bt_total,
                               int64_t *n_bt_concordant, int64_t *n_bt_alternative, int64_t *bt_total,
                               int64_t *bt_concordant, int64_t *bt_alt1, int64_t *bt_alt2);
+
+/* Per-taxon triplet support, same inputs and SCS_EINVAL cases as scs_score_supertree: the
+ * triplet terms of scs_score_triplets attributed to the taxa of every triple, to name the misplaced ones.  Per
+ * supertree tip x, summed over the source trees T on a leaf set L with x in L and m = |L| >= 3, S' = S|L:
+ *   tx_trees[x]  = the number of such trees,      tx_total[x]  = sum of C(m - 1, 2), the triples of L that hold x,
+ *   tx_super[x]  = those of them S' resolves,     tx_source[x] = those T resolves,
+ *   tx_shared[x] = those resolved alike in both   (per-taxon triplet distance = tx_super + tx_source - 2 tx_shared).
+ * Every triple has three taxa: sum_x tx_shared = 3 sum_t t_shared, likewise tx_super and tx_source, and
+ * sum_x tx_total = 3 sum_t C(m, 3).  The outputs are indexed by taxon id and have one entry per supertree tip, so the
+ * tips' ids must be below their number: SCS_EINVAL otherwise, and, as for scs_score_triplets, for a source tree of
+ * more than 327 679 leaves.  Counts are unweighted and exact; taxa no source holds and trees of fewer than 3 leaves
+ * give zeros; output pointers may be null.  max_lds_bytes > 0 caps the LDS a workgroup of the pair kernel takes beyond
+ * one pair of bitset rows (tests: the nodes whose arrays do not fit are counted through global memory); 0: the
+ * default, all a workgroup can take. */
+int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                             const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                             int64_t *tx_trees, int64_t *tx_total, int64_t *tx_super, int64_t *tx_source,
+                             int64_t *tx_shared);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

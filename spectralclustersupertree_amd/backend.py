@@ -238,6 +238,31 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_taxon_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0,
+                             lds_bytes: int = 0) -> dict:
+        """``scs_score_taxon_triplets``: per-taxon triplet support, with the inputs of ``score``.  Returns int64
+        arrays ``tx_trees``, ``tx_total``, ``tx_super``, ``tx_source``, ``tx_shared`` with one entry per supertree tip,
+        indexed by taxon id (the tips' ids must be 0 .. tips - 1, as ``supertree_arrays`` numbers them).
+        ``lds_bytes`` > 0 caps the LDS one workgroup of the pair kernel takes (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        n_nodes = len(parent)
+        if taxon.shape != (n_nodes,):
+            msg = "parent and taxon must have one entry per supertree node"
+            raise ValueError(msg)
+        n_tips = n_nodes - len(np.unique(parent[1:]))
+        out = {k: np.zeros(n_tips, dtype=np.int64)
+               for k in ("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")}
+        rc = self._lib.scs_score_taxon_triplets(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                                int(batch_trees), int(lds_bytes),
+                                                *(nv.lptr(v) for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_taxon_triplets: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

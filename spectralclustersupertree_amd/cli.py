@@ -56,11 +56,18 @@ from spectralclustersupertree_amd import __version__
 @click.option("--branch-triplets-out", default=None,
               help="Also write the supertree with each quartet branch's concordant/alt1/alt2/total triple counts as "
                    "its node name (Newick).")
+@click.option("--taxon-triplets", default=False, is_flag=True,
+              help="Names the per-taxon triplet support that --taxa-out counts and writes; it switches nothing on by "
+                   "itself and needs --taxa-out.")
+@click.option("--taxa-out", default=None,
+              help="Also write a TSV with one row per supertree tip (taxon, name, tx_trees, tx_total, tx_super, "
+                   "tx_source, tx_shared, triplet_distance): the rooted triples that hold the taxon, over its sources.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
         concordance_out: str | None = None, branches_out: str | None = None, branch_triplets: bool = False,
-        branch_triplets_out: str | None = None) -> None:
+        branch_triplets_out: str | None = None, taxon_triplets: bool = False,
+        taxa_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
@@ -73,6 +80,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         raise click.UsageError(msg)
     if branch_triplets and not (scores_out or branches_out):
         msg = "--branch-triplets needs --scores-out or --branches-out"
+        raise click.UsageError(msg)
+    if taxon_triplets and not taxa_out:
+        msg = "--taxon-triplets needs --taxa-out"
         raise click.UsageError(msg)
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
@@ -87,14 +97,18 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     team = default_team()
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
-        if scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out:
+        if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
+                or taxa_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
                                      conflicts=conflicts or conflict_out is not None,
                                      concordance=concordance or concordance_out is not None
                                      or branches_out is not None,
-                                     branch_triplets=branch_triplets or branch_triplets_out is not None)
+                                     branch_triplets=branch_triplets or branch_triplets_out is not None,
+                                     taxon_triplets=taxa_out is not None)
+            if taxa_out:
+                Path(taxa_out).write_text(result.taxon_table())
             if branch_triplets_out:
                 Path(branch_triplets_out).write_text(
                     result.annotate_branch_triplets().get_newick(with_node_names=True) + "\n")

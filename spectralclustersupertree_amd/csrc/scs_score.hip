@@ -1189,6 +1189,328 @@ __global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restri
     }
 }
 
+// ---- per-taxon triplet support (scs_score_taxon_triplets) ----
+//
+// The per-tree sums of section 15 handed to the leaves of every triple.  A shared triple ab|c is counted at one pair
+// (y, z): with I = I(y, z) and J = I(py,pz) - I(y,pz) - I(py,z) + I(y,z), every leaf of cl(y) ∩ cl(z) is a or b in
+// (I - 1) J of the pair's triples and every leaf of (cl(py) ∖ cl(y)) ∩ (cl(pz) ∖ cl(z)) is c in C(I, 2) of them.  T's
+// clusters are ranges of T positions, so for a fixed z both are interval-stabbing sums: difference arrays over the
+// *rank* of a T position among the set bits of cl(z) / cl(pz) -- the tp_count values the sweep reads anyway -- then a
+// prefix sum, and every leaf of z (of pz ∖ z) reads the entry of its own rank.
+//   k_trip_nodes (unchanged) lists the nodes; k_tx_single, one thread per listed node: the single-tree terms
+//     (tx_source over T positions, tx_super over S' positions) as difference rows, and every z into the list of the
+//     bin that holds its two difference arrays (|z| + 1 and |pz| + 1 entries);
+//   k_tx_pairs<false>: the k_trip_pairs grid once per LDS bin, bitset rows and difference arrays in LDS;
+//   k_tx_pairs<true>: the nodes whose arrays fit no bin, one at a time by a bounded grid of persistent workgroups, the
+//     arrays in a slab of the workspace per workgroup (global 64-bit atomics, loads and stores past the L1);
+//   k_tx_scan: per-tree prefix sums of the two single-tree rows; k_tx_fold: the batch's per-leaf sums into the
+//     per-taxon outputs (64-bit atomics: integers, so order-free).
+// Every intermediate is a count of triples of one tree: below m^3 < 2^63 for the m <= 327 679 the rows allow.
+
+constexpr int TX_BINS = 3;           // LDS bins; list TX_BINS is the slab's
+constexpr int TX_SCRATCH = 64;       // bytes ahead of the rows: the wave sums of the workgroup scan
+constexpr int TX_SLAB_PAD = 8;       // entries behind a slab's arrays: the same wave sums
+constexpr int TX_SLAB_WGS = 256;     // persistent workgroups of the slab path, at most
+constexpr uint64_t TX_SLAB_BYTES = (uint64_t)128 << 20;  // all slabs together (fewer workgroups for larger trees)
+// LDS a workgroup of each bin aims at: 8, 3 and 1 workgroups per CU (the last is all a workgroup can take)
+constexpr int TX_BIN_BUDGET[TX_BINS] = {20 << 10, 52 << 10, TP_LDS_MAX};
+// ... and the S' nodes a workgroup takes at most: the last bin gives all of its LDS to one node's arrays
+constexpr int TX_BIN_ZMAX[TX_BINS] = {TP_ZMAX, 2, 1};
+constexpr int TX_SMALL = 192;        // entries a node of bin 0 keeps when the rows grow
+
+struct sc_tx_bins {
+    int dcap[TX_BINS];  // entries (both arrays) a node of the bin may take; 0: the bin is not used
+};
+
+__device__ __forceinline__ void tx_mark(unsigned long long *__restrict__ row, int n, int i, unsigned long long v) {
+    if (i < n && v) atomicAdd(row + i, v);  // (entry n is read by no leaf)
+}
+
+// a node {lo, hi, parent lo, parent hi} of one tree alone: its leaves take (s - 1)(ps - s) each, the parent's other
+// leaves C(s, 2) each
+__device__ __forceinline__ void tx_single(unsigned long long *__restrict__ row, int n, const int4 v) {
+    const int64_t s = v.y - v.x, ps = v.w - v.z;
+    const unsigned long long a = (unsigned long long)((s - 1) * (ps - s)), b = (unsigned long long)(s * (s - 1) / 2);
+    tx_mark(row, n, v.x, a - b);
+    tx_mark(row, n, v.y, b - a);
+    tx_mark(row, n, v.z, b);
+    tx_mark(row, n, v.w, 0ull - b);
+}
+
+// one thread per leaf slot i of a tree: node i of T's list and node i of S''s list
+__global__ void __launch_bounds__(SC_THREADS) k_tx_single(const int64_t *__restrict__ off, int nb,
+                                                          const int4 *__restrict__ ylist,
+                                                          const int4 *__restrict__ zlist,
+                                                          const int32_t *__restrict__ ycnt,
+                                                          const int32_t *__restrict__ zcnt, sc_tx_bins bins, int64_t Lb,
+                                                          int32_t *__restrict__ zbin, int32_t *__restrict__ zbcnt,
+                                                          unsigned long long *__restrict__ d_src,
+                                                          unsigned long long *__restrict__ d_sup, int has_slab,
+                                                          unsigned *__restrict__ flags) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = off[0] + q;
+    if (p >= off[nb]) return;
+    const int t = sc_tree_of(off, nb, p);
+    const int64_t base = off[t] - off[0];
+    const int n = (int)(off[t + 1] - off[t]);
+    const int i = (int)(q - base);
+    if (i < ycnt[t]) tx_single(d_src + base, n, ylist[base + i]);
+    if (i < zcnt[t]) {
+        const int4 z = zlist[base + i];
+        tx_single(d_sup + base, n, z);
+        const int need = (z.y - z.x) + (z.w - z.z) + 2;
+        int bin = TX_BINS;
+        for (int c = TX_BINS - 1; c >= 0; --c)
+            if (need <= bins.dcap[c]) bin = c;
+        // (the host launches the slab path by its own reading of the same plan: a node it does not expect must not
+        // vanish)
+        if (bin == TX_BINS && !has_slab) atomicOr(flags, 8u);
+        const int slot = atomicAdd(zbcnt + (int64_t)bin * nb + t, 1);
+        zbin[bin * Lb + base + slot] = i;
+    }
+}
+
+// the difference arrays live in LDS or, for the slab path, in global memory that other workgroups' lines may share
+// a cache with: those loads and stores go past the L1, as the atomics do
+template <bool SLAB>
+__device__ __forceinline__ unsigned long long tx_ld(const unsigned long long *p) {
+    if constexpr (SLAB) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+
+template <bool SLAB>
+__device__ __forceinline__ void tx_st(unsigned long long *p, unsigned long long v) {
+    if constexpr (SLAB) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+
+template <bool SLAB>
+__device__ __forceinline__ void tx_sync() {
+    if constexpr (SLAB) __threadfence();
+    __syncthreads();
+}
+
+// inclusive prefix sums of d[0, total) by the workgroup, four entries per thread and round; ws: SC_THREADS / 64 sums
+template <bool SLAB>
+__device__ __forceinline__ void tx_scan(unsigned long long *d, int total, unsigned long long *ws) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0;
+    for (int c = 0; c < total; c += 4 * SC_THREADS) {
+        const int i0 = c + 4 * threadIdx.x;
+        unsigned long long v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = i0 + e < total ? tx_ld<SLAB>(d + i0 + e) : 0ull;
+        v[1] += v[0];
+        v[2] += v[1];
+        v[3] += v[2];
+        unsigned long long incl = v[3];
+        for (int s = 1; s < 64; s <<= 1) {
+            const unsigned long long y = __shfl_up(incl, s, 64);
+            if (lane >= s) incl += y;
+        }
+        if (lane == 63) tx_st<SLAB>(ws + wave, incl);
+        tx_sync<SLAB>();
+        unsigned long long before = carry + incl - v[3];
+        for (int w = 0; w < SC_THREADS / 64; ++w) {
+            const unsigned long long s = tx_ld<SLAB>(ws + w);
+            if (w < wave) before += s;
+            carry += s;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (i0 + e < total) tx_st<SLAB>(d + i0 + e, v[e] + before);
+        tx_sync<SLAB>();
+    }
+}
+
+// nz S' nodes of the tree at base (entries zi[0, nz) of its list) against all of T's nodes: rows [2 nz][W] in LDS,
+// diff: node j's `in` array (|z| + 1 entries) and `out` array (|pz| + 1) one after the other.  Every array sums to
+// zero, so one scan over all of them gives each its own prefix sums.
+template <bool SLAB, int ZMAX>
+__device__ __forceinline__ void tx_block(int2 *rows, unsigned long long *diff, unsigned long long *ws, int64_t base,
+                                         const int4 *__restrict__ zlist, const int32_t *__restrict__ zi, int nz,
+                                         const int4 *__restrict__ ylist, int ny, const int2 *__restrict__ tp, int W,
+                                         unsigned long long *__restrict__ acc) {
+    const int nrow = 2 * nz;
+    int oin[ZMAX], oout[ZMAX], total = 0;
+#pragma unroll
+    for (int j = 0; j < ZMAX; ++j) {
+        oin[j] = oout[j] = 0;
+        if (j >= nz) continue;
+        const int4 z = zlist[base + zi[j]];
+        oin[j] = total;
+        oout[j] = total + (z.y - z.x) + 1;
+        total = oout[j] + (z.w - z.z) + 1;
+    }
+    for (int i = threadIdx.x; i < nrow * W; i += SC_THREADS) rows[i] = make_int2(0, 0);
+    for (int i = threadIdx.x; i < total; i += SC_THREADS) tx_st<SLAB>(diff + i, 0ull);
+    __syncthreads();
+    unsigned *bits = reinterpret_cast<unsigned *>(rows);  // (word i of the image: .x of entry i / 2)
+    for (int j = 0; j < nz; ++j) {
+        const int4 z = zlist[base + zi[j]];
+        for (int k = z.x + threadIdx.x; k < z.y; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j) * W + (x >> 5)), 1u << (x & 31));
+        }
+        for (int k = z.z + threadIdx.x; k < z.w; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j + 1) * W + (x >> 5)), 1u << (x & 31));
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < nrow; r += SC_THREADS / 64) {
+        int2 *row = rows + r * W;
+        int run = 0;
+        for (int c = 0; c < W; c += 64) {
+            const int i = c + lane;
+            const int v = i < W ? __popc((unsigned)row[i].x) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    tx_sync<SLAB>();  // (and the zeroed arrays are in place before the first atomic)
+    // the sweep: the eight counts of k_trip_pairs are the ranks the difference arrays are indexed by
+    for (int i = threadIdx.x; i < ny; i += SC_THREADS) {
+        const int4 y = ylist[base + i];  // T positions [y.x, y.y) of y, [y.z, y.w) of py
+        const int wa = y.x >> 5, wb = y.y >> 5, wc = y.z >> 5, wd = y.w >> 5;
+        const unsigned ma = (1u << (y.x & 31)) - 1u, mb = (1u << (y.y & 31)) - 1u;
+        const unsigned mc = (1u << (y.z & 31)) - 1u, md = (1u << (y.w & 31)) - 1u;
+#pragma unroll
+        for (int j = 0; j < ZMAX; ++j) {
+            if (j >= nz) break;
+            const int2 *rz = rows + 2 * j * W, *rp = rz + W;
+            const int cza = tp_count(rz, wa, ma), czb = tp_count(rz, wb, mb);
+            const int iyz = czb - cza;
+            if (iyz < 2) continue;
+            const int czc = tp_count(rz, wc, mc), czd = tp_count(rz, wd, md);
+            const int cpa = tp_count(rp, wa, ma), cpb = tp_count(rp, wb, mb);
+            const int cpc = tp_count(rp, wc, mc), cpd = tp_count(rp, wd, md);
+            const int64_t jj = (int64_t)(cpd - cpc) - (cpb - cpa) - (czd - czc) + iyz;
+            if (jj == 0) continue;  // (no leaf takes the third place: nothing to hand out)
+            const unsigned long long a = (unsigned long long)((int64_t)(iyz - 1) * jj);
+            const unsigned long long b = (unsigned long long)((int64_t)iyz * (iyz - 1) / 2);
+            unsigned long long *in = diff + oin[j], *out = diff + oout[j];
+            atomicAdd(in + cza, a);
+            atomicAdd(in + czb, 0ull - a);
+            // py ∖ y = [py.lo, y.lo) ∪ [y.hi, py.hi): an empty side (y the first or last child) adds nothing
+            if (y.x != y.z) {
+                atomicAdd(out + cpc, b);
+                atomicAdd(out + cpa, 0ull - b);
+            }
+            if (y.y != y.w) {
+                atomicAdd(out + cpb, b);
+                atomicAdd(out + cpd, 0ull - b);
+            }
+        }
+    }
+    tx_sync<SLAB>();
+    tx_scan<SLAB>(diff, total, ws);
+    // the leaf pass: S' position k of pz holds T position x; inside z it reads `in` at its rank in cl(z), else `out`
+    // at its rank in cl(pz)
+#pragma unroll
+    for (int j = 0; j < ZMAX; ++j) {
+        if (j >= nz) break;
+        const int4 z = zlist[base + zi[j]];
+        const int2 *rz = rows + 2 * j * W, *rp = rz + W;
+        for (int k = z.z + threadIdx.x; k < z.w; k += SC_THREADS) {
+            const int x = tp[base + k].x;
+            const unsigned m = (1u << (x & 31)) - 1u;
+            const bool inner = k >= z.x && k < z.y;
+            const int r = inner ? oin[j] + tp_count(rz, x >> 5, m) : oout[j] + tp_count(rp, x >> 5, m);
+            const unsigned long long v = tx_ld<SLAB>(diff + r);
+            if (v) atomicAdd(acc + base + x, v);
+        }
+    }
+}
+
+// SLAB false: one workgroup per (tree t, block of zb of the bin's S' nodes of t), blk and W as in k_trip_pairs, dynamic
+// LDS = TX_SCRATCH + zb (16 W + 8 dcap) bytes.  SLAB true (zb = 1, dynamic LDS = 16 W bytes): the workgroups share
+// the batch's slab-list nodes round robin, each with its own slab of slab_stride entries.
+// zbin / zbcnt: the bin's own list (indices into zlist) and lengths
+template <bool SLAB>
+__global__ void __launch_bounds__(SC_THREADS) k_tx_pairs(const int64_t *__restrict__ blk, int nb,
+                                                         const int64_t *__restrict__ off,
+                                                         const int4 *__restrict__ ylist,
+                                                         const int4 *__restrict__ zlist,
+                                                         const int32_t *__restrict__ ycnt,
+                                                         const int32_t *__restrict__ zbin,
+                                                         const int32_t *__restrict__ zbcnt,
+                                                         const int2 *__restrict__ tp, int zb, int W,
+                                                         unsigned long long *__restrict__ slab, int64_t slab_stride,
+                                                         unsigned long long *__restrict__ acc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tx_lds[];
+    if constexpr (SLAB) {
+        int2 *rows = reinterpret_cast<int2 *>(tx_lds);
+        unsigned long long *diff = slab + (int64_t)blockIdx.x * slab_stride;
+        unsigned long long *ws = diff + slab_stride - TX_SLAB_PAD;
+        int64_t first = 0;  // index of the tree's first slab node among the batch's
+        for (int t = 0; t < nb; ++t) {
+            const int cnt = zbcnt[t];
+            const int64_t base = off[t] - off[0];
+            int j = (int)(((int64_t)blockIdx.x - first % gridDim.x + gridDim.x) % gridDim.x);
+            for (; j < cnt; j += gridDim.x) {
+                tx_block<true, 1>(rows, diff, ws, base, zlist, zbin + base + j, 1, ylist, ycnt[t], tp, W, acc);
+                tx_sync<true>();  // (the rows and the slab are reused)
+            }
+            first += cnt;
+        }
+    } else {
+        unsigned long long *ws = reinterpret_cast<unsigned long long *>(tx_lds);
+        int2 *rows = reinterpret_cast<int2 *>(tx_lds + TX_SCRATCH);
+        const int64_t g = blk[0] + blockIdx.x;
+        const int t = sc_tree_of(blk, nb, g);
+        const int j0 = (int)(g - blk[t]) * zb;
+        const int nz = min(zb, zbcnt[t] - j0);
+        if (nz <= 0) return;  // (the grid counts n - 2 nodes per tree and bin: an upper bound)
+        const int64_t base = off[t] - off[0];
+        unsigned long long *diff = reinterpret_cast<unsigned long long *>(rows + (int64_t)2 * zb * W);
+        tx_block<false, TP_ZMAX>(rows, diff, ws, base, zlist, zbin + base + j0, nz, ylist, ycnt[t], tp, W, acc);
+    }
+}
+
+// inclusive prefix sums of both single-tree rows over every tree's own entries, one workgroup per tree
+__global__ void __launch_bounds__(SC_THREADS) k_tx_scan(const int64_t *__restrict__ off,
+                                                        unsigned long long *__restrict__ d_src,
+                                                        unsigned long long *__restrict__ d_sup) {
+    __shared__ unsigned long long ws[SC_THREADS / 64];
+    const int t = blockIdx.x;
+    const int64_t base = off[t] - off[0];
+    const int n = (int)(off[t + 1] - off[t]);
+    tx_scan<false>(d_src + base, n, ws);
+    tx_scan<false>(d_sup + base, n, ws);
+}
+
+// one thread per leaf of the batch: T position q - base gives its taxon the shared and source sums, S' position
+// q - base gives the taxon of its leaf the super sum; tx: five arrays of n_out entries (trees, total, super, source,
+// shared)
+__global__ void __launch_bounds__(SC_THREADS) k_tx_fold(const int64_t *__restrict__ off, int nb,
+                                                        const int32_t *__restrict__ leaf_taxon,
+                                                        const int2 *__restrict__ tp,
+                                                        const unsigned long long *__restrict__ acc,
+                                                        const unsigned long long *__restrict__ d_src,
+                                                        const unsigned long long *__restrict__ d_sup,
+                                                        unsigned long long *__restrict__ tx, int64_t n_out) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = off[0] + q;
+    if (p >= off[nb]) return;
+    const int t = sc_tree_of(off, nb, p);
+    const int64_t n = off[t + 1] - off[t];
+    if (n < 3) return;
+    const int32_t x = leaf_taxon[p];
+    atomicAdd(tx + x, 1ull);
+    atomicAdd(tx + n_out + x, (unsigned long long)((n - 1) * (n - 2) / 2));
+    if (d_src[q]) atomicAdd(tx + 3 * n_out + x, d_src[q]);
+    if (acc[q]) atomicAdd(tx + 4 * n_out + x, acc[q]);
+    const int32_t xs = leaf_taxon[off[t] + tp[q].x];
+    if (d_sup[q]) atomicAdd(tx + 2 * n_out + xs, d_sup[q]);
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -1412,7 +1734,8 @@ int sc_end(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad) {
         return e == hipErrorOutOfMemory ? SCS_ENOMEM : SCS_EHIP;
     }
     if (bad) {
-        scs_set_error("%s: %s", c.who, (bad & 1u)   ? "a leaf_taxon entry is out of range [0, n_taxa)"
+        scs_set_error("%s: %s", c.who, (bad & 8u)   ? "internal: a node was listed for a slab launch that is not made"
+                                       : (bad & 1u) ? "a leaf_taxon entry is out of range [0, n_taxa)"
                                        : (bad & 2u) ? "a source tree has a taxon the supertree lacks"
                                                     : "a source tree has a taxon twice");
         return SCS_EINVAL;
@@ -1853,5 +2176,192 @@ extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, in
         if (n_bt_concordant) n_bt_concordant[t] = (int64_t)cnt[M + t];
         if (n_bt_alternative) n_bt_alternative[t] = (int64_t)cnt[2 * M + t];
     }
+    return SCS_OK;
+}
+
+namespace {
+
+// the LDS bins of a batch whose rows have W words: nodes per workgroup, entries per node and launch bytes of each
+struct sc_tx_plan {
+    int zb[TX_BINS], lds[TX_BINS];
+    sc_tx_bins bins;
+    int dcap_max;
+};
+
+sc_tx_plan sc_tx_plan_of(int W, int lds_cap) {
+    sc_tx_plan p;
+    p.dcap_max = 0;
+    const int rowb = 16 * W;  // cl(z) and cl(pz)
+    for (int i = 0; i < TX_BINS; ++i) {
+        // (bin 0 grows with the rows, so that eight nodes keep TX_SMALL entries each, up to the budget of bin 1)
+        const int base = i == 0 ? std::min(TX_BIN_BUDGET[1], std::max(TX_BIN_BUDGET[0],
+                                                                      TX_SCRATCH + TP_ZMAX * (rowb + 8 * TX_SMALL)))
+                                : TX_BIN_BUDGET[i];
+        const int budget = std::min(base, lds_cap);
+        // at most half of the budget for rows, the rest for the arrays: no more than the 2 n + 1 entries a node of
+        // the batch can need, at least the 7 of the smallest node
+        const int zb = std::min(TX_BIN_ZMAX[i], std::max(1, budget / (2 * rowb)));
+        const int avail = budget - TX_SCRATCH - zb * rowb;
+        const int dcap = avail > 0 ? std::min(avail / (8 * zb), 64 * W) : 0;
+        p.zb[i] = zb;
+        p.bins.dcap[i] = dcap >= 7 && dcap > p.dcap_max ? dcap : 0;  // (no larger than an earlier bin: never chosen)
+        p.lds[i] = TX_SCRATCH + zb * (rowb + 8 * dcap);
+        p.dcap_max = std::max(p.dcap_max, p.bins.dcap[i]);
+    }
+    return p;
+}
+
+}  // namespace
+
+extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                        const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                        int64_t *tx_trees, int64_t *tx_total, int64_t *tx_super, int64_t *tx_source,
+                                        int64_t *tx_shared) {
+    // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS, as for scs_score_triplets; every
+    // count of one tree is then below m^3 < 2^63
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "scs_score_taxon_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in "
+                "LDS", (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_REQUIRE(max_lds_bytes >= 0, "scs_score_taxon_triplets: max_lds_bytes = %d is negative", max_lds_bytes);
+    // the outputs have one entry per supertree tip: the tips' taxon ids must be below their number
+    int64_t n_out = 0;
+    if (parent && taxon && n_nodes >= 1) {
+        std::vector<char> has_kid((size_t)n_nodes, 0);
+        for (int32_t v = 1; v < n_nodes; ++v)
+            if (parent[v] >= 0 && parent[v] < n_nodes) has_kid[parent[v]] = 1;
+        for (int32_t v = 0; v < n_nodes; ++v) n_out += !has_kid[v];
+        for (int32_t v = 0; v < n_nodes; ++v)
+            SCS_REQUIRE(has_kid[v] || taxon[v] < n_out,
+                        "scs_score_taxon_triplets: tip %d has taxon %d, not below the %lld tips of the supertree", v,
+                        taxon[v], (long long)n_out);
+    }
+    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    // the slab path: needed when a node's arrays (at most 2 m + 1 entries) may exceed the largest bin
+    const int64_t slab_stride = 2 * m_max + 2 + TX_SLAB_PAD;
+    const bool need_slab = 2 * m_max + 1 > sc_tx_plan_of((int)(m_max >> 5) + 1, lds_cap).dcap_max;
+    const int slab_wgs = !need_slab ? 0
+                         : (int)std::min<uint64_t>(TX_SLAB_WGS, std::max<uint64_t>(1, TX_SLAB_BYTES / (slab_stride * 8)));
+    // own arrays: the five outputs per taxon, the first pair workgroup per tree (+ 1) and bin, the slabs; per batch
+    // the two node lists (int4), three sums (shared and source in T order, super in S' order) and the TX_BINS + 1
+    // bin lists per leaf, and per tree the lengths of all those lists
+    const size_t mt = src ? (size_t)src->n_trees : 0;
+    const size_t o_tx = 0, o_blk = sc_up256((size_t)n_out * 40), o_slab = o_blk + sc_up256((mt + 1) * 8 * TX_BINS),
+                 own = o_slab + sc_up256((size_t)slab_wgs * slab_stride * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_taxon_triplets", n_nodes, parent, taxon, max_batch_trees, own,
+                     32 + 24 + 4 * (TX_BINS + 1), 8 + 4 * (TX_BINS + 1), c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_tx = (unsigned long long *)(c.d_extra + o_tx);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    auto *d_slab = (unsigned long long *)(c.d_extra + o_slab);
+    auto *d_ylist = (int4 *)c.d_extra_batch;
+    auto *d_zlist = d_ylist + c.max_lb;
+    auto *d_acc = (unsigned long long *)(d_zlist + c.max_lb);
+    auto *d_dsrc = d_acc + c.max_lb;
+    auto *d_dsup = d_dsrc + c.max_lb;
+    auto *d_zbin = (int32_t *)(d_dsup + c.max_lb);
+    auto *d_ycnt = d_zbin + (TX_BINS + 1) * c.max_lb;
+    // per batch: W words per bitset row (largest tree of the batch) and the plan of its bins; blk: per bin the first
+    // pair workgroup of every tree, ceil((n - 2) / zb) of them (n - 2 bounds the nodes of any list)
+    const size_t n_batches = c.bstart.size() - 1;
+    std::vector<int> words(n_batches);
+    std::vector<sc_tx_plan> plans(n_batches);
+    std::vector<int64_t> blk(((size_t)M + 1) * TX_BINS, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        plans[b] = sc_tx_plan_of(words[b], lds_cap);
+        for (int i = 0; i < TX_BINS; ++i) {
+            int64_t *bl = blk.data() + (size_t)i * (M + 1);
+            for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
+                bl[t + 1] = bl[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + plans[b].zb[i] - 1) / plans[b].zb[i];
+        }
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_tx, 0, (size_t)n_out * 40, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_blk, blk.data(), blk.size() * 8, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_tx_pairs<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                TP_LDS_MAX);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_tx_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * (8 + 4 * (TX_BINS + 1)), s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, (size_t)c.max_lb * 8, s);
+        if (e != hipSuccess) break;
+        sc_trip_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.dep = c.d_dep;
+        a.node = c.d_node;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_tab = c.d_stab;
+        a.s_stride = c.n_gaps;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.ylist = d_ylist;
+        a.zlist = d_zlist;
+        a.ycnt = d_ycnt;
+        a.zcnt = d_ycnt + nb;
+        // k_trip_nodes' own per-tree sums are not wanted here.  They are added at [t], t < nb, of the two rows given
+        // below; a tree has a leaf, so nb <= Lb <= max_lb and the entries lie inside the rows, and the memset after
+        // the launch clears both rows (they are adjacent) before k_tx_single writes its marks
+        a.c_super = d_dsrc;
+        a.c_source = d_dsup;
+        k_trip_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        e = hipMemsetAsync(d_dsrc, 0, (size_t)c.max_lb * 16, s);
+        if (e != hipSuccess) break;
+        int32_t *d_zbcnt = d_ycnt + 2 * nb;
+        const sc_tx_plan &pl = plans[b];
+        const bool slab_launch = slab_wgs > 0 && 2 * ((int64_t)words[b] * 32) > pl.dcap_max;
+        k_tx_single<<<grid_of(Lb), SC_THREADS, 0, s>>>(a.off, nb, d_ylist, d_zlist, a.ycnt, a.zcnt, pl.bins, Lb, d_zbin,
+                                                       d_zbcnt, d_dsrc, d_dsup, slab_launch, c.d_flag);
+        if (!sc_launched(e)) break;
+        for (int i = 0; i < TX_BINS; ++i) {
+            const int64_t *bl = blk.data() + (size_t)i * (M + 1);
+            const int64_t n_wg = bl[t0 + nb] - bl[t0];
+            if (pl.bins.dcap[i] == 0 || n_wg == 0) continue;
+            k_tx_pairs<false><<<(unsigned)n_wg, SC_THREADS, (size_t)pl.lds[i], s>>>(
+                d_blk + (size_t)i * (M + 1) + t0, nb, a.off, d_ylist, d_zlist, a.ycnt, d_zbin + (int64_t)i * Lb,
+                d_zbcnt + (int64_t)i * nb, c.d_mm, pl.zb[i], words[b], nullptr, 0, d_acc);
+            if (!sc_launched(e)) break;
+        }
+        if (e != hipSuccess) break;
+        // k_tx_single lists a node for the slab iff its |z| + |pz| + 2 > pl.dcap_max.  That is at most 2 n + 1 < 64 W,
+        // and dcap_max only grows when W shrinks (bin 2 holds one node: (cap - 64 - 16 W) / 8, capped by 64 W), so a
+        // batch lists such a node only if need_slab held for m_max, that is only if the slabs exist
+        if (slab_launch) {
+            k_tx_pairs<true><<<(unsigned)slab_wgs, SC_THREADS, (size_t)16 * words[b], s>>>(
+                nullptr, nb, a.off, d_ylist, d_zlist, a.ycnt, d_zbin + (int64_t)TX_BINS * Lb,
+                d_zbcnt + (int64_t)TX_BINS * nb, c.d_mm, 1, words[b], d_slab, slab_stride, d_acc);
+            if (!sc_launched(e)) break;
+        }
+        k_tx_scan<<<nb, SC_THREADS, 0, s>>>(a.off, d_dsrc, d_dsup);
+        if (!sc_launched(e)) break;
+        k_tx_fold<<<grid_of(Lb), SC_THREADS, 0, s>>>(a.off, nb, src->d_leaf_taxon, c.d_mm, d_acc, d_dsrc, d_dsup, d_tx,
+                                                     n_out);
+        if (!sc_launched(e)) break;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    int64_t *const outs[5] = {tx_trees, tx_total, tx_super, tx_source, tx_shared};
+    for (int i = 0; i < 5 && e == hipSuccess; ++i)
+        if (outs[i] && n_out) e = hipMemcpyAsync(outs[i], d_tx + i * n_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
     return SCS_OK;
 }

@@ -1,6 +1,7 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
 supertree node, and on request rooted triplet terms per source tree (section 15), clade
-conflict counts (section 16), branch concordance factors (section 17) and per-branch triplet support (section 18).
+conflict counts (section 16), branch concordance factors (section 17), per-branch triplet support (section 18) and
+per-taxon triplet support (section 20).
 Neither the reference nor ``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
@@ -67,9 +68,23 @@ With y over T's non-root nodes, py the parent and I(y, X) = |cl(y) ∩ X|: ``bt_
 Σ_y I(y,A') I(y,B') (I(py,D') - I(y,D')), ``bt_alt1`` with (A', D', B') and ``bt_alt2`` with (B', D', A') in those
 places: a triple resolved ab|d has exactly one y with a, b ∈ y and d ∈ py ∖ y.
 
+Per-taxon triplet support (``taxon_triplets=True``): the triplet terms attributed to the taxa of every triple, to name
+the misplaced (*rogue*) taxa that lower the support of every clade on their path.  Per supertree tip x (taxon id =
+position in ``taxa``, the tips in preorder), summed over the sources T with x ∈ L(T) and m = |L(T)| >= 3:
+
+* ``tx_trees`` = the number of such sources, ``tx_total`` = Σ C(m-1, 2), the triples of L(T) that hold x;
+* ``tx_source`` / ``tx_super`` / ``tx_shared`` = those of them T resolves / S' resolves / both resolve alike;
+* ``taxon_triplet_distance = tx_super + tx_source - 2 tx_shared``, ``taxon_fit = tx_shared / tx_source`` and
+  ``taxon_instability = taxon_triplet_distance / (tx_super + tx_source)`` in [0, 1].
+
+Every triple has three taxa, so Σ_x ``tx_shared`` = 3 Σ_t ``t_shared`` (likewise ``tx_super``, ``tx_source``) and
+Σ_x ``tx_total`` = 3 Σ_t C(m, 3).  A shared triple ab|c is counted at one pair (y, z); with I = I(y,z) and J the
+second factor of ``t_shared``, every leaf of cl(y) ∩ cl(z) takes (I - 1) J of the pair's triples (as a or b) and
+every leaf of (cl(py) ∖ cl(y)) ∩ (cl(pz) ∖ cl(z)) takes C(I, 2) (as c).
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
-``scs_score_conflicts``, ``scs_score_concordance`` and ``scs_score_branch_triplets``; the host only validates and lays
-out.
+``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets`` and ``scs_score_taxon_triplets``; the
+host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -85,6 +100,9 @@ from spectralclustersupertree_amd.treearrays import TreeArrays
 
 # trees per device batch; None: sized by the workspace (a test sets a small value to reach the batch loop)
 BATCH_TREES: int | None = None
+# LDS bytes a workgroup of the per-taxon pair kernel may take; None: the default (a test sets a small value so that
+# small trees reach the path through global memory)
+TAXON_LDS_BYTES: int | None = None
 
 
 @dataclass
@@ -102,7 +120,7 @@ class SupertreeScore:
     # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
     # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
-    # requested)
+    # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -128,6 +146,14 @@ class SupertreeScore:
     bt_concordant: np.ndarray | None = None
     bt_alt1: np.ndarray | None = None
     bt_alt2: np.ndarray | None = None
+    # per-taxon triplet support (``taxon_triplets=True``; None otherwise): the supertree's tip names in taxon-id order
+    # and the counts per taxon
+    taxa: list | None = None
+    tx_trees: np.ndarray | None = None
+    tx_total: np.ndarray | None = None
+    tx_super: np.ndarray | None = None
+    tx_source: np.ndarray | None = None
+    tx_shared: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -330,6 +356,59 @@ class SupertreeScore:
                          f"/{int(self.bt_total[i])}" if self.bt_total[i] > 0 else None)
         return out
 
+    def _need_taxon_triplets(self) -> None:
+        if self.tx_shared is None:
+            msg = "per-taxon triplet counts were not computed: score_supertree(..., taxon_triplets=True)"
+            raise ValueError(msg)
+
+    @property
+    def taxon_triplet_distance(self) -> np.ndarray:
+        """Per taxon: the triples holding it whose topology differs between S|L(T) and T, over its sources."""
+        self._need_taxon_triplets()
+        return self.tx_super + self.tx_source - 2 * self.tx_shared
+
+    @property
+    def taxon_fit(self) -> np.ndarray:
+        """``tx_shared / tx_source`` per taxon (NaN where its sources resolve no triple that holds it)."""
+        self._need_taxon_triplets()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.tx_source > 0, self.tx_shared / np.maximum(self.tx_source, 1), np.nan)
+
+    @property
+    def taxon_instability(self) -> np.ndarray:
+        """``taxon_triplet_distance / (tx_super + tx_source)`` per taxon, in [0, 1]: 0 when every resolved triple that
+        holds the taxon is resolved alike, 1 when none is (NaN where neither tree resolves one)."""
+        dist = self.taxon_triplet_distance
+        both = self.tx_super + self.tx_source
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(both > 0, dist / np.maximum(both, 1), np.nan)
+
+    def rogue_taxa(self, n: int | None = None, min_trees: int = 1) -> list[dict]:
+        """The taxa in at least ``min_trees`` sources (of 3 or more leaves) whose instability is defined: one dict
+        per taxon with ``taxon`` (id), ``name``, ``trees``, ``total``, ``super``, ``source``, ``shared``,
+        ``distance`` and ``instability``; largest instability first, then larger distance, then id.  The first
+        ``n`` when given."""
+        inst = self.taxon_instability
+        dist = self.taxon_triplet_distance
+        out = []
+        for x in np.flatnonzero((self.tx_trees >= min_trees) & ~np.isnan(inst)):
+            out.append({"taxon": int(x), "name": self.taxa[x], "trees": int(self.tx_trees[x]),
+                        "total": int(self.tx_total[x]), "super": int(self.tx_super[x]),
+                        "source": int(self.tx_source[x]), "shared": int(self.tx_shared[x]),
+                        "distance": int(dist[x]), "instability": float(inst[x])})
+        out.sort(key=lambda r: (-r["instability"], -r["distance"], r["taxon"]))
+        return out if n is None else out[:n]
+
+    def taxon_table(self) -> str:
+        """One TSV row per supertree tip: taxon (id), name, tx_trees, tx_total, tx_super, tx_source, tx_shared,
+        triplet_distance.  ``ValueError`` unless the per-taxon counts were computed."""
+        dist = self.taxon_triplet_distance
+        rows = ["taxon\tname\ttx_trees\ttx_total\ttx_super\ttx_source\ttx_shared\ttriplet_distance"]
+        for x, name in enumerate(self.taxa):
+            rows.append(f"{x}\t{name}\t{self.tx_trees[x]}\t{self.tx_total[x]}\t{self.tx_super[x]}"
+                        f"\t{self.tx_source[x]}\t{self.tx_shared[x]}\t{dist[x]}")
+        return "\n".join(rows) + "\n"
+
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
         concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
@@ -432,14 +511,17 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
-                    concordance: bool = False, branch_triplets: bool = False, device=None) -> SupertreeScore:
+                    concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
+                    device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
     ``concordance=True`` the branch concordance counts (``n_decisive``, ``n_concordant``, ``n_alternative`` per
     tree, ``decisive``, ``concordant``, ``alt1``, ``alt2`` per node) and ``branch_triplets=True`` the per-branch
     triplet support (``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative`` per tree, ``bt_total``,
-    ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` per node), all counted on the same device tables as the RF terms.
+    ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` per node) and ``taxon_triplets=True`` the per-taxon triplet support
+    (``taxa``, ``tx_trees``, ``tx_total``, ``tx_super``, ``tx_source``, ``tx_shared`` per supertree tip), all counted
+    on the same device tables as the RF terms.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -465,10 +547,11 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
         out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
-                            concordance, branch_triplets)
+                            concordance, branch_triplets, taxon_triplets, tips)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
                                   - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
-                                  - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0))
+                                  - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0)
+                                  - out.timings.get("taxon_triplets", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -487,19 +570,24 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     t2 = time.perf_counter()
     try:
         res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-        t3 = t4 = t5 = t6 = t7 = time.perf_counter()
+        t3 = t4 = t5 = t6 = t7 = t8 = time.perf_counter()
         if triplets:
             res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t4 = t5 = t6 = t7 = time.perf_counter()
+            t4 = t5 = t6 = t7 = t8 = time.perf_counter()
         if conflicts:
             res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t5 = t6 = t7 = time.perf_counter()
+            t5 = t6 = t7 = t8 = time.perf_counter()
         if concordance:
             res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t6 = t7 = time.perf_counter()
+            t6 = t7 = t8 = time.perf_counter()
         if branch_triplets:
             res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t7 = time.perf_counter()
+            t7 = t8 = time.perf_counter()
+        if taxon_triplets:
+            res.update(dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0,
+                                                lds_bytes=TAXON_LDS_BYTES or 0))
+            res["taxa"] = list(tips)
+            t8 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
@@ -511,6 +599,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         timings["concordance"] = t6 - t5
     if branch_triplets:
         timings["branch_triplets"] = t7 - t6
+    if taxon_triplets:
+        timings["taxon_triplets"] = t8 - t7
     return _result(supertree, np.diff(tables.tree_off), res, timings)
 
 
@@ -522,7 +612,9 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
                           res.get("n_decisive"), res.get("n_concordant"), res.get("n_alternative"),
                           res.get("decisive"), res.get("concordant"), res.get("alt1"), res.get("alt2"),
                           res.get("n_bt_total"), res.get("n_bt_concordant"), res.get("n_bt_alternative"),
-                          res.get("bt_total"), res.get("bt_concordant"), res.get("bt_alt1"), res.get("bt_alt2"))
+                          res.get("bt_total"), res.get("bt_concordant"), res.get("bt_alt1"), res.get("bt_alt2"),
+                          res.get("taxa"), res.get("tx_trees"), res.get("tx_total"), res.get("tx_super"),
+                          res.get("tx_source"), res.get("tx_shared"))
 
 
 def _default_device():
@@ -532,7 +624,8 @@ def _default_device():
 
 
 def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
-                  conflicts, concordance, branch_triplets=False) -> SupertreeScore:
+                  conflicts, concordance, branch_triplets=False, taxon_triplets=False,
+                  tips=None) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -553,6 +646,9 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     per_node += ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2") if branch_triplets else ()
     zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
     node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in per_node}
+    if taxon_triplets:  # (per supertree tip)
+        node0.update({k: np.zeros(n_taxa, dtype=np.int64)
+                      for k in ("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")})
     # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
     universe = max(arrays.n_taxa, n_taxa, 1)
     new_id = np.concatenate([new_id, np.full(universe - len(new_id), -1, dtype=np.int32)])
@@ -567,7 +663,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = t4 = t5 = t6 = time.perf_counter()
+        t1 = t2 = t3 = t4 = t5 = t6 = t7 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
         else:
@@ -577,19 +673,23 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
             t1 = time.perf_counter()
             try:
                 res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-                t2 = t3 = t4 = t5 = t6 = time.perf_counter()
+                t2 = t3 = t4 = t5 = t6 = t7 = time.perf_counter()
                 if triplets:
                     res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t3 = t4 = t5 = t6 = time.perf_counter()
+                    t3 = t4 = t5 = t6 = t7 = time.perf_counter()
                 if conflicts:
                     res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t4 = t5 = t6 = time.perf_counter()
+                    t4 = t5 = t6 = t7 = time.perf_counter()
                 if concordance:
                     res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t5 = t6 = time.perf_counter()
+                    t5 = t6 = t7 = time.perf_counter()
                 if branch_triplets:
                     res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t6 = time.perf_counter()
+                    t6 = t7 = time.perf_counter()
+                if taxon_triplets:
+                    res.update(dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0,
+                                                        lds_bytes=TAXON_LDS_BYTES or 0))
+                    t7 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -608,4 +708,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
         timings["concordance"] = t5 - t4
     if branch_triplets:
         timings["branch_triplets"] = t6 - t5
+    if taxon_triplets:
+        timings["taxon_triplets"] = t7 - t6
+        res["taxa"] = list(tips)
     return _result(supertree, n_leaves, res, timings)

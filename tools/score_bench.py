@@ -7,7 +7,9 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --conflicts          # also the clade conflict counts
     python tools/score_bench.py --concordance        # also the branch concordance counts
     python tools/score_bench.py --branch-triplets    # also the per-branch triplet support
+    python tools/score_bench.py --taxon-triplets     # also the per-taxon triplet support
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
+    python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
 
 from __future__ import annotations
@@ -68,7 +70,8 @@ def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeA
 
 
 def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
-        cat: bool = False, concordance: bool = False, branch_triplets: bool = False) -> dict:
+        cat: bool = False, concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
+        cat_sup: bool = False) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
@@ -78,17 +81,17 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
         sup = caterpillar(np.arange(n_taxa))
     else:
         arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
-        sup = random_binary_tree(2, n_taxa)
+        sup = caterpillar(np.random.RandomState(2).permutation(n_taxa)) if cat_sup else random_binary_tree(2, n_taxa)
     gen_s = time.perf_counter() - t0
     runs = []
     for _ in range(repeats):
         t0 = time.perf_counter()
         res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, concordance=concordance,
-                              branch_triplets=branch_triplets, device=dev)
+                              branch_triplets=branch_triplets, taxon_triplets=taxon_triplets, device=dev)
         runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
-        "size": size, "input": "caterpillar" if cat else "random", "n_taxa": n_taxa, "n_trees": n_trees, "leaves": int(arrays.leaf_counts().sum()),
+        "size": size, "input": "caterpillar" if cat else "caterpillar supertree" if cat_sup else "random", "n_taxa": n_taxa, "n_trees": n_trees, "leaves": int(arrays.leaf_counts().sum()),
         "supertree_nodes": len(res.informative), "repeats": repeats, "input_generation_s": round(gen_s, 3),
         "wall_s": round(wall, 4), "host_prepare_s": round(tim["prepare"], 4),
         "device_tables_s": round(tim["tables"], 4), "score_call_s": round(tim["score"], 4),
@@ -125,6 +128,27 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
         if triplets:
             out["triplets_call_s_min_median_max"] = [round(x, 5) for x in _spread([r[1]["triplets"] for r in runs])]
             out["branch_triplets_over_triplets"] = round(tim["branch_triplets"] / tim["triplets"], 3)
+    if taxon_triplets:
+        # (y, z) pairs of the sweep: T's nontrivial clusters times those of the restricted supertree, per tree
+        pairs = int((res.n_source * res.n_super).sum())
+        med = _spread([r[1]["taxon_triplets"] for r in runs])[1]
+        worst = res.rogue_taxa(1)
+        out.update({"taxon_triplets_call_s": round(tim["taxon_triplets"], 5),
+                    "taxon_triplets_call_s_min_median_max":
+                        [round(x, 5) for x in _spread([r[1]["taxon_triplets"] for r in runs])],
+                    "node_pairs": pairs, "taxon_triplets_pairs_per_s": round(pairs / max(med, 1e-9), 1),
+                    "total_tx_shared": int(res.tx_shared.sum()), "total_tx_source": int(res.tx_source.sum()),
+                    "total_tx_super": int(res.tx_super.sum()), "total_tx_total": int(res.tx_total.sum()),
+                    "worst_instability": worst[0]["instability"] if worst else None})
+        if triplets:
+            tmed = _spread([r[1]["triplets"] for r in runs])[1]
+            out["triplets_call_s_min_median_max"] = [round(x, 5) for x in _spread([r[1]["triplets"] for r in runs])]
+            out["triplets_pairs_per_s"] = round(pairs / max(tmed, 1e-9), 1)
+            out["taxon_triplets_over_triplets"] = round(med / max(tmed, 1e-9), 3)
+            out["sums_are_three_times_the_per_tree_sums"] = bool(
+                int(res.tx_shared.sum()) == 3 * int(res.t_shared.sum())
+                and int(res.tx_source.sum()) == 3 * int(res.t_source.sum())
+                and int(res.tx_super.sum()) == 3 * int(res.t_super.sum()))
     return out
 
 
@@ -141,17 +165,21 @@ def main() -> None:
     ap.add_argument("--conflicts", action="store_true", help="also count the clade conflicts")
     ap.add_argument("--concordance", action="store_true", help="also count the branch concordance factors")
     ap.add_argument("--branch-triplets", action="store_true", help="also count the per-branch triplet support")
+    ap.add_argument("--taxon-triplets", action="store_true", help="also count the per-taxon triplet support")
+    ap.add_argument("--caterpillar-supertree", action="store_true",
+                    help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
                         conflicts=args.conflicts, concordance=args.concordance, branch_triplets=args.branch_triplets,
-                        device=dev)  # warm-up
+                        taxon_triplets=args.taxon_triplets, device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
             print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar,
-                                 args.concordance, args.branch_triplets)), flush=True)
+                                 args.concordance, args.branch_triplets, args.taxon_triplets,
+                                 args.caterpillar_supertree)), flush=True)
 
 
 if __name__ == "__main__":
