@@ -566,6 +566,18 @@ class DeviceForest:
 _FAIL_SMALL_FOR_TESTS = False
 
 
+def _refuse_nonfinite_maps(maps: np.ndarray, lam: np.ndarray, n_groups: np.ndarray) -> None:
+    """A node whose embedding holds a NaN or an infinity is a failed node whatever its eigenvalues say: its
+    ``lambda`` row becomes NaN, the one sign of failure every caller looks at.  No such embedding may reach k-means."""
+    if np.isfinite(maps).all():
+        return
+    at = 0
+    for i, v in enumerate(n_groups):
+        if not np.isfinite(maps[at:at + int(v)]).all():
+            lam[i] = np.nan
+        at += int(v)
+
+
 class SmallTicket:
     """An ``scs_small_solve_begin`` that has not been ended: ``result()`` waits and returns one
     ``(maps, lambdas[, W])`` per node (once; kept).  Dropped unasked-for, it releases its slot."""
@@ -605,13 +617,15 @@ class SmallTicket:
             graph.free()
 
     def raw(self):
-        """Waits and returns ``(maps [sum n_groups, 2], lambdas [K, 3])`` as the library left them (a node whose
-        one-sided Jacobi ran out of sweeps carries NaN eigenvalues: the caller decides)."""
+        """Waits and returns ``(maps [sum n_groups, 2], lambdas [K, 3])``, nothing re-solved: a node whose one-sided
+        Jacobi ran out of sweeps carries NaN eigenvalues from the library, and one whose embedding is not finite is
+        given them here (``_refuse_nonfinite_maps``); the caller decides what to do with such a node."""
         n_groups = self._n_groups
         maps = np.empty((int(n_groups.sum()), 2))
         lam = np.empty((len(n_groups), 3))
         ticket, self._ticket = self._ticket, -1
         nv.check(self.dev._lib.scs_small_solve_end(self.dev._ctx, ticket, nv.dptr(maps), nv.dptr(lam), None))
+        _refuse_nonfinite_maps(maps, lam, n_groups)
         return maps, lam
 
     def result(self):
@@ -625,13 +639,15 @@ class SmallTicket:
             nv.check(self.dev._lib.scs_small_solve_end(self.dev._ctx, ticket, nv.dptr(maps), nv.dptr(lam),
                                                        nv.dptr(w) if want_w else None))
             redo = {}
+            _refuse_nonfinite_maps(maps, lam, n_groups)
             if _FAIL_SMALL_FOR_TESTS:  # (tests/test_gpu_parity.py monkeypatches it: the one-sided Jacobi "gave up")
                 lam[n_groups > 64] = np.nan
             if not np.all(np.isfinite(lam)):
                 # the one-sided Jacobi of a node of more than 64 vertices ran out of sweeps (NaN
-                # eigenvalues, never a half-rotated basis): only THAT node goes through the general
-                # path again; if that fails too the call raises, as the reference's ARPACK call
-                # raises rather than return a guess (scs.py:252)
+                # eigenvalues, never a half-rotated basis), or its embedding is not finite
+                # (_refuse_nonfinite_maps): only THAT node goes through the general path again; if
+                # that fails too the call raises, as the reference's ARPACK call raises rather than
+                # return a guess (scs.py:252)
                 bad = [i for i in range(k) if not np.all(np.isfinite(lam[i]))]
                 if self._nodes is None:
                     msg = f"small-node eigen-solve did not converge (nodes {bad} of a batch of {k})"

@@ -3378,6 +3378,30 @@ __global__ __launch_bounds__(256) void k_small_finish_big(small_batch p) {
         a[g][h] = g == h ? 1.0 : 0.5 * (x + y);
     }
     __syncthreads();
+    // Two vertices that share an edge: S = [[0, s], [s, 0]] with s = 1 up to its last bit, lambda = (s, -s), and
+    // the second eigenvalue is the null direction of A = S + I -- a WANTED column whose norm is 0 (s == 1 exactly:
+    // contracted weights 1, 4, 9, ...) or rounding noise, and the division by that norm below is 0 / 0.  Every other
+    // wanted column is safe: with three vertices or more the trace of S is 0 and lambda_2 >= -1 / (V - 1), a norm
+    // of at least 1 / 2; without an edge A = I.  So this one case is written down in closed form -- eigenvectors
+    // (1, 1) / sqrt(2) and (1, -1) / sqrt(2) -- with the conventions of the general case below.
+    // (the branch is uniform; a NaN weight takes it too and comes back as NaN eigenvalues, which the host refuses)
+    if (v == 2 && a[0][1] != 0.0) {
+        if (tid == 0) {
+            const double s01 = a[0][1], r = 0.70710678118654752440;
+            const double x0 = r / s_dd[0], x1 = r / s_dd[1];
+            // the largest |entry| of a column positive, the first one on a tie
+            const double sg = x1 > x0 ? -1.0 : 1.0;
+            double *out = p.maps + (int64_t)p.vertex_ptr[k] * 2;
+            out[0] = x0;
+            out[2] = x1;
+            out[1] = sg * x0;
+            out[3] = -sg * x1;
+            p.lambda[k * 3 + 0] = s01;
+            p.lambda[k * 3 + 1] = -s01;
+            p.lambda[k * 3 + 2] = 0.0;
+        }
+        return;
+    }
     const bool ok = onesided_sweeps(a, m, &s_rot);
     // eigenvalues of S: column norms - 1 (the padding column of an odd V has norm 0: last)
     if (tid < v) {
