@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets and scs_score_taxon_triplets added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets and scs_score_placements added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -406,6 +406,30 @@ int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_
                              const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
                              int64_t *tx_trees, int64_t *tx_total, int64_t *tx_super, int64_t *tx_source,
                              int64_t *tx_shared);
+
+/* Taxon placement support, same inputs and SCS_EINVAL cases as scs_score_supertree: for each
+ * of n_queries query taxa x (taxon ids of supertree tips, each once) and every node v of the supertree S, the triplet
+ * terms x would have if it were pruned and regrafted on the edge above v.  S_{x->v} has, for every cluster C of S,
+ * (C - x) + x when C belongs to a strict ancestor of v and C - x otherwise, and the new cluster (cl(v) - x) + x; empty
+ * sets are dropped.  Summed over the source trees T on a leaf set L with x in L and m = |L| >= 3, over the C(m - 1, 2)
+ * triples {x, a, b} of L:
+ *   pl_trees[i], pl_total[i]         = tx_trees[x], tx_total[x] of scs_score_taxon_triplets,
+ *   pl_source[i]                     = the triples T resolves (no v in it),
+ *   pl_super[i * n_nodes + v]        = the triples S_{x->v}|L resolves,
+ *   pl_shared[i * n_nodes + v]       = those T and S_{x->v}|L resolve alike,
+ * for query i, so that pl_super + pl_source - 2 pl_shared is the triplet distance x would have there.  The entry at
+ * x's own node (and at its sibling, and at a parent with two children) holds tx_super[x] and tx_shared[x].  Counts are
+ * unweighted and exact; a query no source holds gives zero rows; output pointers may be null.  SCS_EINVAL as well for
+ * a query that is no tip's taxon id or is given twice, for a source tree of more than 327 679 leaves (as for
+ * scs_score_triplets), and when the rows do not fit the call's workspace: three rows of n_nodes + 1 int64 per query
+ * and output and two of n_nodes per 64 queries, 48 n_queries (n_nodes + 1) + 16 ceil(n_queries / 64) n_nodes bytes,
+ * may take at most 1.5 GB (64 queries on 480 000 nodes, 1 500 on 20 000).  Queries go through the batches 64 at a time.
+ * max_lds_bytes > 0 caps the LDS a workgroup of the pair kernel takes (tests: when the sums per node and query do not
+ * fit beside the bitset rows, every node pair sends its own marks); 0: the default, all a workgroup can take. */
+int scs_score_placements(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                         const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
+                         const int32_t *queries, int64_t *pl_trees, int64_t *pl_total, int64_t *pl_source,
+                         int64_t *pl_super, int64_t *pl_shared);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

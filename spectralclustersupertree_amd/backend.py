@@ -263,6 +263,31 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_placements(self, sources, parent: np.ndarray, taxon: np.ndarray, queries, batch_trees: int = 0,
+                         lds_bytes: int = 0) -> dict:
+        """``scs_score_placements``: the triplet terms every query taxon would have on the edge above every supertree
+        node, with the inputs of ``score`` and ``queries`` = taxon ids of supertree tips, each once.  Returns int64
+        arrays ``pl_trees``, ``pl_total``, ``pl_source`` (one entry per query) and ``pl_super``, ``pl_shared``
+        (queries x nodes).  ``lds_bytes`` > 0 caps the LDS one workgroup of the pair kernel takes (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        queries = np.ascontiguousarray(queries, dtype=np.int32)
+        n_nodes, nq = len(parent), len(queries)
+        if taxon.shape != (n_nodes,) or queries.ndim != 1:
+            msg = "parent and taxon must have one entry per supertree node, queries one per query taxon"
+            raise ValueError(msg)
+        out = {k: np.zeros(nq, dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")}
+        out.update({k: np.zeros((nq, n_nodes), dtype=np.int64) for k in ("pl_super", "pl_shared")})
+        rc = self._lib.scs_score_placements(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                            int(batch_trees), int(lds_bytes), nq, nv.iptr(queries),
+                                            *(nv.lptr(v) for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_placements: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

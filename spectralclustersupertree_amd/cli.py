@@ -62,12 +62,18 @@ from spectralclustersupertree_amd import __version__
 @click.option("--taxa-out", default=None,
               help="Also write a TSV with one row per supertree tip (taxon, name, tx_trees, tx_total, tx_super, "
                    "tx_source, tx_shared, triplet_distance): the rooted triples that hold the taxon, over its sources.")
+@click.option("--placements-out", default=None,
+              help="Also write a TSV with one row per placed taxon (taxon, name, trees, node, distance, best_node, "
+                   "best_distance, improvement): where on the supertree the least stable taxa would fit their sources "
+                   "best, by rooted triplet distance.")
+@click.option("--place-taxa", default=10, type=click.IntRange(min=1), show_default=True,
+              help="How many of the least stable taxa --placements-out places.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
         concordance_out: str | None = None, branches_out: str | None = None, branch_triplets: bool = False,
         branch_triplets_out: str | None = None, taxon_triplets: bool = False,
-        taxa_out: str | None = None) -> None:
+        taxa_out: str | None = None, placements_out: str | None = None, place_taxa: int = 10) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
@@ -98,7 +104,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
         if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
-                or taxa_out):
+                or taxa_out or placements_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
@@ -106,7 +112,10 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                                      concordance=concordance or concordance_out is not None
                                      or branches_out is not None,
                                      branch_triplets=branch_triplets or branch_triplets_out is not None,
-                                     taxon_triplets=taxa_out is not None)
+                                     taxon_triplets=taxa_out is not None,
+                                     placements=place_taxa if placements_out else None)
+            if placements_out:
+                Path(placements_out).write_text(result.placement_table())
             if taxa_out:
                 Path(taxa_out).write_text(result.taxon_table())
             if branch_triplets_out:

@@ -1511,6 +1511,419 @@ __global__ void __launch_bounds__(SC_THREADS) k_tx_fold(const int64_t *__restric
     if (d_sup[q]) atomicAdd(tx + 2 * n_out + xs, d_sup[q]);
 }
 
+// ---- taxon placement support (scs_score_placements) ----
+//
+// For a query taxon x and a node v of S, S_{x->v} is S with x pruned and regrafted on the edge above v.  Fix a source T
+// on L with x in L; every set below is restricted to L.  The groups of x in T are the clusters y with x not in y and
+// x in py (the subtrees hanging off x's root path, leaves included); they partition L - {x}.  Of the pairs {a, b} of
+// L - {x}, T says ab|x when a and b share a group and xa|b when a is in y and b outside py.  With
+//   A(z) = sum_y C(|y ∩ z|, 2)   and   X(z) = sum_y |y ∩ z| (|pz - py| - |z - py|)       (z a node of S' = S|L)
+// the triples {x, a, b} that T and S_{x->v} resolve alike are a root-path sum: A(root of S') for every v, and for every
+// node z of S' with parent pz, + A(z) strictly below the S node of pz, - A(z) strictly below z's own S node, and
+// + X(z) on the subtree of the highest S node whose restricted set is z's.  The triples S_{x->v} resolves follow the
+// same sums with A1 = C(|z - x|, 2) and X1 = |z - x| (|pz - x| - |z - x|).  x lies in no group but in every py, so no
+// count over a group needs a correction for it.
+//   k_pl_queries: per (tree, query): x's T position and S' index (-1 when the tree lacks x or has under 3 leaves);
+//     per tree the number of queries it holds.
+//   k_pl_znodes, one thread per leaf: every node of S', leaves and root included, as int4 {lo, hi + 1, parent lo,
+//     parent hi + 1} in S order and int4 {own S node (-1: a leaf), parent's S node (-1: the root), top S node, 0}.
+//   k_pl_groups, one thread per leaf: T's leaf k and the node whose first gap is k go, with their parent's range, into
+//     the list of every query of the tree that the parent holds and the node does not; pl_source on the way.
+//   k_pl_pairs: the grid and rows of k_trip_pairs; the workgroup sweeps the group lists of its tree's queries, adds
+//     A and X per (z, query) in LDS, and issues the non-zero marks as 64-bit atomics on two rows per query: `sub`
+//     (counts for the node's subtree) and `strict` (for its strict descendants).  The super marks of a taxon outside
+//     pz do not depend on the taxon: a tree that holds every query of the pass sends them once, to rows common to the
+//     pass, and a query adds only what its own place in z or pz changes.
+//   k_pl_marks / k_pl_prefix: mark(u) = sub[u] + strict[parent u] on the preorder range [u, end u) of a difference
+//     row, and its prefix sums: the value of every node.
+
+constexpr int PL_QMAX = 64;  // query taxa per pass over a batch (a group list entry per leaf and query: 1 KB a leaf)
+
+// the highest S node below the node of depth d whose leaves hold S position p: its first leaf lies after the nearest
+// gap to the left that is no deeper than d, and the path from a node to its first leaf takes first children only,
+// which follow their parents at once in preorder
+__device__ __forceinline__ int32_t pl_top(const uint64_t *__restrict__ s_tab, int64_t stride, int s_levels,
+                                          const int32_t *__restrict__ tip_node, const int32_t *__restrict__ tip_depth,
+                                          int32_t p, int32_t d) {
+    int64_t pos = p;
+    for (int j = s_levels - 1; j >= 0; --j) {
+        const int64_t w = (int64_t)1 << j;
+        if (pos >= w && (int32_t)(s_tab[j * stride + pos - w] >> 32) > d) pos -= w;
+    }
+    return tip_node[pos] - (tip_depth[pos] - (d + 1));
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_pl_queries(const int64_t *__restrict__ off, int nb,
+                                                           const int32_t *__restrict__ q_spos, int qc,
+                                                           const int32_t *__restrict__ rows, int64_t row_stride,
+                                                           const int32_t *__restrict__ sp, int2 *__restrict__ qinfo,
+                                                           int32_t *__restrict__ gcnt, int32_t *__restrict__ qheld,
+                                                           unsigned long long *__restrict__ q_trees,
+                                                           unsigned long long *__restrict__ q_total) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)nb * qc) return;
+    const int t = (int)(idx / qc), i = (int)(idx % qc);
+    const int64_t base = off[t] - off[0], n = off[t + 1] - off[t];
+    const int32_t s = q_spos[i];
+    int32_t px = -1, kx = -1;
+    if (n >= 3 && s >= 0) {
+        px = rows[(int64_t)t * row_stride + s];
+        if (px >= 0) {
+            kx = (int32_t)sc_first_ge(sp + base, 0, n, s);
+            atomicAdd(qheld + t, 1);
+            atomicAdd(q_trees + i, 1ull);
+            atomicAdd(q_total + i, (unsigned long long)((n - 1) * (n - 2) / 2));
+        }
+    }
+    qinfo[idx] = make_int2(px, kx);
+    gcnt[idx] = 0;
+}
+
+struct sc_pl_args {
+    const int64_t *off;                     // tree_off + t0
+    int nb;
+    const int32_t *sp, *dep, *node;         // [Lb] S positions in S order, D and U of S'
+    const int32_t *adj, *amin;              // T's min table of adj_depth (as in sc_nodes_args)
+    int levels;
+    int64_t Lb;
+    const uint64_t *s_tab;                  // S's packed gap table
+    int64_t s_stride;
+    int s_levels;
+    const int32_t *s_lo, *s_hi;             // leaf range of every S node
+    const int32_t *tip_node, *tip_depth;    // [S leaves] preorder index and depth of the tip at an S position
+    int4 *zlist, *zmeta;                    // [2 Lb]: the nodes of a tree from twice its first leaf on
+    int32_t *zcnt;                          // [nb]
+    const int2 *qinfo;                      // [nb][qc]
+    int qc;
+    int4 *glist;                            // [Lb qc]: tree t, query i from base qc + i n on
+    int32_t *gcnt;                          // [nb][qc]
+    unsigned long long *q_source;           // [qc]
+};
+
+// one thread per leaf k of a tree of 3 or more leaves: S' leaf k, and the S' node whose first gap is k
+__global__ void __launch_bounds__(SC_THREADS) k_pl_znodes(sc_pl_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    const bool leaf = in && n >= 3;
+    bool inner = false;
+    int4 zl = make_int4(0, 0, 0, 0), ml = zl, zi = zl, mi = zl;
+    if (leaf) {
+        const int32_t *sp = a.sp + base;
+        {
+            const int64_t g = k == 0 ? 0 : k == n - 1 ? n - 2 : (a.dep[base + k - 1] >= a.dep[base + k] ? k - 1 : k);
+            const int32_t w = a.node[base + g];
+            const int64_t plo = sc_first_ge(sp, 0, k, a.s_lo[w]);
+            const int64_t phi = sc_last_le(sp, k, n - 1, a.s_hi[w]);
+            zl = make_int4((int)k, (int)k + 1, (int)plo, (int)phi + 1);
+            ml = make_int4(-1, w, pl_top(a.s_tab, a.s_stride, a.s_levels, a.tip_node, a.tip_depth, sp[k],
+                                         a.dep[base + g]), 0);
+        }
+        if (k + 1 < n) {
+            const int32_t u = a.node[q], du = a.dep[q];
+            const int64_t lo_s = sc_first_ge(sp, 0, k, a.s_lo[u]);
+            const int64_t hi_s = sc_last_le(sp, k + 1, n - 1, a.s_hi[u]);
+            inner = lo_s == k ||
+                    (int32_t)(sc_rmq_min(a.s_tab, a.s_stride, (int64_t)sp[lo_s], (int64_t)sp[k] - 1) >> 32) > du;
+            if (inner && lo_s == 0 && hi_s == n - 1) {  // the root: its own parent, and above it every node of S
+                zi = make_int4(0, (int)n, 0, (int)n);
+                mi = make_int4(u, -1, 0, 0);
+            } else if (inner) {
+                const int64_t g = lo_s == 0 ? hi_s
+                                  : hi_s == n - 1 ? lo_s - 1
+                                  : (a.dep[base + lo_s - 1] >= a.dep[base + hi_s] ? lo_s - 1 : hi_s);
+                const int32_t w = a.node[base + g];
+                const int64_t plo = sc_first_ge(sp, 0, lo_s, a.s_lo[w]);
+                const int64_t phi = sc_last_le(sp, hi_s, n - 1, a.s_hi[w]);
+                zi = make_int4((int)lo_s, (int)hi_s + 1, (int)plo, (int)phi + 1);
+                mi = make_int4(u, w, pl_top(a.s_tab, a.s_stride, a.s_levels, a.tip_node, a.tip_depth, sp[lo_s],
+                                            a.dep[base + g]), 0);
+            }
+        }
+    }
+    const int il = sc_append(a.zcnt, t, leaf);
+    if (il >= 0) {
+        a.zlist[2 * base + il] = zl;
+        a.zmeta[2 * base + il] = ml;
+    }
+    const int ii = sc_append(a.zcnt, t, inner);
+    if (ii >= 0) {
+        a.zlist[2 * base + ii] = zi;
+        a.zmeta[2 * base + ii] = mi;
+    }
+}
+
+// node [lo, hi) of T with parent [plo, phi) into the list of every query of tree t that the parent holds and the node
+// does not; the pairs {a, b} it gives T a resolved triple {x, a, b} for: both inside it, or a inside and b outside py
+__device__ __forceinline__ void pl_group(const sc_pl_args &a, int t, int64_t base, int64_t n, int4 e) {
+    const int64_t s = e.y - e.x;
+    const unsigned long long v = (unsigned long long)(s * (s - 1) / 2 + s * (n - (e.w - e.z)));
+    for (int i = 0; i < a.qc; ++i) {
+        const int32_t px = a.qinfo[(int64_t)t * a.qc + i].x;
+        if (px < e.z || px >= e.w || (px >= e.x && px < e.y)) continue;
+        const int slot = atomicAdd(a.gcnt + (int64_t)t * a.qc + i, 1);
+        a.glist[base * a.qc + (int64_t)i * n + slot] = e;
+        atomicAdd(a.q_source + i, v);
+    }
+}
+
+// one thread per leaf k of a tree: T's leaf k, and T's node whose first gap is k (as in k_trip_nodes)
+__global__ void __launch_bounds__(SC_THREADS) k_pl_groups(sc_pl_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    if (p >= a.off[a.nb]) return;
+    const int t = sc_tree_of(a.off, a.nb, p);
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    if (n < 3) return;
+    {
+        const int64_t g = k == 0 ? 0 : k == n - 1 ? n - 2 : (a.adj[base + k - 1] >= a.adj[base + k] ? k - 1 : k);
+        const int32_t dg = a.adj[base + g];
+        const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+        const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+        pl_group(a, t, base, n, make_int4((int)k, (int)k + 1, (int)plo, (int)phi + 1));
+    }
+    if (k + 1 >= n) return;
+    const int32_t d = a.adj[q];
+    const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+    if (lo != 0 && a.adj[base + lo - 1] >= d) return;  // (not the node's first gap)
+    const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+    if (lo == 0 && hi == n - 1) return;  // (the root)
+    const int64_t g = lo == 0 ? hi : hi == n - 1 ? lo - 1 : (a.adj[base + lo - 1] >= a.adj[base + hi] ? lo - 1 : hi);
+    const int32_t dg = a.adj[base + g];
+    const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+    const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+    pl_group(a, t, base, n, make_int4((int)lo, (int)hi + 1, (int)plo, (int)phi + 1));
+}
+
+// the marks of one (z, query) on the query's two rows: av for the strict descendants of pz's S node (every node when
+// z is the root) and not for those of z's own, xv for the subtree of z's top node
+__device__ __forceinline__ void pl_emit(unsigned long long *__restrict__ sub, unsigned long long *__restrict__ strict,
+                                        int4 meta, unsigned long long av, unsigned long long xv) {
+    if (av) {
+        atomicAdd(meta.y < 0 ? sub : strict + meta.y, av);
+        if (meta.x >= 0) atomicAdd(strict + meta.x, 0ull - av);
+    }
+    if (xv) atomicAdd(sub + meta.z, xv);
+}
+
+struct sc_pl_pair_args {
+    const int64_t *blk;       // first workgroup of the batch's tree i (cumulative, blk[0] = the batch's own start)
+    int nb;
+    const int64_t *off;
+    const int4 *glist;
+    const int32_t *gcnt;
+    const int2 *qinfo;
+    const int32_t *qheld;     // [nb] queries of the pass the tree holds
+    int qc;
+    const int4 *zlist, *zmeta;
+    const int32_t *zcnt;
+    const int2 *tp;
+    int zb, W;
+    int lds_sums;             // A and X summed per (z, query) in LDS; else every (z, y) sends its own marks
+    unsigned long long *sub, *strict;  // rows [2][n_queries][n_nodes] (shared, super), at the pass's first query
+    int64_t row_stride;       // n_nodes
+    int64_t super_off;        // n_queries * n_nodes
+    unsigned long long *csub, *cstrict;  // [n_nodes] each: marks of the super rows of every query of the pass
+};
+
+// the hot path: one workgroup per (tree t, block of zb of t's S' nodes).  LDS: with lds_sums the sums [zb][qc]{A, X},
+// the nodes [zb]{range, meta} and the list offsets [qc + 1]; then the rows [2 zb][W] of k_trip_pairs
+__global__ void __launch_bounds__(SC_THREADS) k_pl_pairs(sc_pl_pair_args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pl_lds[];
+    const int64_t g = a.blk[0] + blockIdx.x;
+    const int t = sc_tree_of(a.blk, a.nb, g);
+    const int j0 = (int)(g - a.blk[t]) * a.zb;
+    const int nz = min(a.zb, a.zcnt[t] - j0);
+    if (nz <= 0) return;
+    const int qc = a.qc, W = a.W;
+    const int2 *qinfo = a.qinfo + (int64_t)t * qc;
+    if (a.qheld[t] == 0) return;  // (the tree holds no query of this pass)
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int4 *zlist = a.zlist + 2 * base + j0, *zmeta = a.zmeta + 2 * base + j0;
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(pl_lds);
+    int4 *zs = reinterpret_cast<int4 *>(sums + (a.lds_sums ? 2 * a.zb * qc : 0));
+    int *pref = reinterpret_cast<int *>(zs + (a.lds_sums ? 2 * a.zb : 0));
+    int2 *rows = reinterpret_cast<int2 *>(pl_lds + (a.lds_sums ? 16 * a.zb * qc + 32 * a.zb + 4 * ((qc + 4) & ~3) : 0));
+    const int nrow = 2 * nz;
+    for (int i = threadIdx.x; i < nrow * W; i += SC_THREADS) rows[i] = make_int2(0, 0);
+    if (a.lds_sums) {
+        for (int i = threadIdx.x; i < 2 * nz * qc; i += SC_THREADS) sums[i] = 0;
+        for (int i = threadIdx.x; i < nz; i += SC_THREADS) {
+            zs[2 * i] = zlist[i];
+            zs[2 * i + 1] = zmeta[i];
+        }
+        if (threadIdx.x == 0) {
+            int run = 0;
+            for (int i = 0; i < qc; ++i) {
+                pref[i] = run;
+                run += a.gcnt[(int64_t)t * qc + i];
+            }
+            pref[qc] = run;
+        }
+    }
+    __syncthreads();
+    unsigned *bits = reinterpret_cast<unsigned *>(rows);
+    for (int j = 0; j < nz; ++j) {
+        const int4 z = zlist[j];
+        for (int k = z.x + threadIdx.x; k < z.y; k += SC_THREADS) {
+            const int x = a.tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j) * W + (x >> 5)), 1u << (x & 31));
+        }
+        for (int k = z.z + threadIdx.x; k < z.w; k += SC_THREADS) {
+            const int x = a.tp[base + k].x;
+            atomicOr(bits + 2 * ((2 * j + 1) * W + (x >> 5)), 1u << (x & 31));
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = wave; r < nrow; r += SC_THREADS / 64) {
+        int2 *row = rows + r * W;
+        int run = 0;
+        for (int c = 0; c < W; c += 64) {
+            const int i = c + lane;
+            const int v = i < W ? __popc((unsigned)row[i].x) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    __syncthreads();
+    // A and X of one (z, y): y's T positions [y.x, y.y), py's [y.z, y.w)
+    const auto pair = [&](const int4 y, int j, int4 z, unsigned long long &av, unsigned long long &xv) {
+        const int2 *rz = rows + 2 * j * W, *rp = rz + W;
+        const int wa = y.x >> 5, wb = y.y >> 5;
+        const unsigned ma = (1u << (y.x & 31)) - 1u, mb = (1u << (y.y & 31)) - 1u;
+        const int iyz = tp_count(rz, wb, mb) - tp_count(rz, wa, ma);
+        if (iyz == 0) return false;
+        const int wc = y.z >> 5, wd = y.w >> 5;
+        const unsigned mc = (1u << (y.z & 31)) - 1u, md = (1u << (y.w & 31)) - 1u;
+        const int ipyz = tp_count(rz, wd, md) - tp_count(rz, wc, mc);
+        const int ipp = tp_count(rp, wd, md) - tp_count(rp, wc, mc);
+        av = (unsigned long long)((int64_t)iyz * (iyz - 1) / 2);
+        xv = (unsigned long long)((int64_t)iyz * (((z.w - z.z) - ipp) - ((z.y - z.x) - ipyz)));
+        return true;
+    };
+    if (a.lds_sums) {
+        const int total = pref[qc];
+        for (int e = threadIdx.x; e < total; e += SC_THREADS) {
+            int i = 0, hi = qc;  // pref[i] <= e < pref[hi]
+            while (hi - i > 1) {
+                const int m = (i + hi) >> 1;
+                if (pref[m] <= e) i = m; else hi = m;
+            }
+            const int4 y = a.glist[base * qc + (int64_t)i * n + (e - pref[i])];
+            for (int j = 0; j < nz; ++j) {
+                unsigned long long av, xv;
+                if (!pair(y, j, zs[2 * j], av, xv)) continue;
+                if (av) atomicAdd(sums + 2 * (j * qc + i), av);
+                if (xv) atomicAdd(sums + 2 * (j * qc + i) + 1, xv);
+            }
+        }
+        __syncthreads();
+    } else {
+        for (int i = 0; i < qc; ++i) {
+            const int cnt = a.gcnt[(int64_t)t * qc + i];
+            for (int e = threadIdx.x; e < cnt; e += SC_THREADS) {
+                const int4 y = a.glist[base * qc + (int64_t)i * n + e];
+                for (int j = 0; j < nz; ++j) {
+                    unsigned long long av, xv;
+                    if (!pair(y, j, zlist[j], av, xv)) continue;
+                    pl_emit(a.sub + i * a.row_stride, a.strict + i * a.row_stride, zmeta[j], av, xv);
+                }
+            }
+        }
+    }
+    // a tree that holds every query of the pass sends the super marks of a taxon outside pz once, to the pass's common
+    // rows; a query then adds what its own place in z or pz changes (nothing for most z)
+    const bool common = a.qheld[t] == qc;
+    if (common)
+        for (int j = threadIdx.x; j < nz; j += SC_THREADS) {
+            const int4 z = a.lds_sums ? zs[2 * j] : zlist[j];
+            const int64_t sz = z.y - z.x, spz = z.w - z.z;
+            pl_emit(a.csub, a.cstrict, a.lds_sums ? zs[2 * j + 1] : zmeta[j], (unsigned long long)(sz * (sz - 1) / 2),
+                    (unsigned long long)(sz * (spz - sz)));
+        }
+    // per (z, query the tree holds): the summed marks of the shared row, the closed-form marks of the super row
+    for (int it = threadIdx.x; it < nz * qc; it += SC_THREADS) {
+        const int j = it / qc, i = it % qc;
+        const int kx = qinfo[i].y;
+        if (kx < 0) continue;
+        const int4 z = a.lds_sums ? zs[2 * j] : zlist[j], meta = a.lds_sums ? zs[2 * j + 1] : zmeta[j];
+        if (a.lds_sums)
+            pl_emit(a.sub + i * a.row_stride, a.strict + i * a.row_stride, meta, sums[2 * it], sums[2 * it + 1]);
+        const int64_t sz = (z.y - z.x) - (kx >= z.x && kx < z.y), spz = (z.w - z.z) - (kx >= z.z && kx < z.w);
+        unsigned long long av = (unsigned long long)(sz * (sz - 1) / 2), xv = (unsigned long long)(sz * (spz - sz));
+        if (common) {
+            const int64_t s0 = z.y - z.x, p0 = z.w - z.z;
+            av -= (unsigned long long)(s0 * (s0 - 1) / 2);
+            xv -= (unsigned long long)(s0 * (p0 - s0));
+        }
+        pl_emit(a.sub + a.super_off + i * a.row_stride, a.strict + a.super_off + i * a.row_stride, meta, av, xv);
+    }
+}
+
+// mark(u) = sub[u] + strict[parent u] on [u, end u) of the row's difference array (zeroed; n + 1 entries); the rows
+// [n_rows / 2, n_rows) are the super rows of the queries, pass by pass of qcap queries: they take their pass's common
+// rows [pass][n] as well
+__global__ void __launch_bounds__(SC_THREADS) k_pl_marks(const unsigned long long *__restrict__ sub,
+                                                         const unsigned long long *__restrict__ strict,
+                                                         const unsigned long long *__restrict__ csub,
+                                                         const unsigned long long *__restrict__ cstrict, int qcap,
+                                                         const int32_t *__restrict__ parent,
+                                                         const int32_t *__restrict__ end, int64_t n, int64_t n_rows,
+                                                         unsigned long long *__restrict__ diff) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * n_rows) return;
+    const int64_t r = idx / n, u = idx % n;
+    unsigned long long m = sub[idx] + (u ? strict[r * n + parent[u]] : 0ull);
+    if (2 * r >= n_rows) {
+        const int64_t pass = (r - n_rows / 2) / qcap;
+        m += csub[pass * n + u] + (u ? cstrict[pass * n + parent[u]] : 0ull);
+    }
+    if (!m) return;
+    atomicAdd(diff + r * (n + 1) + u, m);
+    atomicAdd(diff + r * (n + 1) + end[u], 0ull - m);
+}
+
+// inclusive prefix sums of every row's difference array: the values of the row's nodes, one workgroup per row
+__global__ void __launch_bounds__(1024) k_pl_prefix(const unsigned long long *__restrict__ diff, int64_t n,
+                                                    unsigned long long *__restrict__ out) {
+    __shared__ unsigned long long ws[16];
+    const unsigned long long *d = diff + (int64_t)blockIdx.x * (n + 1);
+    unsigned long long *o = out + (int64_t)blockIdx.x * n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long run = 0;
+    for (int64_t c = 0; c < n; c += 1024) {
+        const int64_t i = c + threadIdx.x;
+        unsigned long long x = i < n ? d[i] : 0;
+        for (int s = 1; s < 64; s <<= 1) {
+            const unsigned long long y = __shfl_up(x, s, 64);
+            if (lane >= s) x += y;
+        }
+        if (lane == 63) ws[wave] = x;
+        __syncthreads();
+        unsigned long long before = run, total = 0;
+        for (int w = 0; w < 16; ++w) {
+            if (w < wave) before += ws[w];
+            total += ws[w];
+        }
+        if (i < n) o[i] = before + x;
+        run += total;
+        __syncthreads();
+    }
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -2362,6 +2775,217 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
     int64_t *const outs[5] = {tx_trees, tx_total, tx_super, tx_source, tx_shared};
     for (int i = 0; i < 5 && e == hipSuccess; ++i)
         if (outs[i] && n_out) e = hipMemcpyAsync(outs[i], d_tx + i * n_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    return SCS_OK;
+}
+
+extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                    const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                    int32_t n_queries, const int32_t *queries, int64_t *pl_trees, int64_t *pl_total,
+                                    int64_t *pl_source, int64_t *pl_super, int64_t *pl_shared) {
+    // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS, as for scs_score_triplets; every
+    // count of one tree is then below m^2 < 2^63
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "scs_score_placements: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS",
+                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_REQUIRE(max_lds_bytes >= 0, "scs_score_placements: max_lds_bytes = %d is negative", max_lds_bytes);
+    SCS_REQUIRE(n_queries >= 1 && queries, "scs_score_placements: no query taxon");
+    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= lds_cap,
+                "scs_score_placements: max_lds_bytes = %d does not hold the rows of a source tree of %lld leaves",
+                max_lds_bytes, (long long)m_max);
+    // the queries are tips of the supertree, each once; the tips' preorder index and depth by leaf position
+    std::vector<int32_t> tip_node, tip_depth;
+    if (parent && taxon && n_nodes >= 1) {
+        std::vector<char> has_kid((size_t)n_nodes, 0);
+        std::vector<int32_t> depth((size_t)n_nodes, 0);
+        for (int32_t v = 1; v < n_nodes; ++v)
+            if (parent[v] >= 0 && parent[v] < v) {
+                has_kid[parent[v]] = 1;
+                depth[v] = depth[parent[v]] + 1;
+            }
+        std::vector<int32_t> tips;
+        for (int32_t v = 0; v < n_nodes; ++v)
+            if (!has_kid[v]) {
+                tip_node.push_back(v);
+                tip_depth.push_back(depth[v]);
+                tips.push_back(taxon[v]);
+            }
+        std::sort(tips.begin(), tips.end());
+        std::vector<int32_t> qs(queries, queries + n_queries);
+        std::sort(qs.begin(), qs.end());
+        for (int32_t i = 0; i < n_queries; ++i) {
+            SCS_REQUIRE(std::binary_search(tips.begin(), tips.end(), qs[i]),
+                        "scs_score_placements: query taxon %d is not a tip of the supertree", qs[i]);
+            SCS_REQUIRE(i == 0 || qs[i] != qs[i - 1], "scs_score_placements: query taxon %d is given twice", qs[i]);
+        }
+    }
+    // own arrays: three rows of n_nodes + 1 sums per query and output (`sub`, later the values; `strict`; the
+    // difference row), the two common rows per pass, three sums per query, the queries' S positions, S's parents and tips, the first pair workgroup
+    // per tree (+ 1).  Per batch: a group list entry per leaf and query of a pass, two node lists of two entries per
+    // leaf; per tree and query the query's positions and its list's length, per tree the node list's length and the
+    // number of queries it holds
+    const size_t nn = (size_t)std::max(n_nodes, 0), nq = (size_t)n_queries, mt = src ? (size_t)src->n_trees : 0;
+    const size_t row_bytes = sc_up256(2 * nq * (nn + 1) * 8);
+    const int qcap = std::min<int>(std::max(n_queries, 1), PL_QMAX);
+    const size_t n_pass = (nq + qcap - 1) / qcap, common_bytes = sc_up256(2 * n_pass * nn * 8);
+    SCS_REQUIRE(3 * (uint64_t)row_bytes + common_bytes <= SC_BUDGET,
+                "scs_score_placements: %d query taxa x %d supertree nodes need %llu bytes of rows, more than the %llu "
+                "of the call's workspace", n_queries, n_nodes,
+                (unsigned long long)(3 * (uint64_t)row_bytes + common_bytes), (unsigned long long)SC_BUDGET);
+    const size_t o_sub = 0, o_strict = row_bytes, o_diff = 2 * row_bytes, o_common = 3 * row_bytes,
+                 o_qs = o_common + common_bytes, o_qpos = o_qs + sc_up256(nq * 24), o_par = o_qpos + sc_up256(nq * 4), o_tipn = o_par + sc_up256(nn * 4),
+                 o_tipd = o_tipn + sc_up256(nn * 4), o_blk = o_tipd + sc_up256(nn * 4),
+                 own = o_blk + sc_up256((mt + 1) * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_placements", n_nodes, parent, taxon, max_batch_trees, own,
+                     16 * (uint64_t)qcap + 64, 12 * (uint64_t)qcap + 8, c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_sub = (unsigned long long *)(c.d_extra + o_sub);
+    auto *d_strict = (unsigned long long *)(c.d_extra + o_strict);
+    auto *d_diff = (unsigned long long *)(c.d_extra + o_diff);
+    auto *d_common = (unsigned long long *)(c.d_extra + o_common);
+    auto *d_qs = (unsigned long long *)(c.d_extra + o_qs);
+    auto *d_qpos = (int32_t *)(c.d_extra + o_qpos);
+    auto *d_par = (int32_t *)(c.d_extra + o_par);
+    auto *d_tipn = (int32_t *)(c.d_extra + o_tipn);
+    auto *d_tipd = (int32_t *)(c.d_extra + o_tipd);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    const size_t n_batches = c.bstart.size() - 1;
+    int64_t max_rows = 0;
+    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
+    auto *d_glist = (int4 *)c.d_extra_batch;
+    auto *d_zlist = d_glist + c.max_lb * qcap;
+    auto *d_zmeta = d_zlist + 2 * c.max_lb;
+    auto *d_qinfo = (int2 *)(d_zmeta + 2 * c.max_lb);
+    auto *d_gcnt = (int32_t *)(d_qinfo + max_rows * qcap);
+    auto *d_zcnt = d_gcnt + max_rows * qcap;
+    auto *d_qheld = d_zcnt + max_rows;
+    std::vector<int32_t> q_spos(nq);
+    for (size_t i = 0; i < nq; ++i) q_spos[i] = queries[i] < c.n_taxa ? c.s_pos[queries[i]] : -1;
+    // per batch: W words per bitset row, zb S' nodes per workgroup and whether the sums of a pass fit beside the rows;
+    // blk: the first pair workgroup of every tree, ceil(2 n / zb) of them for a tree of n >= 3 leaves (its S' has n
+    // leaves and at most n - 1 other nodes)
+    const int aux1 = 16 * qcap + 32, auxq = 4 * ((qcap + 4) & ~3);  // LDS bytes beside the rows: per node, per pass
+    std::vector<int> words(n_batches), zbs(n_batches), sums(n_batches);
+    std::vector<int64_t> blk((size_t)M + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        const int rowb = 16 * words[b];
+        int zb = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / rowb));
+        while (zb > 1 && zb * (rowb + aux1) + auxq > lds_cap) --zb;
+        sums[b] = zb * (rowb + aux1) + auxq <= lds_cap;
+        zbs[b] = zb;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) {
+            const int64_t n = off[t + 1] - off[t];
+            blk[t + 1] = blk[t] + (n >= 3 ? (2 * n + zb - 1) / zb : 0);
+        }
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, 3 * row_bytes + common_bytes + sc_up256(nq * 24), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qpos, q_spos.data(), nq * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_par, parent, nn * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tipn, tip_node.data(), tip_node.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tipd, tip_depth.data(), tip_depth.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_pl_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_zcnt, 0, (size_t)nb * 4, s);
+        if (e != hipSuccess) break;
+        sc_pl_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.dep = c.d_dep;
+        a.node = c.d_node;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_tab = c.d_stab;
+        a.s_stride = c.n_gaps;
+        a.s_levels = sc_levels_host(c.n_gaps);
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.tip_node = d_tipn;
+        a.tip_depth = d_tipd;
+        a.zlist = d_zlist;
+        a.zmeta = d_zmeta;
+        a.zcnt = d_zcnt;
+        a.qinfo = d_qinfo;
+        a.glist = d_glist;
+        a.gcnt = d_gcnt;
+        k_pl_znodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        for (int32_t q0 = 0; q0 < n_queries && n_wg > 0; q0 += qcap) {
+            const int qc = std::min<int>(qcap, n_queries - q0);
+            a.qc = qc;
+            a.q_source = d_qs + 2 * nq + q0;
+            e = hipMemsetAsync(d_qheld, 0, (size_t)nb * 4, s);
+            if (e != hipSuccess) break;
+            k_pl_queries<<<grid_of((int64_t)nb * qc), SC_THREADS, 0, s>>>(a.off, nb, d_qpos + q0, qc, c.d_rows,
+                                                                          c.row_stride, c.d_sp, d_qinfo, d_gcnt,
+                                                                          d_qheld, d_qs + q0, d_qs + nq + q0);
+            if (!sc_launched(e)) break;
+            k_pl_groups<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+            if (!sc_launched(e)) break;
+            sc_pl_pair_args pa;
+            pa.blk = d_blk + t0;
+            pa.nb = nb;
+            pa.off = a.off;
+            pa.glist = d_glist;
+            pa.gcnt = d_gcnt;
+            pa.qinfo = d_qinfo;
+            pa.qheld = d_qheld;
+            pa.qc = qc;
+            pa.zlist = d_zlist;
+            pa.zmeta = d_zmeta;
+            pa.zcnt = d_zcnt;
+            pa.tp = c.d_mm;
+            pa.zb = zbs[b];
+            pa.W = words[b];
+            pa.lds_sums = sums[b];
+            pa.sub = d_sub + (size_t)q0 * nn;
+            pa.strict = d_strict + (size_t)q0 * nn;
+            pa.row_stride = (int64_t)nn;
+            pa.super_off = (int64_t)(nq * nn);
+            pa.csub = d_common + (size_t)(q0 / qcap) * nn;
+            pa.cstrict = d_common + (n_pass + (size_t)(q0 / qcap)) * nn;
+            const size_t lds = (size_t)zbs[b] * 16 * words[b] + (sums[b] ? (size_t)zbs[b] * (16 * qc + 32) +
+                                                                              4 * ((qc + 4) & ~3) : 0);
+            k_pl_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(pa);
+            if (!sc_launched(e)) break;
+        }
+    }
+    if (e == hipSuccess && !bad) {
+        k_pl_marks<<<grid_of((int64_t)(2 * nq * nn)), SC_THREADS, 0, s>>>(d_sub, d_strict, d_common,
+                                                                        d_common + n_pass * nn, qcap, d_par, c.d_end,
+                                                                        (int64_t)nn, (int64_t)(2 * nq), d_diff);
+        sc_launched(e);
+    }
+    if (e == hipSuccess && !bad) {
+        k_pl_prefix<<<(unsigned)(2 * nq), 1024, 0, s>>>(d_diff, (int64_t)nn, d_sub);
+        sc_launched(e);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    int64_t *const scal[3] = {pl_trees, pl_total, pl_source};
+    for (int i = 0; i < 3 && e == hipSuccess; ++i)
+        if (scal[i]) e = hipMemcpyAsync(scal[i], d_qs + i * nq, nq * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && pl_shared) e = hipMemcpyAsync(pl_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && pl_super)
+        e = hipMemcpyAsync(pl_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
     SCS_TRY(sc_end(ctx, c, e, bad));
     return SCS_OK;
 }

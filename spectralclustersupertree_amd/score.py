@@ -1,7 +1,7 @@
 """How well a supertree fits its source trees: Robinson-Foulds terms per source tree and clade support per
 supertree node, and on request rooted triplet terms per source tree (section 15), clade
-conflict counts (section 16), branch concordance factors (section 17), per-branch triplet support (section 18) and
-per-taxon triplet support (section 20).
+conflict counts (section 16), branch concordance factors (section 17), per-branch triplet support (section 18),
+per-taxon triplet support (section 20) and taxon placement support (section 22).
 Neither the reference nor ``construct_supertree`` computes them.
 
 For a source tree T with leaf set L(T), clusters are leaf sets and a cluster of a tree on L is nontrivial when
@@ -82,9 +82,30 @@ Every triple has three taxa, so Σ_x ``tx_shared`` = 3 Σ_t ``t_shared`` (likewi
 second factor of ``t_shared``, every leaf of cl(y) ∩ cl(z) takes (I - 1) J of the pair's triples (as a or b) and
 every leaf of (cl(py) ∖ cl(y)) ∩ (cl(pz) ∖ cl(z)) takes C(I, 2) (as c).
 
+Taxon placement support (``placements=[names]`` or ``placements=N``): where a taxon would fit its sources best.  For a
+tip x of S and a node v of S (v may be x itself or an ancestor of x), S_{x→v} is S with x pruned and regrafted on the
+edge above v.  Its clusters are, for every cluster C of S, (C ∖ {x}) ∪ {x} when C belongs to a strict ancestor of v and
+C ∖ {x} otherwise, and the new cluster (cl(v) ∖ {x}) ∪ {x}; empty sets are dropped.  So S_{x→x} has the clusters of S,
+and so has S_{x→v} for x's sibling, for x's parent when it has two children, and for every v with cl(v) ∖ {x} = ∅.
+Per query taxon x (``pl_taxa``), summed over the sources T with x ∈ L = L(T) and m = |L| >= 3, over the C(m-1, 2)
+triples {x, a, b} ⊆ L:
+
+* ``pl_trees`` = ``tx_trees[x]``, ``pl_total`` = ``tx_total[x]``, ``pl_source`` = the triples T resolves;
+* ``pl_super[x][v]`` = the triples S_{x→v}|L resolves, ``pl_shared[x][v]`` = those T and S_{x→v}|L resolve alike;
+* ``placement_distance = pl_super + pl_source - 2 pl_shared`` per (x, v): the triplet distance x would have there.
+  At x's own node the three counts are ``tx_super[x]``, ``tx_source[x]`` and ``tx_shared[x]``.
+
+With every set restricted to L ∖ {x}: the *groups* of x in T are the clusters y with x ∉ y and x ∈ py (the subtrees
+hanging off x's root path, leaves included).  T says ab|x when a and b share a group and xa|b when a ∈ y, b ∉ py.  For
+a set c, A(c) = Σ_y C(|y ∩ c|, 2); for a child c of an S node with set q, X(c, q) = Σ_y |y ∩ c| (|q ∖ py| - |c ∖ py|),
+the pairs a ∈ c, b ∈ q ∖ c with xa|b in T.  Then shared(root) = A(root set) and, for a node v with parent q,
+shared(v) = shared(q) + [Σ_{children s of q} A(s) - A(q)] + X(v, q): moving x from the edge above q to the edge above
+v loses the pairs ab|x whose LCA is q and gains the pairs xa|b with a below v and b below q.  ``pl_super`` follows the
+same recurrence with C(|c|, 2) and |c| (|q| - |c|).  Every term is node-local, so a value is a root-path sum of marks.
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
-``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets`` and ``scs_score_taxon_triplets``; the
-host only validates and lays out.
+``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets`` and
+``scs_score_placements``; the host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -103,6 +124,8 @@ BATCH_TREES: int | None = None
 # LDS bytes a workgroup of the per-taxon pair kernel may take; None: the default (a test sets a small value so that
 # small trees reach the path through global memory)
 TAXON_LDS_BYTES: int | None = None
+# the same for the placement pair kernel (a small value: no room for the sums per node and query beside the rows)
+PLACEMENT_LDS_BYTES: int | None = None
 
 
 @dataclass
@@ -120,7 +143,8 @@ class SupertreeScore:
     # to device tables), "score" (scs_score_supertree: its host layout of the supertree and the kernels),
     # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
-    # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested)
+    # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested), "placements" (scs_score_placements,
+    # when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -154,6 +178,14 @@ class SupertreeScore:
     tx_super: np.ndarray | None = None
     tx_source: np.ndarray | None = None
     tx_shared: np.ndarray | None = None
+    # taxon placement support (``placements=...``; None otherwise): the query taxa (ids into ``taxa``), one entry per
+    # query, and queries x supertree nodes (preorder)
+    pl_taxa: np.ndarray | None = None
+    pl_trees: np.ndarray | None = None
+    pl_total: np.ndarray | None = None
+    pl_source: np.ndarray | None = None
+    pl_super: np.ndarray | None = None
+    pl_shared: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -409,6 +441,103 @@ class SupertreeScore:
                         f"\t{self.tx_source[x]}\t{self.tx_shared[x]}\t{dist[x]}")
         return "\n".join(rows) + "\n"
 
+    def _need_placements(self) -> None:
+        if self.pl_shared is None:
+            msg = "placement counts were not computed: score_supertree(..., placements=...)"
+            raise ValueError(msg)
+
+    @property
+    def placement_distance(self) -> np.ndarray:
+        """Queries x nodes: the triplet distance of the query taxon to its sources if it sat on the edge above the
+        node."""
+        self._need_placements()
+        return self.pl_super + self.pl_source[:, None] - 2 * self.pl_shared
+
+    def _tip_nodes(self) -> np.ndarray:
+        """Preorder index of every tip, by taxon id."""
+        return np.array([i for i, v in enumerate(_preorder(self.supertree)) if v.is_tip()], dtype=np.int64)
+
+    def best_placements(self) -> list[dict]:
+        """One dict per query taxon, in query order: ``taxon`` (id), ``name``, ``trees``, ``node`` (the taxon's own
+        node, preorder index), ``distance`` (its triplet distance there), ``best_node``, ``best_distance`` and
+        ``improvement`` = distance - best_distance >= 0.  The best node has the smallest distance; among equals the
+        taxon's own node, else the lowest preorder index."""
+        dist = self.placement_distance
+        own = self._tip_nodes()
+        out = []
+        for i, x in enumerate(self.pl_taxa):
+            node = int(own[x])
+            low = int(dist[i].min())
+            best = node if dist[i, node] == low else int(np.argmin(dist[i]))
+            out.append({"taxon": int(x), "name": self.taxa[x], "trees": int(self.pl_trees[i]), "node": node,
+                        "distance": int(dist[i, node]), "best_node": best, "best_distance": low,
+                        "improvement": int(dist[i, node]) - low})
+        return out
+
+    def placement_table(self) -> str:
+        """One TSV row per query taxon: taxon (id), name, trees, node, distance, best_node, best_distance,
+        improvement (``best_placements``).  ``ValueError`` unless the placements were computed."""
+        rows = ["taxon\tname\ttrees\tnode\tdistance\tbest_node\tbest_distance\timprovement"]
+        for r in self.best_placements():
+            rows.append(f"{r['taxon']}\t{r['name']}\t{r['trees']}\t{r['node']}\t{r['distance']}\t{r['best_node']}"
+                        f"\t{r['best_distance']}\t{r['improvement']}")
+        return "\n".join(rows) + "\n"
+
+    def regraft(self, taxon, node: int) -> TreeNode:
+        """A copy of the supertree with the tip ``taxon`` (a name, or an id into the tips in preorder) moved onto
+        the edge above ``node`` (preorder index in this supertree): S_{x→node} of the module docstring.  The node the
+        tip leaves behind is suppressed when it keeps one child; when ``node`` is that node, the tip goes above its
+        remaining child.  When ``node`` holds no taxon but the tip itself, the copy is unchanged."""
+        out = self.supertree.copy()
+        nodes = _preorder(out)
+        tips = [v for v in nodes if v.is_tip()]
+        if isinstance(taxon, str):
+            found = [v for v in tips if v.name == taxon]
+            if not found:
+                msg = f"taxon {taxon!r} is not in the supertree"
+                raise ValueError(msg)
+            tip = found[0]
+        else:
+            if not 0 <= int(taxon) < len(tips):
+                msg = f"taxon id {taxon} is not in [0, {len(tips)})"
+                raise ValueError(msg)
+            tip = tips[int(taxon)]
+        if not 0 <= int(node) < len(nodes):
+            msg = f"node {node} is not in [0, {len(nodes)})"
+            raise ValueError(msg)
+        target = nodes[int(node)]
+        if all(t is tip for t in target.iter_tips()):
+            return out
+        # prune: the tip, the nodes it leaves empty, and the node it leaves with one child
+        gone = tip
+        while gone.parent is not None and len(gone.parent.children) == 1:
+            gone = gone.parent
+        above = gone.parent  # (not None: the target holds another taxon, so the root keeps a child)
+        above.children.remove(gone)
+        tip.parent = None
+        if len(above.children) == 1:
+            (kid,) = above.children
+            if target is above:
+                target = kid
+            if above.parent is None:
+                kid.parent = None
+                out = kid
+            else:
+                sibs = above.parent.children
+                sibs[sibs.index(above)] = kid
+                kid.parent = above.parent
+        # regraft: a new node above the target, holding the target and the tip
+        up = target.parent
+        new = TreeNode(None)
+        if up is None:
+            out = new
+        else:
+            up.children[up.children.index(target)] = new
+            new.parent = up
+        new.append(target)
+        new.append(tip)
+        return out
+
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
         concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
@@ -512,7 +641,7 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
                     concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-                    device=None) -> SupertreeScore:
+                    placements=None, device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
@@ -521,7 +650,11 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     triplet support (``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative`` per tree, ``bt_total``,
     ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` per node) and ``taxon_triplets=True`` the per-taxon triplet support
     (``taxa``, ``tx_trees``, ``tx_total``, ``tx_super``, ``tx_source``, ``tx_shared`` per supertree tip), all counted
-    on the same device tables as the RF terms.
+    on the same device tables as the RF terms.  ``placements``: a list of tip names, or an int N for the N least
+    stable taxa (``rogue_taxa(N)``: largest ``taxon_instability`` among the taxa some source of 3 or more leaves
+    holds; this implies ``taxon_triplets=True``): the placement support of those taxa (``pl_taxa``, ``pl_trees``,
+    ``pl_total``, ``pl_source`` per query, ``pl_super``, ``pl_shared`` per query and supertree node).  ``ValueError``
+    for an unknown or repeated name.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -533,6 +666,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     t0 = time.perf_counter()
     parent, taxon, tips = supertree_arrays(supertree)
     index = {name: i for i, name in enumerate(tips)}
+    placements = _check_placements(placements, index)
+    taxon_triplets = taxon_triplets or isinstance(placements, int)
     if isinstance(trees, TreeArrays):
         if trees.n_trees == 0:
             msg = "There must be at least one tree to score against."
@@ -547,11 +682,11 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
         out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
-                            concordance, branch_triplets, taxon_triplets, tips)
+                            concordance, branch_triplets, taxon_triplets, tips, placements)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
                                   - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
                                   - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0)
-                                  - out.timings.get("taxon_triplets", 0.0))
+                                  - out.timings.get("taxon_triplets", 0.0) - out.timings.get("placements", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -588,6 +723,9 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
                                                 lds_bytes=TAXON_LDS_BYTES or 0))
             res["taxa"] = list(tips)
             t8 = time.perf_counter()
+        if placements is not None:
+            res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
+            t9 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
@@ -601,6 +739,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         timings["branch_triplets"] = t7 - t6
     if taxon_triplets:
         timings["taxon_triplets"] = t8 - t7
+    if placements is not None:
+        timings["placements"] = t9 - t8
     return _result(supertree, np.diff(tables.tree_off), res, timings)
 
 
@@ -614,7 +754,55 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
                           res.get("n_bt_total"), res.get("n_bt_concordant"), res.get("n_bt_alternative"),
                           res.get("bt_total"), res.get("bt_concordant"), res.get("bt_alt1"), res.get("bt_alt2"),
                           res.get("taxa"), res.get("tx_trees"), res.get("tx_total"), res.get("tx_super"),
-                          res.get("tx_source"), res.get("tx_shared"))
+                          res.get("tx_source"), res.get("tx_shared"),
+                          res.get("pl_taxa"), res.get("pl_trees"), res.get("pl_total"), res.get("pl_source"),
+                          res.get("pl_super"), res.get("pl_shared"))
+
+
+def _check_placements(placements, index: dict):
+    """``None``, a count or the query taxon ids of ``score_supertree``'s ``placements``."""
+    if placements is None:
+        return None
+    if isinstance(placements, (bool, str)):
+        msg = "placements must be a list of taxon names or a count"
+        raise ValueError(msg)
+    if isinstance(placements, (int, np.integer)):
+        if placements < 0:
+            msg = f"placements = {placements} is negative"
+            raise ValueError(msg)
+        return int(placements)
+    ids = []
+    for name in placements:
+        if name not in index:
+            msg = f"placement taxon {name!r} is not in the supertree"
+            raise ValueError(msg)
+        ids.append(index[name])
+    if len(set(ids)) != len(ids):
+        msg = "a placement taxon is given more than once"
+        raise ValueError(msg)
+    return np.array(ids, dtype=np.int32)
+
+
+def _placement_queries(placements, res: dict, tips) -> np.ndarray:
+    """The query taxon ids: as given, or the least stable taxa of the per-taxon counts in ``res``."""
+    if not isinstance(placements, int):
+        return placements
+    view = SupertreeScore(None, None, None, None, None, None, None, taxa=list(tips), tx_trees=res["tx_trees"],
+                          tx_total=res["tx_total"], tx_super=res["tx_super"], tx_source=res["tx_source"],
+                          tx_shared=res["tx_shared"])
+    return np.array([r["taxon"] for r in view.rogue_taxa(placements)], dtype=np.int32)
+
+
+def _placements(dev, tabs, parent, taxon, placements, res: dict, tips) -> dict:
+    queries = _placement_queries(placements, res, tips)
+    out = {"pl_taxa": queries.astype(np.int64), "taxa": list(tips)}
+    if len(queries) == 0:
+        out.update({k: np.zeros(0, dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")})
+        out.update({k: np.zeros((0, len(parent)), dtype=np.int64) for k in ("pl_super", "pl_shared")})
+        return out
+    out.update(dev.score_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
+                                    lds_bytes=PLACEMENT_LDS_BYTES or 0))
+    return out
 
 
 def _default_device():
@@ -625,7 +813,7 @@ def _default_device():
 
 def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
                   conflicts, concordance, branch_triplets=False, taxon_triplets=False,
-                  tips=None) -> SupertreeScore:
+                  tips=None, placements=None) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -663,9 +851,14 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = t4 = t5 = t6 = t7 = time.perf_counter()
+        t1 = t2 = t3 = t4 = t5 = t6 = t7 = t7p = t8 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
+            if placements is not None:
+                queries = _placement_queries(placements, res, tips)
+                res["pl_taxa"] = queries.astype(np.int64)
+                res.update({k: np.zeros(len(queries), dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")})
+                res.update({k: np.zeros((len(queries), n_nodes), dtype=np.int64) for k in ("pl_super", "pl_shared")})
         else:
             handle = C.c_void_p()
             nv.check(dev._lib.scs_tables_from_forest(dev._ctx, child._h, None, int(n_taxa), C.byref(handle)))
@@ -689,7 +882,11 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
                 if taxon_triplets:
                     res.update(dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0,
                                                         lds_bytes=TAXON_LDS_BYTES or 0))
-                    t7 = time.perf_counter()
+                    t7 = t8 = time.perf_counter()
+                if placements is not None:
+                    t7p = time.perf_counter()
+                    res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
+                    t8 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -710,5 +907,8 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
         timings["branch_triplets"] = t6 - t5
     if taxon_triplets:
         timings["taxon_triplets"] = t7 - t6
+        res["taxa"] = list(tips)
+    if placements is not None:
+        timings["placements"] = t8 - t7p
         res["taxa"] = list(tips)
     return _result(supertree, n_leaves, res, timings)

@@ -8,6 +8,7 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --concordance        # also the branch concordance counts
     python tools/score_bench.py --branch-triplets    # also the per-branch triplet support
     python tools/score_bench.py --taxon-triplets     # also the per-taxon triplet support
+    python tools/score_bench.py --placements 16      # also the placement support of 16 taxa
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -71,7 +72,7 @@ def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeA
 
 def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
         cat: bool = False, concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-        cat_sup: bool = False) -> dict:
+        cat_sup: bool = False, placements: int = 0) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
@@ -87,7 +88,8 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
     for _ in range(repeats):
         t0 = time.perf_counter()
         res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, concordance=concordance,
-                              branch_triplets=branch_triplets, taxon_triplets=taxon_triplets, device=dev)
+                              branch_triplets=branch_triplets, taxon_triplets=taxon_triplets,
+                              placements=_queries(sup, placements) if placements else None, device=dev)
         runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
@@ -149,7 +151,25 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
                 int(res.tx_shared.sum()) == 3 * int(res.t_shared.sum())
                 and int(res.tx_source.sum()) == 3 * int(res.t_source.sum())
                 and int(res.tx_super.sum()) == 3 * int(res.t_super.sum()))
+    if placements:
+        best = res.best_placements()
+        out.update({"placements": placements, "placements_call_s": round(tim["placements"], 5),
+                    "placements_call_s_min_median_max":
+                        [round(x, 5) for x in _spread([r[1]["placements"] for r in runs])],
+                    "placement_entries": int(res.pl_shared.size), "total_pl_trees": int(res.pl_trees.sum()),
+                    "total_best_distance": int(sum(r["best_distance"] for r in best)),
+                    "taxa_with_a_better_place": int(sum(r["improvement"] > 0 for r in best))})
+        if taxon_triplets:
+            xmed = _spread([r[1]["taxon_triplets"] for r in runs])[1]
+            pmed = _spread([r[1]["placements"] for r in runs])[1]
+            out["placements_over_taxon_triplets"] = round(pmed / max(xmed, 1e-9), 3)
     return out
+
+
+def _queries(sup: TreeNode, n: int) -> list[str]:
+    """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
+    tips = sup.get_tip_names()
+    return [tips[i] for i in np.linspace(0, len(tips) - 1, num=min(n, len(tips)), dtype=np.int64)]
 
 
 def _spread(values) -> tuple[float, float, float]:
@@ -166,6 +186,8 @@ def main() -> None:
     ap.add_argument("--concordance", action="store_true", help="also count the branch concordance factors")
     ap.add_argument("--branch-triplets", action="store_true", help="also count the per-branch triplet support")
     ap.add_argument("--taxon-triplets", action="store_true", help="also count the per-taxon triplet support")
+    ap.add_argument("--placements", type=int, default=0, metavar="N",
+                    help="also the placement support of N taxa spread over the supertree's leaf order")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -174,12 +196,13 @@ def main() -> None:
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
                         conflicts=args.conflicts, concordance=args.concordance, branch_triplets=args.branch_triplets,
-                        taxon_triplets=args.taxon_triplets, device=dev)  # warm-up
+                        taxon_triplets=args.taxon_triplets, placements=2 if args.placements else None,
+                        device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
             print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar,
                                  args.concordance, args.branch_triplets, args.taxon_triplets,
-                                 args.caterpillar_supertree)), flush=True)
+                                 args.caterpillar_supertree, args.placements)), flush=True)
 
 
 if __name__ == "__main__":
