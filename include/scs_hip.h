@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets and scs_score_placements added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements and scs_score_clade_placements added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -430,6 +430,33 @@ int scs_score_placements(scs_ctx *ctx, const scs_tables *sources, int32_t n_node
                          const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
                          const int32_t *queries, int64_t *pl_trees, int64_t *pl_total, int64_t *pl_source,
                          int64_t *pl_super, int64_t *pl_shared);
+
+/* Clade placement support, same inputs and SCS_EINVAL cases as scs_score_placements: for each
+ * of n_queries query nodes q of the supertree S (preorder indices; any node but the root, a tip included) with leaf
+ * set Q, and every node v of S, the triplet terms the clade would have if the subtree of q were pruned and regrafted
+ * on the edge above v.  For v outside the subtree of q, S_{q->v} has, for every cluster C of S not inside that subtree,
+ * (C - Q) + Q when C belongs to a strict ancestor of v and C - Q otherwise, the clusters inside the subtree unchanged,
+ * and the new cluster (cl(v) - Q) + Q; empty sets are dropped.  For v inside the subtree of q (q included) S_{q->v} = S:
+ * those entries hold the value of the clade's own position.  Summed over the source trees T on a leaf set L with
+ * Q' = Q & L and R = L - Q both non-empty and m = |L| >= 3, over the crossing triples of L (a taxon in Q', one in R):
+ *   cp_trees[i]                      = the number of such sources,
+ *   cp_total[i]                      = the crossing triples, C(m, 3) - C(|Q'|, 3) - C(|R|, 3) per source,
+ *   cp_source[i]                     = those T resolves (no v in it),
+ *   cp_super[i * n_nodes + v]        = those S_{q->v}|L resolves,
+ *   cp_shared[i * n_nodes + v]       = those T and S_{q->v}|L resolve alike,
+ * so that cp_super + cp_source - 2 cp_shared is the part of the triplet distance the move can change.  For a tip q
+ * the outputs are those of scs_score_placements for its taxon.  Counts are unweighted and exact; a query no source
+ * crosses gives zero rows; nested or overlapping query clades are independent; output pointers may be null.
+ * SCS_EINVAL as well for a query node that is the root, out of range or given twice, for a source tree of more than
+ * 327 679 leaves (as for scs_score_triplets), and when the rows do not fit the call's workspace: three rows of
+ * n_nodes + 1 int64 per query and output, 48 n_queries (n_nodes + 1) bytes, may take at most 1.5 GB (64 clades on
+ * 480 000 nodes, 1 500 on 20 000).  Every tip of a query clade is a sub-query of the sweep, and the sub-queries go
+ * through the batches 64 at a time: the cost grows linearly with the tips of the query clades taken together.
+ * max_lds_bytes as for scs_score_placements. */
+int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                               const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                               int32_t n_queries, const int32_t *query_nodes, int64_t *cp_trees, int64_t *cp_total,
+                               int64_t *cp_source, int64_t *cp_super, int64_t *cp_shared);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

@@ -47,14 +47,16 @@ def sc_supertree(
 @_define_app
 def score_supertree(supertree, trees, *, triplets: bool = False, conflicts: bool = False,
                     concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-                    placements=None):
+                    placements=None, clade_placements=None, clade_max_tips: int = 64):
     """``score.score_supertree``: RF distances of the supertree to the sources and its clades' support, with
     ``triplets=True`` the rooted triplet terms, with ``conflicts=True`` the clade conflict counts, with
     ``concordance=True`` the branch concordance counts, with ``branch_triplets=True`` the per-branch triplet
     support, with ``taxon_triplets=True`` the per-taxon triplet support and with ``placements`` (taxon names, or a
-    count of the least stable taxa) the taxon placement support."""
+    count of the least stable taxa) the taxon placement support and with ``clade_placements`` (nodes or name sets, or
+    a count of the least stable clades of up to ``clade_max_tips`` tips) the clade placement support."""
     return _score(supertree, trees, triplets=triplets, conflicts=conflicts, concordance=concordance,
-                  branch_triplets=branch_triplets, taxon_triplets=taxon_triplets, placements=placements)
+                  branch_triplets=branch_triplets, taxon_triplets=taxon_triplets, placements=placements,
+                  clade_placements=clade_placements, clade_max_tips=clade_max_tips)
 
 
 @_define_app

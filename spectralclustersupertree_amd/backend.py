@@ -288,6 +288,31 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_clade_placements(self, sources, parent: np.ndarray, taxon: np.ndarray, query_nodes,
+                               batch_trees: int = 0, lds_bytes: int = 0) -> dict:
+        """``scs_score_clade_placements``: the triplet terms the subtree of every query node would have on the edge
+        above every supertree node, with the inputs of ``score`` and ``query_nodes`` = preorder indices of supertree
+        nodes (not the root), each once.  Returns int64 arrays ``cp_trees``, ``cp_total``, ``cp_source`` (one entry
+        per query) and ``cp_super``, ``cp_shared`` (queries x nodes).  ``lds_bytes`` as for ``score_placements``."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        query_nodes = np.ascontiguousarray(query_nodes, dtype=np.int32)
+        n_nodes, nq = len(parent), len(query_nodes)
+        if taxon.shape != (n_nodes,) or query_nodes.ndim != 1:
+            msg = "parent and taxon must have one entry per supertree node, query_nodes one per query clade"
+            raise ValueError(msg)
+        out = {k: np.zeros(nq, dtype=np.int64) for k in ("cp_trees", "cp_total", "cp_source")}
+        out.update({k: np.zeros((nq, n_nodes), dtype=np.int64) for k in ("cp_super", "cp_shared")})
+        rc = self._lib.scs_score_clade_placements(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                                  int(batch_trees), int(lds_bytes), nq, nv.iptr(query_nodes),
+                                                  *(nv.lptr(v) for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_clade_placements: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

@@ -68,12 +68,21 @@ from spectralclustersupertree_amd import __version__
                    "best, by rooted triplet distance.")
 @click.option("--place-taxa", default=10, type=click.IntRange(min=1), show_default=True,
               help="How many of the least stable taxa --placements-out places.")
+@click.option("--clade-placements-out", default=None,
+              help="Also write a TSV with one row per placed clade (node, tips, trees, distance, best_node, "
+                   "best_distance, improvement): where on the supertree the least stable small clades would fit "
+                   "their sources best as a whole, by rooted triplet distance.")
+@click.option("--place-clades", default=10, type=click.IntRange(min=1), show_default=True,
+              help="How many clades --clade-placements-out places.")
+@click.option("--clade-max-tips", default=64, type=click.IntRange(min=2), show_default=True,
+              help="The largest clade --clade-placements-out considers.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
         concordance_out: str | None = None, branches_out: str | None = None, branch_triplets: bool = False,
         branch_triplets_out: str | None = None, taxon_triplets: bool = False,
-        taxa_out: str | None = None, placements_out: str | None = None, place_taxa: int = 10) -> None:
+        taxa_out: str | None = None, placements_out: str | None = None, place_taxa: int = 10,
+        clade_placements_out: str | None = None, place_clades: int = 10, clade_max_tips: int = 64) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
@@ -104,7 +113,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
         if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
-                or taxa_out or placements_out):
+                or taxa_out or placements_out or clade_placements_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
@@ -113,7 +122,11 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                                      or branches_out is not None,
                                      branch_triplets=branch_triplets or branch_triplets_out is not None,
                                      taxon_triplets=taxa_out is not None,
-                                     placements=place_taxa if placements_out else None)
+                                     placements=place_taxa if placements_out else None,
+                                     clade_placements=place_clades if clade_placements_out else None,
+                                     clade_max_tips=clade_max_tips)
+            if clade_placements_out:
+                Path(clade_placements_out).write_text(result.clade_placement_table())
             if placements_out:
                 Path(placements_out).write_text(result.placement_table())
             if taxa_out:

@@ -1924,6 +1924,398 @@ __global__ void __launch_bounds__(1024) k_pl_prefix(const unsigned long long *__
     }
 }
 
+// ---- scs_score_clade_placements: the triplet terms a whole clade of the supertree would have on the edge above every
+// node.  Q is the clade's leaf set, Q' = Q ∩ L (a range of S' leaves), R = L ∖ Q.  The triples
+// with two taxa in Q' do not depend on the edge: node sums over T (k_cp_nodes) and a closed form (k_cp_clades).  Those
+// with one taxon x in Q' follow the recurrence of scs_score_placements on the ground set R ∪ {x}: every tip of Q' is a
+// sub-query whose group list is swept against the rows as there, every count is intersected with R (an S' node inside
+// Q' has no taxon of R and sends nothing, one that holds Q' loses |· ∩ Q'|, which a group brings along from a bitset
+// row of Q' over T positions), and the marks of all the tips of a clade go to the clade's own pair of rows.
+//   k_cp_clades, a workgroup per (tree, clade of the pass): Q' as a range of S' leaves, its bitset row over T positions
+//     (global memory, the word format of k_trip_pairs), cp_trees, cp_total and the closed form C(|Q'|, 2) |R|.
+//   k_cp_queries, per (tree, sub-query): the tip's T position, -1 unless the tree crosses the clade.
+//   k_cp_nodes, one thread per leaf: T's node whose first gap it is, against the Q' row of every clade that begins in
+//     this pass: cp_source and the shared triples with two taxa in Q'.
+//   k_cp_groups: k_pl_groups with |y ∩ Q'| and |py ∩ Q'| beside every list entry.
+//   k_cp_pairs, the hot kernel: k_pl_pairs with the masked counts, sums per (z, clade) and the closed-form super marks
+//     once per (z, clade), times |Q'|.
+//   k_cp_marks, then k_pl_prefix: the rows' values.
+
+constexpr int CP_QMAX = 64;  // sub-queries (tips of query clades) per pass over a batch
+
+struct sc_cp_args {
+    const int64_t *off;             // tree_off + t0
+    int nb;
+    const int32_t *sp;              // [Lb] S positions in S order
+    const int2 *tp;                 // [Lb] T position of every S' leaf (.x)
+    const int32_t *rows;            // [nb][row_stride] T position by S position
+    int64_t row_stride;
+    const int32_t *adj, *amin;      // T's min table of adj_depth
+    int levels;
+    int64_t Lb;
+    const int32_t *c_lo, *c_hi;     // [ncl] S leaf range of the pass's clades
+    const int32_t *q_spos, *q_slot; // [qc] S position and clade (slot in the pass) of the pass's sub-queries
+    int ncl, qc;
+    int skip0;                      // the pass's first clade began in an earlier pass: its own sums are done
+    int2 *qrow;                     // [ncl][rstride] Q' rows, tree t from (base >> 5) + t on
+    int64_t rstride;
+    int4 *cinfo;                    // [nb][ncl] {first S' leaf of Q', end, crossing, 0}
+    int2 *qinfo;                    // [nb][qc] {T position of the tip or -1, slot}
+    int32_t *gcnt;                  // [nb][qc]
+    int32_t *qheld;                 // [nb]
+    int4 *glist;                    // [Lb qc]: tree t, sub-query i from base qc + i n on
+    int2 *gq;                       // beside glist: {|y ∩ Q'|, |py ∩ Q'|}
+    unsigned long long *c_trees, *c_total, *c_source;  // [ncl] at the pass's first clade
+    unsigned long long *sub;        // rows [2][n_clades][n_nodes] (shared, super), at the pass's first clade
+    int64_t node_stride, super_off;
+};
+
+__global__ void __launch_bounds__(SC_THREADS) k_cp_clades(sc_cp_args a) {
+    const int t = blockIdx.x / a.ncl, c = blockIdx.x % a.ncl;
+    const int64_t base = a.off[t] - a.off[0], n = a.off[t + 1] - a.off[t];
+    const int32_t *sp = a.sp + base;
+    const int64_t ka = sc_first_ge(sp, 0, n, a.c_lo[c]);
+    const int64_t kb = sc_first_ge(sp, ka, n, a.c_hi[c] + 1);
+    const int64_t nq = kb - ka;
+    const bool cross = n >= 3 && nq > 0 && nq < n;
+    if (threadIdx.x == 0) a.cinfo[(int64_t)t * a.ncl + c] = make_int4((int)ka, (int)kb, cross ? 1 : 0, 0);
+    if (!cross) return;
+    int2 *row = a.qrow + (int64_t)c * a.rstride + (base >> 5) + t;
+    const int W = (int)(n >> 5) + 1;
+    unsigned *bits = reinterpret_cast<unsigned *>(row);  // (zeroed by the host before the launch)
+    for (int64_t k = ka + threadIdx.x; k < kb; k += SC_THREADS) {
+        const int x = a.tp[base + k].x;
+        atomicOr(bits + 2 * (x >> 5), 1u << (x & 31));
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        int run = 0;
+        for (int w0 = 0; w0 < W; w0 += 64) {
+            const int i = w0 + lane;
+            // (the bits were set by atomics of other waves: read them where the atomics ran)
+            const int v = i < W ? __popc(__hip_atomic_load(bits + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    if (threadIdx.x == 0 && !(c == 0 && a.skip0)) {
+        const int64_t r = n - nq;
+        atomicAdd(a.c_trees + c, 1ull);
+        atomicAdd(a.c_total + c, (unsigned long long)(n * (n - 1) * (n - 2) / 6 - nq * (nq - 1) * (nq - 2) / 6 -
+                                                      r * (r - 1) * (r - 2) / 6));
+        // two taxa in Q', one in R: S says xx'|b on every edge
+        if (nq >= 2) atomicAdd(a.sub + a.super_off + c * a.node_stride, (unsigned long long)(nq * (nq - 1) / 2 * r));
+    }
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_cp_queries(sc_cp_args a) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)a.nb * a.qc) return;
+    const int t = (int)(idx / a.qc), i = (int)(idx % a.qc);
+    const int c = a.q_slot[i];
+    int32_t px = -1;
+    if (a.cinfo[(int64_t)t * a.ncl + c].z) {
+        px = a.rows[(int64_t)t * a.row_stride + a.q_spos[i]];
+        if (px >= 0) atomicAdd(a.qheld + t, 1);
+    }
+    a.qinfo[idx] = make_int2(px, c);
+    a.gcnt[idx] = 0;
+}
+
+// |[lo, hi) ∩ Q'| over T positions, from a Q' row
+__device__ __forceinline__ int cp_range(const int2 *__restrict__ row, int lo, int hi) {
+    return tp_count(row, hi >> 5, (1u << (hi & 31)) - 1u) - tp_count(row, lo >> 5, (1u << (lo & 31)) - 1u);
+}
+
+// T's node [lo, hi] whose first gap is k, with its parent [plo, phi]; false for a leaf's thread without one, the root
+__device__ __forceinline__ bool cp_tnode(const sc_cp_args &a, int64_t base, int64_t n, int64_t k, int4 &e) {
+    if (k + 1 >= n) return false;
+    const int32_t d = a.adj[base + k];
+    const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+    if (lo != 0 && a.adj[base + lo - 1] >= d) return false;  // (not the node's first gap)
+    const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+    if (lo == 0 && hi == n - 1) return false;  // (the root)
+    const int64_t g = lo == 0 ? hi : hi == n - 1 ? lo - 1 : (a.adj[base + lo - 1] >= a.adj[base + hi] ? lo - 1 : hi);
+    const int32_t dg = a.adj[base + g];
+    const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+    const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+    e = make_int4((int)lo, (int)hi + 1, (int)plo, (int)phi + 1);
+    return true;
+}
+
+// the node sums of the clades that begin in this pass: cp_source and the shared triples with two taxa in Q'
+__global__ void __launch_bounds__(SC_THREADS) k_cp_nodes(sc_cp_args a) {
+    __shared__ unsigned long long acc[2 * CP_QMAX];
+    for (int i = threadIdx.x; i < 2 * a.ncl; i += SC_THREADS) acc[i] = 0;
+    __syncthreads();
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    if (p < a.off[a.nb]) {
+        const int t = sc_tree_of(a.off, a.nb, p);
+        const int64_t base = a.off[t] - a.off[0], n = a.off[t + 1] - a.off[t];
+        int4 e;
+        if (n >= 3 && cp_tnode(a, base, n, q - base, e)) {
+            const int64_t s = e.y - e.x, out = (e.w - e.z) - s;
+            for (int c = a.skip0 ? 1 : 0; c < a.ncl; ++c) {
+                if (!a.cinfo[(int64_t)t * a.ncl + c].z) continue;
+                const int2 *row = a.qrow + (int64_t)c * a.rstride + (base >> 5) + t;
+                const int64_t pq = cp_range(row, e.z, e.w);
+                if (pq == 0) continue;  // (py lies in R: nothing crosses)
+                const int64_t yq = cp_range(row, e.x, e.y), yr = s - yq, oq = pq - yq, orr = out - oq;
+                const int64_t both = yq * (yq - 1) / 2 * orr;
+                const int64_t src = s * (s - 1) / 2 * out - yq * (yq - 1) / 2 * oq - yr * (yr - 1) / 2 * orr;
+                if (src) atomicAdd(acc + 2 * c, (unsigned long long)src);
+                if (both) atomicAdd(acc + 2 * c + 1, (unsigned long long)both);
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * a.ncl; i += SC_THREADS) {
+        if (!acc[i]) continue;
+        const int c = i >> 1;
+        atomicAdd((i & 1) ? a.sub + c * a.node_stride : a.c_source + c, acc[i]);
+    }
+}
+
+__device__ __forceinline__ void cp_group(const sc_cp_args &a, int t, int64_t base, int64_t n, int4 e) {
+    for (int i = 0; i < a.qc; ++i) {
+        const int2 qi = a.qinfo[(int64_t)t * a.qc + i];
+        const int32_t px = qi.x;
+        if (px < e.z || px >= e.w || (px >= e.x && px < e.y)) continue;
+        const int2 *row = a.qrow + (int64_t)qi.y * a.rstride + (base >> 5) + t;
+        const int slot = atomicAdd(a.gcnt + (int64_t)t * a.qc + i, 1);
+        const int64_t at = base * a.qc + (int64_t)i * n + slot;
+        a.glist[at] = e;
+        a.gq[at] = make_int2(cp_range(row, e.x, e.y), cp_range(row, e.z, e.w));
+    }
+}
+
+// one thread per leaf k of a tree: T's leaf k, and T's node whose first gap is k, into the sub-queries' group lists
+__global__ void __launch_bounds__(SC_THREADS) k_cp_groups(sc_cp_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    if (p >= a.off[a.nb]) return;
+    const int t = sc_tree_of(a.off, a.nb, p);
+    if (a.qheld[t] == 0) return;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    if (n < 3) return;
+    {
+        const int64_t g = k == 0 ? 0 : k == n - 1 ? n - 2 : (a.adj[base + k - 1] >= a.adj[base + k] ? k - 1 : k);
+        const int32_t dg = a.adj[base + g];
+        const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+        const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+        cp_group(a, t, base, n, make_int4((int)k, (int)k + 1, (int)plo, (int)phi + 1));
+    }
+    int4 e;
+    if (cp_tnode(a, base, n, k, e)) cp_group(a, t, base, n, e);
+}
+
+struct sc_cp_pair_args {
+    const int64_t *blk;       // first workgroup of the batch's tree i (cumulative, blk[0] = the batch's own start)
+    int nb;
+    const int64_t *off;
+    const int4 *glist;
+    const int2 *gq;
+    const int32_t *gcnt;
+    const int2 *qinfo;
+    const int4 *cinfo;
+    const int32_t *qheld;
+    int qc, ncl, skip0;
+    const int4 *zlist, *zmeta;
+    const int32_t *zcnt;
+    const int2 *tp;
+    int zb, W;
+    int lds_sums;             // A and X summed per (z, clade) in LDS; else every (z, y) sends its own marks
+    unsigned long long *sub, *strict;  // rows [2][n_clades][n_nodes] (shared, super), at the pass's first clade
+    int64_t row_stride;       // n_nodes
+    int64_t super_off;        // n_clades * n_nodes
+};
+
+// z's and pz's sizes without Q' = [ka, kb) of S' (nq leaves): false when z lies inside Q' and holds no taxon of R
+__device__ __forceinline__ bool cp_masked(int4 z, int ka, int kb, int &cz, int &cp) {
+    if (z.x >= ka && z.y <= kb) return false;
+    cz = z.x <= ka && kb <= z.y;
+    cp = z.z <= ka && kb <= z.w;
+    return true;
+}
+
+// the hot path: one workgroup per (tree t, block of zb of t's S' nodes).  LDS: with lds_sums the sums [zb][qc]{A, X},
+// the nodes [zb]{range, meta} and the list offsets [qc + 1]; then the rows [2 zb][W] of k_trip_pairs
+__global__ void __launch_bounds__(SC_THREADS) k_cp_pairs(sc_cp_pair_args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char cp_lds[];
+    const int64_t g = a.blk[0] + blockIdx.x;
+    const int t = sc_tree_of(a.blk, a.nb, g);
+    const int j0 = (int)(g - a.blk[t]) * a.zb;
+    const int nz = min(a.zb, a.zcnt[t] - j0);
+    if (nz <= 0) return;
+    const int qc = a.qc, W = a.W, ncl = a.ncl;
+    const int2 *qinfo = a.qinfo + (int64_t)t * qc;
+    const int4 *cinfo = a.cinfo + (int64_t)t * ncl;
+    const bool any_first = [&] {
+        for (int c = a.skip0 ? 1 : 0; c < ncl; ++c)
+            if (cinfo[c].z) return true;
+        return false;
+    }();
+    if (a.qheld[t] == 0 && !any_first) return;  // (the tree crosses no clade of this pass)
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int4 *zlist = a.zlist + 2 * base + j0, *zmeta = a.zmeta + 2 * base + j0;
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(cp_lds);
+    int4 *zs = reinterpret_cast<int4 *>(sums + (a.lds_sums ? 2 * a.zb * qc : 0));
+    int *pref = reinterpret_cast<int *>(zs + (a.lds_sums ? 2 * a.zb : 0));
+    int2 *rows = reinterpret_cast<int2 *>(cp_lds + (a.lds_sums ? 16 * a.zb * qc + 32 * a.zb + 4 * ((qc + 4) & ~3) : 0));
+    const int nrow = 2 * nz;
+    if (a.lds_sums) {
+        for (int i = threadIdx.x; i < 2 * nz * qc; i += SC_THREADS) sums[i] = 0;
+        for (int i = threadIdx.x; i < nz; i += SC_THREADS) {
+            zs[2 * i] = zlist[i];
+            zs[2 * i + 1] = zmeta[i];
+        }
+        if (threadIdx.x == 0) {
+            int run = 0;
+            for (int i = 0; i < qc; ++i) {
+                pref[i] = run;
+                run += a.gcnt[(int64_t)t * qc + i];
+            }
+            pref[qc] = run;
+        }
+    }
+    if (a.qheld[t] != 0) {  // (uniform over the workgroup: the rows serve the sweep only)
+        for (int i = threadIdx.x; i < nrow * W; i += SC_THREADS) rows[i] = make_int2(0, 0);
+        __syncthreads();
+        unsigned *bits = reinterpret_cast<unsigned *>(rows);
+        for (int j = 0; j < nz; ++j) {
+            const int4 z = zlist[j];
+            for (int k = z.x + threadIdx.x; k < z.y; k += SC_THREADS) {
+                const int x = a.tp[base + k].x;
+                atomicOr(bits + 2 * ((2 * j) * W + (x >> 5)), 1u << (x & 31));
+            }
+            for (int k = z.z + threadIdx.x; k < z.w; k += SC_THREADS) {
+                const int x = a.tp[base + k].x;
+                atomicOr(bits + 2 * ((2 * j + 1) * W + (x >> 5)), 1u << (x & 31));
+            }
+        }
+        __syncthreads();
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int r = wave; r < nrow; r += SC_THREADS / 64) {
+            int2 *row = rows + r * W;
+            int run = 0;
+            for (int c = 0; c < W; c += 64) {
+                const int i = c + lane;
+                const int v = i < W ? __popc((unsigned)row[i].x) : 0;
+                int incl = v;
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int y = __shfl_up(incl, d, 64);
+                    if (lane >= d) incl += y;
+                }
+                if (i < W) row[i].y = run + incl - v;
+                run += __shfl(incl, 63, 64);
+            }
+        }
+    }
+    __syncthreads();
+    // A and X of one (z, y) on the ground set R: y's T positions [y.x, y.y), py's [y.z, y.w), yq = {|y ∩ Q'|, |py ∩ Q'|}
+    const auto pair = [&](const int4 y, const int2 yq, int j, int4 z, int4 ci, unsigned long long &av,
+                          unsigned long long &xv) {
+        int cz, cp;
+        if (!cp_masked(z, ci.x, ci.y, cz, cp)) return false;
+        const int2 *rz = rows + 2 * j * W, *rp = rz + W;
+        const int wa = y.x >> 5, wb = y.y >> 5;
+        const unsigned ma = (1u << (y.x & 31)) - 1u, mb = (1u << (y.y & 31)) - 1u;
+        const int iyz = tp_count(rz, wb, mb) - tp_count(rz, wa, ma) - (cz ? yq.x : 0);
+        if (iyz == 0) return false;
+        const int wc = y.z >> 5, wd = y.w >> 5;
+        const unsigned mc = (1u << (y.z & 31)) - 1u, md = (1u << (y.w & 31)) - 1u;
+        const int ipyz = tp_count(rz, wd, md) - tp_count(rz, wc, mc) - (cz ? yq.y : 0);
+        const int ipp = tp_count(rp, wd, md) - tp_count(rp, wc, mc) - (cp ? yq.y : 0);
+        const int nq = ci.y - ci.x;
+        const int zr = (z.y - z.x) - (cz ? nq : 0), pr = (z.w - z.z) - (cp ? nq : 0);
+        av = (unsigned long long)((int64_t)iyz * (iyz - 1) / 2);
+        xv = (unsigned long long)((int64_t)iyz * ((pr - ipp) - (zr - ipyz)));
+        return true;
+    };
+    if (a.lds_sums) {
+        const int total = pref[qc];
+        for (int e = threadIdx.x; e < total; e += SC_THREADS) {
+            int i = 0, hi = qc;  // pref[i] <= e < pref[hi]
+            while (hi - i > 1) {
+                const int m = (i + hi) >> 1;
+                if (pref[m] <= e) i = m; else hi = m;
+            }
+            const int64_t at = base * qc + (int64_t)i * n + (e - pref[i]);
+            const int4 y = a.glist[at];
+            const int2 yq = a.gq[at];
+            const int c = qinfo[i].y;
+            const int4 ci = cinfo[c];
+            for (int j = 0; j < nz; ++j) {
+                unsigned long long av, xv;
+                if (!pair(y, yq, j, zs[2 * j], ci, av, xv)) continue;
+                if (av) atomicAdd(sums + 2 * (j * qc + c), av);
+                if (xv) atomicAdd(sums + 2 * (j * qc + c) + 1, xv);
+            }
+        }
+        __syncthreads();
+    } else {
+        for (int i = 0; i < qc; ++i) {
+            const int cnt = a.gcnt[(int64_t)t * qc + i];
+            const int c = qinfo[i].y;
+            const int4 ci = cinfo[c];
+            for (int e = threadIdx.x; e < cnt; e += SC_THREADS) {
+                const int64_t at = base * qc + (int64_t)i * n + e;
+                const int4 y = a.glist[at];
+                const int2 yq = a.gq[at];
+                for (int j = 0; j < nz; ++j) {
+                    unsigned long long av, xv;
+                    if (!pair(y, yq, j, zlist[j], ci, av, xv)) continue;
+                    pl_emit(a.sub + c * a.row_stride, a.strict + c * a.row_stride, zmeta[j], av, xv);
+                }
+            }
+        }
+    }
+    // per (z, clade the tree crosses): the summed marks of the shared row; for a clade that begins in this pass the
+    // closed-form marks of the super row, the same for every tip of Q': once, times |Q'|
+    for (int it = threadIdx.x; it < nz * ncl; it += SC_THREADS) {
+        const int j = it / ncl, c = it % ncl;
+        const int4 ci = cinfo[c];
+        if (!ci.z) continue;
+        const int4 z = a.lds_sums ? zs[2 * j] : zlist[j], meta = a.lds_sums ? zs[2 * j + 1] : zmeta[j];
+        if (a.lds_sums)
+            pl_emit(a.sub + c * a.row_stride, a.strict + c * a.row_stride, meta, sums[2 * (j * qc + c)],
+                    sums[2 * (j * qc + c) + 1]);
+        if (c == 0 && a.skip0) continue;
+        int cz, cp;
+        if (!cp_masked(z, ci.x, ci.y, cz, cp)) continue;
+        const int64_t nq = ci.y - ci.x;
+        const int64_t sz = (z.y - z.x) - (cz ? nq : 0), spz = (z.w - z.z) - (cp ? nq : 0);
+        pl_emit(a.sub + a.super_off + c * a.row_stride, a.strict + a.super_off + c * a.row_stride, meta,
+                (unsigned long long)(nq * (sz * (sz - 1) / 2)), (unsigned long long)(nq * sz * (spz - sz)));
+    }
+}
+
+// mark(u) = sub[u] + strict[parent u] on [u, end u) of the row's difference array (zeroed; n + 1 entries)
+__global__ void __launch_bounds__(SC_THREADS) k_cp_marks(const unsigned long long *__restrict__ sub,
+                                                         const unsigned long long *__restrict__ strict,
+                                                         const int32_t *__restrict__ parent,
+                                                         const int32_t *__restrict__ end, int64_t n, int64_t n_rows,
+                                                         unsigned long long *__restrict__ diff) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * n_rows) return;
+    const int64_t r = idx / n, u = idx % n;
+    const unsigned long long m = sub[idx] + (u ? strict[r * n + parent[u]] : 0ull);
+    if (!m) return;
+    atomicAdd(diff + r * (n + 1) + u, m);
+    atomicAdd(diff + r * (n + 1) + end[u], 0ull - m);
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -2986,6 +3378,275 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
     if (e == hipSuccess && pl_shared) e = hipMemcpyAsync(pl_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && pl_super)
         e = hipMemcpyAsync(pl_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    return SCS_OK;
+}
+
+extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                          const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                          int32_t n_queries, const int32_t *query_nodes, int64_t *cp_trees,
+                                          int64_t *cp_total, int64_t *cp_source, int64_t *cp_super,
+                                          int64_t *cp_shared) {
+    const char *const who = "scs_score_clade_placements";
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
+                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_REQUIRE(max_lds_bytes >= 0, "%s: max_lds_bytes = %d is negative", who, max_lds_bytes);
+    SCS_REQUIRE(n_queries >= 1 && query_nodes, "%s: no query node", who);
+    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= lds_cap,
+                "%s: max_lds_bytes = %d does not hold the rows of a source tree of %lld leaves", who, max_lds_bytes,
+                (long long)m_max);
+    // the query nodes: not the root, in range, each once; their leaf ranges; the tips' preorder index and depth by
+    // leaf position; the sub-queries (the S positions of every clade's tips, clade by clade)
+    std::vector<int32_t> tip_node, tip_depth, c_lo, c_hi, q_spos, q_clade;
+    if (parent && taxon && n_nodes >= 1) {
+        std::vector<char> has_kid((size_t)n_nodes, 0);
+        std::vector<int32_t> depth((size_t)n_nodes, 0), lo((size_t)n_nodes, INT32_MAX), hi((size_t)n_nodes, -1);
+        for (int32_t v = 1; v < n_nodes; ++v)
+            if (parent[v] >= 0 && parent[v] < v) {
+                has_kid[parent[v]] = 1;
+                depth[v] = depth[parent[v]] + 1;
+            }
+        for (int32_t v = 0; v < n_nodes; ++v)
+            if (!has_kid[v]) {
+                lo[v] = hi[v] = (int32_t)tip_node.size();
+                tip_node.push_back(v);
+                tip_depth.push_back(depth[v]);
+            }
+        for (int32_t v = n_nodes - 1; v >= 1; --v)
+            if (parent[v] >= 0 && parent[v] < v) {
+                lo[parent[v]] = std::min(lo[parent[v]], lo[v]);
+                hi[parent[v]] = std::max(hi[parent[v]], hi[v]);
+            }
+        std::vector<char> seen((size_t)n_nodes, 0);
+        for (int32_t i = 0; i < n_queries; ++i) {
+            const int32_t q = query_nodes[i];
+            SCS_REQUIRE(q >= 1 && q < n_nodes, "%s: query node %d is the root or out of range [1, %d)", who, q, n_nodes);
+            SCS_REQUIRE(!seen[q], "%s: query node %d is given twice", who, q);
+            seen[q] = 1;
+            c_lo.push_back(lo[q]);
+            c_hi.push_back(hi[q]);
+            for (int32_t p = lo[q]; p <= hi[q]; ++p) {
+                q_spos.push_back(p);
+                q_clade.push_back(i);
+            }
+        }
+    }
+    // own arrays: three rows of n_nodes + 1 sums per clade and output (`sub`, later the values; `strict`; the
+    // difference row), three sums per clade, the clades' leaf ranges, the sub-queries, S's parents and tips, the first
+    // pair workgroup per tree (+ 1).  Per batch: a group list entry (24 bytes) per leaf and sub-query of a pass, a
+    // word of a Q' row per 32 leaves and clade of a pass, two node lists of two entries per leaf; per tree and
+    // sub-query the clade's range, the tip's position and its list's length
+    const size_t nn = (size_t)std::max(n_nodes, 0), nq = (size_t)n_queries, ns = q_spos.size(),
+                 mt = src ? (size_t)src->n_trees : 0;
+    const size_t row_bytes = sc_up256(2 * nq * (nn + 1) * 8);
+    SCS_REQUIRE(3 * (uint64_t)row_bytes <= SC_BUDGET,
+                "%s: %d query clades x %d supertree nodes need %llu bytes of rows, more than the %llu of the call's "
+                "workspace", who, n_queries, n_nodes, (unsigned long long)(3 * (uint64_t)row_bytes),
+                (unsigned long long)SC_BUDGET);
+    const int qcap = (int)std::min<size_t>(std::max<size_t>(ns, 1), CP_QMAX);
+    const size_t o_sub = 0, o_strict = row_bytes, o_diff = 2 * row_bytes, o_cs = 3 * row_bytes,
+                 o_clo = o_cs + sc_up256(nq * 24), o_chi = o_clo + sc_up256(nq * 4), o_qpos = o_chi + sc_up256(nq * 4),
+                 o_qslot = o_qpos + sc_up256(ns * 4), o_par = o_qslot + sc_up256(ns * 4),
+                 o_tipn = o_par + sc_up256(nn * 4), o_tipd = o_tipn + sc_up256(nn * 4),
+                 o_blk = o_tipd + sc_up256(nn * 4), own = o_blk + sc_up256((mt + 1) * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 25 * (uint64_t)qcap + 64,
+                     36 * (uint64_t)qcap + 8, c, e));
+    const int32_t M = c.M;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_sub = (unsigned long long *)(c.d_extra + o_sub);
+    auto *d_strict = (unsigned long long *)(c.d_extra + o_strict);
+    auto *d_diff = (unsigned long long *)(c.d_extra + o_diff);
+    auto *d_cs = (unsigned long long *)(c.d_extra + o_cs);
+    auto *d_clo = (int32_t *)(c.d_extra + o_clo);
+    auto *d_chi = (int32_t *)(c.d_extra + o_chi);
+    auto *d_qpos = (int32_t *)(c.d_extra + o_qpos);
+    auto *d_qslot = (int32_t *)(c.d_extra + o_qslot);
+    auto *d_par = (int32_t *)(c.d_extra + o_par);
+    auto *d_tipn = (int32_t *)(c.d_extra + o_tipn);
+    auto *d_tipd = (int32_t *)(c.d_extra + o_tipd);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    const size_t n_batches = c.bstart.size() - 1;
+    int64_t max_rows = 0;
+    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
+    const int64_t max_rstride = (c.max_lb >> 5) + max_rows;
+    auto *d_glist = (int4 *)c.d_extra_batch;
+    auto *d_zlist = d_glist + c.max_lb * qcap;
+    auto *d_zmeta = d_zlist + 2 * c.max_lb;
+    auto *d_cinfo = d_zmeta + 2 * c.max_lb;
+    auto *d_gq = (int2 *)(d_cinfo + max_rows * qcap);
+    auto *d_qrow = d_gq + c.max_lb * qcap;
+    auto *d_qinfo = d_qrow + max_rstride * qcap;
+    auto *d_gcnt = (int32_t *)(d_qinfo + max_rows * qcap);
+    auto *d_zcnt = d_gcnt + max_rows * qcap;
+    auto *d_qheld = d_zcnt + max_rows;
+    // the sub-queries' slots: the clade's index less the first clade of the sub-query's pass
+    std::vector<int32_t> q_slot(ns);
+    for (size_t i = 0; i < ns; ++i) q_slot[i] = q_clade[i] - q_clade[i / qcap * qcap];
+    const int aux1 = 16 * qcap + 32, auxq = 4 * ((qcap + 4) & ~3);  // LDS bytes beside the rows: per node, per pass
+    std::vector<int> words(n_batches), zbs(n_batches), sums(n_batches);
+    std::vector<int64_t> blk((size_t)M + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        const int rowb = 16 * words[b];
+        int zb = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / rowb));
+        while (zb > 1 && zb * (rowb + aux1) + auxq > lds_cap) --zb;
+        sums[b] = zb * (rowb + aux1) + auxq <= lds_cap;
+        zbs[b] = zb;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) {
+            const int64_t n = off[t + 1] - off[t];
+            blk[t + 1] = blk[t] + (n >= 3 ? (2 * n + zb - 1) / zb : 0);
+        }
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, 3 * row_bytes + sc_up256(nq * 24), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_clo, c_lo.data(), nq * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_chi, c_hi.data(), nq * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qpos, q_spos.data(), ns * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qslot, q_slot.data(), ns * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_par, parent, nn * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tipn, tip_node.data(), tip_node.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tipd, tip_depth.data(), tip_depth.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_cp_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_zcnt, 0, (size_t)nb * 4, s);
+        if (e != hipSuccess) break;
+        sc_pl_args za;
+        za.off = src->d_tree_off + t0;
+        za.nb = nb;
+        za.sp = c.d_sp;
+        za.dep = c.d_dep;
+        za.node = c.d_node;
+        za.adj = src->d_adj_depth + L0;
+        za.amin = c.d_amin;
+        za.levels = c.levels;
+        za.Lb = Lb;
+        za.s_tab = c.d_stab;
+        za.s_stride = c.n_gaps;
+        za.s_levels = sc_levels_host(c.n_gaps);
+        za.s_lo = c.d_slo;
+        za.s_hi = c.d_shi;
+        za.tip_node = d_tipn;
+        za.tip_depth = d_tipd;
+        za.zlist = d_zlist;
+        za.zmeta = d_zmeta;
+        za.zcnt = d_zcnt;
+        za.qinfo = nullptr;
+        za.qc = 0;
+        za.glist = nullptr;
+        za.gcnt = nullptr;
+        za.q_source = nullptr;
+        k_pl_znodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(za);
+        if (!sc_launched(e)) break;
+        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t rstride = (Lb >> 5) + nb;
+        for (size_t i0 = 0; i0 < ns && n_wg > 0; i0 += qcap) {
+            const int qc = (int)std::min<size_t>(qcap, ns - i0);
+            const int32_t c0 = q_clade[i0], c1 = q_clade[i0 + qc - 1];
+            sc_cp_args a;
+            a.off = za.off;
+            a.nb = nb;
+            a.sp = c.d_sp;
+            a.tp = c.d_mm;
+            a.rows = c.d_rows;
+            a.row_stride = c.row_stride;
+            a.adj = za.adj;
+            a.amin = c.d_amin;
+            a.levels = c.levels;
+            a.Lb = Lb;
+            a.c_lo = d_clo + c0;
+            a.c_hi = d_chi + c0;
+            a.q_spos = d_qpos + i0;
+            a.q_slot = d_qslot + i0;
+            a.ncl = c1 - c0 + 1;
+            a.qc = qc;
+            a.skip0 = i0 > 0 && q_clade[i0 - 1] == c0;
+            a.qrow = d_qrow;
+            a.rstride = rstride;
+            a.cinfo = d_cinfo;
+            a.qinfo = d_qinfo;
+            a.gcnt = d_gcnt;
+            a.qheld = d_qheld;
+            a.glist = d_glist;
+            a.gq = d_gq;
+            a.c_trees = d_cs + c0;
+            a.c_total = d_cs + nq + c0;
+            a.c_source = d_cs + 2 * nq + c0;
+            a.sub = d_sub + (size_t)c0 * nn;
+            a.node_stride = (int64_t)nn;
+            a.super_off = (int64_t)(nq * nn);
+            e = hipMemsetAsync(d_qheld, 0, (size_t)nb * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(d_qrow, 0, (size_t)a.ncl * rstride * 8, s);
+            if (e != hipSuccess) break;
+            k_cp_clades<<<(unsigned)((int64_t)nb * a.ncl), SC_THREADS, 0, s>>>(a);
+            if (!sc_launched(e)) break;
+            k_cp_queries<<<grid_of((int64_t)nb * qc), SC_THREADS, 0, s>>>(a);
+            if (!sc_launched(e)) break;
+            if (a.ncl > a.skip0) {
+                k_cp_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+                if (!sc_launched(e)) break;
+            }
+            k_cp_groups<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+            if (!sc_launched(e)) break;
+            sc_cp_pair_args pa;
+            pa.blk = d_blk + t0;
+            pa.nb = nb;
+            pa.off = a.off;
+            pa.glist = d_glist;
+            pa.gq = d_gq;
+            pa.gcnt = d_gcnt;
+            pa.qinfo = d_qinfo;
+            pa.cinfo = d_cinfo;
+            pa.qheld = d_qheld;
+            pa.qc = qc;
+            pa.ncl = a.ncl;
+            pa.skip0 = a.skip0;
+            pa.zlist = d_zlist;
+            pa.zmeta = d_zmeta;
+            pa.zcnt = d_zcnt;
+            pa.tp = c.d_mm;
+            pa.zb = zbs[b];
+            pa.W = words[b];
+            pa.lds_sums = sums[b];
+            pa.sub = a.sub;
+            pa.strict = d_strict + (size_t)c0 * nn;
+            pa.row_stride = (int64_t)nn;
+            pa.super_off = a.super_off;
+            const size_t lds = (size_t)zbs[b] * 16 * words[b] + (sums[b] ? (size_t)zbs[b] * (16 * qc + 32) +
+                                                                              4 * ((qc + 4) & ~3) : 0);
+            k_cp_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(pa);
+            if (!sc_launched(e)) break;
+        }
+    }
+    if (e == hipSuccess && !bad) {
+        k_cp_marks<<<grid_of((int64_t)(2 * nq * nn)), SC_THREADS, 0, s>>>(d_sub, d_strict, d_par, c.d_end, (int64_t)nn,
+                                                                        (int64_t)(2 * nq), d_diff);
+        sc_launched(e);
+    }
+    if (e == hipSuccess && !bad) {
+        k_pl_prefix<<<(unsigned)(2 * nq), 1024, 0, s>>>(d_diff, (int64_t)nn, d_sub);
+        sc_launched(e);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    int64_t *const scal[3] = {cp_trees, cp_total, cp_source};
+    for (int i = 0; i < 3 && e == hipSuccess; ++i)
+        if (scal[i]) e = hipMemcpyAsync(scal[i], d_cs + i * nq, nq * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && cp_shared) e = hipMemcpyAsync(cp_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && cp_super)
+        e = hipMemcpyAsync(cp_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
     SCS_TRY(sc_end(ctx, c, e, bad));
     return SCS_OK;
 }

@@ -106,6 +106,22 @@ same recurrence with C(|c|, 2) and |c| (|q| - |c|).  Every term is node-local, s
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
 ``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets`` and
 ``scs_score_placements``; the host only validates and lays out.
+
+Clade placement support (``clade_placements=[nodes or name sets]`` or ``clade_placements=N``): the same question for a
+whole subtree.  For a non-root node q of S with leaf set Q and a node v outside its subtree, S_{q→v} is S with the
+subtree of q pruned and regrafted on the edge above v: every cluster C outside the subtree becomes (C ∖ Q) ∪ Q when it
+belongs to a strict ancestor of v and C ∖ Q otherwise, the clusters inside the subtree stay, and (cl(v) ∖ Q) ∪ Q is
+new.  For v inside the subtree S_{q→v} = S.  Per query (``cp_nodes``), summed over the sources T on L with Q' = Q ∩ L
+and R = L ∖ Q both non-empty and |L| >= 3, over the *crossing* triples of L (a taxon in Q' and one in R; no other
+triple changes when the clade moves):
+
+* ``cp_trees`` = those sources, ``cp_total`` = their crossing triples, ``cp_source`` = those T resolves;
+* ``cp_super[q][v]`` = those S_{q→v}|L resolves, ``cp_shared[q][v]`` = those T and S_{q→v}|L resolve alike;
+* ``clade_placement_distance = cp_super + cp_source - 2 cp_shared``: the part of the total triplet distance that the
+  move can change, so that distance[q][v] - distance[q][q] is what moving the clade to v adds to it.
+
+For a tip q these are the ``pl_*`` of its taxon.  All of it is counted on the device by
+``scs_score_clade_placements``.
 """
 
 from __future__ import annotations
@@ -126,6 +142,8 @@ BATCH_TREES: int | None = None
 TAXON_LDS_BYTES: int | None = None
 # the same for the placement pair kernel (a small value: no room for the sums per node and query beside the rows)
 PLACEMENT_LDS_BYTES: int | None = None
+# and for the clade placement pair kernel
+CLADE_PLACEMENT_LDS_BYTES: int | None = None
 
 
 @dataclass
@@ -144,7 +162,7 @@ class SupertreeScore:
     # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
     # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested), "placements" (scs_score_placements,
-    # when requested)
+    # when requested), "clade_placements" (scs_score_clade_placements, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -186,6 +204,14 @@ class SupertreeScore:
     pl_source: np.ndarray | None = None
     pl_super: np.ndarray | None = None
     pl_shared: np.ndarray | None = None
+    # clade placement support (``clade_placements=...``; None otherwise): the query nodes (preorder indices), one entry
+    # per query, and queries x supertree nodes (preorder)
+    cp_nodes: np.ndarray | None = None
+    cp_trees: np.ndarray | None = None
+    cp_total: np.ndarray | None = None
+    cp_source: np.ndarray | None = None
+    cp_super: np.ndarray | None = None
+    cp_shared: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -538,6 +564,99 @@ class SupertreeScore:
         new.append(tip)
         return out
 
+    def _need_clade_placements(self) -> None:
+        if self.cp_shared is None:
+            msg = "clade placement counts were not computed: score_supertree(..., clade_placements=...)"
+            raise ValueError(msg)
+
+    @property
+    def clade_placement_distance(self) -> np.ndarray:
+        """Queries x nodes: the crossing triples whose topology would differ between the sources and the supertree if
+        the query clade sat on the edge above the node."""
+        self._need_clade_placements()
+        return self.cp_super + self.cp_source[:, None] - 2 * self.cp_shared
+
+    def best_clade_placements(self) -> list[dict]:
+        """One dict per query clade, in query order: ``node`` (the clade's own node, preorder index), ``tips`` (its
+        size), ``trees``, ``distance`` (its value at its own place), ``best_node``, ``best_distance`` and
+        ``improvement`` = distance - best_distance >= 0.  The best node has the smallest distance; among equals the
+        clade's own node, else the lowest preorder index."""
+        dist = self.clade_placement_distance
+        lo, hi = _leaf_ranges(np.asarray(self.supertree.to_flat()[0], dtype=np.int64))
+        out = []
+        for i, q in enumerate(self.cp_nodes):
+            node = int(q)
+            low = int(dist[i].min())
+            best = node if dist[i, node] == low else int(np.argmin(dist[i]))
+            out.append({"node": node, "tips": int(hi[node] - lo[node] + 1), "trees": int(self.cp_trees[i]),
+                        "distance": int(dist[i, node]), "best_node": best, "best_distance": low,
+                        "improvement": int(dist[i, node]) - low})
+        return out
+
+    def clade_placement_table(self) -> str:
+        """One TSV row per query clade: node, tips, trees, distance, best_node, best_distance, improvement
+        (``best_clade_placements``).  ``ValueError`` unless the clade placements were computed."""
+        rows = ["node\ttips\ttrees\tdistance\tbest_node\tbest_distance\timprovement"]
+        for r in self.best_clade_placements():
+            rows.append(f"{r['node']}\t{r['tips']}\t{r['trees']}\t{r['distance']}\t{r['best_node']}"
+                        f"\t{r['best_distance']}\t{r['improvement']}")
+        return "\n".join(rows) + "\n"
+
+    def regraft_clade(self, node: int, target: int) -> TreeNode:
+        """A copy of the supertree with the subtree of ``node`` moved onto the edge above ``target`` (preorder indices
+        in this supertree): S_{node→target} of the module docstring.  The node the clade leaves behind is suppressed
+        when it keeps one child; when ``target`` is that node, the clade goes above its remaining child.  When
+        ``target`` holds no taxon outside the clade (a unary ancestor), the copy is unchanged.  ``ValueError`` when
+        ``node`` is the root or out of range, or ``target`` is out of range or lies inside the subtree of ``node``."""
+        out = self.supertree.copy()
+        nodes = _preorder(out)
+        if not 1 <= int(node) < len(nodes):
+            msg = f"node {node} is the root or not in [1, {len(nodes)})"
+            raise ValueError(msg)
+        if not 0 <= int(target) < len(nodes):
+            msg = f"target {target} is not in [0, {len(nodes)})"
+            raise ValueError(msg)
+        clade, goal = nodes[int(node)], nodes[int(target)]
+        up = goal
+        while up is not None:
+            if up is clade:
+                msg = f"target {target} lies inside the subtree of node {node}"
+                raise ValueError(msg)
+            up = up.parent
+        # prune: the clade, the nodes it leaves empty, and the node it leaves with one child
+        gone = clade
+        while gone.parent is not None and len(gone.parent.children) == 1:
+            if gone.parent is goal:
+                return out
+            gone = gone.parent
+        above = gone.parent
+        if above is None:  # (the clade holds every taxon)
+            return out
+        above.children.remove(gone)
+        clade.parent = None
+        if len(above.children) == 1:
+            (kid,) = above.children
+            if goal is above:
+                goal = kid
+            if above.parent is None:
+                kid.parent = None
+                out = kid
+            else:
+                sibs = above.parent.children
+                sibs[sibs.index(above)] = kid
+                kid.parent = above.parent
+        # regraft: a new node above the target, holding the target and the clade
+        up = goal.parent
+        new = TreeNode(None)
+        if up is None:
+            out = new
+        else:
+            up.children[up.children.index(goal)] = new
+            new.parent = up
+        new.append(goal)
+        new.append(clade)
+        return out
+
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
         concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
@@ -606,6 +725,22 @@ def _preorder(tree: TreeNode) -> list[TreeNode]:
     return out
 
 
+def _leaf_ranges(parent: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """First and last tip (taxon id = position among the tips in preorder) below every preorder node."""
+    n = len(parent)
+    has_child = np.zeros(n, dtype=bool)
+    has_child[parent[1:]] = True
+    lo = np.full(n, n, dtype=np.int64)
+    hi = np.full(n, -1, dtype=np.int64)
+    tips = np.flatnonzero(~has_child)
+    lo[tips] = hi[tips] = np.arange(len(tips))
+    for v in range(n - 1, 0, -1):
+        u = parent[v]
+        lo[u] = min(lo[u], lo[v])
+        hi[u] = max(hi[u], hi[v])
+    return lo, hi
+
+
 def quartet_branches(parent: np.ndarray) -> np.ndarray:
     """Bool mask over preorder nodes given their ``parent`` array (root -1): the nodes with exactly two children
     whose parent has exactly two children."""
@@ -641,7 +776,8 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
                     concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-                    placements=None, device=None) -> SupertreeScore:
+                    placements=None, clade_placements=None, clade_max_tips: int = 64,
+                    device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
@@ -654,7 +790,12 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     stable taxa (``rogue_taxa(N)``: largest ``taxon_instability`` among the taxa some source of 3 or more leaves
     holds; this implies ``taxon_triplets=True``): the placement support of those taxa (``pl_taxa``, ``pl_trees``,
     ``pl_total``, ``pl_source`` per query, ``pl_super``, ``pl_shared`` per query and supertree node).  ``ValueError``
-    for an unknown or repeated name.
+    for an unknown or repeated name.  ``clade_placements``: a list whose items are preorder node indices or iterables
+    of tip names that are exactly one node's cluster (the topmost such node), or an int N for N clades picked by
+    ``select_clades`` from the per-taxon counts (this implies ``taxon_triplets=True``; ``clade_max_tips`` bounds
+    their size): the clade placement support of those nodes (``cp_nodes``, ``cp_trees``, ``cp_total``, ``cp_source``
+    per query, ``cp_super``, ``cp_shared`` per query and supertree node).  ``ValueError`` for the root, a node out of
+    range or given twice, or names that are no node's cluster.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -667,7 +808,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     parent, taxon, tips = supertree_arrays(supertree)
     index = {name: i for i, name in enumerate(tips)}
     placements = _check_placements(placements, index)
-    taxon_triplets = taxon_triplets or isinstance(placements, int)
+    clades = _check_clade_placements(clade_placements, parent, index, clade_max_tips)
+    taxon_triplets = taxon_triplets or isinstance(placements, int) or isinstance(clades, int)
     if isinstance(trees, TreeArrays):
         if trees.n_trees == 0:
             msg = "There must be at least one tree to score against."
@@ -682,11 +824,12 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
             new_id[int(x)] = index[name]
         dev = device if device is not None else _default_device()
         out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
-                            concordance, branch_triplets, taxon_triplets, tips, placements)
+                            concordance, branch_triplets, taxon_triplets, tips, placements, clades, clade_max_tips)
         out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
                                   - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
                                   - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0)
-                                  - out.timings.get("taxon_triplets", 0.0) - out.timings.get("placements", 0.0))
+                                  - out.timings.get("taxon_triplets", 0.0) - out.timings.get("placements", 0.0)
+                                  - out.timings.get("clade_placements", 0.0))
         return out
 
     trees = [t for t in trees if not is_not_completed(t)]
@@ -726,6 +869,10 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         if placements is not None:
             res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
             t9 = time.perf_counter()
+        if clades is not None:
+            t9c = time.perf_counter()
+            res.update(_clade_placements(dev, tabs, parent, taxon, clades, res, clade_max_tips))
+            t10 = time.perf_counter()
     finally:
         tabs.free()
     timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
@@ -741,6 +888,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
         timings["taxon_triplets"] = t8 - t7
     if placements is not None:
         timings["placements"] = t9 - t8
+    if clades is not None:
+        timings["clade_placements"] = t10 - t9c
     return _result(supertree, np.diff(tables.tree_off), res, timings)
 
 
@@ -756,7 +905,9 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
                           res.get("taxa"), res.get("tx_trees"), res.get("tx_total"), res.get("tx_super"),
                           res.get("tx_source"), res.get("tx_shared"),
                           res.get("pl_taxa"), res.get("pl_trees"), res.get("pl_total"), res.get("pl_source"),
-                          res.get("pl_super"), res.get("pl_shared"))
+                          res.get("pl_super"), res.get("pl_shared"),
+                          res.get("cp_nodes"), res.get("cp_trees"), res.get("cp_total"), res.get("cp_source"),
+                          res.get("cp_super"), res.get("cp_shared"))
 
 
 def _check_placements(placements, index: dict):
@@ -805,6 +956,100 @@ def _placements(dev, tabs, parent, taxon, placements, res: dict, tips) -> dict:
     return out
 
 
+def _check_clade_placements(clades, parent: np.ndarray, index: dict, max_tips):
+    """``None``, a count or the query nodes (preorder indices) of ``score_supertree``'s ``clade_placements``."""
+    if clades is None:
+        return None
+    if isinstance(clades, (bool, str)):
+        msg = "clade_placements must be a list of nodes or name sets, or a count"
+        raise ValueError(msg)
+    if isinstance(clades, (int, np.integer)):
+        if clades < 0 or int(max_tips) < 2:
+            msg = f"clade_placements = {clades} is negative or clade_max_tips = {max_tips} is under 2"
+            raise ValueError(msg)
+        return int(clades)
+    lo, hi = _leaf_ranges(parent.astype(np.int64))
+    by_range: dict = {}
+    for v in range(len(parent) - 1, -1, -1):  # (the topmost node of a range wins)
+        by_range[(int(lo[v]), int(hi[v]))] = v
+    nodes = []
+    for item in clades:
+        if isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+            if not 1 <= int(item) < len(parent):
+                msg = f"clade node {item} is the root or not in [1, {len(parent)})"
+                raise ValueError(msg)
+            nodes.append(int(item))
+            continue
+        names = [item] if isinstance(item, str) else list(item)
+        ids = set()
+        for name in names:
+            if name not in index:
+                msg = f"clade taxon {name!r} is not in the supertree"
+                raise ValueError(msg)
+            ids.add(index[name])
+        key = (min(ids), max(ids)) if ids else None
+        if key is None or len(ids) != len(names) or key[1] - key[0] + 1 != len(ids) or key not in by_range:
+            msg = f"the names {sorted(names)!r} are not exactly one node's cluster"
+            raise ValueError(msg)
+        if by_range[key] == 0:
+            msg = "a clade to place may not be the whole supertree"
+            raise ValueError(msg)
+        nodes.append(by_range[key])
+    if len(set(nodes)) != len(nodes):
+        msg = "a clade node is given more than once"
+        raise ValueError(msg)
+    return np.array(nodes, dtype=np.int32)
+
+
+def select_clades(n: int, parent, instability, tx_trees, max_tips: int = 64) -> np.ndarray:
+    """The ``n`` clades ``clade_placements=n`` scores, as preorder node indices: the non-root nodes with 2 to
+    ``max_tips`` tips, ranked by the mean ``taxon_instability`` of their tips over those with ``tx_trees`` >= 1 and a
+    defined instability (a clade without one is no candidate), largest first, then the larger clade, then the lower
+    preorder index; taken greedily, skipping a node nested in or containing one already taken."""
+    parent = np.asarray(parent, dtype=np.int64)
+    lo, hi = _leaf_ranges(parent)
+    inst = np.asarray(instability, dtype=np.float64)
+    ok = (np.asarray(tx_trees) >= 1) & ~np.isnan(inst)
+    total = np.concatenate([[0.0], np.cumsum(np.where(ok, inst, 0.0))])
+    count = np.concatenate([[0], np.cumsum(ok)])
+    size = hi - lo + 1
+    ranked = []
+    for v in range(1, len(parent)):
+        held = count[hi[v] + 1] - count[lo[v]]
+        if 2 <= size[v] <= max_tips and held > 0:
+            ranked.append((-(total[hi[v] + 1] - total[lo[v]]) / held, -int(size[v]), v))
+    ranked.sort()
+    taken: list[int] = []
+    for _, _, v in ranked:
+        if len(taken) == n:
+            break
+        if all(hi[v] < lo[u] or hi[u] < lo[v] for u in taken):
+            taken.append(v)
+    return np.array(taken, dtype=np.int32)
+
+
+def _clade_queries(clades, parent, res: dict, max_tips) -> np.ndarray:
+    if not isinstance(clades, int):
+        return clades
+    dist = res["tx_super"] + res["tx_source"] - 2 * res["tx_shared"]
+    both = res["tx_super"] + res["tx_source"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        inst = np.where(both > 0, dist / np.maximum(both, 1), np.nan)
+    return select_clades(clades, parent, inst, res["tx_trees"], max_tips)
+
+
+def _clade_placements(dev, tabs, parent, taxon, clades, res: dict, max_tips) -> dict:
+    queries = _clade_queries(clades, parent, res, max_tips)
+    out = {"cp_nodes": queries.astype(np.int64)}
+    if len(queries) == 0 or tabs is None:
+        out.update({k: np.zeros(len(queries), dtype=np.int64) for k in ("cp_trees", "cp_total", "cp_source")})
+        out.update({k: np.zeros((len(queries), len(parent)), dtype=np.int64) for k in ("cp_super", "cp_shared")})
+        return out
+    out.update(dev.score_clade_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
+                                          lds_bytes=CLADE_PLACEMENT_LDS_BYTES or 0))
+    return out
+
+
 def _default_device():
     from spectralclustersupertree_amd.scs import default_device
 
@@ -813,7 +1058,7 @@ def _default_device():
 
 def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
                   conflicts, concordance, branch_triplets=False, taxon_triplets=False,
-                  tips=None, placements=None) -> SupertreeScore:
+                  tips=None, placements=None, clades=None, clade_max_tips=64) -> SupertreeScore:
     """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
     (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
     import ctypes as C
@@ -851,7 +1096,7 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     finally:
         forest.free()
     try:
-        t1 = t2 = t3 = t4 = t5 = t6 = t7 = t7p = t8 = time.perf_counter()
+        t1 = t2 = t3 = t4 = t5 = t6 = t7 = t7p = t8 = t8c = t9 = time.perf_counter()
         if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
             res = {**zeros, **node0}
             if placements is not None:
@@ -859,6 +1104,8 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
                 res["pl_taxa"] = queries.astype(np.int64)
                 res.update({k: np.zeros(len(queries), dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")})
                 res.update({k: np.zeros((len(queries), n_nodes), dtype=np.int64) for k in ("pl_super", "pl_shared")})
+            if clades is not None:
+                res.update(_clade_placements(dev, None, parent, taxon, clades, res, clade_max_tips))
         else:
             handle = C.c_void_p()
             nv.check(dev._lib.scs_tables_from_forest(dev._ctx, child._h, None, int(n_taxa), C.byref(handle)))
@@ -887,6 +1134,10 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
                     t7p = time.perf_counter()
                     res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
                     t8 = time.perf_counter()
+                if clades is not None:
+                    t8c = time.perf_counter()
+                    res.update(_clade_placements(dev, tabs, parent, taxon, clades, res, clade_max_tips))
+                    t9 = time.perf_counter()
             finally:
                 tabs.free()
             tree_index = np.array(child.tables()[4], dtype=np.int64)
@@ -911,4 +1162,6 @@ def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new
     if placements is not None:
         timings["placements"] = t8 - t7p
         res["taxa"] = list(tips)
+    if clades is not None:
+        timings["clade_placements"] = t9 - t8c
     return _result(supertree, n_leaves, res, timings)

@@ -9,6 +9,10 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --branch-triplets    # also the per-branch triplet support
     python tools/score_bench.py --taxon-triplets     # also the per-taxon triplet support
     python tools/score_bench.py --placements 16      # also the placement support of 16 taxa
+    python tools/score_bench.py --triplets --clade-placements 16 --placements-as-clade-tips
+                                                     # also the placement support of 16 clades,
+                                                     # beside as many taxon placements as the clades hold tips
+    python tools/score_bench.py --large-clade        # the same for one clade: the first child of the root's first child
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -27,6 +31,7 @@ import numpy as np  # noqa: E402
 
 from spectralclustersupertree_amd import score_supertree, synthetic  # noqa: E402
 from spectralclustersupertree_amd.backend import Device  # noqa: E402
+from spectralclustersupertree_amd.score import _leaf_ranges, select_clades  # noqa: E402
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
 from spectralclustersupertree_amd.treearrays import TreeArrays  # noqa: E402
 
@@ -72,7 +77,8 @@ def caterpillar_arrays(n_taxa: int, n_trees: int, per_tree: int | None) -> TreeA
 
 def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts: bool = False,
         cat: bool = False, concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-        cat_sup: bool = False, placements: int = 0) -> dict:
+        cat_sup: bool = False, placements: int = 0, clades: int = 0, clade_max_tips: int = 64,
+        large_clade: bool = False, match_tips: bool = False) -> dict:
     dims = [int(x) for x in size.split("x")]
     n_taxa, n_trees = dims[0], dims[1]
     per_tree = dims[2] if len(dims) > 2 else None
@@ -84,13 +90,27 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
         arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
         sup = caterpillar(np.random.RandomState(2).permutation(n_taxa)) if cat_sup else random_binary_tree(2, n_taxa)
     gen_s = time.perf_counter() - t0
+    nodes = None
+    if clades or large_clade:  # the query nodes, fixed before the timed calls
+        parent = np.asarray(sup.to_flat()[0], dtype=np.int64)
+        lo, hi = _leaf_ranges(parent)
+        if large_clade:
+            nodes = np.array([2], dtype=np.int32)  # (preorder: the root, its first child, that child's first child)
+        else:
+            first = score_supertree(sup, arrays, taxon_triplets=True, device=dev)
+            nodes = select_clades(clades, parent, first.taxon_instability, first.tx_trees, clade_max_tips)
+        clade_tips = int((hi[nodes] - lo[nodes] + 1).sum())
+        if match_tips and clade_tips <= 1024:  # (more query taxa than that need more rows than a call may take)
+            placements = clade_tips
     runs = []
-    for _ in range(repeats):
+    for i in range(repeats + (nodes is not None)):  # (with clades: a warm-up call at this size, not timed)
         t0 = time.perf_counter()
         res = score_supertree(sup, arrays, triplets=triplets, conflicts=conflicts, concordance=concordance,
                               branch_triplets=branch_triplets, taxon_triplets=taxon_triplets,
-                              placements=_queries(sup, placements) if placements else None, device=dev)
-        runs.append((time.perf_counter() - t0, res.timings))
+                              placements=_queries(sup, placements) if placements else None,
+                              clade_placements=nodes, device=dev)
+        if i or nodes is None:
+            runs.append((time.perf_counter() - t0, res.timings))
     wall, tim = min(runs, key=lambda r: r[0])
     out = {
         "size": size, "input": "caterpillar" if cat else "caterpillar supertree" if cat_sup else "random", "n_taxa": n_taxa, "n_trees": n_trees, "leaves": int(arrays.leaf_counts().sum()),
@@ -159,6 +179,24 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
                     "placement_entries": int(res.pl_shared.size), "total_pl_trees": int(res.pl_trees.sum()),
                     "total_best_distance": int(sum(r["best_distance"] for r in best)),
                     "taxa_with_a_better_place": int(sum(r["improvement"] > 0 for r in best))})
+    if nodes is not None:
+        best = res.best_clade_placements()
+        cmed = _spread([r[1]["clade_placements"] for r in runs])[1]
+        out.update({"clade_placements": len(nodes), "clade_tips": clade_tips,
+                    "clade_placements_call_s": round(tim["clade_placements"], 5),
+                    "clade_placements_call_s_min_median_max":
+                        [round(x, 5) for x in _spread([r[1]["clade_placements"] for r in runs])],
+                    "clade_placement_entries": int(res.cp_shared.size), "total_cp_trees": int(res.cp_trees.sum()),
+                    "total_best_clade_distance": int(sum(r["best_distance"] for r in best)),
+                    "clades_with_a_better_place": int(sum(r["improvement"] > 0 for r in best))})
+        if placements:
+            pmed = _spread([r[1]["placements"] for r in runs])[1]
+            out["clade_placements_over_placements"] = round(cmed / max(pmed, 1e-9), 3)
+        if triplets:
+            tmed = _spread([r[1]["triplets"] for r in runs])[1]
+            out["triplets_call_s_min_median_max"] = [round(x, 5) for x in _spread([r[1]["triplets"] for r in runs])]
+            out["clade_placements_over_triplets"] = round(cmed / max(tmed, 1e-9), 3)
+    if placements:
         if taxon_triplets:
             xmed = _spread([r[1]["taxon_triplets"] for r in runs])[1]
             pmed = _spread([r[1]["placements"] for r in runs])[1]
@@ -188,6 +226,13 @@ def main() -> None:
     ap.add_argument("--taxon-triplets", action="store_true", help="also count the per-taxon triplet support")
     ap.add_argument("--placements", type=int, default=0, metavar="N",
                     help="also the placement support of N taxa spread over the supertree's leaf order")
+    ap.add_argument("--clade-placements", type=int, default=0, metavar="N",
+                    help="also the placement support of N clades (the choice of score_supertree(clade_placements=N))")
+    ap.add_argument("--clade-max-tips", type=int, default=64, help="the largest clade --clade-placements considers")
+    ap.add_argument("--large-clade", action="store_true",
+                    help="also the placement support of one clade: the first child of the root's first child")
+    ap.add_argument("--placements-as-clade-tips", action="store_true",
+                    help="--placements N with N = the number of tips the query clades hold in all")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -196,13 +241,17 @@ def main() -> None:
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
                         conflicts=args.conflicts, concordance=args.concordance, branch_triplets=args.branch_triplets,
-                        taxon_triplets=args.taxon_triplets, placements=2 if args.placements else None,
+                        taxon_triplets=args.taxon_triplets,
+                        placements=2 if args.placements or args.placements_as_clade_tips else None,
+                        clade_placements=2 if args.clade_placements or args.large_clade else None,
                         device=dev)  # warm-up
         for size in args.size or SIZES:
             reps = 1 if int(size.split("x")[0]) * int(size.split("x")[1]) > 10**8 else args.repeats
             print(json.dumps(run(dev, size, reps, args.triplets, args.conflicts, args.caterpillar,
                                  args.concordance, args.branch_triplets, args.taxon_triplets,
-                                 args.caterpillar_supertree, args.placements)), flush=True)
+                                 args.caterpillar_supertree, args.placements, args.clade_placements,
+                                 args.clade_max_tips, args.large_clade, args.placements_as_clade_tips)),
+                  flush=True)
 
 
 if __name__ == "__main__":
