@@ -100,7 +100,7 @@ typedef struct scs_build_stats {
     int32_t reserved;
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements and scs_score_clade_placements added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements, scs_score_clade_placements and scs_score_clade_moves added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -457,6 +457,24 @@ int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *sources, int32_t 
                                const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
                                int32_t n_queries, const int32_t *query_nodes, int64_t *cp_trees, int64_t *cp_total,
                                int64_t *cp_source, int64_t *cp_super, int64_t *cp_shared);
+
+/* The best regraft targets of every query clade: the sweep, the inputs, the SCS_EINVAL cases
+ * and the workspace rule of scs_score_clade_placements, but the two rows per query (cp_super, cp_shared) stay on the
+ * device and a kernel reduces each of them there; cp_trees, cp_total and cp_source are as there.  top_k is 1 to 8
+ * (SCS_EINVAL otherwise).  Per query i with node q = query_nodes[i]:
+ *   mv_own_super[i], mv_own_shared[i] = the row entries at q itself: the clade where it is;
+ *   mv_node[i * top_k + j]            = the j-th best candidate node, int32,
+ *   mv_super[i * top_k + j], mv_shared[i * top_k + j] = the row entries there.
+ * The candidates are the nodes v outside the preorder range [q, end of the subtree of q): the whole subtree is left
+ * out.  They are ordered by the key (d, v) ascending with d = cp_super[i][v] - 2 cp_shared[i][v] (signed; cp_source is
+ * the same along a row, so this is the order of the clade placement distance) and ties go to the lower preorder index.
+ * The root is always a candidate, so j = 0 always holds a node; where fewer than top_k candidates exist the further
+ * entries hold mv_node = -1 and zeros.  Output pointers may be null. */
+int scs_score_clade_moves(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                          const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
+                          const int32_t *query_nodes, int32_t top_k, int64_t *cp_trees, int64_t *cp_total,
+                          int64_t *cp_source, int64_t *mv_own_super, int64_t *mv_own_shared, int32_t *mv_node,
+                          int64_t *mv_super, int64_t *mv_shared);
 
 /* ---- proper cluster graph ---------------------------------------------- */
 

@@ -313,6 +313,37 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_clade_moves(self, sources, parent: np.ndarray, taxon: np.ndarray, query_nodes, top_k: int = 4,
+                          batch_trees: int = 0, lds_bytes: int = 0) -> dict:
+        """``scs_score_clade_moves``: the sweep of ``score_clade_placements`` with every row reduced on the device to
+        the clade's own entry and its ``top_k`` (1 to 8) best regraft targets outside its subtree, by
+        (``mv_super`` - 2 ``mv_shared``, node) ascending.  Returns int64 arrays ``cp_trees``, ``cp_total``,
+        ``cp_source``, ``mv_own_super``, ``mv_own_shared`` (one entry per query), ``mv_node`` (int32) and ``mv_super``,
+        ``mv_shared`` (queries x top_k; -1 and zeros where fewer candidates exist)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        query_nodes = np.ascontiguousarray(query_nodes, dtype=np.int32)
+        n_nodes, nq, k = len(parent), len(query_nodes), max(int(top_k), 0)
+        if taxon.shape != (n_nodes,) or query_nodes.ndim != 1:
+            msg = "parent and taxon must have one entry per supertree node, query_nodes one per query clade"
+            raise ValueError(msg)
+        out = {k_: np.zeros(nq, dtype=np.int64)
+               for k_ in ("cp_trees", "cp_total", "cp_source", "mv_own_super", "mv_own_shared")}
+        out["mv_node"] = np.full((nq, k), -1, dtype=np.int32)
+        out.update({k_: np.zeros((nq, k), dtype=np.int64) for k_ in ("mv_super", "mv_shared")})
+        rc = self._lib.scs_score_clade_moves(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
+                                             int(batch_trees), int(lds_bytes), nq, nv.iptr(query_nodes), int(top_k),
+                                             *(nv.lptr(out[k_]) for k_ in ("cp_trees", "cp_total", "cp_source",
+                                                                           "mv_own_super", "mv_own_shared")),
+                                             nv.iptr(out["mv_node"]), nv.lptr(out["mv_super"]),
+                                             nv.lptr(out["mv_shared"]))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_clade_moves: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.

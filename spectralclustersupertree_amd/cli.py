@@ -76,14 +76,27 @@ from spectralclustersupertree_amd import __version__
               help="How many clades --clade-placements-out places.")
 @click.option("--clade-max-tips", default=64, type=click.IntRange(min=2), show_default=True,
               help="The largest clade --clade-placements-out considers.")
+@click.option("--refined-out", default=None,
+              help="Also refine the supertree by prune-and-regraft moves that lower its rooted triplet distance to "
+                   "the source trees (refine_supertree) and write the refined tree here; -o and every other output "
+                   "keep describing the constructed tree.")
+@click.option("--refine-rounds", default=50, type=click.IntRange(min=0), show_default=True,
+              help="The most rounds --refined-out runs.")
+@click.option("--refine-log", default=None,
+              help="With --refined-out: a TSV with one row per move (round, kind, node, target, tips, gain, "
+                   "distance_after).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
         concordance_out: str | None = None, branches_out: str | None = None, branch_triplets: bool = False,
         branch_triplets_out: str | None = None, taxon_triplets: bool = False,
         taxa_out: str | None = None, placements_out: str | None = None, place_taxa: int = 10,
-        clade_placements_out: str | None = None, place_clades: int = 10, clade_max_tips: int = 64) -> None:
+        clade_placements_out: str | None = None, place_clades: int = 10, clade_max_tips: int = 64,
+        refined_out: str | None = None, refine_rounds: int = 50, refine_log: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
+    if refine_log and not refined_out:
+        msg = "--refine-log needs --refined-out"
+        raise click.UsageError(msg)
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
         raise click.UsageError(msg)
@@ -148,6 +161,13 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                     result.annotate_concordance().get_newick(with_node_names=True) + "\n")
             if branches_out:
                 Path(branches_out).write_text(result.branch_table())
+        if refined_out:
+            from spectralclustersupertree_amd.refine import refine_supertree
+
+            refined = refine_supertree(supertree, load_tree_arrays(in_file), max_rounds=refine_rounds)
+            refined.supertree.write(refined_out)
+            if refine_log:
+                Path(refine_log).write_text(refined.table())
 
 
 def _without_branch_triplets(result):

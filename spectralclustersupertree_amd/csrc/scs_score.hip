@@ -2316,6 +2316,83 @@ __global__ void __launch_bounds__(SC_THREADS) k_cp_marks(const unsigned long lon
     atomicAdd(diff + r * (n + 1) + end[u], 0ull - m);
 }
 
+// ---- scs_score_clade_moves: the rows of scs_score_clade_placements stay on the device and every
+// row is reduced to the clade's own entry and its top_k best regraft targets.  One workgroup per query.  A candidate is
+// a node v outside the preorder range [q, end q); its key is (d, v) with d = super[v] - 2 shared[v], signed.  Keys are
+// unique, so pass j takes the smallest key above the winner of pass j - 1: a strided scan per thread, a wave-64 shuffle
+// reduction of the pair and one LDS step across the waves.  The sentinel (INT64_MAX, INT32_MAX) is above every real
+// key and marks "no candidate left".  The row is 16 bytes a node and is read top_k times (L2).
+constexpr int MV_KMAX = 8;
+
+__device__ __forceinline__ bool mv_less(long long d0, int v0, long long d1, int v1) {
+    return d0 < d1 || (d0 == d1 && v0 < v1);
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_cp_best(const long long *__restrict__ shared,
+                                                        const long long *__restrict__ super, int64_t n,
+                                                        const int32_t *__restrict__ qnode,
+                                                        const int32_t *__restrict__ end, int top_k,
+                                                        int32_t *__restrict__ mv_node, long long *__restrict__ mv_super,
+                                                        long long *__restrict__ mv_shared,
+                                                        long long *__restrict__ own_super,
+                                                        long long *__restrict__ own_shared) {
+    __shared__ long long wd[SC_THREADS / 64];
+    __shared__ int wv[SC_THREADS / 64];
+    __shared__ long long bd;
+    __shared__ int bv;
+    const int64_t i = blockIdx.x;
+    const long long *sh = shared + i * n, *su = super + i * n;
+    const int q = qnode[i], qe = end[q];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        own_super[i] = su[q];
+        own_shared[i] = sh[q];
+    }
+    long long pd = INT64_MIN;  // the winner of the pass before: below every key at first
+    int pv = -1;
+    for (int j = 0; j < top_k; ++j) {
+        long long d = INT64_MAX;
+        int v = INT32_MAX;
+        for (int64_t u = threadIdx.x; u < n; u += SC_THREADS) {
+            if (u >= q && u < qe) continue;
+            const long long k = su[u] - 2 * sh[u];
+            if (mv_less(pd, pv, k, (int)u) && mv_less(k, (int)u, d, v)) {
+                d = k;
+                v = (int)u;
+            }
+        }
+        for (int s = 32; s >= 1; s >>= 1) {
+            const long long od = __shfl_xor(d, s, 64);
+            const int ov = __shfl_xor(v, s, 64);
+            if (mv_less(od, ov, d, v)) {
+                d = od;
+                v = ov;
+            }
+        }
+        if (lane == 0) {
+            wd[wave] = d;
+            wv[wave] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < SC_THREADS / 64; ++w)
+                if (mv_less(wd[w], wv[w], d, v)) {
+                    d = wd[w];
+                    v = wv[w];
+                }
+            bd = d;
+            bv = v;
+            const bool found = v != INT32_MAX;
+            mv_node[i * top_k + j] = found ? v : -1;
+            mv_super[i * top_k + j] = found ? su[v] : 0;
+            mv_shared[i * top_k + j] = found ? sh[v] : 0;
+        }
+        __syncthreads();
+        pd = bd;
+        pv = bv;
+    }
+}
+
 // levels of a sparse table over n entries: 2^levels > n (the binary descent's widest step covers any stretch)
 int sc_levels_host(int64_t n) {
     int l = 1;
@@ -3382,12 +3459,15 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
     return SCS_OK;
 }
 
-extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
-                                          const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
-                                          int32_t n_queries, const int32_t *query_nodes, int64_t *cp_trees,
-                                          int64_t *cp_total, int64_t *cp_source, int64_t *cp_super,
-                                          int64_t *cp_shared) {
-    const char *const who = "scs_score_clade_placements";
+// what scs_score_clade_placements and scs_score_clade_moves share: the checks, the sweep and the rows in the call's
+// workspace.  top_k = 0: the rows are copied out (cp_super, cp_shared); top_k >= 1: k_cp_best reduces them where they
+// are and only its outputs come down
+static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *src, int32_t n_nodes,
+                         const int32_t *parent, const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                         int32_t n_queries, const int32_t *query_nodes, int32_t top_k, int64_t *cp_trees,
+                         int64_t *cp_total, int64_t *cp_source, int64_t *cp_super, int64_t *cp_shared,
+                         int64_t *mv_own_super, int64_t *mv_own_shared, int32_t *mv_node, int64_t *mv_super,
+                         int64_t *mv_shared) {
     const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
     SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
                 "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
@@ -3451,7 +3531,11 @@ extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, i
                  o_clo = o_cs + sc_up256(nq * 24), o_chi = o_clo + sc_up256(nq * 4), o_qpos = o_chi + sc_up256(nq * 4),
                  o_qslot = o_qpos + sc_up256(ns * 4), o_par = o_qslot + sc_up256(ns * 4),
                  o_tipn = o_par + sc_up256(nn * 4), o_tipd = o_tipn + sc_up256(nn * 4),
-                 o_blk = o_tipd + sc_up256(nn * 4), own = o_blk + sc_up256((mt + 1) * 8);
+                 o_blk = o_tipd + sc_up256(nn * 4), o_mv = o_blk + sc_up256((mt + 1) * 8);
+    // the reduced rows (top_k >= 1): the query nodes, then per query its own pair and top_k (node, super, shared)
+    const size_t kk = (size_t)top_k, o_mvn = o_mv + (kk ? sc_up256(nq * 4) : 0), o_mvs = o_mvn + sc_up256(nq * kk * 4),
+                 o_mvh = o_mvs + sc_up256(nq * kk * 8), o_own = o_mvh + sc_up256(nq * kk * 8),
+                 own = o_own + (kk ? sc_up256(2 * nq * 8) : 0);
     sc_call c;
     hipError_t e = hipSuccess;
     SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 25 * (uint64_t)qcap + 64,
@@ -3647,6 +3731,48 @@ extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, i
     if (e == hipSuccess && cp_shared) e = hipMemcpyAsync(cp_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && cp_super)
         e = hipMemcpyAsync(cp_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
+    if (top_k > 0 && e == hipSuccess && !bad) {
+        auto *d_qnode = (int32_t *)(c.d_extra + o_mv);
+        auto *d_mvn = (int32_t *)(c.d_extra + o_mvn);
+        auto *d_mvs = (long long *)(c.d_extra + o_mvs);
+        auto *d_mvh = (long long *)(c.d_extra + o_mvh);
+        auto *d_own = (long long *)(c.d_extra + o_own);
+        e = hipMemcpyAsync(d_qnode, query_nodes, nq * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            k_cp_best<<<(unsigned)nq, SC_THREADS, 0, s>>>((const long long *)d_sub, (const long long *)(d_sub + nq * nn),
+                                                         (int64_t)nn, d_qnode, c.d_end, top_k, d_mvn, d_mvs, d_mvh,
+                                                         d_own, d_own + nq);
+            sc_launched(e);
+        }
+        if (e == hipSuccess && mv_node) e = hipMemcpyAsync(mv_node, d_mvn, nq * kk * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && mv_super) e = hipMemcpyAsync(mv_super, d_mvs, nq * kk * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && mv_shared) e = hipMemcpyAsync(mv_shared, d_mvh, nq * kk * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && mv_own_super)
+            e = hipMemcpyAsync(mv_own_super, d_own, nq * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && mv_own_shared)
+            e = hipMemcpyAsync(mv_own_shared, d_own + nq, nq * 8, hipMemcpyDeviceToHost, s);
+    }
     SCS_TRY(sc_end(ctx, c, e, bad));
     return SCS_OK;
+}
+
+extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                          const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                          int32_t n_queries, const int32_t *query_nodes, int64_t *cp_trees,
+                                          int64_t *cp_total, int64_t *cp_source, int64_t *cp_super,
+                                          int64_t *cp_shared) {
+    return sc_clade_rows("scs_score_clade_placements", ctx, src, n_nodes, parent, taxon, max_batch_trees,
+                         max_lds_bytes, n_queries, query_nodes, 0, cp_trees, cp_total, cp_source, cp_super, cp_shared,
+                         nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int scs_score_clade_moves(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                     const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                     int32_t n_queries, const int32_t *query_nodes, int32_t top_k, int64_t *cp_trees,
+                                     int64_t *cp_total, int64_t *cp_source, int64_t *mv_own_super,
+                                     int64_t *mv_own_shared, int32_t *mv_node, int64_t *mv_super, int64_t *mv_shared) {
+    SCS_REQUIRE(top_k >= 1 && top_k <= MV_KMAX, "scs_score_clade_moves: top_k = %d is not in [1, %d]", top_k, MV_KMAX);
+    return sc_clade_rows("scs_score_clade_moves", ctx, src, n_nodes, parent, taxon, max_batch_trees, max_lds_bytes,
+                         n_queries, query_nodes, top_k, cp_trees, cp_total, cp_source, nullptr, nullptr, mv_own_super,
+                         mv_own_shared, mv_node, mv_super, mv_shared);
 }

@@ -13,6 +13,8 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
                                                      # also the placement support of 16 clades,
                                                      # beside as many taxon placements as the clades hold tips
     python tools/score_bench.py --large-clade        # the same for one clade: the first child of the root's first child
+    python tools/score_bench.py --refine --size 10000x500   # refine_supertree on a model tree with 20 planted regrafts
+                                                     # against restrictions of the model
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -29,9 +31,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 import numpy as np  # noqa: E402
 
-from spectralclustersupertree_amd import score_supertree, synthetic  # noqa: E402
+from spectralclustersupertree_amd import refine_supertree, score_supertree, synthetic  # noqa: E402
+from spectralclustersupertree_amd import refine as refine_mod  # noqa: E402
 from spectralclustersupertree_amd.backend import Device  # noqa: E402
-from spectralclustersupertree_amd.score import _leaf_ranges, select_clades  # noqa: E402
+from spectralclustersupertree_amd.score import _leaf_ranges, select_clades, supertree_arrays  # noqa: E402
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
 from spectralclustersupertree_amd.treearrays import TreeArrays  # noqa: E402
 
@@ -204,6 +207,86 @@ def run(dev: Device, size: str, repeats: int, triplets: bool = False, conflicts:
     return out
 
 
+def model_arrays(model: TreeNode, n_trees: int, per_tree: int | None, seed: int) -> TreeArrays:
+    """``n_trees`` restrictions of ``model`` to ``per_tree`` random taxa each (copies of it when None)."""
+    taxa = model.get_tip_names()
+    one = TreeArrays.from_trees([model], [1.0], taxa)
+    rs = np.random.RandomState(seed)
+    parts = [one if per_tree is None or per_tree >= len(taxa)
+             else one.restrict(np.sort(rs.choice(len(taxa), size=per_tree, replace=False)).astype(np.int32))
+             for _ in range(n_trees)]
+    off = np.concatenate([[0], np.cumsum([len(p.parent) for p in parts])]).astype(np.int64)
+    return TreeArrays(n_taxa=len(taxa), node_off=off, parent=np.concatenate([p.parent for p in parts]),
+                      taxon=np.concatenate([p.taxon for p in parts]), length=np.concatenate([p.length for p in parts]),
+                      support=np.concatenate([p.support for p in parts]), weights=np.ones(n_trees), taxa=list(taxa))
+
+
+def run_refine(dev: Device, size: str, planted: int = 20, repeats: int = 5) -> dict:
+    """``refine_supertree`` on a random binary model tree with ``planted`` clades of up to 8 tips regrafted at random,
+    against restrictions of the model: a warm-up and ``repeats`` timed runs; beside them the calls a hand-written loop
+    makes per turn (one ``score_supertree`` with the three options), and ``scs_score_clade_moves`` against
+    ``scs_score_clade_placements`` on resident tables for the same 64 clades and for 1 500 tip queries."""
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    model = random_binary_tree(2, n_taxa)
+    arrays = model_arrays(model, n_trees, per_tree, 3)
+    rs = np.random.RandomState(4)
+    start = model
+    for _ in range(planted):
+        end = refine_mod.subtree_ends(start.to_flat()[0])
+        at = np.arange(len(end))
+        q = int(rs.choice(np.flatnonzero((end - at <= 15) & (at > 0))))
+        v = int(rs.randint(len(end)))
+        while q <= v < end[q]:
+            v = int(rs.randint(len(end)))
+        start = refine_mod.apply_moves(start, [(q, v)])
+    runs = []
+    for _ in range(repeats + 1):
+        t0 = time.perf_counter()
+        res = refine_supertree(start, arrays, device=dev)
+        runs.append((time.perf_counter() - t0, res))
+    runs = runs[1:]
+    per_round = {k: [float(np.mean(r.timings[k])) for _, r in runs]
+                 for k in ("taxon_triplets", "branch_triplets", "clade_moves")}
+    res = runs[0][1]
+    out = {"size": size, "refine": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "planted": planted, "rounds": len(res.rounds), "moves": [len(r["moves"]) for r in res.rounds],
+           "initial_distance": res.initial_distance, "final_distance": res.final_distance,
+           "refine_wall_s_min_median_max": [round(x, 4) for x in _spread([w for w, _ in runs])],
+           "tables_s_min_median_max": [round(x, 4) for x in _spread([r.timings["tables"] for _, r in runs])],
+           "round_s_min_median_max": [round(x, 4) for x in _spread(
+               [float(np.mean([rnd["seconds"] for rnd in r.rounds])) for _, r in runs])]}
+    for k, v in per_round.items():
+        out[f"{k}_s_per_round_min_median_max"] = [round(x, 5) for x in _spread(v)]
+    hand = []
+    for _ in range(repeats + 1):
+        t0 = time.perf_counter()
+        sc = score_supertree(start, arrays, taxon_triplets=True, branch_triplets=True, clade_placements=64, device=dev)
+        hand.append((time.perf_counter() - t0, sc.timings))
+    hand = hand[1:]
+    out["hand_turn_wall_s_min_median_max"] = [round(x, 4) for x in _spread([w for w, _ in hand])]
+    for k in ("tables", "taxon_triplets", "branch_triplets", "clade_placements"):
+        out[f"hand_turn_{k}_s_min_median_max"] = [round(x, 5) for x in _spread([t[k] for _, t in hand])]
+    parent, _, tips = supertree_arrays(start)
+    index = {x: i for i, x in enumerate(tips)}
+    parent, taxon = refine_mod.tree_arrays_with_ids(start, index)
+    tip_nodes = np.flatnonzero(taxon >= 0)
+    sets = {"64_clades": sc.cp_nodes.astype(np.int32),
+            "1500_tips": tip_nodes[np.linspace(0, len(tip_nodes) - 1, num=min(1500, len(tip_nodes)), dtype=np.int64)]}
+    with refine_mod._resident_tables(dev, arrays, tips, index) as tabs:
+        for name, nodes in sets.items():
+            for what, call in (("placements", lambda n=nodes: dev.score_clade_placements(tabs, parent, taxon, n)),
+                               ("moves", lambda n=nodes: dev.score_clade_moves(tabs, parent, taxon, n, top_k=4))):
+                times = []
+                for _ in range(repeats + 1):
+                    t0 = time.perf_counter()
+                    call()
+                    times.append(time.perf_counter() - t0)
+                out[f"{name}_{what}_s_min_median_max"] = [round(x, 5) for x in _spread(times[1:])]
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -233,11 +316,20 @@ def main() -> None:
                     help="also the placement support of one clade: the first child of the root's first child")
     ap.add_argument("--placements-as-clade-tips", action="store_true",
                     help="--placements N with N = the number of tips the query clades hold in all")
+    ap.add_argument("--refine", action="store_true",
+                    help="time refine_supertree instead (a model tree with planted regrafts; --planted N)")
+    ap.add_argument("--planted", type=int, default=20, help="how many clades --refine regrafts at random")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
+    if args.refine:
+        with Device(0) as dev:
+            run_refine(dev, "60x6", planted=2, repeats=1)  # warm-up
+            for size in args.size or SIZES[:1]:
+                print(json.dumps(run_refine(dev, size, args.planted)), flush=True)
+        return
     with Device(0) as dev:
         score_supertree(random_binary_tree(0, 50), synthetic.tree_arrays(0, 50, 4), triplets=args.triplets,
                         conflicts=args.conflicts, concordance=args.concordance, branch_triplets=args.branch_triplets,
