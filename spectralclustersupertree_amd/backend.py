@@ -19,6 +19,9 @@ from spectralclustersupertree_amd.flatten import TreeTables
 DEFAULT_TOL = 1e-13
 DEFAULT_MAX_ITER = 2000
 
+# output dims of ``Device._score_call``: per source tree, per supertree node, per query, queries x nodes, queries x top_k
+_M, _N, _Q, _QN, _QK = ("m",), ("n_nodes",), ("nq",), ("nq", "n_nodes"), ("nq", "top_k")
+
 
 def _resident_solve() -> bool:
     """SCS_RESIDENT_SOLVE=0 (diagnostic): small nodes pack their tables on the host even when the
@@ -127,6 +130,46 @@ class Device:
         return out
 
     # -- scoring a supertree ----------------------------------------------------
+    def _score_call(self, export: str, sources, parent, taxon, ints, outputs, queries=None, noun: str = "",
+                    top_k=None) -> dict:
+        """One ``scs_score_*`` export.  ``sources`` are uploaded when they are ``TreeTables``; ``parent`` / ``taxon``
+        (and ``queries``, which ``noun`` names in the shape message) travel as int32.  The export takes the context,
+        the tables, the supertree, ``ints``, then the query count and ``queries``, then ``top_k``, then one buffer per
+        output.  ``outputs``: ``(names, dims[, dtype, fill])`` entries with ``dims`` out of ``m`` (source trees),
+        ``n_nodes``, ``n_tips``, ``nq`` and ``top_k``; int64 zeros unless said otherwise.  Returns name -> array in
+        that order; SCS_EINVAL becomes ``ValueError`` with the library's message."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        parent = np.ascontiguousarray(parent, dtype=np.int32)
+        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
+        size = {"m": tabs.n_trees, "n_nodes": len(parent)}
+        args = [int(x) for x in ints]
+        ok, msg = taxon.shape == (len(parent),), "parent and taxon must have one entry per supertree node"
+        if queries is not None:
+            queries = np.ascontiguousarray(queries, dtype=np.int32)
+            size["nq"] = len(queries)
+            args += [size["nq"], nv.iptr(queries)]
+            ok, msg = ok and queries.ndim == 1, f"{msg}, {noun}"
+        if not ok:
+            raise ValueError(msg)
+        if top_k is not None:
+            size["top_k"] = max(int(top_k), 0)
+            args.append(int(top_k))
+        if any("n_tips" in dims for _, dims, *_ in outputs):
+            size["n_tips"] = len(parent) - len(np.unique(parent[1:]))
+        out = {}
+        for names, dims, *rest in outputs:
+            dtype, fill = rest or (np.int64, 0)
+            shape = tuple(size[d] for d in dims)
+            for name in names:
+                out[name] = np.zeros(shape, dtype=dtype) if fill == 0 else np.full(shape, fill, dtype=dtype)
+        rc = getattr(self._lib, export)(self._ctx, tabs._h, len(parent), nv.iptr(parent), nv.iptr(taxon), *args,
+                                        *(v.ctypes.data for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else f"{export}: invalid input")
+        nv.check(rc)
+        return out
+
     def score(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
         """``scs_score_supertree``: RF terms per source tree and clade support per supertree node.
 
@@ -135,108 +178,36 @@ class Device:
         taxon -1 at inner nodes).  ``batch_trees`` > 0 caps the trees of one device batch.  Returns int64
         arrays ``n_super``, ``n_source``, ``shared`` (per tree) and ``informative``, ``supported`` (per node).
         """
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes, m = len(parent), tabs.n_trees
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_super", "n_source", "shared")}
-        out.update({k: np.zeros(n_nodes, dtype=np.int64) for k in ("informative", "supported")})
-        rc = self._lib.scs_score_supertree(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                           int(batch_trees), nv.lptr(out["n_super"]), nv.lptr(out["n_source"]),
-                                           nv.lptr(out["shared"]), nv.lptr(out["informative"]),
-                                           nv.lptr(out["supported"]))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_supertree: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_supertree", sources, parent, taxon, (batch_trees,),
+                                ((("n_super", "n_source", "shared"), _M), (("informative", "supported"), _N)))
 
     def score_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
         """``scs_score_triplets``: rooted triplet terms per source tree, with the inputs of ``score``.  Returns int64
         arrays ``t_super``, ``t_source``, ``t_shared`` (per tree)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes, m = len(parent), tabs.n_trees
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        out = {k: np.zeros(m, dtype=np.int64) for k in ("t_super", "t_source", "t_shared")}
-        rc = self._lib.scs_score_triplets(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                          int(batch_trees), nv.lptr(out["t_super"]), nv.lptr(out["t_source"]),
-                                          nv.lptr(out["t_shared"]))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_triplets: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_triplets", sources, parent, taxon, (batch_trees,),
+                                ((("t_super", "t_source", "t_shared"), _M),))
 
     def score_conflicts(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
         """``scs_score_conflicts``: clade conflict counts, with the inputs of ``score``.  Returns int64 arrays
         ``n_super_conflict``, ``n_source_conflict`` (per tree) and ``conflicting`` (per node)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes, m = len(parent), tabs.n_trees
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_super_conflict", "n_source_conflict")}
-        out["conflicting"] = np.zeros(n_nodes, dtype=np.int64)
-        rc = self._lib.scs_score_conflicts(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                           int(batch_trees), nv.lptr(out["n_super_conflict"]),
-                                           nv.lptr(out["n_source_conflict"]), nv.lptr(out["conflicting"]))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_conflicts: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_conflicts", sources, parent, taxon, (batch_trees,),
+                                ((("n_super_conflict", "n_source_conflict"), _M), (("conflicting",), _N)))
 
     def score_concordance(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
         """``scs_score_concordance``: branch concordance counts, with the inputs of ``score``.  Returns int64 arrays
         ``n_decisive``, ``n_concordant``, ``n_alternative`` (per tree) and ``decisive``, ``concordant``, ``alt1``,
         ``alt2`` (per node)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes, m = len(parent), tabs.n_trees
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_decisive", "n_concordant", "n_alternative")}
-        out.update({k: np.zeros(n_nodes, dtype=np.int64) for k in ("decisive", "concordant", "alt1", "alt2")})
-        rc = self._lib.scs_score_concordance(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                             int(batch_trees), *(nv.lptr(v) for v in out.values()))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_concordance: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_concordance", sources, parent, taxon, (batch_trees,),
+                                ((("n_decisive", "n_concordant", "n_alternative"), _M),
+                                 (("decisive", "concordant", "alt1", "alt2"), _N)))
 
     def score_branch_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0) -> dict:
         """``scs_score_branch_triplets``: per-branch triplet support, with the inputs of ``score``.  Returns int64
         arrays ``n_bt_total``, ``n_bt_concordant``, ``n_bt_alternative`` (per tree) and ``bt_total``,
         ``bt_concordant``, ``bt_alt1``, ``bt_alt2`` (per node)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes, m = len(parent), tabs.n_trees
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        out = {k: np.zeros(m, dtype=np.int64) for k in ("n_bt_total", "n_bt_concordant", "n_bt_alternative")}
-        out.update({k: np.zeros(n_nodes, dtype=np.int64)
-                    for k in ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2")})
-        rc = self._lib.scs_score_branch_triplets(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                                 int(batch_trees), *(nv.lptr(v) for v in out.values()))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_branch_triplets: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_branch_triplets", sources, parent, taxon, (batch_trees,),
+                                ((("n_bt_total", "n_bt_concordant", "n_bt_alternative"), _M),
+                                 (("bt_total", "bt_concordant", "bt_alt1", "bt_alt2"), _N)))
 
     def score_taxon_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0,
                              lds_bytes: int = 0) -> dict:
@@ -244,24 +215,8 @@ class Device:
         arrays ``tx_trees``, ``tx_total``, ``tx_super``, ``tx_source``, ``tx_shared`` with one entry per supertree tip,
         indexed by taxon id (the tips' ids must be 0 .. tips - 1, as ``supertree_arrays`` numbers them).
         ``lds_bytes`` > 0 caps the LDS one workgroup of the pair kernel takes (tests)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        n_nodes = len(parent)
-        if taxon.shape != (n_nodes,):
-            msg = "parent and taxon must have one entry per supertree node"
-            raise ValueError(msg)
-        n_tips = n_nodes - len(np.unique(parent[1:]))
-        out = {k: np.zeros(n_tips, dtype=np.int64)
-               for k in ("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")}
-        rc = self._lib.scs_score_taxon_triplets(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                                int(batch_trees), int(lds_bytes),
-                                                *(nv.lptr(v) for v in out.values()))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_taxon_triplets: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_taxon_triplets", sources, parent, taxon, (batch_trees, lds_bytes),
+                                ((("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared"), ("n_tips",)),))
 
     def score_placements(self, sources, parent: np.ndarray, taxon: np.ndarray, queries, batch_trees: int = 0,
                          lds_bytes: int = 0) -> dict:
@@ -269,24 +224,9 @@ class Device:
         node, with the inputs of ``score`` and ``queries`` = taxon ids of supertree tips, each once.  Returns int64
         arrays ``pl_trees``, ``pl_total``, ``pl_source`` (one entry per query) and ``pl_super``, ``pl_shared``
         (queries x nodes).  ``lds_bytes`` > 0 caps the LDS one workgroup of the pair kernel takes (tests)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        queries = np.ascontiguousarray(queries, dtype=np.int32)
-        n_nodes, nq = len(parent), len(queries)
-        if taxon.shape != (n_nodes,) or queries.ndim != 1:
-            msg = "parent and taxon must have one entry per supertree node, queries one per query taxon"
-            raise ValueError(msg)
-        out = {k: np.zeros(nq, dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")}
-        out.update({k: np.zeros((nq, n_nodes), dtype=np.int64) for k in ("pl_super", "pl_shared")})
-        rc = self._lib.scs_score_placements(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                            int(batch_trees), int(lds_bytes), nq, nv.iptr(queries),
-                                            *(nv.lptr(v) for v in out.values()))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_placements: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_placements", sources, parent, taxon, (batch_trees, lds_bytes),
+                                ((("pl_trees", "pl_total", "pl_source"), _Q), (("pl_super", "pl_shared"), _QN)),
+                                queries, "queries one per query taxon")
 
     def score_clade_placements(self, sources, parent: np.ndarray, taxon: np.ndarray, query_nodes,
                                batch_trees: int = 0, lds_bytes: int = 0) -> dict:
@@ -294,24 +234,9 @@ class Device:
         above every supertree node, with the inputs of ``score`` and ``query_nodes`` = preorder indices of supertree
         nodes (not the root), each once.  Returns int64 arrays ``cp_trees``, ``cp_total``, ``cp_source`` (one entry
         per query) and ``cp_super``, ``cp_shared`` (queries x nodes).  ``lds_bytes`` as for ``score_placements``."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        query_nodes = np.ascontiguousarray(query_nodes, dtype=np.int32)
-        n_nodes, nq = len(parent), len(query_nodes)
-        if taxon.shape != (n_nodes,) or query_nodes.ndim != 1:
-            msg = "parent and taxon must have one entry per supertree node, query_nodes one per query clade"
-            raise ValueError(msg)
-        out = {k: np.zeros(nq, dtype=np.int64) for k in ("cp_trees", "cp_total", "cp_source")}
-        out.update({k: np.zeros((nq, n_nodes), dtype=np.int64) for k in ("cp_super", "cp_shared")})
-        rc = self._lib.scs_score_clade_placements(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                                  int(batch_trees), int(lds_bytes), nq, nv.iptr(query_nodes),
-                                                  *(nv.lptr(v) for v in out.values()))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_clade_placements: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_clade_placements", sources, parent, taxon, (batch_trees, lds_bytes),
+                                ((("cp_trees", "cp_total", "cp_source"), _Q), (("cp_super", "cp_shared"), _QN)),
+                                query_nodes, "query_nodes one per query clade")
 
     def score_clade_moves(self, sources, parent: np.ndarray, taxon: np.ndarray, query_nodes, top_k: int = 4,
                           batch_trees: int = 0, lds_bytes: int = 0) -> dict:
@@ -320,29 +245,10 @@ class Device:
         (``mv_super`` - 2 ``mv_shared``, node) ascending.  Returns int64 arrays ``cp_trees``, ``cp_total``,
         ``cp_source``, ``mv_own_super``, ``mv_own_shared`` (one entry per query), ``mv_node`` (int32) and ``mv_super``,
         ``mv_shared`` (queries x top_k; -1 and zeros where fewer candidates exist)."""
-        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
-        parent = np.ascontiguousarray(parent, dtype=np.int32)
-        taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        query_nodes = np.ascontiguousarray(query_nodes, dtype=np.int32)
-        n_nodes, nq, k = len(parent), len(query_nodes), max(int(top_k), 0)
-        if taxon.shape != (n_nodes,) or query_nodes.ndim != 1:
-            msg = "parent and taxon must have one entry per supertree node, query_nodes one per query clade"
-            raise ValueError(msg)
-        out = {k_: np.zeros(nq, dtype=np.int64)
-               for k_ in ("cp_trees", "cp_total", "cp_source", "mv_own_super", "mv_own_shared")}
-        out["mv_node"] = np.full((nq, k), -1, dtype=np.int32)
-        out.update({k_: np.zeros((nq, k), dtype=np.int64) for k_ in ("mv_super", "mv_shared")})
-        rc = self._lib.scs_score_clade_moves(self._ctx, tabs._h, n_nodes, nv.iptr(parent), nv.iptr(taxon),
-                                             int(batch_trees), int(lds_bytes), nq, nv.iptr(query_nodes), int(top_k),
-                                             *(nv.lptr(out[k_]) for k_ in ("cp_trees", "cp_total", "cp_source",
-                                                                           "mv_own_super", "mv_own_shared")),
-                                             nv.iptr(out["mv_node"]), nv.lptr(out["mv_super"]),
-                                             nv.lptr(out["mv_shared"]))
-        if rc == nv.EINVAL:
-            msg = self._lib.scs_last_error()
-            raise ValueError(msg.decode() if msg else "scs_score_clade_moves: invalid input")
-        nv.check(rc)
-        return out
+        return self._score_call("scs_score_clade_moves", sources, parent, taxon, (batch_trees, lds_bytes),
+                                ((("cp_trees", "cp_total", "cp_source", "mv_own_super", "mv_own_shared"), _Q),
+                                 (("mv_node",), _QK, np.int32, -1), (("mv_super", "mv_shared"), _QK)),
+                                query_nodes, "query_nodes one per query clade", top_k)
 
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64

@@ -29,17 +29,14 @@ The search stops when a round takes no move or after ``max_rounds``; the last tr
 from __future__ import annotations
 
 import time
-from contextlib import contextmanager
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from spectralclustersupertree_amd import score as _score
-from spectralclustersupertree_amd.flatten import flatten_trees
-from spectralclustersupertree_amd.score import (SupertreeScore, _leaf_ranges, _preorder, quartet_branches,
-                                                select_clades, supertree_arrays)
-from spectralclustersupertree_amd.tree import TreeNode, is_not_completed
-from spectralclustersupertree_amd.treearrays import TreeArrays
+from spectralclustersupertree_amd.score import (SupertreeScore, _leaf_ranges, _move_clade, _preorder,
+                                                _resident_tables, quartet_branches, select_clades, supertree_arrays)
+from spectralclustersupertree_amd.tree import TreeNode
 
 
 @dataclass
@@ -184,105 +181,8 @@ def apply_moves(tree: TreeNode, moves) -> TreeNode:
                 msg = f"an earlier move put target {target} inside the subtree of node {node}"
                 raise ValueError(msg)
             up = up.parent
-        # prune: the clade, the nodes it leaves empty, and the node it leaves with one child
-        gone = clade
-        unchanged = False
-        while gone.parent is not None and len(gone.parent.children) == 1:
-            if gone.parent is goal:
-                unchanged = True
-                break
-            gone = gone.parent
-        above = gone.parent
-        if unchanged or above is None:  # (a unary ancestor as the target; the clade holds every taxon)
-            continue
-        above.children.remove(gone)
-        clade.parent = None
-        if len(above.children) == 1:
-            (kid,) = above.children
-            replaced[id(above)] = kid
-            if goal is above:
-                goal = kid
-            if above.parent is None:
-                kid.parent = None
-                out = kid
-            else:
-                sibs = above.parent.children
-                sibs[[s is above for s in sibs].index(True)] = kid
-                kid.parent = above.parent
-        # regraft: a new node above the target, holding the target and the clade
-        up = goal.parent
-        new = TreeNode(None)
-        if up is None:
-            out = new
-        else:
-            up.children[[s is goal for s in up.children].index(True)] = new
-            new.parent = up
-        new.append(goal)
-        new.append(clade)
+        out = _move_clade(out, clade, goal, replaced)
     return out
-
-
-@contextmanager
-def _resident_tables(dev, trees, tips: list, index: dict):
-    """The source tables on the device over the ids of ``index``, through either input path of ``score_supertree``
-    and with its checks; None when no source tree has two leaves."""
-    if isinstance(trees, TreeArrays):
-        import ctypes as C
-
-        from spectralclustersupertree_amd import _native as nv
-        from spectralclustersupertree_amd.backend import DeviceForest, DeviceTables
-
-        if trees.n_trees == 0:
-            msg = "There must be at least one tree to score against."
-            raise ValueError(msg)
-        n_taxa = len(tips)
-        universe = max(trees.n_taxa, n_taxa, 1)
-        new_id = np.full(universe, -1, dtype=np.int32)
-        for x in trees.present_taxa():
-            name = trees.name(int(x))
-            if name not in index:
-                msg = f"taxon {name!r} of a source tree is not in the supertree"
-                raise ValueError(msg)
-            new_id[int(x)] = index[name]
-        m = trees.n_trees
-        forest = DeviceForest.upload(
-            dev, universe, np.ascontiguousarray(trees.node_off, dtype=np.int64),
-            np.ascontiguousarray(trees.parent, dtype=np.int32), np.ascontiguousarray(trees.taxon, dtype=np.int32),
-            np.ascontiguousarray(trees.length, dtype=np.float64), np.ascontiguousarray(trees.support, dtype=np.float64),
-            np.ones(m, dtype=np.float64), int(trees.leaf_counts().sum()))
-        try:
-            part_of = np.where(new_id >= 0, 0, -1).astype(np.int32)
-            (child,) = forest.split(part_of, new_id, [n_taxa], 0)
-        finally:
-            forest.free()
-        try:
-            if child.n_trees == 0:
-                yield None
-                return
-            handle = C.c_void_p()
-            nv.check(dev._lib.scs_tables_from_forest(dev._ctx, child._h, None, int(n_taxa), C.byref(handle)))
-            tabs = DeviceTables(dev, handle, int(n_taxa), child.n_trees)
-            try:
-                yield tabs
-            finally:
-                tabs.free()
-        finally:
-            child.free()
-        return
-    trees = [t for t in trees if not is_not_completed(t)]
-    if len(trees) == 0:
-        msg = "There must be at least one tree to score against."
-        raise ValueError(msg)
-    for tree in trees:
-        for name in tree.get_tip_names():
-            if name not in index:
-                msg = f"taxon {name!r} of a source tree is not in the supertree"
-                raise ValueError(msg)
-    tabs = dev.upload(flatten_trees(trees, [1.0] * len(trees), "one", taxa=tips))
-    try:
-        yield tabs
-    finally:
-        tabs.free()
 
 
 def _round_queries(parent, taxon, tips, tx: dict, taxa_per_round: int, clades_per_round: int,
@@ -325,7 +225,8 @@ def refine_supertree(supertree: TreeNode, trees, *, max_rounds: int = 50, clades
     rounds: list = []
     timings = {"tables": 0.0, "taxon_triplets": [], "branch_triplets": [], "clade_moves": []}
     t0 = time.perf_counter()
-    with _resident_tables(dev, trees, tips, index) as tabs:
+    with _resident_tables(dev, trees, tips, index) as src:
+        tabs = src.tabs
         timings["tables"] = time.perf_counter() - t0
         if tabs is None:  # (no source tree has two leaves: nothing to fit)
             return RefineResult(tree, 0, 0, rounds, timings)

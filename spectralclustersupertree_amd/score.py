@@ -103,10 +103,6 @@ shared(v) = shared(q) + [Σ_{children s of q} A(s) - A(q)] + X(v, q): moving x f
 v loses the pairs ab|x whose LCA is q and gains the pairs xa|b with a below v and b below q.  ``pl_super`` follows the
 same recurrence with C(|c|, 2) and |c| (|q| - |c|).  Every term is node-local, so a value is a root-path sum of marks.
 
-Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
-``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets`` and
-``scs_score_placements``; the host only validates and lays out.
-
 Clade placement support (``clade_placements=[nodes or name sets]`` or ``clade_placements=N``): the same question for a
 whole subtree.  For a non-root node q of S with leaf set Q and a node v outside its subtree, S_{q→v} is S with the
 subtree of q pruned and regrafted on the edge above v: every cluster C outside the subtree becomes (C ∖ Q) ∪ Q when it
@@ -120,14 +116,19 @@ triple changes when the clade moves):
 * ``clade_placement_distance = cp_super + cp_source - 2 cp_shared``: the part of the total triplet distance that the
   move can change, so that distance[q][v] - distance[q][q] is what moving the clade to v adds to it.
 
-For a tip q these are the ``pl_*`` of its taxon.  All of it is counted on the device by
-``scs_score_clade_placements``.
+For a tip q these are the ``pl_*`` of its taxon.
+
+Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
+``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets``,
+``scs_score_placements``, ``scs_score_clade_placements`` and (for ``refine_supertree``) ``scs_score_clade_moves``;
+the host only validates and lays out.
 """
 
 from __future__ import annotations
 
 import time
-from dataclasses import dataclass, field
+from contextlib import contextmanager
+from dataclasses import dataclass, field, fields
 
 import numpy as np
 
@@ -493,8 +494,7 @@ class SupertreeScore:
         out = []
         for i, x in enumerate(self.pl_taxa):
             node = int(own[x])
-            low = int(dist[i].min())
-            best = node if dist[i, node] == low else int(np.argmin(dist[i]))
+            best, low = _best_node(dist[i], node)
             out.append({"taxon": int(x), "name": self.taxa[x], "trees": int(self.pl_trees[i]), "node": node,
                         "distance": int(dist[i, node]), "best_node": best, "best_distance": low,
                         "improvement": int(dist[i, node]) - low})
@@ -534,35 +534,7 @@ class SupertreeScore:
         target = nodes[int(node)]
         if all(t is tip for t in target.iter_tips()):
             return out
-        # prune: the tip, the nodes it leaves empty, and the node it leaves with one child
-        gone = tip
-        while gone.parent is not None and len(gone.parent.children) == 1:
-            gone = gone.parent
-        above = gone.parent  # (not None: the target holds another taxon, so the root keeps a child)
-        above.children.remove(gone)
-        tip.parent = None
-        if len(above.children) == 1:
-            (kid,) = above.children
-            if target is above:
-                target = kid
-            if above.parent is None:
-                kid.parent = None
-                out = kid
-            else:
-                sibs = above.parent.children
-                sibs[sibs.index(above)] = kid
-                kid.parent = above.parent
-        # regraft: a new node above the target, holding the target and the tip
-        up = target.parent
-        new = TreeNode(None)
-        if up is None:
-            out = new
-        else:
-            up.children[up.children.index(target)] = new
-            new.parent = up
-        new.append(target)
-        new.append(tip)
-        return out
+        return _move_clade(out, tip, target)
 
     def _need_clade_placements(self) -> None:
         if self.cp_shared is None:
@@ -586,8 +558,7 @@ class SupertreeScore:
         out = []
         for i, q in enumerate(self.cp_nodes):
             node = int(q)
-            low = int(dist[i].min())
-            best = node if dist[i, node] == low else int(np.argmin(dist[i]))
+            best, low = _best_node(dist[i], node)
             out.append({"node": node, "tips": int(hi[node] - lo[node] + 1), "trees": int(self.cp_trees[i]),
                         "distance": int(dist[i, node]), "best_node": best, "best_distance": low,
                         "improvement": int(dist[i, node]) - low})
@@ -623,39 +594,7 @@ class SupertreeScore:
                 msg = f"target {target} lies inside the subtree of node {node}"
                 raise ValueError(msg)
             up = up.parent
-        # prune: the clade, the nodes it leaves empty, and the node it leaves with one child
-        gone = clade
-        while gone.parent is not None and len(gone.parent.children) == 1:
-            if gone.parent is goal:
-                return out
-            gone = gone.parent
-        above = gone.parent
-        if above is None:  # (the clade holds every taxon)
-            return out
-        above.children.remove(gone)
-        clade.parent = None
-        if len(above.children) == 1:
-            (kid,) = above.children
-            if goal is above:
-                goal = kid
-            if above.parent is None:
-                kid.parent = None
-                out = kid
-            else:
-                sibs = above.parent.children
-                sibs[sibs.index(above)] = kid
-                kid.parent = above.parent
-        # regraft: a new node above the target, holding the target and the clade
-        up = goal.parent
-        new = TreeNode(None)
-        if up is None:
-            out = new
-        else:
-            up.children[up.children.index(goal)] = new
-            new.parent = up
-        new.append(goal)
-        new.append(clade)
-        return out
+        return _move_clade(out, clade, goal)
 
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
@@ -723,6 +662,61 @@ def _preorder(tree: TreeNode) -> list[TreeNode]:
         out.append(node)
         stack.extend(reversed(node.children))
     return out
+
+
+def _at(children: list, node: TreeNode) -> int:
+    """The position of ``node`` itself among ``children``."""
+    return [c is node for c in children].index(True)
+
+
+def _move_clade(root: TreeNode, clade: TreeNode, goal: TreeNode, replaced: dict | None = None) -> TreeNode:
+    """Prunes the subtree of ``clade`` and regrafts it on the edge above ``goal``, in place in the tree of ``root`` (a
+    copy the caller owns; ``goal`` is not inside the clade), and returns the root, which the move may replace.  Nodes
+    are compared by identity.  The node the clade leaves behind is suppressed when it keeps one child (``replaced``,
+    when given, then maps its ``id`` to that child); when ``goal`` is that node, the clade goes above the remaining
+    child.  Nothing moves when ``goal`` holds no taxon outside the clade (a unary ancestor) or the clade holds every
+    taxon.  The new node holds ``[goal, clade]``."""
+    # prune: the clade, the nodes it leaves empty, and the node it leaves with one child
+    gone = clade
+    while gone.parent is not None and len(gone.parent.children) == 1:
+        if gone.parent is goal:
+            return root
+        gone = gone.parent
+    above = gone.parent
+    if above is None:
+        return root
+    del above.children[_at(above.children, gone)]
+    clade.parent = None
+    if len(above.children) == 1:
+        (kid,) = above.children
+        if replaced is not None:
+            replaced[id(above)] = kid
+        if goal is above:
+            goal = kid
+        kid.parent = above.parent
+        if above.parent is None:
+            root = kid
+        else:
+            sibs = above.parent.children
+            sibs[_at(sibs, above)] = kid
+    # regraft: a new node above the target, holding the target and the clade
+    up = goal.parent
+    new = TreeNode(None)
+    if up is None:
+        root = new
+    else:
+        up.children[_at(up.children, goal)] = new
+        new.parent = up
+    new.append(goal)
+    new.append(clade)
+    return root
+
+
+def _best_node(row: np.ndarray, own: int) -> tuple[int, int]:
+    """``(node, distance)`` of the best place in one row of distances: the smallest distance; among equals the query's
+    ``own`` node, else the lowest preorder index."""
+    low = int(row.min())
+    return (own if row[own] == low else int(np.argmin(row))), low
 
 
 def _leaf_ranges(parent: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
@@ -809,105 +803,22 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     index = {name: i for i, name in enumerate(tips)}
     placements = _check_placements(placements, index)
     clades = _check_clade_placements(clade_placements, parent, index, clade_max_tips)
-    taxon_triplets = taxon_triplets or isinstance(placements, int) or isinstance(clades, int)
-    if isinstance(trees, TreeArrays):
-        if trees.n_trees == 0:
-            msg = "There must be at least one tree to score against."
-            raise ValueError(msg)
-        present = trees.present_taxa()
-        new_id = np.full(max(trees.n_taxa, 1), -1, dtype=np.int32)
-        for x in present:
-            name = trees.name(int(x))
-            if name not in index:
-                msg = f"taxon {name!r} of a source tree is not in the supertree"
-                raise ValueError(msg)
-            new_id[int(x)] = index[name]
-        dev = device if device is not None else _default_device()
-        out = _score_arrays(dev, supertree, parent, taxon, len(tips), trees, new_id, triplets, conflicts,
-                            concordance, branch_triplets, taxon_triplets, tips, placements, clades, clade_max_tips)
-        out.timings["prepare"] = (time.perf_counter() - t0 - out.timings["tables"] - out.timings["score"]
-                                  - out.timings.get("triplets", 0.0) - out.timings.get("conflicts", 0.0)
-                                  - out.timings.get("concordance", 0.0) - out.timings.get("branch_triplets", 0.0)
-                                  - out.timings.get("taxon_triplets", 0.0) - out.timings.get("placements", 0.0)
-                                  - out.timings.get("clade_placements", 0.0))
-        return out
+    req = _Request(triplets, conflicts, concordance, branch_triplets,
+                   taxon_triplets or isinstance(placements, int) or isinstance(clades, int), placements, clades,
+                   clade_max_tips, tips)
+    with _resident_tables(device, trees, tips, index) as src:
+        timings = {"prepare": 0.0, "tables": src.seconds}
+        res = _run_passes(src, parent, taxon, req, timings)
+    timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
+    return _result(supertree, src.n_leaves, res, timings)
 
-    trees = [t for t in trees if not is_not_completed(t)]
-    if len(trees) == 0:
-        msg = "There must be at least one tree to score against."
-        raise ValueError(msg)
-    for tree in trees:
-        for name in tree.get_tip_names():
-            if name not in index:
-                msg = f"taxon {name!r} of a source tree is not in the supertree"
-                raise ValueError(msg)
-    tables = flatten_trees(trees, [1.0] * len(trees), "one", taxa=tips)
-    dev = device if device is not None else _default_device()
-    t1 = time.perf_counter()
-    tabs = dev.upload(tables)
-    t2 = time.perf_counter()
-    try:
-        res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-        t3 = t4 = t5 = t6 = t7 = t8 = time.perf_counter()
-        if triplets:
-            res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t4 = t5 = t6 = t7 = t8 = time.perf_counter()
-        if conflicts:
-            res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t5 = t6 = t7 = t8 = time.perf_counter()
-        if concordance:
-            res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t6 = t7 = t8 = time.perf_counter()
-        if branch_triplets:
-            res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-            t7 = t8 = time.perf_counter()
-        if taxon_triplets:
-            res.update(dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0,
-                                                lds_bytes=TAXON_LDS_BYTES or 0))
-            res["taxa"] = list(tips)
-            t8 = time.perf_counter()
-        if placements is not None:
-            res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
-            t9 = time.perf_counter()
-        if clades is not None:
-            t9c = time.perf_counter()
-            res.update(_clade_placements(dev, tabs, parent, taxon, clades, res, clade_max_tips))
-            t10 = time.perf_counter()
-    finally:
-        tabs.free()
-    timings = {"prepare": t1 - t0, "tables": t2 - t1, "score": t3 - t2}
-    if triplets:
-        timings["triplets"] = t4 - t3
-    if conflicts:
-        timings["conflicts"] = t5 - t4
-    if concordance:
-        timings["concordance"] = t6 - t5
-    if branch_triplets:
-        timings["branch_triplets"] = t7 - t6
-    if taxon_triplets:
-        timings["taxon_triplets"] = t8 - t7
-    if placements is not None:
-        timings["placements"] = t9 - t8
-    if clades is not None:
-        timings["clade_placements"] = t10 - t9c
-    return _result(supertree, np.diff(tables.tree_off), res, timings)
+
+_COUNTS = tuple(f.name for f in fields(SupertreeScore) if f.name not in ("supertree", "n_leaves", "timings"))
 
 
 def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
-    return SupertreeScore(supertree, n_leaves, res["n_super"], res["n_source"], res["shared"],
-                          res["informative"], res["supported"], timings,
-                          res.get("t_super"), res.get("t_source"), res.get("t_shared"),
-                          res.get("n_super_conflict"), res.get("n_source_conflict"), res.get("conflicting"),
-                          res.get("n_decisive"), res.get("n_concordant"), res.get("n_alternative"),
-                          res.get("decisive"), res.get("concordant"), res.get("alt1"), res.get("alt2"),
-                          res.get("n_bt_total"), res.get("n_bt_concordant"), res.get("n_bt_alternative"),
-                          res.get("bt_total"), res.get("bt_concordant"), res.get("bt_alt1"), res.get("bt_alt2"),
-                          res.get("taxa"), res.get("tx_trees"), res.get("tx_total"), res.get("tx_super"),
-                          res.get("tx_source"), res.get("tx_shared"),
-                          res.get("pl_taxa"), res.get("pl_trees"), res.get("pl_total"), res.get("pl_source"),
-                          res.get("pl_super"), res.get("pl_shared"),
-                          res.get("cp_nodes"), res.get("cp_trees"), res.get("cp_total"), res.get("cp_source"),
-                          res.get("cp_super"), res.get("cp_shared"))
+    return SupertreeScore(supertree=supertree, n_leaves=n_leaves, timings=timings,
+                          **{k: res.get(k) for k in _COUNTS})
 
 
 def _check_placements(placements, index: dict):
@@ -944,15 +855,21 @@ def _placement_queries(placements, res: dict, tips) -> np.ndarray:
     return np.array([r["taxon"] for r in view.rogue_taxa(placements)], dtype=np.int32)
 
 
-def _placements(dev, tabs, parent, taxon, placements, res: dict, tips) -> dict:
-    queries = _placement_queries(placements, res, tips)
-    out = {"pl_taxa": queries.astype(np.int64), "taxa": list(tips)}
-    if len(queries) == 0:
-        out.update({k: np.zeros(0, dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")})
-        out.update({k: np.zeros((0, len(parent)), dtype=np.int64) for k in ("pl_super", "pl_shared")})
-        return out
-    out.update(dev.score_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
-                                    lds_bytes=PLACEMENT_LDS_BYTES or 0))
+def _no_rows(prefix: str, nq: int, n_nodes: int) -> dict:
+    """The ``pl_*`` / ``cp_*`` counts of ``nq`` queries that were not sent to the device: zeros."""
+    out = {f"{prefix}_{k}": np.zeros(nq, dtype=np.int64) for k in ("trees", "total", "source")}
+    out.update({f"{prefix}_{k}": np.zeros((nq, n_nodes), dtype=np.int64) for k in ("super", "shared")})
+    return out
+
+
+def _placements(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    queries = _placement_queries(req.placements, res, req.tips)
+    out = {"pl_taxa": queries.astype(np.int64)}
+    if len(queries) == 0 or tabs is None:
+        out.update(_no_rows("pl", len(queries), len(parent)))
+    else:
+        out.update(dev.score_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
+                                        lds_bytes=PLACEMENT_LDS_BYTES or 0))
     return out
 
 
@@ -1038,15 +955,14 @@ def _clade_queries(clades, parent, res: dict, max_tips) -> np.ndarray:
     return select_clades(clades, parent, inst, res["tx_trees"], max_tips)
 
 
-def _clade_placements(dev, tabs, parent, taxon, clades, res: dict, max_tips) -> dict:
-    queries = _clade_queries(clades, parent, res, max_tips)
+def _clade_placements(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    queries = _clade_queries(req.clades, parent, res, req.clade_max_tips)
     out = {"cp_nodes": queries.astype(np.int64)}
     if len(queries) == 0 or tabs is None:
-        out.update({k: np.zeros(len(queries), dtype=np.int64) for k in ("cp_trees", "cp_total", "cp_source")})
-        out.update({k: np.zeros((len(queries), len(parent)), dtype=np.int64) for k in ("cp_super", "cp_shared")})
-        return out
-    out.update(dev.score_clade_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
-                                          lds_bytes=CLADE_PLACEMENT_LDS_BYTES or 0))
+        out.update(_no_rows("cp", len(queries), len(parent)))
+    else:
+        out.update(dev.score_clade_placements(tabs, parent, taxon, queries, batch_trees=BATCH_TREES or 0,
+                                              lds_bytes=CLADE_PLACEMENT_LDS_BYTES or 0))
     return out
 
 
@@ -1056,112 +972,178 @@ def _default_device():
     return default_device()
 
 
-def _score_arrays(dev, supertree, parent, taxon, n_taxa, arrays: TreeArrays, new_id, triplets,
-                  conflicts, concordance, branch_triplets=False, taxon_triplets=False,
-                  tips=None, placements=None, clades=None, clade_max_tips=64) -> SupertreeScore:
-    """Source tables built on the device: the forest is uploaded and restricted to all of its taxa in one part
-    (``scs_forest_split``), which renumbers them to the supertree's ids and flattens every tree in HBM."""
-    import ctypes as C
+@dataclass
+class _Sources:
+    """What ``_resident_tables`` yields: the device, the source tables on it (None when no source tree has two
+    leaves), the leaf count of every source tree as given, the wall seconds the tables took and, for a ``TreeArrays``
+    input, the split forest the tables were made from."""
 
-    from spectralclustersupertree_amd import _native as nv
-    from spectralclustersupertree_amd.backend import DeviceForest, DeviceTables
+    dev: object
+    tabs: object
+    n_leaves: np.ndarray
+    seconds: float
+    forest: object = None
 
-    t0 = time.perf_counter()
-    m = arrays.n_trees
-    n_leaves = arrays.leaf_counts().astype(np.int64)
-    n_nodes = len(parent)
-    per_tree = ("n_super", "n_source", "shared") + (("t_super", "t_source", "t_shared") if triplets else ())
-    per_tree += ("n_super_conflict", "n_source_conflict") if conflicts else ()
-    per_tree += ("n_decisive", "n_concordant", "n_alternative") if concordance else ()
-    per_node = ("informative", "supported") + (("conflicting",) if conflicts else ())
-    per_node += ("decisive", "concordant", "alt1", "alt2") if concordance else ()
-    per_tree += ("n_bt_total", "n_bt_concordant", "n_bt_alternative") if branch_triplets else ()
-    per_node += ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2") if branch_triplets else ()
-    zeros = {k: np.zeros(m, dtype=np.int64) for k in per_tree}
-    node0 = {k: np.zeros(n_nodes, dtype=np.int64) for k in per_node}
-    if taxon_triplets:  # (per supertree tip)
-        node0.update({k: np.zeros(n_taxa, dtype=np.int64)
-                      for k in ("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")})
-    # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
-    universe = max(arrays.n_taxa, n_taxa, 1)
-    new_id = np.concatenate([new_id, np.full(universe - len(new_id), -1, dtype=np.int32)])
-    forest = DeviceForest.upload(
-        dev, universe, np.ascontiguousarray(arrays.node_off, dtype=np.int64),
-        np.ascontiguousarray(arrays.parent, dtype=np.int32), np.ascontiguousarray(arrays.taxon, dtype=np.int32),
-        np.ascontiguousarray(arrays.length, dtype=np.float64), np.ascontiguousarray(arrays.support, dtype=np.float64),
-        np.ones(m, dtype=np.float64), int(n_leaves.sum()))
-    try:
-        part_of = np.where(new_id >= 0, 0, -1).astype(np.int32)
-        (child,) = forest.split(part_of, new_id, [n_taxa], 0)
-    finally:
-        forest.free()
-    try:
-        t1 = t2 = t3 = t4 = t5 = t6 = t7 = t7p = t8 = t8c = t9 = time.perf_counter()
-        if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
-            res = {**zeros, **node0}
-            if placements is not None:
-                queries = _placement_queries(placements, res, tips)
-                res["pl_taxa"] = queries.astype(np.int64)
-                res.update({k: np.zeros(len(queries), dtype=np.int64) for k in ("pl_trees", "pl_total", "pl_source")})
-                res.update({k: np.zeros((len(queries), n_nodes), dtype=np.int64) for k in ("pl_super", "pl_shared")})
-            if clades is not None:
-                res.update(_clade_placements(dev, None, parent, taxon, clades, res, clade_max_tips))
-        else:
+    def tree_index(self) -> np.ndarray | None:
+        """``TreeArrays`` input: the given tree behind every tree of the tables (trees of fewer than two leaves have
+        none).  None for tree objects, whose tables hold every tree in its place."""
+        return None if self.forest is None else np.array(self.forest.tables()[4], dtype=np.int64)
+
+
+@contextmanager
+def _resident_tables(device, trees, tips: list, index: dict):
+    """The source tables on the device over the taxon ids of ``index`` (name -> id; ``tips`` = the names by id), for
+    either input of ``score_supertree`` and with its checks, which come before the first device call (``device``
+    None: the process's device, asked for after them).  A ``TreeArrays`` forest is uploaded and restricted to all of
+    its taxa in one part (``scs_forest_split``), which renumbers them to the ids of ``index`` and flattens every tree
+    in HBM.  Yields a ``_Sources``; the tables are freed on the way out."""
+    if isinstance(trees, TreeArrays):
+        import ctypes as C
+
+        from spectralclustersupertree_amd import _native as nv
+        from spectralclustersupertree_amd.backend import DeviceForest, DeviceTables
+
+        if trees.n_trees == 0:
+            msg = "There must be at least one tree to score against."
+            raise ValueError(msg)
+        n_taxa = len(tips)
+        # (the forest's id range is widened to the supertree's: the split's parts may not hold more taxa than it)
+        universe = max(trees.n_taxa, n_taxa, 1)
+        new_id = np.full(universe, -1, dtype=np.int32)
+        for x in trees.present_taxa():
+            name = trees.name(int(x))
+            if name not in index:
+                msg = f"taxon {name!r} of a source tree is not in the supertree"
+                raise ValueError(msg)
+            new_id[int(x)] = index[name]
+        dev = device if device is not None else _default_device()
+        t0 = time.perf_counter()
+        n_leaves = trees.leaf_counts().astype(np.int64)
+        forest = DeviceForest.upload(
+            dev, universe, np.ascontiguousarray(trees.node_off, dtype=np.int64),
+            np.ascontiguousarray(trees.parent, dtype=np.int32), np.ascontiguousarray(trees.taxon, dtype=np.int32),
+            np.ascontiguousarray(trees.length, dtype=np.float64), np.ascontiguousarray(trees.support, dtype=np.float64),
+            np.ones(trees.n_trees, dtype=np.float64), int(n_leaves.sum()))
+        try:
+            part_of = np.where(new_id >= 0, 0, -1).astype(np.int32)
+            (child,) = forest.split(part_of, new_id, [n_taxa], 0)
+        finally:
+            forest.free()
+        try:
+            if child.n_trees == 0:  # (every tree has fewer than two leaves: nothing to count)
+                yield _Sources(dev, None, n_leaves, time.perf_counter() - t0)
+                return
             handle = C.c_void_p()
             nv.check(dev._lib.scs_tables_from_forest(dev._ctx, child._h, None, int(n_taxa), C.byref(handle)))
             tabs = DeviceTables(dev, handle, int(n_taxa), child.n_trees)
-            t1 = time.perf_counter()
             try:
-                res = dev.score(tabs, parent, taxon, batch_trees=BATCH_TREES or 0)
-                t2 = t3 = t4 = t5 = t6 = t7 = time.perf_counter()
-                if triplets:
-                    res.update(dev.score_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t3 = t4 = t5 = t6 = t7 = time.perf_counter()
-                if conflicts:
-                    res.update(dev.score_conflicts(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t4 = t5 = t6 = t7 = time.perf_counter()
-                if concordance:
-                    res.update(dev.score_concordance(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t5 = t6 = t7 = time.perf_counter()
-                if branch_triplets:
-                    res.update(dev.score_branch_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0))
-                    t6 = t7 = time.perf_counter()
-                if taxon_triplets:
-                    res.update(dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0,
-                                                        lds_bytes=TAXON_LDS_BYTES or 0))
-                    t7 = t8 = time.perf_counter()
-                if placements is not None:
-                    t7p = time.perf_counter()
-                    res.update(_placements(dev, tabs, parent, taxon, placements, res, tips))
-                    t8 = time.perf_counter()
-                if clades is not None:
-                    t8c = time.perf_counter()
-                    res.update(_clade_placements(dev, tabs, parent, taxon, clades, res, clade_max_tips))
-                    t9 = time.perf_counter()
+                yield _Sources(dev, tabs, n_leaves, time.perf_counter() - t0, child)
             finally:
                 tabs.free()
-            tree_index = np.array(child.tables()[4], dtype=np.int64)
-            for k in per_tree:
-                full = zeros[k]
-                full[tree_index] = res[k]
-                res[k] = full
+        finally:
+            child.free()
+        return
+    trees = [t for t in trees if not is_not_completed(t)]
+    if len(trees) == 0:
+        msg = "There must be at least one tree to score against."
+        raise ValueError(msg)
+    for tree in trees:
+        for name in tree.get_tip_names():
+            if name not in index:
+                msg = f"taxon {name!r} of a source tree is not in the supertree"
+                raise ValueError(msg)
+    tables = flatten_trees(trees, [1.0] * len(trees), "one", taxa=tips)
+    dev = device if device is not None else _default_device()
+    t0 = time.perf_counter()
+    tabs = dev.upload(tables)
+    try:
+        yield _Sources(dev, tabs, np.diff(tables.tree_off), time.perf_counter() - t0)
     finally:
-        child.free()
-    timings = {"tables": t1 - t0, "score": t2 - t1}
-    if triplets:
-        timings["triplets"] = t3 - t2
-    if conflicts:
-        timings["conflicts"] = t4 - t3
-    if concordance:
-        timings["concordance"] = t5 - t4
-    if branch_triplets:
-        timings["branch_triplets"] = t6 - t5
-    if taxon_triplets:
-        timings["taxon_triplets"] = t7 - t6
-        res["taxa"] = list(tips)
-    if placements is not None:
-        timings["placements"] = t8 - t7p
-        res["taxa"] = list(tips)
-    if clades is not None:
-        timings["clade_placements"] = t9 - t8c
-    return _result(supertree, n_leaves, res, timings)
+        tabs.free()
+
+
+@dataclass(frozen=True)
+class _Request:
+    """What one ``score_supertree`` call asks for, after its checks (``placements`` / ``clades``: None, a count or
+    the query ids; ``tips``: the supertree's tip names by taxon id)."""
+
+    triplets: bool
+    conflicts: bool
+    concordance: bool
+    branch_triplets: bool
+    taxon_triplets: bool
+    placements: object
+    clades: object
+    clade_max_tips: int
+    tips: list
+
+
+@dataclass(frozen=True)
+class _Pass:
+    """One scoring pass: its key in ``timings``, whether a request wants it, the call ``(dev, tabs, parent, taxon,
+    res, req) -> dict`` (``res``: what the passes before it returned) and the names of its outputs with one entry per
+    source tree, per supertree node and per supertree tip.  A pass with ``queries`` picks its queries from ``res`` and
+    has one row per query; it is also called without tables (``tabs`` None) and then fills its rows with zeros."""
+
+    key: str
+    wanted: object
+    run: object
+    per_tree: tuple = ()
+    per_node: tuple = ()
+    per_tip: tuple = ()
+    queries: bool = False
+
+
+def _on_tables(method: str):
+    """The pass that is the ``Device`` method of that name and nothing else."""
+    return lambda dev, tabs, parent, taxon, res, req: getattr(dev, method)(tabs, parent, taxon,
+                                                                           batch_trees=BATCH_TREES or 0)
+
+
+def _taxon_triplets(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    return dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0, lds_bytes=TAXON_LDS_BYTES or 0)
+
+
+# in call order (the query passes read the per-taxon counts)
+_PASSES = (
+    _Pass("score", lambda req: True, _on_tables("score"),
+          ("n_super", "n_source", "shared"), ("informative", "supported")),
+    _Pass("triplets", lambda req: req.triplets, _on_tables("score_triplets"), ("t_super", "t_source", "t_shared")),
+    _Pass("conflicts", lambda req: req.conflicts, _on_tables("score_conflicts"),
+          ("n_super_conflict", "n_source_conflict"), ("conflicting",)),
+    _Pass("concordance", lambda req: req.concordance, _on_tables("score_concordance"),
+          ("n_decisive", "n_concordant", "n_alternative"), ("decisive", "concordant", "alt1", "alt2")),
+    _Pass("branch_triplets", lambda req: req.branch_triplets, _on_tables("score_branch_triplets"),
+          ("n_bt_total", "n_bt_concordant", "n_bt_alternative"), ("bt_total", "bt_concordant", "bt_alt1", "bt_alt2")),
+    _Pass("taxon_triplets", lambda req: req.taxon_triplets, _taxon_triplets,
+          per_tip=("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")),
+    _Pass("placements", lambda req: req.placements is not None, _placements, queries=True),
+    _Pass("clade_placements", lambda req: req.clades is not None, _clade_placements, queries=True),
+)
+
+
+def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> dict:
+    """Runs the passes ``req`` wants on the tables of ``src`` and times each into ``timings``.  Counts per source tree
+    go back to the places of the trees as given (``src.tree_index``); without tables every output is zeros."""
+    m = len(src.n_leaves)
+    tree_index = None if src.tabs is None else src.tree_index()
+    res: dict = {}
+    for p in _PASSES:
+        if not p.wanted(req):
+            continue
+        t = time.perf_counter()
+        if src.tabs is not None or p.queries:
+            out = p.run(src.dev, src.tabs, parent, taxon, res, req)
+        else:
+            sized = ((p.per_tree, m), (p.per_node, len(parent)), (p.per_tip, len(req.tips)))
+            out = {k: np.zeros(n, dtype=np.int64) for names, n in sized for k in names}
+        timings[p.key] = time.perf_counter() - t
+        if tree_index is not None:
+            for k in p.per_tree:
+                full = np.zeros(m, dtype=np.int64)
+                full[tree_index] = out[k]
+                out[k] = full
+        res.update(out)
+    if req.taxon_triplets or req.placements is not None:
+        res["taxa"] = list(req.tips)
+    return res

@@ -12,7 +12,8 @@ from spectralclustersupertree_amd import score as score_mod
 from spectralclustersupertree_amd.backend import Device
 from spectralclustersupertree_amd.cli import scs
 from spectralclustersupertree_amd.load import load_tree_arrays
-from spectralclustersupertree_amd.tree import load_tree, make_tree
+from spectralclustersupertree_amd.tree import TreeNode, load_tree, make_tree
+from spectralclustersupertree_amd.treearrays import TreeArrays
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +87,34 @@ def test_tree_arrays_and_tree_objects_score_alike(dev):
     b = score_supertree(sup, objects, device=dev)
     for k in (*KEYS, "n_leaves"):
         assert np.array_equal(getattr(a, k), getattr(b, k)), k
+
+
+def test_tree_arrays_without_a_tree_of_two_leaves_score_zero(dev):
+    """No source tree has two leaves, so no tables exist: every requested output is there, zero-filled, and the
+    counted queries (the least stable taxa and clades of all-zero counts) are none."""
+    sup = make_tree("((a,b),(c,d));")
+    names = ["a", "b", "c", "d"]
+    arrays = TreeArrays.from_trees([make_tree("(a);"), TreeNode("c"), make_tree("((d));")], [1.0] * 3, names)
+    res = score_supertree(sup, arrays, triplets=True, conflicts=True, concordance=True, branch_triplets=True,
+                          taxon_triplets=True, placements=2, clade_placements=1, device=dev)
+    zero = lambda *shape: np.zeros(shape, dtype=np.int64)  # noqa: E731
+    want = {"n_leaves": np.ones(3, dtype=np.int64), "pl_taxa": zero(0), "cp_nodes": zero(0)}
+    want.update({k: zero(3) for k in (
+        "n_super", "n_source", "shared", "t_super", "t_source", "t_shared", "n_super_conflict", "n_source_conflict",
+        "n_decisive", "n_concordant", "n_alternative", "n_bt_total", "n_bt_concordant", "n_bt_alternative")})
+    want.update({k: zero(7) for k in ("informative", "supported", "conflicting", "decisive", "concordant", "alt1",
+                                      "alt2", "bt_total", "bt_concordant", "bt_alt1", "bt_alt2")})
+    want.update({k: zero(4) for k in ("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")})
+    want.update({k: zero(0) for k in ("pl_trees", "pl_total", "pl_source", "cp_trees", "cp_total", "cp_source")})
+    want.update({k: zero(0, 7) for k in ("pl_super", "pl_shared", "cp_super", "cp_shared")})
+    for k, v in want.items():
+        got = getattr(res, k)
+        assert got.dtype == np.int64 and got.shape == v.shape and np.array_equal(got, v), (k, got)
+    assert res.taxa == names
+    assert set(res.timings) == {"prepare", "tables", "score", "triplets", "conflicts", "concordance",
+                                "branch_triplets", "taxon_triplets", "placements", "clade_placements"}
+    assert res.total_rf == 0 and res.total_triplet_distance == 0
+    assert res.best_placements() == [] and res.best_clade_placements() == []
 
 
 def test_compatible_sources_score_zero(dev):

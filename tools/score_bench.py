@@ -34,7 +34,7 @@ import numpy as np  # noqa: E402
 from spectralclustersupertree_amd import refine_supertree, score_supertree, synthetic  # noqa: E402
 from spectralclustersupertree_amd import refine as refine_mod  # noqa: E402
 from spectralclustersupertree_amd.backend import Device  # noqa: E402
-from spectralclustersupertree_amd.score import _leaf_ranges, select_clades, supertree_arrays  # noqa: E402
+from spectralclustersupertree_amd.score import _leaf_ranges, _resident_tables, select_clades, supertree_arrays  # noqa: E402
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
 from spectralclustersupertree_amd.treearrays import TreeArrays  # noqa: E402
 
@@ -274,7 +274,8 @@ def run_refine(dev: Device, size: str, planted: int = 20, repeats: int = 5) -> d
     tip_nodes = np.flatnonzero(taxon >= 0)
     sets = {"64_clades": sc.cp_nodes.astype(np.int32),
             "1500_tips": tip_nodes[np.linspace(0, len(tip_nodes) - 1, num=min(1500, len(tip_nodes)), dtype=np.int64)]}
-    with refine_mod._resident_tables(dev, arrays, tips, index) as tabs:
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
         for name, nodes in sets.items():
             for what, call in (("placements", lambda n=nodes: dev.score_clade_placements(tabs, parent, taxon, n)),
                                ("moves", lambda n=nodes: dev.score_clade_moves(tabs, parent, taxon, n, top_k=4))):
