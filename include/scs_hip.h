@@ -476,6 +476,30 @@ int scs_score_clade_moves(scs_ctx *ctx, const scs_tables *sources, int32_t n_nod
                           int64_t *cp_source, int64_t *mv_own_super, int64_t *mv_own_shared, int32_t *mv_node,
                           int64_t *mv_super, int64_t *mv_shared);
 
+/* Supertree polytomies, with the inputs and SCS_EINVAL cases of scs_score_branch_triplets:
+ * what the sources say about grouping the children of an unresolved node.  query_nodes: n_queries preorder indices of
+ * nodes of S with k = 3 to 64 children c_0 .. c_{k-1} (child order; the root may be one).  For a source tree T on the
+ * leaf set L, colour i is C_i' = cl(c_i) & L; T is decisive when at least three colours are non-empty.  Per query q:
+ *   py_degree[q] = k (int32),   py_trees[q] = the decisive sources,
+ *   py_total / py_joint: one dense block of k^3 int64 per query, the blocks one after the other in query order (block
+ *   q starts at the sum of the earlier queries' k^3); entry [(i k + j) k + l] is filled for i < j and l not in
+ *   {i, j}, zero elsewhere.  Over the decisive sources:
+ *   py_total[i][j][l] = sum |C_i'| |C_j'| |C_l'|: the triples (a in C_i, b in C_j, d in C_l), all fans in S,
+ *   py_joint[i][j][l] = those of them T resolves ab|d.
+ * Merging the groups G and H of a partition of the children under a new node (a third group remaining) lowers the
+ * summed triplet distance by exactly 2 M(G, H) - N(G, H), M and N the sums of py_joint and py_total over i in G,
+ * j in H (ordered so that i < j), l in neither.  Counts are unweighted and exact; output pointers may be null.
+ * SCS_EINVAL, before any kernel runs, as well for: a query that is no node, has fewer than 3 or more than 64 children
+ * or is given twice; the k rows of the largest source tree (m leaves) not fitting a workgroup's LDS,
+ * 8 k ceil(m / 32) bytes > 160 KiB (218 432 leaves at k = 3, 10 240 at k = 64) or > max_lds_bytes when that is
+ * positive; the tensors not fitting the call's workspace, 16 sum k^3 bytes > 1.5 GB; sum (m_t / 3)^3 not fitting
+ * int64.  max_lds_bytes > 0 caps the LDS a workgroup of the sweep takes (tests: where the k^2 sums do not fit beside
+ * the rows, the sweep adds straight onto the output); 0: the default, all a workgroup can take. */
+int scs_score_polytomies(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                         const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
+                         const int32_t *query_nodes, int32_t *py_degree, int64_t *py_trees, int64_t *py_total,
+                         int64_t *py_joint);
+
 /* ---- proper cluster graph ---------------------------------------------- */
 
 /* Build rows [row_begin, row_end) of the N x N fp64 weight matrix W on the

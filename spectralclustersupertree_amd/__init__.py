@@ -2,14 +2,16 @@
 
 Public API mirrors the reference package (reference: src/sc_supertree/__init__.py:6-9):
 ``construct_supertree`` and ``load_trees``; ``score_supertree`` (RF distances to the sources, clade
-support) and ``refine_supertree`` (a hill-climb on the triplet distance) are this package's own.
+support), ``refine_supertree`` (a hill-climb on the triplet distance) and ``resolve_polytomies`` (the
+supertree's polytomies resolved from the sources' triples) are this package's own.
 """
 
 from spectralclustersupertree_amd.load import load_trees
 from spectralclustersupertree_amd.scs import construct_supertree
 from spectralclustersupertree_amd.score import SupertreeScore, score_supertree
 from spectralclustersupertree_amd.refine import RefineResult, apply_moves, refine_supertree  # noqa: I001
+from spectralclustersupertree_amd.resolve import ResolveResult, resolve_polytomies  # noqa: I001
 
-__all__ = ["RefineResult", "SupertreeScore", "apply_moves", "construct_supertree", "load_trees", "refine_supertree",
-           "score_supertree"]
+__all__ = ["RefineResult", "ResolveResult", "SupertreeScore", "apply_moves", "construct_supertree", "load_trees",
+           "refine_supertree", "resolve_polytomies", "score_supertree"]
 __version__ = "0.1.0"

@@ -131,17 +131,17 @@ class Device:
 
     # -- scoring a supertree ----------------------------------------------------
     def _score_call(self, export: str, sources, parent, taxon, ints, outputs, queries=None, noun: str = "",
-                    top_k=None) -> dict:
+                    top_k=None, sizes=None) -> dict:
         """One ``scs_score_*`` export.  ``sources`` are uploaded when they are ``TreeTables``; ``parent`` / ``taxon``
         (and ``queries``, which ``noun`` names in the shape message) travel as int32.  The export takes the context,
         the tables, the supertree, ``ints``, then the query count and ``queries``, then ``top_k``, then one buffer per
         output.  ``outputs``: ``(names, dims[, dtype, fill])`` entries with ``dims`` out of ``m`` (source trees),
-        ``n_nodes``, ``n_tips``, ``nq`` and ``top_k``; int64 zeros unless said otherwise.  Returns name -> array in
-        that order; SCS_EINVAL becomes ``ValueError`` with the library's message."""
+        ``n_nodes``, ``n_tips``, ``nq``, ``top_k`` and the keys of ``sizes``; int64 zeros unless said otherwise.
+        Returns name -> array in that order; SCS_EINVAL becomes ``ValueError`` with the library's message."""
         tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
         parent = np.ascontiguousarray(parent, dtype=np.int32)
         taxon = np.ascontiguousarray(taxon, dtype=np.int32)
-        size = {"m": tabs.n_trees, "n_nodes": len(parent)}
+        size = {"m": tabs.n_trees, "n_nodes": len(parent), **(sizes or {})}
         args = [int(x) for x in ints]
         ok, msg = taxon.shape == (len(parent),), "parent and taxon must have one entry per supertree node"
         if queries is not None:
@@ -249,6 +249,28 @@ class Device:
                                 ((("cp_trees", "cp_total", "cp_source", "mv_own_super", "mv_own_shared"), _Q),
                                  (("mv_node",), _QK, np.int32, -1), (("mv_super", "mv_shared"), _QK)),
                                 query_nodes, "query_nodes one per query clade", top_k)
+
+    def score_polytomies(self, sources, parent: np.ndarray, taxon: np.ndarray, query_nodes, batch_trees: int = 0,
+                         lds_bytes: int = 0) -> dict:
+        """``scs_score_polytomies``: what the sources say about grouping the children of every query node, with the
+        inputs of ``score`` and ``query_nodes`` = preorder indices of supertree nodes with 3 to 64 children, each once.
+        Returns ``py_degree`` (int32) and ``py_trees`` (int64), one entry per query, and ``py_total``, ``py_joint``:
+        lists with one int64 array k x k x k per query, entry [i][j][l] filled for i < j and l not in {i, j}.
+        ``lds_bytes`` > 0 caps the LDS one workgroup of the sweep takes (tests)."""
+        par = np.asarray(parent, dtype=np.int64)
+        kids = np.bincount(par[1:], minlength=len(par)) if len(par) > 1 else np.zeros(len(par), dtype=np.int64)
+        q = np.asarray(query_nodes, dtype=np.int64)
+        ok = q.ndim == 1 and bool(np.all((q >= 0) & (q < len(par))))
+        # (an out-of-range query has no size: one cell, and the library names the query in its message)
+        cubes = kids[q] ** 3 if ok else np.ones(q.size, dtype=np.int64)
+        out = self._score_call("scs_score_polytomies", sources, parent, taxon, (batch_trees, lds_bytes),
+                               ((("py_degree",), _Q, np.int32, 0), (("py_trees",), _Q), (("py_total", "py_joint"), ("k3",))),
+                               query_nodes, "query_nodes one per polytomy", sizes={"k3": int(cubes.sum())})
+        ends = np.cumsum(cubes)
+        for name in ("py_total", "py_joint"):
+            out[name] = [out[name][e - c:e].reshape(int(k), int(k), int(k))
+                         for e, c, k in zip(ends, cubes, out["py_degree"])]
+        return out
 
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64

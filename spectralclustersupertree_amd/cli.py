@@ -85,6 +85,17 @@ from spectralclustersupertree_amd import __version__
 @click.option("--refine-log", default=None,
               help="With --refined-out: a TSV with one row per move (round, kind, node, target, tips, gain, "
                    "distance_after).")
+@click.option("--polytomies-out", default=None,
+              help="Also write a TSV with one row per polytomy of the supertree and pair of its children (node, i, j, "
+                   "tips, total, joint, gain): what the sources' rooted triples say about grouping the two.")
+@click.option("--resolved-out", default=None,
+              help="Also resolve the supertree's polytomies by greedy pairwise merges that lower its rooted triplet "
+                   "distance to the source trees (resolve_polytomies) and write the resolved tree here; -o and every "
+                   "other output keep describing the constructed tree.")
+@click.option("--resolve-min-gain", default=1, type=int, show_default=True,
+              help="The least gain in triplet distance a merge of --resolved-out must have.")
+@click.option("--resolve-polytomies", "resolve_first", default=False, is_flag=True,
+              help="With --refined-out: resolve the polytomies before the first round (refine_supertree(resolve=True)).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
@@ -92,8 +103,13 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         branch_triplets_out: str | None = None, taxon_triplets: bool = False,
         taxa_out: str | None = None, placements_out: str | None = None, place_taxa: int = 10,
         clade_placements_out: str | None = None, place_clades: int = 10, clade_max_tips: int = 64,
-        refined_out: str | None = None, refine_rounds: int = 50, refine_log: str | None = None) -> None:
+        refined_out: str | None = None, refine_rounds: int = 50, refine_log: str | None = None,
+        polytomies_out: str | None = None, resolved_out: str | None = None, resolve_min_gain: int = 1,
+        resolve_first: bool = False) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
+    if resolve_first and not refined_out:
+        msg = "--resolve-polytomies needs --refined-out"
+        raise click.UsageError(msg)
     if refine_log and not refined_out:
         msg = "--refine-log needs --refined-out"
         raise click.UsageError(msg)
@@ -126,7 +142,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
         if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
-                or taxa_out or placements_out or clade_placements_out):
+                or taxa_out or placements_out or clade_placements_out or polytomies_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
@@ -137,7 +153,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                                      taxon_triplets=taxa_out is not None,
                                      placements=place_taxa if placements_out else None,
                                      clade_placements=place_clades if clade_placements_out else None,
-                                     clade_max_tips=clade_max_tips)
+                                     clade_max_tips=clade_max_tips, polytomies=True if polytomies_out else None)
+            if polytomies_out:
+                Path(polytomies_out).write_text(result.polytomy_table())
             if clade_placements_out:
                 Path(clade_placements_out).write_text(result.clade_placement_table())
             if placements_out:
@@ -161,10 +179,16 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                     result.annotate_concordance().get_newick(with_node_names=True) + "\n")
             if branches_out:
                 Path(branches_out).write_text(result.branch_table())
+        if resolved_out:
+            from spectralclustersupertree_amd.resolve import resolve_polytomies
+
+            resolve_polytomies(supertree, load_tree_arrays(in_file),
+                               min_gain=resolve_min_gain).supertree.write(resolved_out)
         if refined_out:
             from spectralclustersupertree_amd.refine import refine_supertree
 
-            refined = refine_supertree(supertree, load_tree_arrays(in_file), max_rounds=refine_rounds)
+            refined = refine_supertree(supertree, load_tree_arrays(in_file), max_rounds=refine_rounds,
+                                       resolve=resolve_first)
             refined.supertree.write(refined_out)
             if refine_log:
                 Path(refine_log).write_text(refined.table())

@@ -3776,3 +3776,398 @@ extern "C" int scs_score_clade_moves(scs_ctx *ctx, const scs_tables *src, int32_
                          n_queries, query_nodes, top_k, cp_trees, cp_total, cp_source, nullptr, nullptr, mv_own_super,
                          mv_own_shared, mv_node, mv_super, mv_shared);
 }
+
+// ---- supertree polytomies (scs_score_polytomies) ----
+//
+// A polytomy p of S with children c_0 .. c_{k-1} (k >= 3) colours the leaves of a source tree T: colour i is
+// C_i' = cl(c_i) ∩ L(T), a stretch of S' indices (the children of p are contiguous in S's leaf order).  T is decisive
+// when three colours or more are not empty.  For i < j and l not in {i, j}, over the decisive trees:
+//   py_total[i][j][l] = sum_T |C_i'| |C_j'| |C_l'|
+//   py_joint[i][j][l] = sum_T sum_y I(y,C_i') I(y,C_j') (I(py,C_l') - I(y,C_l'))     (the node sum of section 18)
+//   k_py_records: one thread per gap lists T's non-root nodes {lo, hi + 1, parent lo, parent hi + 1} (k_bt_records'
+//     T half); k_py_colours: one thread per (tree, query) finds the k + 1 colour boundaries in S' order, says whether
+//     the tree is decisive and counts it in py_trees; k_py_total: one thread per output entry sums the batch's sizes.
+//   k_py_sweep, the hot path: one workgroup per (tree, query, colour i).  The k colours become bitset rows over T
+//     positions in LDS ({bits, prefix}, as k_bt_pairs); a wave takes a node y with lane = colour: lane c holds
+//     h[c] = I(y,C_c') and d[c] = I(py,C_c') - h[c] from four reads of its own row, a ballot names the colours j > i
+//     present in y, and for each of them lane l adds h[i] h[j] d[l] onto accumulator [j][l] -- 64-bit atomics, in LDS
+//     where k^2 sums fit beside the rows (one flush of the non-zero ones at the end), else straight onto the output.
+
+namespace {
+
+constexpr int PY_KMAX = 64;  // children of a query node: one lane each
+
+struct sc_py_rec_args {
+    const int64_t *off;         // tree_off + t0
+    int nb;
+    const int32_t *adj, *amin;  // T's min table of adj_depth (as in sc_nodes_args)
+    int levels;
+    int64_t Lb;
+    int4 *ylist;                // [Lb] T's nodes of a tree from its first leaf on
+    int32_t *ycnt;              // [nb] list lengths
+};
+
+// one thread per gap: T's non-root internal node that starts here (as k_bt_records lists it)
+__global__ void __launch_bounds__(SC_THREADS) k_py_records(sc_py_rec_args a) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t p = a.off[0] + q;
+    const bool in = p < a.off[a.nb];
+    const int t = in ? sc_tree_of(a.off, a.nb, p) : a.nb - 1;
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int64_t k = q - base;
+    int4 ny = make_int4(0, 0, 0, 0);
+    bool t_node = false;
+    if (in && k + 1 < n) {
+        const int32_t d = a.adj[q];
+        const int64_t lo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, k, d, false);
+        if (lo == 0 || a.adj[base + lo - 1] < d) {
+            const int64_t hi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, k + 1, n - 1, d);
+            if (lo > 0 || hi < n - 1) {  // (not the root)
+                const int64_t g = lo == 0 ? hi
+                                  : hi == n - 1 ? lo - 1
+                                  : (a.adj[base + lo - 1] >= a.adj[base + hi] ? lo - 1 : hi);
+                const int32_t dg = a.adj[base + g];
+                const int64_t plo = sc_stretch_left(a.adj, a.amin, a.Lb, a.levels, base, g, dg, true);
+                const int64_t phi = sc_stretch_right(a.adj, a.amin, a.Lb, a.levels, base, g + 1, n - 1, dg);
+                t_node = true;
+                ny = make_int4((int)lo, (int)hi + 1, (int)plo, (int)phi + 1);
+            }
+        }
+    }
+    const int iy = sc_append(a.ycnt, t, t_node);
+    if (iy >= 0) a.ylist[base + iy] = ny;
+}
+
+// what the colour, total and sweep kernels share: query q has k = coff[q + 1] - coff[q] - 1 children, its k + 1
+// boundaries (S positions: the first leaf of every child, then one past the node's last) at bnd[coff[q] ...], the same
+// slots in a tree's row of cidx (S' indices), and its k^3 output entries at ooff[q]
+struct sc_py_args {
+    const int64_t *off;       // tree_off + t0
+    int nb, nq, totb;         // trees of the batch, queries, boundaries of all queries
+    const int32_t *sp;        // [Lb] S positions in S order
+    const int32_t *coff;      // [nq + 1]
+    const int64_t *ooff;      // [nq + 1]
+    const int32_t *bnd;       // [totb]
+    int32_t *cidx;            // [nb][totb]
+    int32_t *dec;             // [nb][nq] 1: the tree is decisive at the query
+    unsigned long long *trees, *total, *joint;  // py_trees [nq], py_total / py_joint [ooff[nq]]
+    // the sweep alone: the queries of one degree k, T's node lists, tp, the words of a row and its stride in LDS
+    const int32_t *gq;
+    int ngq, k, W, Ws, acc_lds;
+    const int4 *ylist;
+    const int32_t *ycnt;
+    const int2 *tp;
+};
+
+// one thread per (tree, query): the colour boundaries in the tree's S' order; decisive trees counted
+__global__ void __launch_bounds__(SC_THREADS) k_py_colours(sc_py_args a) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)a.nb * a.nq) return;
+    const int t = (int)(idx / a.nq), q = (int)(idx % a.nq);
+    const int64_t base = a.off[t] - a.off[0];
+    const int64_t n = a.off[t + 1] - a.off[t];
+    const int32_t c0 = a.coff[q], k = a.coff[q + 1] - c0 - 1;
+    int32_t *cx = a.cidx + (int64_t)t * a.totb + c0;
+    int32_t prev = 0, present = 0;
+    for (int i = 0; i <= k; ++i) {
+        const int32_t c = (int32_t)sc_first_ge(a.sp + base, 0, n, a.bnd[c0 + i]);
+        cx[i] = c;
+        if (i > 0 && c > prev) ++present;
+        prev = c;
+    }
+    const int32_t dec = present >= 3;
+    a.dec[idx] = dec;
+    if (dec) atomicAdd(a.trees + q, 1ull);
+}
+
+// one thread per output entry [i][j][l] with i < j, l not in {i, j}: the batch's decisive trees' |C_i'| |C_j'| |C_l'|
+// (one thread owns the entry and the batches follow each other on the stream: a plain add)
+__global__ void __launch_bounds__(SC_THREADS) k_py_total(sc_py_args a) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.ooff[a.nq]) return;
+    const int q = sc_tree_of(a.ooff, a.nq, e);
+    const int32_t c0 = a.coff[q], k = a.coff[q + 1] - c0 - 1;
+    const int64_t r = e - a.ooff[q];
+    const int l = (int)(r % k), j = (int)(r / k % k), i = (int)(r / ((int64_t)k * k));
+    if (!(i < j && l != i && l != j)) return;
+    unsigned long long sum = 0;
+    for (int t = 0; t < a.nb; ++t) {
+        if (!a.dec[(int64_t)t * a.nq + q]) continue;
+        const int32_t *cx = a.cidx + (int64_t)t * a.totb + c0;
+        sum += (unsigned long long)((int64_t)(cx[i + 1] - cx[i]) * (cx[j + 1] - cx[j]) * (cx[l + 1] - cx[l]));
+    }
+    if (sum) a.total[e] += sum;
+}
+
+// set bits of a bitset row at the T positions below x: the word of position x - 1 and the bits up to it (a row of
+// ceil(n / 32) words answers every x <= n)
+__device__ __forceinline__ int py_count(const int2 *row, int x) {
+    if (x == 0) return 0;
+    const int2 r = row[(x - 1) >> 5];
+    return r.y + __popc((unsigned)r.x & (0xffffffffu >> (31 - ((x - 1) & 31))));
+}
+
+// the hot path: workgroup (x, y) = (query of the degree and colour i, tree of the chunk at a.off)
+__global__ void __launch_bounds__(SC_THREADS) k_py_sweep(sc_py_args a) {
+    extern __shared__ __attribute__((aligned(16))) int2 rows[];  // [k][Ws], then k^2 sums when acc_lds
+    const int k = a.k, Ws = a.Ws;
+    const int t = blockIdx.y;
+    const int q = a.gq[blockIdx.x / (k - 1)], ci = (int)(blockIdx.x % (k - 1));
+    if (!a.dec[(int64_t)t * a.nq + q]) return;
+    const int32_t *cx = a.cidx + (int64_t)t * a.totb + a.coff[q];
+    // every term has the factors I(y, C_i') and I(y, C_j') of a j > i
+    if (cx[ci + 1] == cx[ci] || cx[k] == cx[ci + 1]) return;
+    const int64_t base = a.off[t] - a.off[0];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(rows + k * Ws);
+    for (int i = threadIdx.x; i < k * Ws; i += SC_THREADS) rows[i] = make_int2(0, 0);
+    if (a.acc_lds)
+        for (int i = threadIdx.x; i < k * k; i += SC_THREADS) acc[i] = 0;
+    __syncthreads();
+    unsigned *bits = reinterpret_cast<unsigned *>(rows);  // (word i of the image: .x of entry i / 2)
+    for (int c = wave; c < k; c += SC_THREADS / 64)
+        for (int s = cx[c] + lane; s < cx[c + 1]; s += 64) {
+            const int x = a.tp[base + s].x;
+            atomicOr(bits + 2 * (c * Ws + (x >> 5)), 1u << (x & 31));
+        }
+    __syncthreads();
+    // every word's .y = set bits in the words before it: one wave per row, wave64 scans of 64 words
+    for (int r = wave; r < k; r += SC_THREADS / 64) {
+        int2 *row = rows + r * Ws;
+        int run = 0;
+        for (int c = 0; c < a.W; c += 64) {
+            const int i = c + lane;
+            const int v = i < a.W ? __popc((unsigned)row[i].x) : 0;
+            int incl = v;
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += y;
+            }
+            if (i < a.W) row[i].y = run + incl - v;
+            run += __shfl(incl, 63, 64);
+        }
+    }
+    __syncthreads();
+    unsigned long long *out = a.joint + a.ooff[q] + (int64_t)ci * k * k;  // entries [ci][j][l] at j * k + l
+    const bool mine = lane < k;
+    const int2 *row = rows + (mine ? lane : 0) * Ws, *row_i = rows + ci * Ws;
+    const int ny = a.ycnt[t];
+    for (int iy = wave; iy < ny; iy += SC_THREADS / 64) {
+        const int4 y = a.ylist[base + iy];  // T positions [y.x, y.y) of y, [y.z, y.w) of py
+        const int hi = py_count(row_i, y.y) - py_count(row_i, y.x);  // (the same for every lane)
+        if (hi == 0) continue;
+        int h = 0, d = 0;
+        if (mine) {
+            h = py_count(row, y.y) - py_count(row, y.x);
+            d = py_count(row, y.w) - py_count(row, y.z) - h;
+        }
+        unsigned long long mj = __ballot(h > 0) & ~((2ull << ci) - 1ull);
+        const bool third = d != 0 && lane != ci;
+        if (mj == 0 || !__any(third)) continue;
+        while (mj) {
+            const int j = __ffsll((long long)mj) - 1;
+            mj &= mj - 1;
+            const int hj = __shfl(h, j, 64);
+            if (third && lane != j) {
+                const unsigned long long v = (unsigned long long)((int64_t)hi * hj * d);
+                if (a.acc_lds) atomicAdd(acc + j * k + lane, v);
+                else atomicAdd(out + j * k + lane, v);
+            }
+        }
+    }
+    if (!a.acc_lds) return;
+    __syncthreads();
+    for (int i = threadIdx.x; i < k * k; i += SC_THREADS) {
+        const unsigned long long v = acc[i];
+        if (v) atomicAdd(out + i, v);
+    }
+}
+
+}  // namespace
+
+extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                    const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                    int32_t n_queries, const int32_t *query_nodes, int32_t *py_degree,
+                                    int64_t *py_trees, int64_t *py_total, int64_t *py_joint) {
+    const char *const who = "scs_score_polytomies";
+    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    SCS_REQUIRE(max_lds_bytes >= 0, "%s: max_lds_bytes = %d is negative", who, max_lds_bytes);
+    SCS_REQUIRE(n_queries >= 1 && query_nodes, "%s: no query node", who);
+    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    // the query nodes: nodes, each once, 3 to PY_KMAX children; their children in child order
+    const size_t nq = (size_t)n_queries;
+    std::vector<int32_t> coff(nq + 1, 0), kid_of;  // kid_of: the children of query i at coff[i] - i ...
+    std::vector<int64_t> ooff(nq + 1, 0);
+    int k_max = 0;
+    if (parent && taxon && n_nodes >= 1) {
+        std::vector<int32_t> n_kids((size_t)n_nodes, 0), slot((size_t)n_nodes, -1);
+        for (int32_t v = 1; v < n_nodes; ++v)
+            if (parent[v] >= 0 && parent[v] < v) n_kids[parent[v]]++;
+        for (size_t i = 0; i < nq; ++i) {
+            const int32_t q = query_nodes[i];
+            SCS_REQUIRE(q >= 0 && q < n_nodes, "%s: query node %d is not in [0, %d)", who, q, n_nodes);
+            SCS_REQUIRE(slot[q] < 0, "%s: query node %d is given twice", who, q);
+            const int32_t k = n_kids[q];
+            SCS_REQUIRE(k >= 3, "%s: query node %d has %d children, fewer than the 3 of a polytomy", who, q, k);
+            SCS_REQUIRE(k <= PY_KMAX, "%s: query node %d has %d children, more than the %d the sweep has lanes for",
+                        who, q, k, PY_KMAX);
+            slot[q] = (int32_t)i;
+            coff[i + 1] = coff[i] + k + 1;
+            ooff[i + 1] = ooff[i] + (int64_t)k * k * k;
+            k_max = std::max(k_max, (int)k);
+        }
+        kid_of.assign((size_t)coff[nq], -1);
+        std::vector<int32_t> fill(nq, 0);
+        for (int32_t v = 1; v < n_nodes; ++v)
+            if (parent[v] >= 0 && parent[v] < v && slot[parent[v]] >= 0) {
+                const int32_t i = slot[parent[v]];
+                kid_of[coff[i] + fill[i]++] = v;
+            }
+    }
+    const int64_t w_max = std::max<int64_t>((m_max + 31) >> 5, 1);
+    SCS_REQUIRE((int64_t)k_max * w_max * 8 <= lds_cap,
+                "%s: the %d rows of a source tree of %lld leaves take %lld bytes, more than the %d of a workgroup's "
+                "LDS%s", who, k_max, (long long)m_max, (long long)k_max * w_max * 8, lds_cap,
+                max_lds_bytes > 0 ? " (max_lds_bytes)" : "");
+    SCS_REQUIRE((uint64_t)ooff[nq] * 16 <= SC_BUDGET,
+                "%s: the tensors of %d query nodes need %llu bytes, more than the %llu of the call's workspace", who,
+                n_queries, (unsigned long long)ooff[nq] * 16, (unsigned long long)SC_BUDGET);
+    // an entry is at most sum_t (m_t / 3)^3: it must fit int64
+    if (src) {
+        unsigned __int128 cubes = 0;
+        for (int32_t t = 0; t < src->n_trees; ++t) {
+            const unsigned __int128 m = (unsigned __int128)(src->h_tree_off[t + 1] - src->h_tree_off[t]);
+            cubes += m * m * m;
+        }
+        SCS_REQUIRE(cubes / 27 <= (unsigned __int128)INT64_MAX,
+                    "%s: the triple counts of %d source trees may not fit 64 bits", who, src->n_trees);
+    }
+    // own arrays: the two tensors, py_trees, the offsets, the boundaries and the queries by degree; per batch T's node
+    // list (int4) per leaf, its length per tree, and per tree the boundaries in S' order and the decisive flags
+    const size_t totb = (size_t)coff[nq], n_out = (size_t)ooff[nq];
+    const size_t o_total = 0, o_joint = o_total + sc_up256(n_out * 8), o_trees = o_joint + sc_up256(n_out * 8),
+                 o_coff = o_trees + sc_up256(nq * 8), o_ooff = o_coff + sc_up256((nq + 1) * 4),
+                 o_bnd = o_ooff + sc_up256((nq + 1) * 8), o_gq = o_bnd + sc_up256(totb * 4),
+                 own = o_gq + sc_up256(nq * 4);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 16, 4 + 4 * (totb + nq), c, e));
+    const std::vector<int64_t> &off = src->h_tree_off;
+    hipStream_t s = ctx->stream;
+    auto *d_total = (unsigned long long *)(c.d_extra + o_total);
+    auto *d_joint = (unsigned long long *)(c.d_extra + o_joint);
+    auto *d_trees = (unsigned long long *)(c.d_extra + o_trees);
+    auto *d_coff = (int32_t *)(c.d_extra + o_coff);
+    auto *d_ooff = (int64_t *)(c.d_extra + o_ooff);
+    auto *d_bnd = (int32_t *)(c.d_extra + o_bnd);
+    auto *d_gq = (int32_t *)(c.d_extra + o_gq);
+    const size_t n_batches = c.bstart.size() - 1;
+    int64_t max_rows = 0;
+    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
+    auto *d_ylist = (int4 *)c.d_extra_batch;
+    auto *d_ycnt = (int32_t *)(d_ylist + c.max_lb);
+    auto *d_cidx = d_ycnt + max_rows;
+    auto *d_dec = d_cidx + max_rows * (int64_t)totb;
+    // the boundaries (S positions, sc_begin's leaf ranges) and the queries grouped by degree
+    std::vector<int32_t> bnd(totb), gq(nq), g_first(PY_KMAX + 2, 0);
+    for (size_t i = 0; i < nq; ++i) {
+        const int32_t k = coff[i + 1] - coff[i] - 1;
+        for (int32_t j = 0; j < k; ++j) bnd[coff[i] + j] = c.s_lo[kid_of[coff[i] + j]];
+        bnd[coff[i] + k] = c.s_hi[query_nodes[i]] + 1;
+        if (py_degree) py_degree[i] = k;
+        g_first[k + 1]++;
+    }
+    for (int k = 0; k <= PY_KMAX; ++k) g_first[k + 1] += g_first[k];
+    {
+        std::vector<int32_t> at(g_first.begin(), g_first.end() - 1);
+        for (size_t i = 0; i < nq; ++i) gq[at[coff[i + 1] - coff[i] - 1]++] = (int32_t)i;
+    }
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, o_coff, s);  // (both tensors and py_trees)
+    if (e == hipSuccess) e = hipMemcpyAsync(d_coff, coff.data(), (nq + 1) * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ooff, ooff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_bnd, bnd.data(), totb * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_gq, gq.data(), nq * 4, hipMemcpyHostToDevice, s);
+    // (the attribute is per function and device: set on every call)
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_py_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 4, s);
+        if (e != hipSuccess) break;
+        sc_py_rec_args r;
+        r.off = src->d_tree_off + t0;
+        r.nb = nb;
+        r.adj = src->d_adj_depth + L0;
+        r.amin = c.d_amin;
+        r.levels = c.levels;
+        r.Lb = Lb;
+        r.ylist = d_ylist;
+        r.ycnt = d_ycnt;
+        k_py_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(r);
+        if (!sc_launched(e)) break;
+        sc_py_args a;
+        a.off = r.off;
+        a.nb = nb;
+        a.nq = n_queries;
+        a.totb = (int)totb;
+        a.sp = c.d_sp;
+        a.coff = d_coff;
+        a.ooff = d_ooff;
+        a.bnd = d_bnd;
+        a.cidx = d_cidx;
+        a.dec = d_dec;
+        a.trees = d_trees;
+        a.total = d_total;
+        a.joint = d_joint;
+        a.gq = d_gq;
+        a.ngq = a.k = a.W = a.Ws = a.acc_lds = 0;
+        a.ylist = d_ylist;
+        a.ycnt = d_ycnt;
+        a.tp = c.d_mm;
+        k_py_colours<<<grid_of((int64_t)nb * n_queries), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        k_py_total<<<grid_of((int64_t)n_out), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        // the sweep, one launch per degree (and chunk of 65535 trees): W words per row; the rows' stride is odd where
+        // that fits (lane = row: an even stride puts the lanes' reads on few banks); the sums in LDS where they fit
+        int64_t nmax = 0;
+        for (int32_t t = t0; t < t0 + nb; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        a.W = (int)std::max<int64_t>((nmax + 31) >> 5, 1);
+        for (int k = 3; k <= PY_KMAX && e == hipSuccess; ++k) {
+            const int ng = g_first[k + 1] - g_first[k];
+            if (ng == 0) continue;
+            const int64_t accb = (int64_t)k * k * 8, odd = a.W | 1;
+            const bool acc_odd = k * odd * 8 + accb <= lds_cap, acc_even = (int64_t)k * a.W * 8 + accb <= lds_cap;
+            a.acc_lds = acc_odd || acc_even;
+            a.Ws = (a.acc_lds ? acc_odd : k * odd * 8 <= lds_cap) ? (int)odd : a.W;
+            a.k = k;
+            a.gq = d_gq + g_first[k];
+            a.ngq = ng;
+            const size_t lds = (size_t)k * a.Ws * 8 + (a.acc_lds ? (size_t)accb : 0);
+            for (int32_t ty = 0; ty < nb && e == hipSuccess; ty += 65535) {
+                sc_py_args ac = a;
+                ac.off = a.off + ty;
+                ac.cidx = d_cidx + (int64_t)ty * (int64_t)totb;
+                ac.dec = d_dec + (int64_t)ty * n_queries;
+                ac.ycnt = d_ycnt + ty;
+                // (lists and tp are indexed from the batch's first leaf: off[t] - off[0] of the chunk's own off)
+                const int64_t shift = off[t0 + ty] - L0;
+                ac.ylist = d_ylist + shift;
+                ac.tp = c.d_mm + shift;
+                k_py_sweep<<<dim3((unsigned)(ng * (k - 1)), (unsigned)std::min<int32_t>(nb - ty, 65535)), SC_THREADS,
+                             lds, s>>>(ac);
+                sc_launched(e);
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && py_trees) e = hipMemcpyAsync(py_trees, d_trees, nq * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && py_total) e = hipMemcpyAsync(py_total, d_total, n_out * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && py_joint) e = hipMemcpyAsync(py_joint, d_joint, n_out * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    return SCS_OK;
+}

@@ -24,6 +24,11 @@ positions of the input supertree and do not move with the edits):
 5. ``apply_moves``; the prediction is D - Σ gains.
 
 The search stops when a round takes no move or after ``max_rounds``; the last tree is scored once more by step 1.
+
+With ``resolve=True`` the polytomies of the start tree are resolved first (``resolve.agglomerate`` on one
+``scs_score_polytomies`` call) and recorded as a round 0 whose moves have ``kind`` "resolve",
+``node`` = ``target`` = the polytomy and ``groups``; round 1 then scores the resolved tree and holds the resolution to
+its prediction like any other round.
 """
 
 from __future__ import annotations
@@ -206,12 +211,13 @@ def _round_queries(parent, taxon, tips, tx: dict, taxa_per_round: int, clades_pe
 
 def refine_supertree(supertree: TreeNode, trees, *, max_rounds: int = 50, clades_per_round: int = 64,
                      taxa_per_round: int = 64, clade_max_tips: int = 64, top_k: int = 4, nni: bool = True,
-                     device=None) -> RefineResult:
+                     resolve: bool = False, device=None) -> RefineResult:
     """Lowers the summed rooted triplet distance of ``supertree`` to ``trees`` by rounds of prune-and-regraft moves
     with disjoint footprints (module docstring) until a round finds none or ``max_rounds`` have run.  ``trees`` as for
     ``score_supertree`` (either input path, the same ``ValueError``s, weights ignored).  ``taxa_per_round`` tips and
     ``clades_per_round`` clades of up to ``clade_max_tips`` tips are queried per round, ``top_k`` (1 to 8) targets
-    each; ``nni`` adds the nearest-neighbour interchanges of every quartet branch.  The input tree is not modified."""
+    each; ``nni`` adds the nearest-neighbour interchanges of every quartet branch; ``resolve`` resolves the polytomies
+    of the start tree before the first round (module docstring).  The input tree is not modified."""
     if max_rounds < 0 or clades_per_round < 0 or taxa_per_round < 0 or clade_max_tips < 2 or not 1 <= top_k <= 8:
         msg = (f"max_rounds = {max_rounds}, clades_per_round = {clades_per_round} or taxa_per_round = "
                f"{taxa_per_round} is negative, clade_max_tips = {clade_max_tips} is under 2 or top_k = {top_k} is "
@@ -224,6 +230,8 @@ def refine_supertree(supertree: TreeNode, trees, *, max_rounds: int = 50, clades
     tree = supertree.copy()
     rounds: list = []
     timings = {"tables": 0.0, "taxon_triplets": [], "branch_triplets": [], "clade_moves": []}
+    if resolve:
+        timings["polytomies"] = []
     t0 = time.perf_counter()
     with _resident_tables(dev, trees, tips, index) as src:
         tabs = src.tabs
@@ -242,6 +250,25 @@ def refine_supertree(supertree: TreeNode, trees, *, max_rounds: int = 50, clades
 
         predicted = None
         initial = final = None
+        if resolve:
+            from spectralclustersupertree_amd.resolve import resolve_from_tensors
+
+            t_round = time.perf_counter()
+            parent, taxon = tree_arrays_with_ids(tree, index)
+            _, initial = distance(parent, taxon)
+            sent, _ = _score.polytomy_queries(parent, True, _score.PY_MAX_DEGREE, int(np.max(src.n_leaves)),
+                                              _score.POLYTOMY_LDS_BYTES or 0)
+            moves = []
+            if len(sent):
+                t = time.perf_counter()
+                py = dev.score_polytomies(tabs, parent, taxon, sent, batch_trees=batch,
+                                          lds_bytes=_score.POLYTOMY_LDS_BYTES or 0)
+                timings["polytomies"].append(time.perf_counter() - t)
+                done = resolve_from_tensors(tree, sent, py["py_total"], py["py_joint"], [], initial)
+                tree, predicted = done.supertree, done.predicted_distance
+                moves = [{"kind": "resolve", "node": m["node"], "target": m["node"], "gain": m["gain"],
+                          "tips": m["tips"], "groups": m["groups"]} for m in done.merges]
+            rounds.append({"distance": initial, "moves": moves, "seconds": time.perf_counter() - t_round})
         for r in range(max_rounds + 1):
             t_round = time.perf_counter()
             parent, taxon = tree_arrays_with_ids(tree, index)

@@ -118,17 +118,29 @@ triple changes when the clade moves):
 
 For a tip q these are the ``pl_*`` of its taxon.
 
+Polytomy support (``polytomies=True`` or ``polytomies=[nodes or name sets]``): what the sources say about grouping the
+children c_0 .. c_{k-1} of a node with three or more of them, where every count above is blind.  Per polytomy
+(``py_nodes``), over the sources T on L that hold leaves of at least three children (``py_trees``), with
+C_i' = cl(c_i) ∩ L, for i < j and l not in {i, j}:
+
+* ``py_total[q][i][j][l]`` = Σ |C_i'| |C_j'| |C_l'|: the triples with a leaf below c_i, c_j and c_l, all fans in S;
+* ``py_joint[q][i][j][l]`` = those of them T resolves with the leaves of c_i and c_j together.
+
+Two groups G and H of children put under one new node lower the summed triplet distance by exactly 2 M - N, M and N
+the sums of ``py_joint`` and ``py_total`` over i in G, j in H and l in neither (``polytomy_merge_gain``;
+``resolve.resolve_polytomies`` builds a whole resolution on it).
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
 ``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets``,
-``scs_score_placements``, ``scs_score_clade_placements`` and (for ``refine_supertree``) ``scs_score_clade_moves``;
-the host only validates and lays out.
+``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies`` and (for ``refine_supertree``)
+``scs_score_clade_moves``; the host only validates and lays out.
 """
 
 from __future__ import annotations
 
 import time
 from contextlib import contextmanager
-from dataclasses import dataclass, field, fields
+from dataclasses import dataclass, field, fields, replace
 
 import numpy as np
 
@@ -145,6 +157,8 @@ TAXON_LDS_BYTES: int | None = None
 PLACEMENT_LDS_BYTES: int | None = None
 # and for the clade placement pair kernel
 CLADE_PLACEMENT_LDS_BYTES: int | None = None
+# and for the polytomy sweep (a small value: no room for the k x k sums beside the rows, or none for the rows)
+POLYTOMY_LDS_BYTES: int | None = None
 
 
 @dataclass
@@ -163,7 +177,8 @@ class SupertreeScore:
     # "triplets" (scs_score_triplets, when requested), "conflicts" (scs_score_conflicts, when requested),
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
     # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested), "placements" (scs_score_placements,
-    # when requested), "clade_placements" (scs_score_clade_placements, when requested)
+    # when requested), "clade_placements" (scs_score_clade_placements, when requested), "polytomies"
+    # (scs_score_polytomies, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -596,6 +611,83 @@ class SupertreeScore:
             up = up.parent
         return _move_clade(out, clade, goal)
 
+    # polytomy support (``polytomies=...``; None otherwise), kept beside the dataclass fields: a dict with the keys
+    # of ``_PY_KEYS``, read through the properties below
+    _py = None
+
+    @property
+    def py_nodes(self) -> np.ndarray | None:
+        """The polytomies that were scored (preorder indices), one entry per query."""
+        return None if self._py is None else self._py["py_nodes"]
+
+    @property
+    def py_degree(self) -> np.ndarray | None:
+        """Their numbers of children."""
+        return None if self._py is None else self._py["py_degree"]
+
+    @property
+    def py_trees(self) -> np.ndarray | None:
+        """The sources with three or more of a polytomy's children among their leaves (decisive)."""
+        return None if self._py is None else self._py["py_trees"]
+
+    @property
+    def py_total(self) -> list | None:
+        """Per polytomy a k x k x k array: [i][j][l], i < j, l not in {i, j}: the triples with a leaf below child i,
+        one below child j and one below child l, over the decisive sources."""
+        return None if self._py is None else self._py["py_total"]
+
+    @property
+    def py_joint(self) -> list | None:
+        """Those of ``py_total`` the source resolves with the leaves of i and j together."""
+        return None if self._py is None else self._py["py_joint"]
+
+    @property
+    def py_skipped(self) -> list | None:
+        """The polytomies that were not scored: dicts with ``node``, ``degree`` and ``reason``."""
+        return None if self._py is None else self._py["py_skipped"]
+
+    def _need_polytomies(self) -> None:
+        if self._py is None:
+            msg = "polytomy counts were not computed: score_supertree(..., polytomies=True)"
+            raise ValueError(msg)
+
+    def polytomy_merge_gain(self, q: int, G, H) -> int:
+        """What the summed triplet distance falls by when the children ``G`` and ``H`` (two disjoint, non-empty
+        lists of child positions that leave a child out) of polytomy ``q`` (a position in ``py_nodes``) go under one
+        new node: 2 M(G, H) - N(G, H)."""
+        self._need_polytomies()
+        from spectralclustersupertree_amd.resolve import merge_gain
+
+        return merge_gain(self.py_total[q], self.py_joint[q], G, H)
+
+    def polytomy_table(self) -> str:
+        """One TSV row per polytomy and pair of its children: node (preorder index), i, j (child positions), tips
+        (below the two children), total and joint (the triples with a leaf below each of the two and one below a third
+        child, and those the sources resolve with the two together), gain (of merging just that pair)."""
+        self._need_polytomies()
+        parent = np.asarray(self.supertree.to_flat()[0], dtype=np.int64)
+        lo, hi = _leaf_ranges(parent)
+        rows = ["node\ti\tj\ttips\ttotal\tjoint\tgain"]
+        for q, node in enumerate(self.py_nodes):
+            kids = np.flatnonzero(parent == node)
+            size = hi[kids] - lo[kids] + 1
+            total, joint = self.py_total[q].sum(axis=2), self.py_joint[q].sum(axis=2)
+            for i in range(len(kids)):
+                for j in range(i + 1, len(kids)):
+                    rows.append(f"{node}\t{i}\t{j}\t{size[i] + size[j]}\t{total[i, j]}\t{joint[i, j]}"
+                                f"\t{2 * joint[i, j] - total[i, j]}")
+        return "\n".join(rows) + "\n"
+
+    def resolve_polytomies(self, min_gain: int = 1):
+        """The greedy resolution of the scored polytomies from the tensors held here (``resolve.ResolveResult``; no
+        device call).  ``initial_distance`` / ``predicted_distance`` are None unless the triplet terms were computed."""
+        self._need_polytomies()
+        from spectralclustersupertree_amd.resolve import resolve_from_tensors
+
+        initial = self.total_triplet_distance if self.t_shared is not None else None
+        return resolve_from_tensors(self.supertree, self.py_nodes, self.py_total, self.py_joint, self.py_skipped,
+                                    initial, min_gain)
+
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
         concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
@@ -770,8 +862,8 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
                     concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
-                    placements=None, clade_placements=None, clade_max_tips: int = 64,
-                    device=None) -> SupertreeScore:
+                    placements=None, clade_placements=None, clade_max_tips: int = 64, polytomies=None,
+                    polytomy_max_degree: int = 64, device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
@@ -789,7 +881,13 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     ``select_clades`` from the per-taxon counts (this implies ``taxon_triplets=True``; ``clade_max_tips`` bounds
     their size): the clade placement support of those nodes (``cp_nodes``, ``cp_trees``, ``cp_total``, ``cp_source``
     per query, ``cp_super``, ``cp_shared`` per query and supertree node).  ``ValueError`` for the root, a node out of
-    range or given twice, or names that are no node's cluster.
+    range or given twice, or names that are no node's cluster.  ``polytomies``: True for every node with three or more
+    children, or a list whose items are preorder node indices or iterables of tip names that are exactly the cluster
+    of such a node: what the sources say about grouping the children (``py_nodes``, ``py_degree``, ``py_trees`` per
+    polytomy, ``py_total``, ``py_joint`` one k x k x k array each; ``polytomy_table``, ``polytomy_merge_gain``,
+    ``resolve_polytomies``).  Polytomies of more than ``polytomy_max_degree`` (at most 64) children, or whose rows of
+    the largest source do not fit a workgroup's LDS, are not scored and listed in ``py_skipped``.  ``ValueError`` for
+    a node with fewer than three children, out of range or given twice.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -805,7 +903,8 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     clades = _check_clade_placements(clade_placements, parent, index, clade_max_tips)
     req = _Request(triplets, conflicts, concordance, branch_triplets,
                    taxon_triplets or isinstance(placements, int) or isinstance(clades, int), placements, clades,
-                   clade_max_tips, tips)
+                   clade_max_tips, tips, _check_polytomies(polytomies, parent, index, polytomy_max_degree),
+                   int(polytomy_max_degree))
     with _resident_tables(device, trees, tips, index) as src:
         timings = {"prepare": 0.0, "tables": src.seconds}
         res = _run_passes(src, parent, taxon, req, timings)
@@ -816,9 +915,15 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
 _COUNTS = tuple(f.name for f in fields(SupertreeScore) if f.name not in ("supertree", "n_leaves", "timings"))
 
 
+_PY_KEYS = ("py_nodes", "py_degree", "py_trees", "py_total", "py_joint", "py_skipped")
+
+
 def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
-    return SupertreeScore(supertree=supertree, n_leaves=n_leaves, timings=timings,
-                          **{k: res.get(k) for k in _COUNTS})
+    out = SupertreeScore(supertree=supertree, n_leaves=n_leaves, timings=timings,
+                         **{k: res.get(k) for k in _COUNTS})
+    if "py_nodes" in res:
+        out._py = {k: res[k] for k in _PY_KEYS}
+    return out
 
 
 def _check_placements(placements, index: dict):
@@ -966,6 +1071,96 @@ def _clade_placements(dev, tabs, parent, taxon, res: dict, req) -> dict:
     return out
 
 
+PY_MAX_DEGREE = 64        # children of a polytomy the sweep has lanes for
+PY_LDS_BYTES = 160 << 10  # all the LDS a workgroup can take
+
+
+def _check_polytomies(polytomies, parent: np.ndarray, index: dict, max_degree):
+    """``None``, True or the query nodes (preorder indices) of ``score_supertree``'s ``polytomies``."""
+    if polytomies is None or polytomies is False:
+        return None
+    if not 3 <= int(max_degree) <= PY_MAX_DEGREE:
+        msg = f"polytomy_max_degree = {max_degree} is not in [3, {PY_MAX_DEGREE}]"
+        raise ValueError(msg)
+    if polytomies is True:
+        return True
+    if isinstance(polytomies, (str, int, np.integer)):
+        msg = "polytomies must be True or a list of nodes or name sets"
+        raise ValueError(msg)
+    kids = np.bincount(parent[1:], minlength=len(parent)) if len(parent) > 1 else np.zeros(len(parent), dtype=int)
+    lo, hi = _leaf_ranges(parent.astype(np.int64))
+    by_range: dict = {}
+    for v in range(len(parent)):  # (of a chain of unary nodes the lowest can have the children)
+        by_range[(int(lo[v]), int(hi[v]))] = v
+    nodes = []
+    for item in polytomies:
+        if isinstance(item, (int, np.integer)) and not isinstance(item, bool):
+            if not 0 <= int(item) < len(parent):
+                msg = f"polytomy node {item} is not in [0, {len(parent)})"
+                raise ValueError(msg)
+            node = int(item)
+        else:
+            names = [item] if isinstance(item, str) else list(item)
+            ids = set()
+            for name in names:
+                if name not in index:
+                    msg = f"polytomy taxon {name!r} is not in the supertree"
+                    raise ValueError(msg)
+                ids.add(index[name])
+            key = (min(ids), max(ids)) if ids else None
+            if key is None or len(ids) != len(names) or key[1] - key[0] + 1 != len(ids) or key not in by_range:
+                msg = f"the names {sorted(names)!r} are not exactly one node's cluster"
+                raise ValueError(msg)
+            node = by_range[key]
+        if kids[node] < 3:
+            msg = f"node {node} has {kids[node]} children: not a polytomy"
+            raise ValueError(msg)
+        nodes.append(node)
+    if len(set(nodes)) != len(nodes):
+        msg = "a polytomy node is given more than once"
+        raise ValueError(msg)
+    return np.array(nodes, dtype=np.int32)
+
+
+def polytomy_queries(parent, nodes, max_degree: int, max_leaves: int, lds_bytes: int = 0):
+    """``(sent, skipped)``: of the polytomies ``nodes`` (True: every node of ``parent`` with three or more children)
+    those ``scs_score_polytomies`` takes, and dicts ``node``, ``degree``, ``reason`` for those over ``max_degree``
+    children or whose k rows of a source of ``max_leaves`` leaves, 8 k ceil(max_leaves / 32) bytes, do not fit a
+    workgroup's LDS (``lds_bytes`` > 0: that many bytes)."""
+    parent = np.asarray(parent, dtype=np.int64)
+    kids = np.bincount(parent[1:], minlength=len(parent)) if len(parent) > 1 else np.zeros(len(parent), dtype=int)
+    if nodes is True:
+        nodes = np.flatnonzero(kids >= 3)
+    cap = min(int(lds_bytes), PY_LDS_BYTES) if lds_bytes and lds_bytes > 0 else PY_LDS_BYTES
+    words = max((int(max_leaves) + 31) // 32, 1)
+    sent, skipped = [], []
+    for v in np.asarray(nodes, dtype=np.int64):
+        k = int(kids[v])
+        if k > max_degree:
+            skipped.append({"node": int(v), "degree": k, "reason": f"more than {max_degree} children"})
+        elif 8 * k * words > cap:
+            skipped.append({"node": int(v), "degree": k,
+                            "reason": f"{k} rows of a source of {int(max_leaves)} leaves take {8 * k * words} bytes "
+                                      f"of LDS, more than {cap}"})
+        else:
+            sent.append(int(v))
+    return np.array(sent, dtype=np.int32), skipped
+
+
+def _polytomies(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    lds = POLYTOMY_LDS_BYTES or 0
+    sent, skipped = polytomy_queries(parent, req.polytomies, req.polytomy_max_degree, req.max_leaves, lds)
+    out = {"py_nodes": sent.astype(np.int64), "py_skipped": skipped}
+    if len(sent) == 0 or tabs is None:
+        kids = np.bincount(np.asarray(parent[1:], dtype=np.int64), minlength=len(parent))[sent]
+        out.update({"py_degree": kids.astype(np.int32), "py_trees": np.zeros(len(sent), dtype=np.int64),
+                    "py_total": [np.zeros((k, k, k), dtype=np.int64) for k in kids],
+                    "py_joint": [np.zeros((k, k, k), dtype=np.int64) for k in kids]})
+    else:
+        out.update(dev.score_polytomies(tabs, parent, taxon, sent, batch_trees=BATCH_TREES or 0, lds_bytes=lds))
+    return out
+
+
 def _default_device():
     from spectralclustersupertree_amd.scs import default_device
 
@@ -1076,6 +1271,9 @@ class _Request:
     clades: object
     clade_max_tips: int
     tips: list
+    polytomies: object = None       # None, True or the query nodes
+    polytomy_max_degree: int = 64
+    max_leaves: int = 0             # of the largest source tree (set by ``_run_passes``)
 
 
 @dataclass(frozen=True)
@@ -1119,6 +1317,7 @@ _PASSES = (
           per_tip=("tx_trees", "tx_total", "tx_super", "tx_source", "tx_shared")),
     _Pass("placements", lambda req: req.placements is not None, _placements, queries=True),
     _Pass("clade_placements", lambda req: req.clades is not None, _clade_placements, queries=True),
+    _Pass("polytomies", lambda req: req.polytomies is not None, _polytomies, queries=True),
 )
 
 
@@ -1127,6 +1326,7 @@ def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> d
     go back to the places of the trees as given (``src.tree_index``); without tables every output is zeros."""
     m = len(src.n_leaves)
     tree_index = None if src.tabs is None else src.tree_index()
+    req = replace(req, max_leaves=int(np.max(src.n_leaves)) if m else 0)
     res: dict = {}
     for p in _PASSES:
         if not p.wanted(req):

@@ -15,6 +15,9 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --large-clade        # the same for one clade: the first child of the root's first child
     python tools/score_bench.py --refine --size 10000x500   # refine_supertree on a model tree with 20 planted regrafts
                                                      # against restrictions of the model
+    python tools/score_bench.py --polytomies --size 10000x500   # scs_score_polytomies on a supertree with collapsed
+                                                     # edges (degrees 3, 8, 32; --collapse N nodes of each) beside one
+                                                     # scs_score_triplets call
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -288,6 +291,96 @@ def run_refine(dev: Device, size: str, planted: int = 20, repeats: int = 5) -> d
     return out
 
 
+def collapse_to_degrees(tree: TreeNode, degrees, per_degree: int, seed: int) -> TreeNode:
+    """A copy of the binary ``tree`` in which, for every k of ``degrees``, ``per_degree`` disjoint inner nodes with at
+    least 2 k tips below have the children of their largest inner children pulled up until they hold k children."""
+    out = tree.copy()
+    rs = np.random.RandomState(seed)
+    nodes = [out]
+    for v in nodes:  # (preorder without recursion)
+        nodes.extend(v.children)
+    tips = {id(v): 1 for v in nodes if not v.children}
+    for v in reversed(nodes):
+        if v.children:
+            tips[id(v)] = sum(tips[id(c)] for c in v.children)
+    taken: set = set()
+
+    def free(v):
+        while v is not None:
+            if id(v) in taken:
+                return False
+            v = v.parent
+        return True
+
+    for k in sorted(degrees, reverse=True):
+        room = [v for v in nodes if v.children and v.parent is not None and 2 * k <= tips[id(v)] <= 40 * k]
+        rs.shuffle(room)
+        made = 0
+        for v in room:
+            if made == per_degree:
+                break
+            below = [v]
+            for u in below:
+                below.extend(u.children)
+            if not free(v) or any(id(u) in taken for u in below):
+                continue
+            while len(v.children) < k:
+                c = max((c for c in v.children if c.children), key=lambda c: tips[id(c)])
+                at = [x is c for x in v.children].index(True)
+                kids = list(c.children)
+                v.children[at:at + 1] = kids
+                for x in kids:
+                    x.parent = v
+            taken.add(id(v))
+            made += 1
+    return out
+
+
+def run_polytomies(dev: Device, size: str, per_degree: int = 4, repeats: int = 5, degrees=(3, 8, 32)) -> dict:
+    """``scs_score_polytomies`` on resident tables, a warm-up and ``repeats`` timed calls: all collapsed nodes in one
+    call, and per degree its nodes in one call and one node alone; beside them one ``scs_score_triplets`` call, the
+    rescoring that resolving a polytomy pair by pair would make k (k - 1) / 2 times."""
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    sup = collapse_to_degrees(random_binary_tree(2, n_taxa), degrees, per_degree, 5)
+    parent, taxon, tips = supertree_arrays(sup)
+    index = {x: i for i, x in enumerate(tips)}
+    kids = np.bincount(parent[1:], minlength=len(parent))
+    out = {"size": size, "polytomies": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "repeats": repeats,
+           "collapsed": {int(k): int((kids == k).sum()) for k in degrees}}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        out["triplets_s_min_median_max"], trip = timed(lambda: dev.score_triplets(tabs, parent, taxon))
+        every = np.flatnonzero(kids >= 3).astype(np.int32)
+        out["all_nodes_s_min_median_max"], res = timed(lambda: dev.score_polytomies(tabs, parent, taxon, every))
+        out["py_trees"] = res["py_trees"].tolist()
+        out["joint_over_total"] = round(sum(int(j.sum()) for j in res["py_joint"])
+                                        / max(sum(int(t.sum()) for t in res["py_total"]), 1), 4)
+        for k in degrees:
+            nodes = np.flatnonzero(kids == k).astype(np.int32)
+            if len(nodes) == 0:
+                continue
+            out[f"degree_{k}_nodes_s_min_median_max"], _ = timed(
+                lambda n=nodes: dev.score_polytomies(tabs, parent, taxon, n))
+            one, _ = timed(lambda n=nodes[:1]: dev.score_polytomies(tabs, parent, taxon, n))
+            out[f"degree_{k}_one_node_s_min_median_max"] = one
+            out[f"degree_{k}_rescorings_s"] = round(k * (k - 1) // 2 * out["triplets_s_min_median_max"][1], 5)
+            out[f"degree_{k}_one_node_over_rescorings"] = round(one[1] / max(out[f"degree_{k}_rescorings_s"], 1e-9), 4)
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -320,11 +413,20 @@ def main() -> None:
     ap.add_argument("--refine", action="store_true",
                     help="time refine_supertree instead (a model tree with planted regrafts; --planted N)")
     ap.add_argument("--planted", type=int, default=20, help="how many clades --refine regrafts at random")
+    ap.add_argument("--polytomies", action="store_true",
+                    help="time scs_score_polytomies instead (a supertree with collapsed edges; --collapse N)")
+    ap.add_argument("--collapse", type=int, default=4, help="how many nodes --polytomies collapses to each degree")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
+    if args.polytomies:
+        with Device(0) as dev:
+            run_polytomies(dev, "200x6", per_degree=1, repeats=1)  # warm-up
+            for size in args.size or SIZES[:1]:
+                print(json.dumps(run_polytomies(dev, size, args.collapse)), flush=True)
+        return
     if args.refine:
         with Device(0) as dev:
             run_refine(dev, "60x6", planted=2, repeats=1)  # warm-up
