@@ -500,6 +500,25 @@ int scs_score_polytomies(scs_ctx *ctx, const scs_tables *sources, int32_t n_node
                          const int32_t *query_nodes, int32_t *py_degree, int64_t *py_trees, int64_t *py_total,
                          int64_t *py_joint);
 
+/* Resampled and weighted branch triplet support, with the inputs of
+ * scs_score_branch_triplets.  weights: n_rep rows of n_trees non-negative int32 tree weights, in the tables' tree
+ * order; a tree of weight w counts exactly like w copies of it.  With bt_x(T, u) what T alone contributes to bt_x[u]
+ * (x = total, concordant, alt1, alt2 in this order; 0 where T is not decisive for u):
+ *   rs_x[r][u] = sum_T weights[r][T] bt_x(T, u).
+ * Row 0 is the point estimate (all ones: the outputs of scs_score_branch_triplets); rows 1 .. n_rep - 1 are
+ * replicates.  A replicate with rs_total[r][u] > 0 is counted once at u: in win_concordant when concordant is strictly
+ * greater than both alternatives, else in win_alt1 / win_alt2 when that alternative is strictly greatest, else in
+ * win_tie.  Outputs:
+ *   rs_point[4][n_nodes] (int64): row 0;   rs_wins[4][n_nodes] (int32): win_concordant, win_alt1, win_alt2, win_tie;
+ *   rs_rows[4][n_rep][n_nodes] (int64): every row, or NULL (not downloaded).
+ * Nodes that are no quartet branch hold zeros.  The section 18 sweep runs once per batch and keeps its per-tree terms
+ * in a slab of 32 n_nodes bytes per tree, which bounds the trees of a batch.  SCS_EINVAL, before any kernel runs, as
+ * well for: n_rep < 1; a negative weight; a source tree of more than 218 431 leaves; a row whose
+ * sum_T weights[r][T] floor(m_T^3 / 27) does not fit int64; accumulators of 32 n_rep n_nodes bytes > 1.5 GB. */
+int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                              const int32_t *taxon, int32_t max_batch_trees, int32_t n_rep, const int32_t *weights,
+                              int64_t *rs_point, int32_t *rs_wins, int64_t *rs_rows);
+
 /* ---- proper cluster graph ---------------------------------------------- */
 
 /* Build rows [row_begin, row_end) of the N x N fp64 weight matrix W on the

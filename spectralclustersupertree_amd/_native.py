@@ -171,6 +171,7 @@ SIGNATURES = {
     "scs_score_clade_moves": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _I32, _I32, _IP, _I32, _LP, _LP, _LP, _LP, _LP,
                                         _IP, _LP, _LP]),
     "scs_score_polytomies": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _I32, _I32, _IP, _IP, _LP, _LP, _LP]),
+    "scs_score_branch_resample": (C.c_int, [_P, _P, _I32, _IP, _IP, _I32, _I32, _IP, _LP, _IP, _LP]),
     "scs_pcg_build": (C.c_int, [_P, _P, _I32, _I32, _I32, _PP, C.POINTER(BuildStats)]),
     "scs_graph_contract": (C.c_int, [_P, _P, _IP, _I32, _PP]),
     "scs_graph_matrix_free": (C.c_int, [_P, _P, _I32, _PP]),

@@ -131,12 +131,14 @@ class Device:
 
     # -- scoring a supertree ----------------------------------------------------
     def _score_call(self, export: str, sources, parent, taxon, ints, outputs, queries=None, noun: str = "",
-                    top_k=None, sizes=None) -> dict:
+                    top_k=None, sizes=None, weights=None) -> dict:
         """One ``scs_score_*`` export.  ``sources`` are uploaded when they are ``TreeTables``; ``parent`` / ``taxon``
         (and ``queries``, which ``noun`` names in the shape message) travel as int32.  The export takes the context,
         the tables, the supertree, ``ints``, then the query count and ``queries``, then ``top_k``, then one buffer per
         output.  ``outputs``: ``(names, dims[, dtype, fill])`` entries with ``dims`` out of ``m`` (source trees),
-        ``n_nodes``, ``n_tips``, ``nq``, ``top_k`` and the keys of ``sizes``; int64 zeros unless said otherwise.
+        ``n_nodes``, ``n_tips``, ``nq``, ``top_k`` and the keys of ``sizes``; int64 zeros unless said otherwise; ``dims``
+        None: not asked for (a null pointer, and None in the result).  ``weights``: one more int32 input, rows x ``m``,
+        sent after ``ints`` as its row count (``n_rep`` in ``dims``) and the array.
         Returns name -> array in that order; SCS_EINVAL becomes ``ValueError`` with the library's message."""
         tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
         parent = np.ascontiguousarray(parent, dtype=np.int32)
@@ -149,21 +151,28 @@ class Device:
             size["nq"] = len(queries)
             args += [size["nq"], nv.iptr(queries)]
             ok, msg = ok and queries.ndim == 1, f"{msg}, {noun}"
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.int32)
+            ok = ok and weights.ndim == 2 and weights.shape[1] == size["m"]
+            msg = f"{msg}, weights one row per replicate with one entry per source tree"
+            size["n_rep"] = len(weights)
+            args += [size["n_rep"], nv.iptr(weights)]
         if not ok:
             raise ValueError(msg)
         if top_k is not None:
             size["top_k"] = max(int(top_k), 0)
             args.append(int(top_k))
-        if any("n_tips" in dims for _, dims, *_ in outputs):
+        if any(dims is not None and "n_tips" in dims for _, dims, *_ in outputs):
             size["n_tips"] = len(parent) - len(np.unique(parent[1:]))
         out = {}
         for names, dims, *rest in outputs:
             dtype, fill = rest or (np.int64, 0)
-            shape = tuple(size[d] for d in dims)
+            shape = None if dims is None else tuple(size[d] for d in dims)
             for name in names:
-                out[name] = np.zeros(shape, dtype=dtype) if fill == 0 else np.full(shape, fill, dtype=dtype)
+                out[name] = (None if shape is None else np.zeros(shape, dtype=dtype) if fill == 0
+                             else np.full(shape, fill, dtype=dtype))
         rc = getattr(self._lib, export)(self._ctx, tabs._h, len(parent), nv.iptr(parent), nv.iptr(taxon), *args,
-                                        *(v.ctypes.data for v in out.values()))
+                                        *(None if v is None else v.ctypes.data for v in out.values()))
         if rc == nv.EINVAL:
             msg = self._lib.scs_last_error()
             raise ValueError(msg.decode() if msg else f"{export}: invalid input")
@@ -208,6 +217,22 @@ class Device:
         return self._score_call("scs_score_branch_triplets", sources, parent, taxon, (batch_trees,),
                                 ((("n_bt_total", "n_bt_concordant", "n_bt_alternative"), _M),
                                  (("bt_total", "bt_concordant", "bt_alt1", "bt_alt2"), _N)))
+
+    def score_branch_resample(self, sources, parent: np.ndarray, taxon: np.ndarray, weights, rows: bool = False,
+                              batch_trees: int = 0) -> dict:
+        """``scs_score_branch_resample``: the per-branch triplet counts under ``weights``, R rows of one non-negative
+        integer weight per tree of the tables (row 0 the point estimate, the others replicates), with the inputs of
+        ``score``.  Returns ``rs_point`` (int64, 4 x nodes: total, concordant, alt1, alt2 of row 0), ``rs_wins``
+        (int32, 4 x nodes: the replicates won by concordant, alt1, alt2 and tied) and ``rs_rows`` (int64,
+        4 x R x nodes with ``rows``, else None)."""
+        w = np.asarray(weights)
+        if w.size and (w.min() < np.iinfo(np.int32).min or w.max() > np.iinfo(np.int32).max):
+            msg = "scs_score_branch_resample: a tree weight does not fit int32 (at most 2^31 - 1)"
+            raise ValueError(msg)
+        return self._score_call("scs_score_branch_resample", sources, parent, taxon, (batch_trees,),
+                                ((("rs_point",), ("x4", "n_nodes")), (("rs_wins",), ("x4", "n_nodes"), np.int32, 0),
+                                 (("rs_rows",), ("x4", "n_rep", "n_nodes") if rows else None)),
+                                sizes={"x4": 4}, weights=w)
 
     def score_taxon_triplets(self, sources, parent: np.ndarray, taxon: np.ndarray, batch_trees: int = 0,
                              lds_bytes: int = 0) -> dict:

@@ -56,6 +56,18 @@ from spectralclustersupertree_amd import __version__
 @click.option("--branch-triplets-out", default=None,
               help="Also write the supertree with each quartet branch's concordant/alt1/alt2/total triple counts as "
                    "its node name (Newick).")
+@click.option("--branch-resample", default=0, type=click.IntRange(min=0), metavar="N",
+              help="Resample the source trees N times and count, per quartet branch, the replicates in which the "
+                   "branch's concordant triples outnumber both alternatives: adds win_concordant, win_alt1, win_alt2, "
+                   "win_tie and support to --branches-out; needs --branches-out or --branch-support-out.")
+@click.option("--resample-seed", default=0, type=int, show_default=True,
+              help="The seed of the --branch-resample draws.")
+@click.option("--jackknife", default=False, is_flag=True,
+              help="--branch-resample keeps each source tree with probability 1/2 instead of drawing as many trees as "
+                   "there are with replacement (bootstrap).")
+@click.option("--branch-support-out", default=None,
+              help="Also write the supertree with each quartet branch's --branch-resample support in percent as its "
+                   "node name (Newick).")
 @click.option("--taxon-triplets", default=False, is_flag=True,
               help="Names the per-taxon triplet support that --taxa-out counts and writes; it switches nothing on by "
                    "itself and needs --taxa-out.")
@@ -105,8 +117,15 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         clade_placements_out: str | None = None, place_clades: int = 10, clade_max_tips: int = 64,
         refined_out: str | None = None, refine_rounds: int = 50, refine_log: str | None = None,
         polytomies_out: str | None = None, resolved_out: str | None = None, resolve_min_gain: int = 1,
-        resolve_first: bool = False) -> None:
+        resolve_first: bool = False, branch_resample: int = 0, resample_seed: int = 0, jackknife: bool = False,
+        branch_support_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
+    if branch_resample and not (branches_out or branch_support_out):
+        msg = "--branch-resample needs --branches-out or --branch-support-out"
+        raise click.UsageError(msg)
+    if (branch_support_out or jackknife) and not branch_resample:
+        msg = "--branch-support-out and --jackknife need --branch-resample N"
+        raise click.UsageError(msg)
     if resolve_first and not refined_out:
         msg = "--resolve-polytomies needs --refined-out"
         raise click.UsageError(msg)
@@ -142,7 +161,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
         if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
-                or taxa_out or placements_out or clade_placements_out or polytomies_out):
+                or taxa_out or placements_out or clade_placements_out or polytomies_out or branch_support_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
@@ -153,7 +172,13 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                                      taxon_triplets=taxa_out is not None,
                                      placements=place_taxa if placements_out else None,
                                      clade_placements=place_clades if clade_placements_out else None,
-                                     clade_max_tips=clade_max_tips, polytomies=True if polytomies_out else None)
+                                     clade_max_tips=clade_max_tips, polytomies=True if polytomies_out else None,
+                                     branch_resample=branch_resample or None, resample_seed=resample_seed,
+                                     resample="jackknife" if jackknife else "bootstrap")
+            resampled = result._rs  # (a non-field attribute: the copies made below do not carry it)
+            if branch_support_out:
+                Path(branch_support_out).write_text(
+                    result.annotate_branch_support().get_newick(with_node_names=True) + "\n")
             if polytomies_out:
                 Path(polytomies_out).write_text(result.polytomy_table())
             if clade_placements_out:
@@ -178,6 +203,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                 Path(concordance_out).write_text(
                     result.annotate_concordance().get_newick(with_node_names=True) + "\n")
             if branches_out:
+                result._rs = resampled
                 Path(branches_out).write_text(result.branch_table())
         if resolved_out:
             from spectralclustersupertree_amd.resolve import resolve_polytomies

@@ -1009,10 +1009,14 @@ struct sc_bt_args {
     int32_t *ycnt, *rcnt;        // [nb] list lengths
     unsigned long long *n_tot;   // [S nodes] bt_total
     unsigned long long *c_tot;   // [nb] n_bt_total of the batch
+    int64_t nn;                  // S nodes (the resample sweep: n_tot is the batch's slab [nb][4][nn], no c_tot)
 };
 
-// one thread per gap: T's non-root internal node that starts here, and the quartet branch the tree is decisive for
-__global__ void __launch_bounds__(SC_THREADS) k_bt_records(sc_bt_args a) {
+// one thread per gap: T's non-root internal node that starts here, and the quartet branch the tree is decisive for.
+// SLAB (scs_score_branch_resample, section 26): the tree's own total is stored, not added over the trees -- a tree has
+// one record per branch (a quartet branch has two children: one gap of S' lies between them), so the entry has one owner
+template <bool SLAB>
+__device__ __forceinline__ void bt_records(const sc_bt_args &a) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t p = a.off[0] + q;
     const bool in = p < a.off[a.nb];
@@ -1064,7 +1068,10 @@ __global__ void __launch_bounds__(SC_THREADS) k_bt_records(sc_bt_args a) {
                 dec = true;
                 r = {u, (int32_t)lo_s, (int32_t)k, (int32_t)hi_s, (int32_t)dlo, (int32_t)dhi};
                 vt = (unsigned long long)((k - lo_s + 1) * (hi_s - k) * (dhi - dlo + 1));
-                atomicAdd(a.n_tot + u, vt);
+                if (SLAB)
+                    a.n_tot[(int64_t)t * 4 * a.nn + u] = vt;
+                else
+                    atomicAdd(a.n_tot + u, vt);
             }
         }
     }
@@ -1072,21 +1079,25 @@ __global__ void __launch_bounds__(SC_THREADS) k_bt_records(sc_bt_args a) {
     if (iy >= 0) a.ylist[base + iy] = ny;
     const int ir = sc_append(a.rcnt, t, dec);
     if (ir >= 0) a.recs[base + ir] = r;
-    sc_add64(a.c_tot, t, vt);
+    if (!SLAB) sc_add64(a.c_tot, t, vt);
 }
 
+__global__ void __launch_bounds__(SC_THREADS) k_bt_records(sc_bt_args a) { bt_records<false>(a); }
+
+__global__ void __launch_bounds__(SC_THREADS) k_rs_records(sc_bt_args a) { bt_records<true>(a); }
+
 // the hot path: one workgroup per (tree t, block of zb of t's records); blk and W as in k_trip_pairs.  node_ctr holds
-// bt_concordant, bt_alt1, bt_alt2 as three arrays of nn entries; c_con / c_alt are the batch's per-tree counters
-__global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restrict__ blk, int nb,
-                                                         const int64_t *__restrict__ off,
-                                                         const int4 *__restrict__ ylist,
-                                                         const sc_bt_rec *__restrict__ recs,
-                                                         const int32_t *__restrict__ ycnt,
-                                                         const int32_t *__restrict__ rcnt,
-                                                         const int2 *__restrict__ tp, int zb, int W,
-                                                         unsigned long long *__restrict__ node_ctr, int64_t nn,
-                                                         unsigned long long *__restrict__ c_con,
-                                                         unsigned long long *__restrict__ c_alt) {
+// bt_concordant, bt_alt1, bt_alt2 as three arrays of nn entries; c_con / c_alt are the batch's per-tree counters.
+// SLAB: node_ctr is the batch's slab [nb][4][nn] and lane 3 j + c stores counter c of record j into rows 1 - 3 of its
+// tree (one owner per entry, as in bt_records<true>); no per-tree counters
+template <bool SLAB>
+__device__ __forceinline__ void bt_pairs(const int64_t *__restrict__ blk, int nb, const int64_t *__restrict__ off,
+                                         const int4 *__restrict__ ylist, const sc_bt_rec *__restrict__ recs,
+                                         const int32_t *__restrict__ ycnt, const int32_t *__restrict__ rcnt,
+                                         const int2 *__restrict__ tp, int zb, int W,
+                                         unsigned long long *__restrict__ node_ctr, int64_t nn,
+                                         unsigned long long *__restrict__ c_con,
+                                         unsigned long long *__restrict__ c_alt) {
     // [3 zb][W]: rows 3j, 3j + 1, 3j + 2 = A', A' ∪ B', A' ∪ B' ∪ D' of record j
     extern __shared__ __attribute__((aligned(16))) int2 rows[];
     const int64_t g = blk[0] + blockIdx.x;
@@ -1178,6 +1189,10 @@ __global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restri
         if (lane < 3 * nz)
             for (int w = 0; w < SC_THREADS / 64; ++w) tot += ws[w * BT_ZMAX * 3 + lane];
         const int c = lane % 3;
+        if (SLAB) {
+            if (tot) node_ctr[((int64_t)t * 4 + 1 + c) * nn + recs[base + j0 + lane / 3].u] = tot;
+            return;
+        }
         if (tot) atomicAdd(node_ctr + c * nn + recs[base + j0 + lane / 3].u, tot);
         unsigned long long con = c == 0 ? tot : 0, alt = c == 0 ? 0 : tot;
         for (int d = 32; d >= 1; d >>= 1) {
@@ -1187,6 +1202,32 @@ __global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restri
         if (lane == 0 && con) atomicAdd(c_con + t, con);
         if (lane == 0 && alt) atomicAdd(c_alt + t, alt);
     }
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_bt_pairs(const int64_t *__restrict__ blk, int nb,
+                                                         const int64_t *__restrict__ off,
+                                                         const int4 *__restrict__ ylist,
+                                                         const sc_bt_rec *__restrict__ recs,
+                                                         const int32_t *__restrict__ ycnt,
+                                                         const int32_t *__restrict__ rcnt,
+                                                         const int2 *__restrict__ tp, int zb, int W,
+                                                         unsigned long long *__restrict__ node_ctr, int64_t nn,
+                                                         unsigned long long *__restrict__ c_con,
+                                                         unsigned long long *__restrict__ c_alt) {
+    bt_pairs<false>(blk, nb, off, ylist, recs, ycnt, rcnt, tp, zb, W, node_ctr, nn, c_con, c_alt);
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_rs_pairs(const int64_t *__restrict__ blk, int nb,
+                                                         const int64_t *__restrict__ off,
+                                                         const int4 *__restrict__ ylist,
+                                                         const sc_bt_rec *__restrict__ recs,
+                                                         const int32_t *__restrict__ ycnt,
+                                                         const int32_t *__restrict__ rcnt,
+                                                         const int2 *__restrict__ tp, int zb, int W,
+                                                         unsigned long long *__restrict__ node_ctr, int64_t nn,
+                                                         unsigned long long *__restrict__ c_con,
+                                                         unsigned long long *__restrict__ c_alt) {
+    bt_pairs<true>(blk, nb, off, ylist, recs, ycnt, rcnt, tp, zb, W, node_ctr, nn, c_con, c_alt);
 }
 
 // ---- per-taxon triplet support (scs_score_taxon_triplets) ----
@@ -3034,6 +3075,7 @@ extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, in
         a.rcnt = d_ycnt + nb;
         a.n_tot = d_node;
         a.c_tot = d_cnt + t0;
+        a.nn = (int64_t)nn;
         k_bt_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
         const int64_t n_wg = blk[t0 + nb] - blk[t0];
@@ -4168,6 +4210,230 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
     if (e == hipSuccess && py_trees) e = hipMemcpyAsync(py_trees, d_trees, nq * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_total) e = hipMemcpyAsync(py_total, d_total, n_out * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_joint) e = hipMemcpyAsync(py_joint, d_joint, n_out * 8, hipMemcpyDeviceToHost, s);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    return SCS_OK;
+}
+
+// ---- resampled and weighted branch triplet support (scs_score_branch_resample) ----
+//
+// rs_x[r][u] = sum_T w[r][T] bt_x(T, u) for the four counters x of section 18 and R rows of non-negative integer tree
+// weights: row 0 the point estimate, rows 1 .. R - 1 replicates (a bootstrap or jackknife draw of the sources).  The
+// sweep of section 18 runs once per batch and keeps its per-(tree, branch) terms:
+//   k_rs_records / k_rs_pairs: bt_records<true> / bt_pairs<true>, plain stores into the batch's slab [tree][x][u];
+//   k_rs_reduce: acc[x][r][u] += sum_t w[r][t] slab[t][x][u], one thread per (x, u) and tile of RS_TILE replicates in
+//     registers, the slab read coalesced over u, a tree whose 64 entries are zero skipped by the wave, the tile's
+//     weights in LDS (every lane reads the same address: a broadcast);
+//   k_rs_wins: one thread per node decides every replicate and counts the four outcomes.
+
+namespace {
+
+constexpr int RS_TILE = 8;     // replicates a thread of k_rs_reduce accumulates
+constexpr int RS_CHUNK = 512;  // trees whose weights a workgroup holds in LDS at a time (16 KiB)
+constexpr int RS_AHEAD = 4;    // slab loads in flight per thread
+
+// acc += w * v for 0 <= w < 2^31: a 32 x 32 -> 64 multiply-add on v's low word, a 32-bit one on its high word
+__device__ __forceinline__ void rs_mad(unsigned long long &acc, uint32_t w, uint32_t lo, uint32_t hi) {
+    acc += (unsigned long long)w * lo + ((unsigned long long)(w * hi) << 32);
+}
+
+// grid (node blocks x replicate tiles, 4): slab [nb][4][nn] of the batch, w = weights + t0 with row stride M
+__global__ void __launch_bounds__(SC_THREADS) k_rs_reduce(const unsigned long long *__restrict__ slab, int nb,
+                                                          int64_t nn, int n_ub, const int32_t *__restrict__ w,
+                                                          int64_t M, int R, unsigned long long *__restrict__ acc) {
+    __shared__ __attribute__((aligned(16))) uint32_t ws[RS_CHUNK][RS_TILE];
+    const int64_t u = (int64_t)(blockIdx.x % n_ub) * SC_THREADS + threadIdx.x;
+    const int r0 = (int)(blockIdx.x / n_ub) * RS_TILE, x = blockIdx.y;
+    const bool in = u < nn;
+    unsigned long long a[RS_TILE];
+#pragma unroll
+    for (int j = 0; j < RS_TILE; ++j) a[j] = 0;
+    for (int c0 = 0; c0 < nb; c0 += RS_CHUNK) {
+        const int nc = min(RS_CHUNK, nb - c0);
+        __syncthreads();  // (the chunk before is read)
+        for (int i = threadIdx.x; i < nc * RS_TILE; i += SC_THREADS) {
+            const int j = i / nc, tt = i - j * nc;
+            ws[tt][j] = r0 + j < R ? (uint32_t)w[(int64_t)(r0 + j) * M + c0 + tt] : 0u;
+        }
+        __syncthreads();
+        const unsigned long long *p = slab + ((int64_t)c0 * 4 + x) * nn + (in ? u : 0);
+        for (int tt = 0; tt < nc; tt += RS_AHEAD, p += RS_AHEAD * 4 * nn) {
+            unsigned long long v[RS_AHEAD];
+#pragma unroll
+            for (int k = 0; k < RS_AHEAD; ++k) v[k] = in && tt + k < nc ? p[(int64_t)k * 4 * nn] : 0ull;
+#pragma unroll
+            for (int k = 0; k < RS_AHEAD; ++k) {
+                if (__ballot(v[k] != 0) == 0) continue;  // (sparse sources: most (tree, 64 nodes) are empty)
+                const uint32_t lo = (uint32_t)v[k], hi = (uint32_t)(v[k] >> 32);
+                const uint32_t *wt = ws[min(tt + k, nc - 1)];
+#pragma unroll
+                for (int j = 0; j < RS_TILE; ++j) rs_mad(a[j], wt[j], lo, hi);
+            }
+        }
+    }
+    if (!in) return;
+#pragma unroll
+    for (int j = 0; j < RS_TILE; ++j)
+        if (r0 + j < R) acc[((int64_t)x * R + r0 + j) * nn + u] += a[j];  // (one owner per entry, batches in order)
+}
+
+// one thread per node: every replicate r >= 1 with rs_total > 0 counts once, for the arrangement that is strictly
+// greatest or as a tie; wins [4][nn] = concordant, alt1, alt2, tie
+__global__ void __launch_bounds__(SC_THREADS) k_rs_wins(const unsigned long long *__restrict__ acc, int64_t nn, int R,
+                                                        int32_t *__restrict__ wins) {
+    const int64_t u = (int64_t)blockIdx.x * SC_THREADS + threadIdx.x;
+    if (u >= nn) return;
+    const int64_t row = (int64_t)R * nn;
+    int32_t n_con = 0, n_a1 = 0, n_a2 = 0, n_tie = 0;
+    for (int r = 1; r < R; ++r) {
+        const unsigned long long *p = acc + (int64_t)r * nn + u;
+        if (p[0] == 0) continue;
+        const unsigned long long con = p[row], a1 = p[2 * row], a2 = p[3 * row];
+        if (con > a1 && con > a2) ++n_con;
+        else if (a1 > con && a1 > a2) ++n_a1;
+        else if (a2 > con && a2 > a1) ++n_a2;
+        else ++n_tie;
+    }
+    wins[u] = n_con;
+    wins[nn + u] = n_a1;
+    wins[2 * nn + u] = n_a2;
+    wins[3 * nn + u] = n_tie;
+}
+
+}  // namespace
+
+extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                         const int32_t *taxon, int32_t max_batch_trees, int32_t n_rep,
+                                         const int32_t *weights, int64_t *rs_point, int32_t *rs_wins,
+                                         int64_t *rs_rows) {
+    const char *const who = "scs_score_branch_resample";
+    SCS_REQUIRE(ctx && src && parent && taxon && weights && rs_point && rs_wins, "%s: null argument", who);
+    SCS_REQUIRE(n_rep >= 1, "%s: n_rep = %d: at least row 0, the point estimate, is needed", who, n_rep);
+    const int32_t M = src->n_trees;
+    const std::vector<int64_t> &off = src->h_tree_off;
+    // the three rows of one record of the largest tree must fit one workgroup's LDS (section 18)
+    const int64_t m_max = std::max<int64_t>(src->max_leaves, 0);
+    SCS_REQUIRE(BT_ROW_BYTES * ((m_max >> 5) + 1) <= TP_LDS_MAX,
+                "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
+                (long long)m_max, TP_LDS_MAX / BT_ROW_BYTES * 32 - 1);
+    // a row's entry is at most sum_t w[r][t] floor(m_t^3 / 27): it must fit int64
+    {
+        std::vector<unsigned __int128> cube((size_t)M);
+        for (int32_t t = 0; t < M; ++t) {
+            const unsigned __int128 m = (unsigned __int128)(off[t + 1] - off[t]);
+            cube[t] = m * m * m / 27;
+        }
+        for (int32_t r = 0; r < n_rep; ++r) {
+            unsigned __int128 sum = 0;
+            for (int32_t t = 0; t < M; ++t) {
+                const int32_t wt = weights[(size_t)r * M + t];
+                SCS_REQUIRE(wt >= 0, "%s: weights[%d][%d] = %d is negative", who, r, t, wt);
+                sum += (unsigned __int128)wt * cube[t];
+            }
+            SCS_REQUIRE(sum <= (unsigned __int128)INT64_MAX,
+                        "%s: the weighted triple counts of row %d may not fit 64 bits (the sum of weight x "
+                        "leaves^3 / 27 over the %d source trees exceeds 2^63 - 1)", who, r, M);
+        }
+    }
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = (size_t)M, R = (size_t)n_rep;
+    SCS_REQUIRE((unsigned __int128)32 * R * nn <= SC_BUDGET,
+                "%s: the accumulators of %d rows x %d nodes need %llu bytes, more than the %llu of the call's "
+                "workspace", who, n_rep, n_nodes, (unsigned long long)(32 * R * nn), (unsigned long long)SC_BUDGET);
+    // own arrays: the accumulators [4][R][nn], the wins [4][nn], the weights, the quartet-branch record per S node and
+    // the first pair workgroup per tree (+ 1); per batch the lists of section 18 and the slab [tree][4][nn]
+    const size_t o_acc = 0, o_wins = o_acc + sc_up256(32 * R * nn), o_w = o_wins + sc_up256(nn * 16),
+                 o_qp = o_w + sc_up256(R * mt * 4), o_blk = o_qp + sc_up256(nn * 4),
+                 own = o_blk + sc_up256((mt + 1) * 8);
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 16 + sizeof(sc_bt_rec),
+                     8 + 32 * (uint64_t)nn, c, e));
+    hipStream_t s = ctx->stream;
+    auto *d_acc = (unsigned long long *)(c.d_extra + o_acc);
+    auto *d_wins = (int32_t *)(c.d_extra + o_wins);
+    auto *d_w = (int32_t *)(c.d_extra + o_w);
+    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
+    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
+    const size_t n_batches = c.bstart.size() - 1;
+    int64_t max_rows = 0;
+    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
+    auto *d_ylist = (int4 *)c.d_extra_batch;
+    auto *d_recs = (sc_bt_rec *)(d_ylist + c.max_lb);
+    auto *d_ycnt = (int32_t *)(d_recs + c.max_lb);
+    auto *d_slab = (unsigned long long *)(d_ycnt + 2 * max_rows);
+    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
+    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
+    for (int32_t v = 1; v < n_nodes; ++v)
+        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    // W, zb and blk per batch as in scs_score_branch_triplets
+    std::vector<int> words(n_batches), zbs(n_batches);
+    std::vector<int64_t> blk((size_t)M + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
+        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
+            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+    }
+    const int n_ub = grid_of((int64_t)nn), n_tiles = (n_rep + RS_TILE - 1) / RS_TILE;
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_w, weights, R * mt * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, 32 * R * nn, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void *)k_rs_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
+    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
+        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_slab, 0, (size_t)nb * 32 * nn, s);
+        if (e != hipSuccess) break;
+        sc_bt_args a;
+        a.off = src->d_tree_off + t0;
+        a.nb = nb;
+        a.sp = c.d_sp;
+        a.node = c.d_node;
+        a.adj = src->d_adj_depth + L0;
+        a.amin = c.d_amin;
+        a.levels = c.levels;
+        a.Lb = Lb;
+        a.s_lo = c.d_slo;
+        a.s_hi = c.d_shi;
+        a.q_parent = d_qp;
+        a.ylist = d_ylist;
+        a.recs = d_recs;
+        a.ycnt = d_ycnt;
+        a.rcnt = d_ycnt + nb;
+        a.n_tot = d_slab;
+        a.c_tot = nullptr;
+        a.nn = (int64_t)nn;
+        k_rs_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        if (n_wg > 0) {
+            const size_t lds = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b],
+                                                (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
+            k_rs_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
+                                                               c.d_mm, zbs[b], words[b], d_slab, (int64_t)nn, nullptr,
+                                                               nullptr);
+            if (!sc_launched(e)) break;
+        }
+        k_rs_reduce<<<dim3((unsigned)n_ub * (unsigned)n_tiles, 4), SC_THREADS, 0, s>>>(d_slab, nb, (int64_t)nn, n_ub,
+                                                                                      d_w + t0, (int64_t)M, n_rep,
+                                                                                      d_acc);
+        if (!sc_launched(e)) break;
+    }
+    if (e == hipSuccess && !bad) {
+        k_rs_wins<<<n_ub, SC_THREADS, 0, s>>>(d_acc, (int64_t)nn, n_rep, d_wins);
+        sc_launched(e);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
+    for (size_t x = 0; x < 4 && e == hipSuccess; ++x)  // (row 0 of every counter)
+        e = hipMemcpyAsync(rs_point + x * nn, d_acc + x * R * nn, nn * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(rs_wins, d_wins, nn * 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && rs_rows) e = hipMemcpyAsync(rs_rows, d_acc, 32 * R * nn, hipMemcpyDeviceToHost, s);
     SCS_TRY(sc_end(ctx, c, e, bad));
     return SCS_OK;
 }

@@ -130,10 +130,19 @@ Two groups G and H of children put under one new node lower the summed triplet d
 the sums of ``py_joint`` and ``py_total`` over i in G, j in H and l in neither (``polytomy_merge_gain``;
 ``resolve.resolve_polytomies`` builds a whole resolution on it).
 
+Resampled and weighted branch triplet support (``branch_resample=...`` and / or ``tree_weights=...``): the per-branch
+triple counts under R rows of non-negative integer tree weights, rs_x[r][u] = Σ_T w[r][T] bt_x(T, u) with bt_x(T, u)
+what T alone adds to ``bt_x[u]``.  A tree of weight w counts exactly like w copies of it, so every number stays an
+exact int64.  Row 0 is the point estimate (``tree_weights``, all ones by default: then ``rs_total`` = ``bt_total`` and
+so on); rows 1 .. R - 1 are replicates, bootstrap or jackknife draws of the sources (``resample_weights``).  A
+replicate with rs_total > 0 at a branch is counted once there: for the arrangement whose count is strictly greatest
+(``win_concordant``, ``win_alt1``, ``win_alt2``) or as ``win_tie``; ``branch_support`` = win_concordant over the four
+together.  Only this pass is weighted; every other count of this module ignores tree weights.
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
-``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_taxon_triplets``,
-``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies`` and (for ``refine_supertree``)
-``scs_score_clade_moves``; the host only validates and lays out.
+``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_branch_resample``,
+``scs_score_taxon_triplets``, ``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies`` and
+(for ``refine_supertree``) ``scs_score_clade_moves``; the host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -178,7 +187,7 @@ class SupertreeScore:
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
     # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested), "placements" (scs_score_placements,
     # when requested), "clade_placements" (scs_score_clade_placements, when requested), "polytomies"
-    # (scs_score_polytomies, when requested)
+    # (scs_score_polytomies, when requested), "branch_resample" (scs_score_branch_resample, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -353,16 +362,23 @@ class SupertreeScore:
                          if mask[i] else None)
         return out
 
-    def nni_candidates(self, by: str = "sources") -> list[dict]:
+    def nni_candidates(self, by: str = "sources", min_support: float | None = None) -> list[dict]:
         """The quartet branches where an alternative arrangement has more sources than the branch itself: one dict
         per branch with ``node`` (preorder index), ``alternative`` (``"alt1"`` or ``"alt2"``, the larger; alt1 on
         a tie), ``decisive``, ``concordant``, ``alt1``, ``alt2`` and ``margin`` = that alternative's count minus
         ``concordant``; largest margin first, then by node.  ``by="triplets"`` compares the per-branch triple
         counts instead (``branch_triplets=True``): the same keys, holding ``bt_total``, ``bt_concordant``,
-        ``bt_alt1`` and ``bt_alt2``."""
+        ``bt_alt1`` and ``bt_alt2`` (the point estimates ``rs_*`` where only the resampling was computed).
+        ``min_support`` (``by="triplets"``, with ``branch_resample=...``): only the branches whose alternative also
+        wins in at least that share of the informative replicates, which ``replicate_share`` then holds."""
+        if min_support is not None and (by != "triplets" or self.rs_wins is None):
+            msg = "min_support needs by='triplets' and replicates: score_supertree(..., branch_resample=N)"
+            raise ValueError(msg)
         if by == "sources":
             self._need_concordance()
             dec, con, alt1, alt2 = self.decisive, self.concordant, self.alt1, self.alt2
+        elif by == "triplets" and self.bt_total is None and self._rs is not None:
+            dec, con, alt1, alt2 = self.rs_total, self.rs_concordant, self.rs_alt1, self.rs_alt2
         elif by == "triplets":
             self._need_branch_triplets()
             dec, con, alt1, alt2 = self.bt_total, self.bt_concordant, self.bt_alt1, self.bt_alt2
@@ -376,6 +392,13 @@ class SupertreeScore:
                         "decisive": int(dec[i]), "concordant": int(con[i]),
                         "alt1": int(alt1[i]), "alt2": int(alt2[i]),
                         "margin": int(best[i] - con[i])})
+        if min_support is not None:
+            wins = self.rs_wins
+            informative = sum(wins.values())
+            for r in out:
+                n = int(informative[r["node"]])
+                r["replicate_share"] = int(wins["win_" + r["alternative"]][r["node"]]) / n if n else float("nan")
+            out = [r for r in out if r["replicate_share"] >= min_support]
         out.sort(key=lambda r: (-r["margin"], r["node"]))
         return out
 
@@ -688,12 +711,94 @@ class SupertreeScore:
         return resolve_from_tensors(self.supertree, self.py_nodes, self.py_total, self.py_joint, self.py_skipped,
                                     initial, min_gain)
 
+    # resampled / weighted branch triplet support (``branch_resample=...`` or ``tree_weights=...``; None otherwise),
+    # kept beside the dataclass fields like ``_py``: a dict with the keys of ``_RS_KEYS``
+    _rs = None
+
+    def _rs_counter(self, x: int, rows: bool) -> np.ndarray | None:
+        got = None if self._rs is None else self._rs["rs_rows" if rows else "rs_point"]
+        return None if got is None else got[x]
+
+    @property
+    def rs_weights(self) -> np.ndarray | None:
+        """The R x trees weight matrix that was scored, columns in the order of ``trees`` as given: row 0 the point
+        estimate's weights, the others the replicates."""
+        return None if self._rs is None else self._rs["rs_weights"]
+
+    @property
+    def rs_total(self) -> np.ndarray | None:
+        """Per node, row 0: ``bt_total`` with every source counted ``tree_weights`` times."""
+        return self._rs_counter(0, False)
+
+    @property
+    def rs_concordant(self) -> np.ndarray | None:
+        return self._rs_counter(1, False)
+
+    @property
+    def rs_alt1(self) -> np.ndarray | None:
+        return self._rs_counter(2, False)
+
+    @property
+    def rs_alt2(self) -> np.ndarray | None:
+        return self._rs_counter(3, False)
+
+    @property
+    def rs_total_rows(self) -> np.ndarray | None:
+        """R x nodes: every row of ``rs_weights`` (``resample_rows=True``; None otherwise)."""
+        return self._rs_counter(0, True)
+
+    @property
+    def rs_concordant_rows(self) -> np.ndarray | None:
+        return self._rs_counter(1, True)
+
+    @property
+    def rs_alt1_rows(self) -> np.ndarray | None:
+        return self._rs_counter(2, True)
+
+    @property
+    def rs_alt2_rows(self) -> np.ndarray | None:
+        return self._rs_counter(3, True)
+
+    @property
+    def rs_wins(self) -> dict | None:
+        """``win_concordant``, ``win_alt1``, ``win_alt2``, ``win_tie`` per node: the informative replicates (rs_total
+        > 0 there) by the arrangement whose count is strictly greatest, or tied.  None without replicates."""
+        return None if self._rs is None else self._rs["rs_wins"]
+
+    @property
+    def branch_support(self) -> np.ndarray | None:
+        """``win_concordant`` over the informative replicates per node (NaN where there is none)."""
+        wins = self.rs_wins
+        if wins is None:
+            return None
+        n = sum(wins.values())
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, wins["win_concordant"] / np.maximum(n, 1), np.nan)
+
+    def annotate_branch_support(self) -> TreeNode:
+        """A copy of the supertree whose quartet branches are named by their ``branch_support`` in percent (one
+        decimal; no name where no replicate is informative) and whose other internal nodes carry no name, so that
+        ``get_newick(with_node_names=True)`` writes it.  ``ValueError`` unless replicates were scored."""
+        values = self.branch_support
+        if values is None:
+            msg = "no replicates were scored: score_supertree(..., branch_resample=N)"
+            raise ValueError(msg)
+        out = self.supertree.copy()
+        mask = self.quartet_branch
+        for i, node in enumerate(_preorder(out)):
+            if node.is_tip():
+                continue
+            node.name = f"{100.0 * values[i]:.1f}" if mask[i] and not np.isnan(values[i]) else None
+        return out
+
     def branch_table(self) -> str:
         """One TSV row per quartet branch: node (preorder index), clade_size, informative, supported, decisive,
         concordant, alt1, alt2, other, then bt_total, bt_concordant, bt_alt1, bt_alt2 when the branch triplet counts
-        were computed.  ``ValueError`` unless the concordance was computed."""
+        were computed, then win_concordant, win_alt1, win_alt2, win_tie, support when replicates were scored.
+        ``ValueError`` unless the concordance was computed."""
         self._need_concordance()
         bt = self.bt_total is not None
+        wins, support = self.rs_wins, self.branch_support
         nodes = _preorder(self.supertree)
         size = np.array([1 if v.is_tip() else 0 for v in nodes], dtype=np.int64)
         parent = self.supertree.to_flat()[0]
@@ -701,12 +806,15 @@ class SupertreeScore:
             size[parent[i]] += size[i]
         other = self.other
         rows = ["node\tclade_size\tinformative\tsupported\tdecisive\tconcordant\talt1\talt2\tother"
-                + ("\tbt_total\tbt_concordant\tbt_alt1\tbt_alt2" if bt else "")]
+                + ("\tbt_total\tbt_concordant\tbt_alt1\tbt_alt2" if bt else "")
+                + ("\twin_concordant\twin_alt1\twin_alt2\twin_tie\tsupport" if wins else "")]
         for i in np.flatnonzero(self.quartet_branch):
             row = (f"{i}\t{size[i]}\t{self.informative[i]}\t{self.supported[i]}\t{self.decisive[i]}"
                    f"\t{self.concordant[i]}\t{self.alt1[i]}\t{self.alt2[i]}\t{other[i]}")
             if bt:
                 row += f"\t{self.bt_total[i]}\t{self.bt_concordant[i]}\t{self.bt_alt1[i]}\t{self.bt_alt2[i]}"
+            if wins:
+                row += "".join(f"\t{wins[k][i]}" for k in _WIN_KEYS) + f"\t{support[i]:.4f}"
             rows.append(row)
         return "\n".join(rows) + "\n"
 
@@ -863,7 +971,9 @@ def supertree_arrays(supertree: TreeNode) -> tuple[np.ndarray, np.ndarray, list[
 def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, conflicts: bool = False,
                     concordance: bool = False, branch_triplets: bool = False, taxon_triplets: bool = False,
                     placements=None, clade_placements=None, clade_max_tips: int = 64, polytomies=None,
-                    polytomy_max_degree: int = 64, device=None) -> SupertreeScore:
+                    polytomy_max_degree: int = 64, branch_resample=None, tree_weights=None,
+                    resample: str = "bootstrap", resample_seed: int = 0, resample_rows: bool = False,
+                    device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
@@ -887,11 +997,20 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     polytomy, ``py_total``, ``py_joint`` one k x k x k array each; ``polytomy_table``, ``polytomy_merge_gain``,
     ``resolve_polytomies``).  Polytomies of more than ``polytomy_max_degree`` (at most 64) children, or whose rows of
     the largest source do not fit a workgroup's LDS, are not scored and listed in ``py_skipped``.  ``ValueError`` for
-    a node with fewer than three children, out of range or given twice.
+    a node with fewer than three children, out of range or given twice.  ``branch_resample``: a replicate count N or
+    an explicit N x trees matrix of non-negative integer weights, and / or ``tree_weights``: one non-negative integer
+    per tree (both in the order of ``trees`` as given; integral floats are taken, anything else is a ``ValueError``:
+    scoring is exact and takes integer weights): the per-branch triple counts under those weights (``rs_weights``,
+    ``rs_total``, ``rs_concordant``, ``rs_alt1``, ``rs_alt2``: row 0, the point estimate under ``tree_weights``;
+    ``rs_wins`` and ``branch_support`` over the replicates; ``rs_total_rows`` and so on, R x nodes, with
+    ``resample_rows=True``; ``annotate_branch_support``, ``nni_candidates(by="triplets", min_support=p)``).  The
+    replicates of a count are drawn by ``resample_weights`` (``resample``: ``"bootstrap"`` or ``"jackknife"``, from
+    ``numpy.random.RandomState(resample_seed)``).  With ``tree_weights`` alone there is row 0 and no replicate.
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
-    by those inputs and ignored: every count is unweighted.  The supertree must hold every taxon of every source
+    by those inputs and ignored: every count is unweighted but those of ``branch_resample`` / ``tree_weights``, which
+    take the weights given here.  The supertree must hold every taxon of every source
     tree exactly once (``ValueError`` otherwise); it may hold taxa no source has.  ``device``: a
     ``backend.Device``; default the process's device (in a launched multi-rank job the caller's own: scoring is
     not spread over ranks).
@@ -904,7 +1023,10 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     req = _Request(triplets, conflicts, concordance, branch_triplets,
                    taxon_triplets or isinstance(placements, int) or isinstance(clades, int), placements, clades,
                    clade_max_tips, tips, _check_polytomies(polytomies, parent, index, polytomy_max_degree),
-                   int(polytomy_max_degree))
+                   int(polytomy_max_degree),
+                   resample=None if branch_resample is None and tree_weights is None else resample_weights(
+                       _n_given(trees), branch_resample, tree_weights, resample, resample_seed),
+                   resample_rows=bool(resample_rows))
     with _resident_tables(device, trees, tips, index) as src:
         timings = {"prepare": 0.0, "tables": src.seconds}
         res = _run_passes(src, parent, taxon, req, timings)
@@ -923,7 +1045,66 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
                          **{k: res.get(k) for k in _COUNTS})
     if "py_nodes" in res:
         out._py = {k: res[k] for k in _PY_KEYS}
+    if "rs_point" in res:
+        out._rs = {k: res[k] for k in _RS_KEYS}
     return out
+
+
+_RS_KEYS = ("rs_weights", "rs_point", "rs_wins", "rs_rows")
+_WIN_KEYS = ("win_concordant", "win_alt1", "win_alt2", "win_tie")
+
+
+def _n_given(trees) -> int:
+    """The trees ``score_supertree`` counts in ``trees``: what its weights have one entry for."""
+    return trees.n_trees if isinstance(trees, TreeArrays) else sum(not is_not_completed(t) for t in trees)
+
+
+def _integers(values, what: str) -> np.ndarray:
+    """``values`` as int64 when they are non-negative integers (integral floats included)."""
+    a = np.asarray(values)
+    ok = a.dtype != bool and (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating))
+    if not ok or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)) or np.any(a < 0):
+        msg = f"{what} must be non-negative integers: scoring is exact and takes integer weights"
+        raise ValueError(msg)
+    return a.astype(np.int64)
+
+
+def resample_weights(n_trees: int, branch_resample=None, tree_weights=None, resample: str = "bootstrap",
+                     seed: int = 0) -> np.ndarray | None:
+    """The R x ``n_trees`` int64 weight matrix ``score_supertree`` scores for these arguments, or None when neither
+    ``branch_resample`` nor ``tree_weights`` is given.  Row 0 = ``tree_weights`` (ones by default).  An explicit
+    ``branch_resample`` matrix gives rows 1 .. R - 1 as they are.  A count N draws them one after the other from
+    ``rs = numpy.random.RandomState(seed)``: ``"bootstrap"``: ``rs.multinomial(n_trees, numpy.full(n_trees,
+    1 / n_trees)) * tree_weights`` (n_trees draws with replacement); ``"jackknife"``: ``rs.randint(0, 2, n_trees) *
+    tree_weights`` (each tree kept with probability 1/2)."""
+    if branch_resample is None and tree_weights is None:
+        return None
+    if resample not in ("bootstrap", "jackknife"):
+        msg = f"resample must be 'bootstrap' or 'jackknife', not {resample!r}"
+        raise ValueError(msg)
+    m = int(n_trees)
+    if m == 0:  # (nothing to weight: ``score_supertree`` refuses an empty list itself)
+        return None
+    point = np.ones(m, dtype=np.int64) if tree_weights is None else _integers(tree_weights, "tree_weights")
+    if point.shape != (m,):
+        msg = f"tree_weights must have one entry per source tree ({m}), not shape {point.shape}"
+        raise ValueError(msg)
+    if branch_resample is None:
+        reps = np.zeros((0, m), dtype=np.int64)
+    elif np.ndim(branch_resample) == 0:
+        n = _integers(branch_resample, "branch_resample")
+        rs = np.random.RandomState(seed)
+        if resample == "bootstrap":
+            draws = [rs.multinomial(m, np.full(m, 1.0 / m)) for _ in range(int(n))]
+        else:
+            draws = [rs.randint(0, 2, m) for _ in range(int(n))]
+        reps = np.array(draws, dtype=np.int64).reshape(int(n), m) * point
+    else:
+        reps = _integers(branch_resample, "branch_resample")
+        if reps.ndim != 2 or reps.shape[1] != m:
+            msg = f"a branch_resample matrix must be replicates x source trees ({m}), not shape {reps.shape}"
+            raise ValueError(msg)
+    return np.vstack([point[None, :], reps])
 
 
 def _check_placements(placements, index: dict):
@@ -1274,6 +1455,9 @@ class _Request:
     polytomies: object = None       # None, True or the query nodes
     polytomy_max_degree: int = 64
     max_leaves: int = 0             # of the largest source tree (set by ``_run_passes``)
+    resample: object = None         # None or the R x trees weight matrix, columns in the order of the trees as given
+    resample_rows: bool = False
+    tree_index: object = None       # the given tree behind every tree of the tables (set by ``_run_passes``)
 
 
 @dataclass(frozen=True)
@@ -1302,6 +1486,19 @@ def _taxon_triplets(dev, tabs, parent, taxon, res: dict, req) -> dict:
     return dev.score_taxon_triplets(tabs, parent, taxon, batch_trees=BATCH_TREES or 0, lds_bytes=TAXON_LDS_BYTES or 0)
 
 
+def _branch_resample(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    w, n = req.resample, len(parent)
+    if tabs is None:
+        out = {"rs_point": np.zeros((4, n), dtype=np.int64), "rs_wins": np.zeros((4, n), dtype=np.int32),
+               "rs_rows": np.zeros((4, len(w), n), dtype=np.int64) if req.resample_rows else None}
+    else:
+        out = dev.score_branch_resample(tabs, parent, taxon, w if req.tree_index is None else w[:, req.tree_index],
+                                        rows=req.resample_rows, batch_trees=BATCH_TREES or 0)
+    out["rs_weights"] = w
+    out["rs_wins"] = dict(zip(_WIN_KEYS, out["rs_wins"])) if len(w) > 1 else None
+    return out
+
+
 # in call order (the query passes read the per-taxon counts)
 _PASSES = (
     _Pass("score", lambda req: True, _on_tables("score"),
@@ -1318,6 +1515,7 @@ _PASSES = (
     _Pass("placements", lambda req: req.placements is not None, _placements, queries=True),
     _Pass("clade_placements", lambda req: req.clades is not None, _clade_placements, queries=True),
     _Pass("polytomies", lambda req: req.polytomies is not None, _polytomies, queries=True),
+    _Pass("branch_resample", lambda req: req.resample is not None, _branch_resample, queries=True),
 )
 
 
@@ -1326,7 +1524,7 @@ def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> d
     go back to the places of the trees as given (``src.tree_index``); without tables every output is zeros."""
     m = len(src.n_leaves)
     tree_index = None if src.tabs is None else src.tree_index()
-    req = replace(req, max_leaves=int(np.max(src.n_leaves)) if m else 0)
+    req = replace(req, max_leaves=int(np.max(src.n_leaves)) if m else 0, tree_index=tree_index)
     res: dict = {}
     for p in _PASSES:
         if not p.wanted(req):

@@ -18,6 +18,9 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --polytomies --size 10000x500   # scs_score_polytomies on a supertree with collapsed
                                                      # edges (degrees 3, 8, 32; --collapse N nodes of each) beside one
                                                      # scs_score_triplets call
+    python tools/score_bench.py --branch-resample 100 --size 10000x500   # scs_score_branch_resample with 100 weight
+                                                     # rows (repeatable) beside one scs_score_branch_triplets call
+                                                     # 
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -37,7 +40,8 @@ import numpy as np  # noqa: E402
 from spectralclustersupertree_amd import refine_supertree, score_supertree, synthetic  # noqa: E402
 from spectralclustersupertree_amd import refine as refine_mod  # noqa: E402
 from spectralclustersupertree_amd.backend import Device  # noqa: E402
-from spectralclustersupertree_amd.score import _leaf_ranges, _resident_tables, select_clades, supertree_arrays  # noqa: E402
+from spectralclustersupertree_amd.score import (_leaf_ranges, _resident_tables, resample_weights,  # noqa: E402
+                                                select_clades, supertree_arrays)
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
 from spectralclustersupertree_amd.treearrays import TreeArrays  # noqa: E402
 
@@ -381,6 +385,45 @@ def run_polytomies(dev: Device, size: str, per_degree: int = 4, repeats: int = 5
     return out
 
 
+def run_resample(dev: Device, size: str, n_rows, repeats: int = 5) -> dict:
+    """``scs_score_branch_resample`` on resident tables, a warm-up and ``repeats`` timed calls per row count R (row 0
+    of ones and R - 1 bootstrap replicates, seed 0; the rows stay on the device); beside it one
+    ``scs_score_branch_triplets`` call, which the same answer takes R of without the export."""
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    sup = random_binary_tree(2, n_taxa)
+    parent, taxon, tips = supertree_arrays(sup)
+    index = {x: i for i, x in enumerate(tips)}
+    out = {"size": size, "branch_resample": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "supertree_nodes": len(parent), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        out["branch_triplets_s_min_median_max"], bt = timed(lambda: dev.score_branch_triplets(tabs, parent, taxon))
+        one = out["branch_triplets_s_min_median_max"][1]
+        for rows in n_rows:
+            w = resample_weights(tabs.n_trees, rows - 1, None, "bootstrap", 0)
+            spread, res = timed(lambda w=w: dev.score_branch_resample(tabs, parent, taxon, w))
+            same = all(np.array_equal(res["rs_point"][x], bt[k])
+                       for x, k in enumerate(("bt_total", "bt_concordant", "bt_alt1", "bt_alt2")))
+            wins = res["rs_wins"].sum(axis=1)
+            out[f"rows_{rows}"] = {"s_min_median_max": spread, "over_one_branch_triplets_call": round(spread[1] / one, 3),
+                                   "rows_times_one_call_s": round(rows * one, 4),
+                                   "over_rows_times_one_call": round(spread[1] / (rows * one), 5),
+                                   "row_0_equals_branch_triplets": bool(same), "wins": [int(x) for x in wins]}
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -416,11 +459,19 @@ def main() -> None:
     ap.add_argument("--polytomies", action="store_true",
                     help="time scs_score_polytomies instead (a supertree with collapsed edges; --collapse N)")
     ap.add_argument("--collapse", type=int, default=4, help="how many nodes --polytomies collapses to each degree")
+    ap.add_argument("--branch-resample", type=int, action="append", metavar="R",
+                    help="time scs_score_branch_resample instead, with R weight rows (repeatable)")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
                     help="a caterpillar supertree in taxon order against caterpillar sources in reverse order")
     args = ap.parse_args()
+    if args.branch_resample:
+        with Device(0) as dev:
+            run_resample(dev, "200x6", [3], repeats=1)  # warm-up
+            for size in args.size or SIZES[:1]:
+                print(json.dumps(run_resample(dev, size, args.branch_resample)), flush=True)
+        return
     if args.polytomies:
         with Device(0) as dev:
             run_polytomies(dev, "200x6", per_degree=1, repeats=1)  # warm-up
