@@ -752,6 +752,20 @@ int scs_debug_comm_selftest(scs_ctx *ctx, int32_t count, const double *host_in, 
  * and writes every byte once). */
 int scs_debug_copy_bandwidth(scs_ctx *ctx, int64_t bytes, int32_t reps, double *gbs_out);
 
+/* The multi-block exclusive scan that carries the node-parallel forest split, the offsets of a level's
+ * trees and the analysis (csrc/scs_forest.hip, 4096 items per workgroup; the same code the product runs) on
+ * host rows: out[part][i] = op over in[part][j], j < i, for i in [0, n] -- entry n is the row's total.  op 0:
+ * sum (identity 0), op 1: maximum (identity -1).  in is n_parts x n, out n_parts x (n + 1), row-major;
+ * 1 <= n_parts <= 8. */
+int scs_debug_scan(scs_ctx *ctx, int32_t op, int32_t n_parts, int64_t n, const int32_t *in, int32_t *out);
+
+/* The plan of the thread-per-tree split kernels for a forest's offsets (node_off[n_trees + 1]), by the launcher's
+ * rule and the kernels' predicate, on the host (no device): *tpb_out trees per workgroup (64 ... 8),
+ * *n_groups_out workgroups, staged_out[g] = 1 where workgroup g copies its trees to LDS (at most SPLIT_CAP nodes),
+ * 0 where it walks them in place.  staged_out holds (n_trees + 7) / 8 bytes at least. */
+int scs_debug_split_plan(int32_t n_trees, const int64_t *node_off, int32_t *tpb_out, int32_t *n_groups_out,
+                         uint8_t *staged_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -446,6 +446,15 @@ class Device:
                                             nv.dptr(a), a.shape[1], a_col0, ka, nv.dptr(c), c.shape[1],
                                             float(sign), y.shape[0]))
 
+    def debug_scan(self, op: int, rows: np.ndarray) -> np.ndarray:
+        """The exclusive scan of every row of ``rows`` (int32 ``[n_parts, n]``; ``op`` 0 sum, 1 max) through the
+        multi-block scan of the forest split (``scs_debug_scan``): ``[n_parts, n + 1]``, the last entry the total."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        assert rows.ndim == 2
+        out = np.empty((rows.shape[0], rows.shape[1] + 1), dtype=np.int32)
+        nv.check(self._lib.scs_debug_scan(self._ctx, int(op), rows.shape[0], rows.shape[1], nv.iptr(rows), nv.iptr(out)))
+        return out
+
 
 class DeviceForest:
     """A source forest resident in HBM (``scs_forest``): preorder node arrays, and -- for the
@@ -593,6 +602,17 @@ class DeviceForest:
                                                    nv.dptr(length) if n else None, nv.dptr(support) if n else None,
                                                    nv.dptr(weights) if m else None))
         return node_off, parent, taxon, length, support, weights
+
+
+def debug_split_plan(node_off: np.ndarray):
+    """``scs_debug_split_plan``: ``(trees per workgroup, staged [workgroups] bool)`` of the thread-per-tree split
+    kernels for a forest's offsets -- the launcher's rule and the kernels' predicate, evaluated on the host."""
+    node_off = np.ascontiguousarray(node_off, dtype=np.int64)
+    m = len(node_off) - 1
+    tpb, groups = C.c_int32(0), C.c_int32(0)
+    staged = np.zeros((m + 7) // 8 + 1, dtype=np.uint8)
+    nv.check(nv.load_library().scs_debug_split_plan(m, nv.lptr(node_off), C.byref(tpb), C.byref(groups), staged.ctypes.data))
+    return int(tpb.value), staged[: groups.value].astype(bool)
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

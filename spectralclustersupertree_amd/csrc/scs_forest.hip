@@ -38,6 +38,14 @@ constexpr int SPLIT_THREADS = 64;   // trees per workgroup (one thread each)
 // loads, 100 cycles each from LDS against 2 000 from memory: 446 -> ~100 us per split of 5 000
 // trees of 47 nodes); larger trees are walked in place.
 constexpr int SPLIT_CAP = 2304;
+// (one predicate for both kernels, and for scs_debug_split_plan, which tells the tests which workgroups stage)
+__host__ __device__ inline bool split_staged(int64_t nodes) { return nodes <= SPLIT_CAP; }
+// trees per workgroup: as many as keep the workgroup's nodes inside the LDS copy, by the forest's average tree
+inline int split_trees_per_block(int64_t n_nodes, int n_trees) {
+    int tpb = SPLIT_THREADS;
+    while (tpb > 8 && (double)n_nodes / n_trees * tpb > 0.85 * SPLIT_CAP) tpb >>= 1;
+    return tpb;
+}
 constexpr size_t SPLIT_FILL_LDS = (size_t)SPLIT_CAP * (4 + 4 + 8 + 8 + 4 + 4 + 4 + 4 + 8 + 1) + 64;
 
 struct split_params {
@@ -78,7 +86,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_split_count(split_params p) {
     const int t = t0 + tid;
     const int np = p.n_parts;
     const int64_t n0 = p.node_off[t0], n1 = p.node_off[t1];
-    const bool stage = n1 - n0 <= SPLIT_CAP;
+    const bool stage = split_staged(n1 - n0);
     if (stage) {
         for (int i = tid; i < (int)(n1 - n0); i += SPLIT_THREADS) {
             l_par[i] = p.parent[n0 + i];
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_split_fill(split_params p) {
     const int np = p.n_parts;
     const int M = p.n_trees;
     const int64_t n0 = p.node_off[t0], n1 = p.node_off[t1];
-    const bool stage = n1 - n0 <= SPLIT_CAP;
+    const bool stage = split_staged(n1 - n0);
     const bool failed = p.flags[0] != 0;  // (uniform: written by the count kernel only)
     if (stage && !failed) {
         for (int i = tid; i < (int)(n1 - n0); i += SPLIT_THREADS) {
@@ -548,6 +556,14 @@ static int scan_exclusive(F in, int32_t *out, int64_t out_stride, int n_parts, i
     SCS_HIP_CHECK(hipGetLastError());
     return SCS_OK;
 }
+
+// scs_debug_scan: a plain row per part
+struct f_row {
+    const int32_t *a;
+    int64_t stride;
+    __device__ f_row with(int part) const { return f_row{a + (int64_t)part * stride, stride}; }
+    __device__ int32_t operator()(int64_t i) const { return a[i]; }
+};
 
 struct par_params {
     int32_t n_trees, n_parts, strategy, n_taxa;
@@ -1546,9 +1562,7 @@ static int forest_split(scs_ctx *ctx, const scs_forest *f, const int32_t *part_o
         SCS_TRY(scratch.alloc((size_t)N * 4, (void **)&p.stk_c));
         SCS_TRY(scratch.alloc((size_t)N, (void **)&p.mark));
         SCS_HIP_CHECK(hipMemsetAsync(p.mark, 0, (size_t)N, s));
-        // trees per workgroup: as many as keep the workgroup's nodes inside the LDS copy
-        int tpb = SPLIT_THREADS;
-        while (tpb > 8 && (double)N / M * tpb > 0.85 * SPLIT_CAP) tpb >>= 1;
+        const int tpb = split_trees_per_block(N, M);
         p.tpb = tpb;
         const unsigned grid = (unsigned)((M + tpb - 1) / tpb);
         // (once per process: a recursion makes tens of thousands of splits; a part with less LDS per workgroup than
@@ -1882,5 +1896,61 @@ extern "C" int scs_forest_slice(scs_ctx *ctx, const scs_forest *f, int32_t t_beg
         c->n_leaves = c->n_nodes;
     }
     *out = c.release();
+    return SCS_OK;
+}
+
+
+// The multi-block exclusive scan every split and every analysis runs on (scan_exclusive above: the SAME template
+// the product calls, over a functor that reads the uploaded row), on host rows -- for the tests of its block
+// edges: out[part][i] = op over in[part][j], j < i, i in [0, n]; identity 0 for the sum, -1 for the maximum, row
+// stride n + 1 and block sums sized as the callers size them.
+extern "C" int scs_debug_scan(scs_ctx *ctx, int32_t op, int32_t n_parts, int64_t n, const int32_t *in, int32_t *out) {
+    SCS_REQUIRE(ctx && out && (in || n == 0), "scs_debug_scan: null argument");
+    SCS_REQUIRE(op == SCAN_SUM || op == SCAN_MAX, "scs_debug_scan: op must be 0 (sum) or 1 (max)");
+    SCS_REQUIRE(n_parts >= 1 && n_parts <= SPLIT_MAX_PARTS, "scs_debug_scan: 1 .. %d parts (asked: %d)", SPLIT_MAX_PARTS,
+                n_parts);
+    SCS_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) - 8, "scs_debug_scan: n must be in [0, 2^31 - 8)");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    struct scratch_t {
+        scs_ctx *ctx;
+        std::vector<void *> blocks;
+        ~scratch_t() {
+            for (void *p : blocks) scs_block_release(ctx, p);
+        }
+        int alloc(size_t bytes, void **out) {
+            SCS_TRY(scs_block_alloc(ctx, bytes, out));
+            blocks.push_back(*out);
+            return SCS_OK;
+        }
+    } scratch{ctx, {}};
+    const int64_t row = n + 1;
+    int32_t *d_in = nullptr, *d_out = nullptr, *block_sums = nullptr;
+    SCS_TRY(scratch.alloc((size_t)n_parts * std::max<int64_t>(n, 1) * 4, (void **)&d_in));
+    SCS_TRY(scratch.alloc((size_t)n_parts * row * 4, (void **)&d_out));
+    SCS_TRY(scratch.alloc((size_t)((row + 4095) / 4096 + 1) * 4 * SPLIT_MAX_PARTS, (void **)&block_sums));
+    if (n > 0) SCS_HIP_CHECK(hipMemcpyAsync(d_in, in, (size_t)n_parts * n * 4, hipMemcpyHostToDevice, s));
+    if (op == SCAN_SUM) SCS_TRY((scan_exclusive<SCAN_SUM>(f_row{d_in, n}, d_out, row, n_parts, n, 0, block_sums, s)));
+    else SCS_TRY((scan_exclusive<SCAN_MAX>(f_row{d_in, n}, d_out, row, n_parts, n, -1, block_sums, s)));
+    SCS_HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n_parts * row * 4, hipMemcpyDeviceToHost, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
+    return SCS_OK;
+}
+
+// What the thread-per-tree kernels make of a forest's offsets, computed on the host by the launcher's own rule and
+// the kernels' own predicate (no device involved): the trees per workgroup, and per workgroup whether its trees are
+// copied to LDS (1) or walked in place (0) -- so that a test can place a workgroup on either side of SPLIT_CAP and
+// know that it is there.
+extern "C" int scs_debug_split_plan(int32_t n_trees, const int64_t *node_off, int32_t *tpb_out, int32_t *n_groups_out,
+                                    uint8_t *staged_out) {
+    SCS_REQUIRE(node_off && tpb_out && n_groups_out && staged_out && n_trees >= 1, "scs_debug_split_plan: bad argument");
+    const int tpb = split_trees_per_block(node_off[n_trees] - node_off[0], n_trees);
+    const int groups = (n_trees + tpb - 1) / tpb;
+    for (int g = 0; g < groups; ++g) {
+        const int t0 = g * tpb, t1 = std::min(n_trees, t0 + tpb);
+        staged_out[g] = split_staged(node_off[t1] - node_off[t0]) ? 1 : 0;
+    }
+    *tpb_out = tpb;
+    *n_groups_out = groups;
     return SCS_OK;
 }

@@ -25,6 +25,7 @@ from spectralclustersupertree_amd import levels, scs, synthetic
 from spectralclustersupertree_amd.backend import Device
 from spectralclustersupertree_amd.scs import trace_nodes
 from spectralclustersupertree_amd.treearrays import _STRATEGY_CODE, ResidentArrays, TreeArrays
+from tests.forest_reference import same_partition
 from tests.test_gpu_recursion import compare_with_oracle, recursion_input
 from tests.test_treearrays import random_forest, tables_equal
 
@@ -360,11 +361,11 @@ def test_level_split_equals_the_host_split_of_every_node(dev, monkeypatch, strat
             for i, c in enumerate(comp):
                 first_of.setdefault(int(c), int(want.present_taxa()[i]))
             assert [first_of[int(c)] for c in comp] == roots.tolist()
+            # the signatures part the child's taxa exactly as the contraction groups do, in both directions: contracted
+            # taxa carry equal pairs, and no two groups share one (all-zero signatures would pass the first half alone)
             groups = fl.contraction_groups(local)
             s = sig[base:base + size][here]
-            for i in range(len(groups)):
-                for j in range(i + 1, len(groups)):
-                    if groups[i] == groups[j]:  # contracted taxa carry equal signatures (the converse: exact path)
-                        assert s[i, 0] == s[j, 0] and s[i, 1] == s[j, 1]
+            assert same_partition(groups.tolist(), [(int(a), int(b)) for a, b in s])
+            assert not sig[base:base + size][~here].any()  # an id no tree holds carries (0, 0)
         t_at += m
     assert t_at == union.n_trees
