@@ -759,6 +759,17 @@ int scs_debug_copy_bandwidth(scs_ctx *ctx, int64_t bytes, int32_t reps, double *
  * 1 <= n_parts <= 8. */
 int scs_debug_scan(scs_ctx *ctx, int32_t op, int32_t n_parts, int64_t n, const int32_t *in, int32_t *out);
 
+/* The stored block of a graph as it lies in device memory, padding columns included: what = 0 the rows of W
+ * (rows x ld doubles), what = 1 the single-precision image (rows x ld floats), made if the graph has none by the
+ * degree pass the solver runs, what = 2 the degrees of ALL V vertices as this rank holds them (V doubles; what the
+ * solver scales by).  Modes 1 and 2 are collective over the communicator when world > 1 and the degrees are not
+ * known yet; nothing else is run.  info_out[4]: [0] rows, [1] ld (elements), [2] the first stored column (SCS_BUILD_UPPER
+ * graphs store columns [col0, V)), [3] image only: 1 when whole rows are defined (a row-partitioned rank), 0 when
+ * row r (global) is defined from column (r / 512) * 512 on.  out may be NULL: info_out alone is filled (no image is
+ * made).  SCS_EUNSUP, never something else, where the library makes no image: a matrix-free graph (what = 0 as
+ * well: it has no matrix), an SCS_BUILD_UPPER graph, a row block on one rank, no memory. */
+int scs_debug_graph_raw(scs_ctx *ctx, scs_graph *graph, int32_t what, void *out, int32_t *info_out);
+
 /* The plan of the thread-per-tree split kernels for a forest's offsets (node_off[n_trees + 1]), by the launcher's
  * rule and the kernels' predicate, on the host (no device): *tpb_out trees per workgroup (64 ... 8),
  * *n_groups_out workgroups, staged_out[g] = 1 where workgroup g copies its trees to LDS (at most SPLIT_CAP nodes),

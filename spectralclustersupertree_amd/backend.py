@@ -867,6 +867,32 @@ class DeviceGraph:
                                                   int(reps), nv.dptr(y), nv.iptr(info)))
         return y, dict(zip(self.APPLY_INFO, (int(v) for v in info)))
 
+    def raw(self, what: int = 0):
+        """``scs_debug_graph_raw``: the stored block with all ``ld`` columns -- ``what`` 0 the rows of W (float64),
+        1 the single-precision image (float32; made by the solver's degree pass if missing) -- and a dict with
+        ``rows``, ``ld``, ``col0`` and ``first_col`` (the first defined column of every row; all zero for W and for
+        a row-partitioned rank's image).  ``ScsError`` with code ``EUNSUP`` where the library makes no image.  Mode 2
+        of the entry has another shape: ``degrees_all``."""
+        if what not in (0, 1):
+            msg = f"DeviceGraph.raw: what must be 0 (W) or 1 (image), not {what!r}"
+            raise ValueError(msg)
+        info = np.zeros(4, dtype=np.int32)
+        nv.check(self.dev._lib.scs_debug_graph_raw(self.dev._ctx, self._h, int(what), None, nv.iptr(info)))
+        rows, ld = int(info[0]), int(info[1])
+        out = np.empty((rows, ld), dtype=np.float32 if what else np.float64)
+        nv.check(self.dev._lib.scs_debug_graph_raw(self.dev._ctx, self._h, int(what), out.ctypes.data, nv.iptr(info)))
+        rb = self.shape[1]
+        first = (np.zeros(rows, dtype=np.int64) if (not what or info[3])
+                 else (rb + np.arange(rows, dtype=np.int64)) // 512 * 512)
+        return out, {"rows": rows, "ld": ld, "col0": int(info[2]), "first_col": first}
+
+    def degrees_all(self) -> np.ndarray:
+        """The degrees of ALL vertices as this rank holds them (``scs_debug_graph_raw``, mode 2)."""
+        info = np.zeros(4, dtype=np.int32)
+        out = np.empty(self.shape[0])
+        nv.check(self.dev._lib.scs_debug_graph_raw(self.dev._ctx, self._h, 2, out.ctypes.data, nv.iptr(info)))
+        return out
+
     def fiedler(self, x_init: np.ndarray | None = None, tol: float = DEFAULT_TOL,
                 max_iter: int = DEFAULT_MAX_ITER, block: int = 0):
         """V x 2 spectral embedding + solver report (reference: scs.py:252).

@@ -1519,3 +1519,53 @@ extern "C" int scs_graph_degrees(scs_ctx *ctx, scs_graph *g, double *out) {
                             (size_t)(g->row_end - g->row_begin) * 8, hipMemcpyDeviceToHost));
     return SCS_OK;
 }
+
+// The stored block as it lies in memory, padding columns included (tests/test_gpu_build_edges.py): what = 0 the
+// rows of W, what = 1 the single-precision image, made by the product's own degree pass, what = 2 the degrees of
+// ALL vertices as this rank holds them.  No kernel of its own.
+extern "C" int scs_debug_graph_raw(scs_ctx *ctx, scs_graph *g, int32_t what, void *out, int32_t *info_out) {
+    SCS_REQUIRE(ctx && g && info_out, "scs_debug_graph_raw: null argument");
+    SCS_REQUIRE(what >= 0 && what <= 2, "scs_debug_graph_raw: what must be 0 (W), 1 (image) or 2 (degrees), not %d",
+                what);
+    if (g->mf && what != 2) {
+        scs_set_error("scs_debug_graph_raw: a matrix-free graph has neither a matrix nor an image");
+        return SCS_EUNSUP;
+    }
+    const int rows = g->row_end - g->row_begin;
+    const bool img_rows = ctx->comm.world > 1;  // (a row-partitioned rank keeps whole rows: w32_full)
+    if (what == 1) {
+        // scs_graph_prepare_degrees_begin's own conditions: where it makes no image there is none to return
+        if (g->upper) {
+            scs_set_error("scs_debug_graph_raw: an SCS_BUILD_UPPER graph has no image");
+            return SCS_EUNSUP;
+        }
+        if (!img_rows && !(g->row_begin == 0 && rows == g->n)) {
+            scs_set_error("scs_debug_graph_raw: a row block [%d, %d) of %d on one rank has no image", g->row_begin,
+                          g->row_end, g->n);
+            return SCS_EUNSUP;
+        }
+    }
+    info_out[0] = rows;
+    info_out[1] = (int32_t)g->ld;
+    info_out[2] = g->col0;
+    info_out[3] = (what == 1 && img_rows) ? 1 : 0;
+    if (!out) return SCS_OK;
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    if (what == 1) {
+        SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, true));
+        SCS_TRY(scs_graph_prepare_degrees(ctx, g));
+        if (!g->have_w32 || !g->d_w32) {
+            scs_set_error("scs_debug_graph_raw: the image could not be made (no memory)");
+            return SCS_EUNSUP;
+        }
+    }
+    if (what == 2) SCS_TRY(scs_graph_prepare_degrees(ctx, g));
+    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (what == 2)
+        SCS_HIP_CHECK(hipMemcpy(out, g->d_deg, (size_t)g->n * 8, hipMemcpyDeviceToHost));
+    else if (what == 1)
+        SCS_HIP_CHECK(hipMemcpy(out, g->d_w32, (size_t)rows * (size_t)g->ld * 4, hipMemcpyDeviceToHost));
+    else
+        SCS_HIP_CHECK(hipMemcpy(out, g->d_w, (size_t)rows * (size_t)g->ld * 8, hipMemcpyDeviceToHost));
+    return SCS_OK;
+}
