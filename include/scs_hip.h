@@ -777,6 +777,21 @@ int scs_debug_graph_raw(scs_ctx *ctx, scs_graph *graph, int32_t what, void *out,
 int scs_debug_split_plan(int32_t n_trees, const int64_t *node_off, int32_t *tpb_out, int32_t *n_groups_out,
                          uint8_t *staged_out);
 
+/* The plan of one scs_score_* call on the host (no device work, no device memory): the batches sc_begin makes of the
+ * source trees and what scs_score_triplets decides per batch, by the functions the exports call.  The trees are
+ * those of `sources`, or, when `sources` is NULL, tree_off[n_trees + 1] (with `sources`, n_trees must be its tree
+ * count and tree_off is not read).  super_leaves: the supertree's tips; max_batch_trees as for the exports;
+ * extra_per_leaf / extra_per_tree: the export's own workspace bytes per leaf and per tree of a batch (0 / 0 for
+ * scs_score_supertree and scs_score_concordance, 32 / 8 for scs_score_triplets, 8 * levels + 8 / 0 for
+ * scs_score_conflicts).  *n_batches_out batches; bstart_out[n_batches + 1] (room for n_trees + 1) the first tree of
+ * every batch and n_trees; info_out[2] = {levels of the per-tree tables, row stride in entries}; per batch (room for
+ * max(n_trees, 1)): words_out the 32-bit words of a bitset row of the pair kernel, zb_out its S' nodes per workgroup,
+ * wg_out its workgroups. */
+int scs_debug_score_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t super_leaves,
+                         int32_t max_batch_trees, int64_t extra_per_leaf, int64_t extra_per_tree,
+                         int32_t *n_batches_out, int32_t *bstart_out, int64_t *info_out, int32_t *words_out,
+                         int32_t *zb_out, int64_t *wg_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -455,6 +455,11 @@ class Device:
         nv.check(self._lib.scs_debug_scan(self._ctx, int(op), rows.shape[0], rows.shape[1], nv.iptr(rows), nv.iptr(out)))
         return out
 
+    def debug_score_plan(self, sources, super_leaves: int, batch_trees: int = 0, extra_per_leaf: int = 0,
+                         extra_per_tree: int = 0) -> dict:
+        """``debug_score_plan`` (below) for tables on this device."""
+        return debug_score_plan(sources, super_leaves, batch_trees, extra_per_leaf, extra_per_tree)
+
 
 class DeviceForest:
     """A source forest resident in HBM (``scs_forest``): preorder node arrays, and -- for the
@@ -613,6 +618,29 @@ def debug_split_plan(node_off: np.ndarray):
     staged = np.zeros((m + 7) // 8 + 1, dtype=np.uint8)
     nv.check(nv.load_library().scs_debug_split_plan(m, nv.lptr(node_off), C.byref(tpb), C.byref(groups), staged.ctypes.data))
     return int(tpb.value), staged[: groups.value].astype(bool)
+
+
+def debug_score_plan(sources, super_leaves: int, batch_trees: int = 0, extra_per_leaf: int = 0,
+                     extra_per_tree: int = 0) -> dict:
+    """``scs_debug_score_plan``: the batches a ``scs_score_*`` export makes of ``sources`` (``DeviceTables``, or the
+    ``tree_off`` array of tables that need not be on a device) for a supertree of ``super_leaves`` tips, and the pair
+    kernel's plan per batch -- ``bstart`` (the first tree of every batch, then the tree count), ``levels``,
+    ``row_stride``, and per batch ``words``, ``zb``, ``workgroups``.  The library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    nb = C.c_int32(0)
+    bstart = np.zeros(m + 1, dtype=np.int32)
+    info = np.zeros(2, dtype=np.int64)
+    words, zb = np.zeros(max(m, 1), dtype=np.int32), np.zeros(max(m, 1), dtype=np.int32)
+    wg = np.zeros(max(m, 1), dtype=np.int64)
+    nv.check(nv.load_library().scs_debug_score_plan(
+        handle, m, None if off is None else nv.lptr(off), int(super_leaves), int(batch_trees), int(extra_per_leaf),
+        int(extra_per_tree), C.byref(nb), nv.iptr(bstart), nv.lptr(info), nv.iptr(words), nv.iptr(zb), nv.lptr(wg)))
+    k = int(nb.value)
+    return {"bstart": bstart[: k + 1].astype(np.int64), "levels": int(info[0]), "row_stride": int(info[1]),
+            "words": words[:k].astype(np.int64), "zb": zb[:k].astype(np.int64), "workgroups": wg[:k].copy()}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

@@ -2469,6 +2469,52 @@ struct sc_call {
     char *d_extra = nullptr, *d_extra_batch = nullptr;
 };
 
+// the batches of one call, for sc_begin and scs_debug_score_plan alike: rows (V per tree) + per-leaf arrays and tables
+// (levels of the call's largest tree) + the caller's bytes per leaf and per tree; a batch ends before the tree that
+// would take it past SC_BUDGET, or at max_batch_trees trees (> 0).  off[M + 1]; bstart gets the first tree of every
+// batch and M
+void sc_plan_batches(const int64_t *off, int32_t M, int64_t max_leaves, int64_t s_leaves, int32_t max_batch_trees,
+                     uint64_t extra_per_leaf, uint64_t extra_per_tree, int &levels_out, int64_t &row_stride_out,
+                     std::vector<int32_t> &bstart) {
+    const int64_t row_stride = row_stride_out = scs_round_up(std::max<int64_t>(s_leaves, 1), SC_ROW_ALIGN);
+    const int levels = levels_out = sc_levels_host(std::max<int64_t>(max_leaves, 1));
+    const auto per_tree = [&](int32_t t) {
+        const int64_t n = off[t + 1] - off[t];
+        return (uint64_t)row_stride * 4 + (uint64_t)n * (4 * 3 + 8 * levels + 4 * (levels - 1) + extra_per_leaf) +
+               extra_per_tree;
+    };
+    bstart.assign(1, 0);
+    uint64_t acc = 0;
+    for (int32_t t = 0; t < M; ++t) {
+        const int32_t nb = t - bstart.back();
+        if (nb > 0 && (acc + per_tree(t) > SC_BUDGET || (max_batch_trees > 0 && nb >= max_batch_trees))) {
+            bstart.push_back(t);
+            acc = 0;
+        }
+        acc += per_tree(t);
+    }
+    bstart.push_back(M);
+}
+
+// the pair kernel's plan per batch, for scs_score_triplets and scs_debug_score_plan alike: W words per bitset row
+// (largest tree of the batch), zb S' nodes per workgroup; blk: the first pair workgroup of every tree, ceil((n - 2) /
+// zb) of them (n - 2 bounds the non-root internal nodes)
+void sc_trip_plan(const int64_t *off, const std::vector<int32_t> &bstart, std::vector<int> &words,
+                  std::vector<int> &zbs, std::vector<int64_t> &blk) {
+    const size_t n_batches = bstart.size() - 1;
+    words.assign(n_batches, 0);
+    zbs.assign(n_batches, 0);
+    blk.assign((size_t)bstart.back() + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        zbs[b] = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (16 * words[b])));
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t)
+            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+    }
+}
+
 // checks, host layout, block, uploads (their errors in e); SCS_OK or the code of a failure before the block exists
 int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nodes, const int32_t *parent,
              const int32_t *taxon, int32_t max_batch_trees, size_t extra_bytes, uint64_t extra_per_leaf,
@@ -2537,27 +2583,11 @@ int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nod
     hipStream_t s = ctx->stream;
 
     // ---- batches: rows (V per tree) + per-leaf arrays and tables (levels of the batch's largest tree) ----
-    const int64_t row_stride = c.row_stride = scs_round_up(std::max<int64_t>(n_leaves, 1), SC_ROW_ALIGN);
-    const int levels = c.levels = sc_levels_host(std::max<int64_t>(src->max_leaves, 1));
-    const auto per_tree = [&](int32_t t) {
-        const int64_t n = off[t + 1] - off[t];
-        return (uint64_t)row_stride * 4 + (uint64_t)n * (4 * 3 + 8 * levels + 4 * (levels - 1) + extra_per_leaf) +
-               extra_per_tree;
-    };
     std::vector<int32_t> &bstart = c.bstart;
-    bstart.assign(1, 0);
-    {
-        uint64_t acc = 0;
-        for (int32_t t = 0; t < M; ++t) {
-            const int32_t nb = t - bstart.back();
-            if (nb > 0 && (acc + per_tree(t) > SC_BUDGET || (max_batch_trees > 0 && nb >= max_batch_trees))) {
-                bstart.push_back(t);
-                acc = 0;
-            }
-            acc += per_tree(t);
-        }
-        bstart.push_back(M);
-    }
+    sc_plan_batches(off.data(), M, src->max_leaves, n_leaves, max_batch_trees, extra_per_leaf, extra_per_tree, c.levels,
+                    c.row_stride, bstart);
+    const int64_t row_stride = c.row_stride;
+    const int levels = c.levels;
     int64_t max_rows = 0, max_lb = 0;
     for (size_t b = 0; b + 1 < bstart.size(); ++b) {
         max_rows = std::max<int64_t>(max_rows, bstart[b + 1] - bstart[b]);
@@ -2765,19 +2795,11 @@ extern "C" int scs_score_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n
     auto *d_ylist = (int4 *)c.d_extra_batch;
     auto *d_zlist = d_ylist + c.max_lb;
     auto *d_ycnt = (int32_t *)(d_zlist + c.max_lb);
-    // per batch: W words per bitset row (largest tree of the batch), zb S' nodes per workgroup; blk: the first pair
-    // workgroup of every tree, ceil((n - 2) / zb) of them (n - 2 bounds the non-root internal nodes)
+    // per batch: W words per bitset row, zb S' nodes per workgroup; blk: the first pair workgroup of every tree
     const size_t n_batches = c.bstart.size() - 1;
-    std::vector<int> words(n_batches), zbs(n_batches);
-    std::vector<int64_t> blk((size_t)M + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        zbs[b] = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (16 * words[b])));
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
-            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
-    }
+    std::vector<int> words, zbs;
+    std::vector<int64_t> blk;
+    sc_trip_plan(off.data(), c.bstart, words, zbs, blk);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
@@ -2827,6 +2849,45 @@ extern "C" int scs_score_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n
         if (t_super) t_super[t] = (int64_t)cnt[t];
         if (t_source) t_source[t] = (int64_t)cnt[M + t];
         if (t_shared) t_shared[t] = (int64_t)cnt[2 * M + t];
+    }
+    return SCS_OK;
+}
+
+// the plan of one scoring call on the host: what sc_begin and scs_score_triplets decide, by their own functions
+extern "C" int scs_debug_score_plan(const scs_tables *src, int32_t n_trees, const int64_t *tree_off,
+                                    int32_t super_leaves, int32_t max_batch_trees, int64_t extra_per_leaf,
+                                    int64_t extra_per_tree, int32_t *n_batches_out, int32_t *bstart_out,
+                                    int64_t *info_out, int32_t *words_out, int32_t *zb_out, int64_t *wg_out) {
+    SCS_REQUIRE((src || tree_off) && n_batches_out && bstart_out && info_out && words_out && zb_out && wg_out,
+                "scs_debug_score_plan: null argument");
+    SCS_REQUIRE(!src || n_trees == src->n_trees, "scs_debug_score_plan: the tables hold %d trees, not %d",
+                src ? src->n_trees : 0, n_trees);
+    SCS_REQUIRE(n_trees >= 0 && super_leaves >= 0 && extra_per_leaf >= 0 && extra_per_tree >= 0,
+                "scs_debug_score_plan: negative argument");
+    const int64_t *off = src ? src->h_tree_off.data() : tree_off;
+    int64_t max_leaves = src ? src->max_leaves : 0;
+    if (!src)
+        for (int32_t t = 0; t < n_trees; ++t) {
+            SCS_REQUIRE(off[t + 1] >= off[t], "scs_debug_score_plan: tree_off decreases at tree %d", t);
+            max_leaves = std::max(max_leaves, off[t + 1] - off[t]);
+        }
+    int levels = 0;
+    int64_t row_stride = 0;
+    std::vector<int32_t> bstart;
+    sc_plan_batches(off, n_trees, max_leaves, super_leaves, max_batch_trees, (uint64_t)extra_per_leaf,
+                    (uint64_t)extra_per_tree, levels, row_stride, bstart);
+    std::vector<int> words, zbs;
+    std::vector<int64_t> blk;
+    sc_trip_plan(off, bstart, words, zbs, blk);
+    const size_t n_batches = bstart.size() - 1;
+    *n_batches_out = (int32_t)n_batches;
+    std::copy(bstart.begin(), bstart.end(), bstart_out);
+    info_out[0] = levels;
+    info_out[1] = row_stride;
+    for (size_t b = 0; b < n_batches; ++b) {
+        words_out[b] = words[b];
+        zb_out[b] = zbs[b];
+        wg_out[b] = blk[bstart[b + 1]] - blk[bstart[b]];
     }
     return SCS_OK;
 }
