@@ -792,6 +792,21 @@ int scs_debug_score_plan(const scs_tables *sources, int32_t n_trees, const int64
                          int32_t *n_batches_out, int32_t *bstart_out, int64_t *info_out, int32_t *words_out,
                          int32_t *zb_out, int64_t *wg_out);
 
+/* The same for scs_score_branch_triplets / scs_score_branch_resample (one plan: both call sc_bt_plan) and for
+ * scs_score_taxon_triplets, on the host, by the functions those exports call.  Inputs as for scs_debug_score_plan
+ * (extra_per_leaf / extra_per_tree: 40 / 8 for the branch export, 40 / 8 + 32 x supertree nodes for the resample,
+ * 72 / 24 for the taxon export) and max_lds_bytes as for scs_score_taxon_triplets (0: no cap).  *n_batches_out and
+ * bstart_out as there.  bt_out[4 x batch] = {words, zb, dynamic LDS bytes of the launch, workgroups} of k_bt_pairs /
+ * k_rs_pairs.  tx_out[14 x batch]: for each of the three LDS bins {zb, dcap (0: the bin is not used and not
+ * launched), dynamic LDS bytes, workgroups} of k_tx_pairs<false>, then 1 when the batch launches the slab kernel, and
+ * the dynamic LDS bytes of that launch.
+ * call_out[3] = {need_slab, slab_wgs, slab_stride} of the call.  Room for max(n_trees, 1) batches in bt_out and
+ * tx_out. */
+int scs_debug_branch_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t super_leaves,
+                          int32_t max_batch_trees, int64_t extra_per_leaf, int64_t extra_per_tree,
+                          int32_t max_lds_bytes, int32_t *n_batches_out, int32_t *bstart_out, int64_t *bt_out,
+                          int64_t *tx_out, int64_t *call_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -460,6 +460,11 @@ class Device:
         """``debug_score_plan`` (below) for tables on this device."""
         return debug_score_plan(sources, super_leaves, batch_trees, extra_per_leaf, extra_per_tree)
 
+    def debug_branch_plan(self, sources, super_leaves: int, batch_trees: int = 0, extra_per_leaf: int = 0,
+                          extra_per_tree: int = 0, lds_bytes: int = 0) -> dict:
+        """``debug_branch_plan`` (below) for tables on this device."""
+        return debug_branch_plan(sources, super_leaves, batch_trees, extra_per_leaf, extra_per_tree, lds_bytes)
+
 
 class DeviceForest:
     """A source forest resident in HBM (``scs_forest``): preorder node arrays, and -- for the
@@ -641,6 +646,36 @@ def debug_score_plan(sources, super_leaves: int, batch_trees: int = 0, extra_per
     k = int(nb.value)
     return {"bstart": bstart[: k + 1].astype(np.int64), "levels": int(info[0]), "row_stride": int(info[1]),
             "words": words[:k].astype(np.int64), "zb": zb[:k].astype(np.int64), "workgroups": wg[:k].copy()}
+
+
+def debug_branch_plan(sources, super_leaves: int, batch_trees: int = 0, extra_per_leaf: int = 0,
+                      extra_per_tree: int = 0, lds_bytes: int = 0) -> dict:
+    """``scs_debug_branch_plan``: the plans of ``scs_score_branch_triplets`` / ``scs_score_branch_resample`` and of
+    ``scs_score_taxon_triplets`` for ``sources`` (as for ``debug_score_plan``) -- ``bstart``; per batch ``bt_words``,
+    ``bt_zb``, ``bt_lds``, ``bt_workgroups``; per batch and LDS bin ``tx_zb``, ``tx_dcap``, ``tx_lds``,
+    ``tx_workgroups`` (batches x 3; ``tx_dcap`` 0: the bin is not launched); per batch ``tx_slab_launch`` and
+    ``tx_slab_lds`` (the slab kernel's launch bytes); and once
+    ``need_slab``, ``slab_wgs``, ``slab_stride``.  The library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    nb = C.c_int32(0)
+    bstart = np.zeros(m + 1, dtype=np.int32)
+    bt = np.zeros((max(m, 1), 4), dtype=np.int64)
+    tx = np.zeros((max(m, 1), 14), dtype=np.int64)
+    call = np.zeros(3, dtype=np.int64)
+    nv.check(nv.load_library().scs_debug_branch_plan(
+        handle, m, None if off is None else nv.lptr(off), int(super_leaves), int(batch_trees), int(extra_per_leaf),
+        int(extra_per_tree), int(lds_bytes), C.byref(nb), nv.iptr(bstart), nv.lptr(bt), nv.lptr(tx), nv.lptr(call)))
+    k = int(nb.value)
+    bins = tx[:k, :12].reshape(k, 3, 4)
+    return {"bstart": bstart[: k + 1].astype(np.int64), "bt_words": bt[:k, 0].copy(), "bt_zb": bt[:k, 1].copy(),
+            "bt_lds": bt[:k, 2].copy(), "bt_workgroups": bt[:k, 3].copy(), "tx_zb": bins[:, :, 0].copy(),
+            "tx_dcap": bins[:, :, 1].copy(), "tx_lds": bins[:, :, 2].copy(), "tx_workgroups": bins[:, :, 3].copy(),
+            "tx_slab_launch": tx[:k, 12].copy(), "tx_slab_lds": tx[:k, 13].copy(), "need_slab": int(call[0]),
+            "slab_wgs": int(call[1]),
+            "slab_stride": int(call[2])}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

@@ -2515,6 +2515,28 @@ void sc_trip_plan(const int64_t *off, const std::vector<int32_t> &bstart, std::v
     }
 }
 
+// the same for k_bt_pairs / k_rs_pairs, for scs_score_branch_triplets, scs_score_branch_resample and
+// scs_debug_branch_plan alike: zb records per workgroup (three rows of int2 each), lds the launch's dynamic LDS (at
+// least the 768 bytes of the workgroup's wave sums); blk: ceil((n - 2) / zb) workgroups a tree (a tree is decisive for
+// at most n - 2 branches)
+void sc_bt_plan(const int64_t *off, const std::vector<int32_t> &bstart, std::vector<int> &words,
+                std::vector<int> &zbs, std::vector<size_t> &lds, std::vector<int64_t> &blk) {
+    const size_t n_batches = bstart.size() - 1;
+    words.assign(n_batches, 0);
+    zbs.assign(n_batches, 0);
+    lds.assign(n_batches, 0);
+    blk.assign((size_t)bstart.back() + 1, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
+        lds[b] = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b], (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t)
+            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+    }
+}
+
 // checks, host layout, block, uploads (their errors in e); SCS_OK or the code of a failure before the block exists
 int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nodes, const int32_t *parent,
              const int32_t *taxon, int32_t max_batch_trees, size_t extra_bytes, uint64_t extra_per_leaf,
@@ -3091,19 +3113,13 @@ extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, in
     for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
     for (int32_t v = 1; v < n_nodes; ++v)
         if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
-    // per batch: W words per bitset row (largest tree of the batch), zb records per workgroup; blk: the first pair
-    // workgroup of every tree, ceil((n - 2) / zb) of them (a tree is decisive for at most n - 2 branches)
+    // per batch: W words per bitset row, zb records per workgroup and the launch's LDS; blk: the first pair workgroup
+    // of every tree
     const size_t n_batches = c.bstart.size() - 1;
-    std::vector<int> words(n_batches), zbs(n_batches);
-    std::vector<int64_t> blk((size_t)M + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
-            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
-    }
+    std::vector<int> words, zbs;
+    std::vector<size_t> ldss;
+    std::vector<int64_t> blk;
+    sc_bt_plan(off.data(), c.bstart, words, zbs, ldss, blk);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_node, 0, nn * 32, s);
@@ -3141,10 +3157,7 @@ extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, in
         if (!sc_launched(e)) break;
         const int64_t n_wg = blk[t0 + nb] - blk[t0];
         if (n_wg == 0) continue;
-        // (at least the 768 bytes of the workgroup's wave sums)
-        const size_t lds = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b],
-                                            (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
-        k_bt_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
+        k_bt_pairs<<<(unsigned)n_wg, SC_THREADS, ldss[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
                                                            c.d_mm, zbs[b], words[b], d_node + nn, (int64_t)nn,
                                                            d_cnt + M + t0, d_cnt + 2 * (int64_t)M + t0);
         if (!sc_launched(e)) break;
@@ -3196,6 +3209,54 @@ sc_tx_plan sc_tx_plan_of(int W, int lds_cap) {
     return p;
 }
 
+// what a call decides once, for scs_score_taxon_triplets and scs_debug_branch_plan alike: the LDS cap, and the slab
+// path -- needed when a node's arrays (at most 2 m + 1 entries) may exceed the largest bin of the largest tree
+struct sc_tx_call {
+    int lds_cap = 0, slab_wgs = 0;
+    int64_t slab_stride = 0;
+    bool need_slab = false;
+};
+
+sc_tx_call sc_tx_call_of(int64_t m_max, int32_t max_lds_bytes) {
+    sc_tx_call tc;
+    tc.lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    tc.slab_stride = 2 * m_max + 2 + TX_SLAB_PAD;
+    tc.need_slab = 2 * m_max + 1 > sc_tx_plan_of((int)(m_max >> 5) + 1, tc.lds_cap).dcap_max;
+    tc.slab_wgs = !tc.need_slab ? 0
+                                : (int)std::min<uint64_t>(TX_SLAB_WGS,
+                                                          std::max<uint64_t>(1, TX_SLAB_BYTES / (tc.slab_stride * 8)));
+    return tc;
+}
+
+// the slab kernel's dynamic LDS: the two rows of its one node
+size_t sc_tx_slab_lds(int W) { return (size_t)16 * W; }
+
+// ... and per batch: W words per bitset row (largest tree of the batch), the plan of its bins and whether the slab
+// kernel is launched; blk[TX_BINS][M + 1]: per bin the first pair workgroup of every tree, ceil((n - 2) / zb) of them
+// (n - 2 bounds the nodes of any list)
+void sc_tx_batches(const int64_t *off, const std::vector<int32_t> &bstart, const sc_tx_call &tc,
+                   std::vector<int> &words, std::vector<sc_tx_plan> &plans, std::vector<char> &slab_launch,
+                   std::vector<int64_t> &blk) {
+    const size_t n_batches = bstart.size() - 1;
+    const int32_t M = bstart.back();
+    words.assign(n_batches, 0);
+    plans.resize(n_batches);
+    slab_launch.assign(n_batches, 0);
+    blk.assign(((size_t)M + 1) * TX_BINS, 0);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t nmax = 0;
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+        words[b] = (int)(nmax >> 5) + 1;
+        plans[b] = sc_tx_plan_of(words[b], tc.lds_cap);
+        slab_launch[b] = tc.slab_wgs > 0 && 2 * ((int64_t)words[b] * 32) > plans[b].dcap_max;
+        for (int i = 0; i < TX_BINS; ++i) {
+            int64_t *bl = blk.data() + (size_t)i * (M + 1);
+            for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t)
+                bl[t + 1] = bl[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + plans[b].zb[i] - 1) / plans[b].zb[i];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
@@ -3221,12 +3282,10 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
                         "scs_score_taxon_triplets: tip %d has taxon %d, not below the %lld tips of the supertree", v,
                         taxon[v], (long long)n_out);
     }
-    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
-    // the slab path: needed when a node's arrays (at most 2 m + 1 entries) may exceed the largest bin
-    const int64_t slab_stride = 2 * m_max + 2 + TX_SLAB_PAD;
-    const bool need_slab = 2 * m_max + 1 > sc_tx_plan_of((int)(m_max >> 5) + 1, lds_cap).dcap_max;
-    const int slab_wgs = !need_slab ? 0
-                         : (int)std::min<uint64_t>(TX_SLAB_WGS, std::max<uint64_t>(1, TX_SLAB_BYTES / (slab_stride * 8)));
+    // the LDS cap and the slab path
+    const sc_tx_call tc = sc_tx_call_of(m_max, max_lds_bytes);
+    const int64_t slab_stride = tc.slab_stride;
+    const int slab_wgs = tc.slab_wgs;
     // own arrays: the five outputs per taxon, the first pair workgroup per tree (+ 1) and bin, the slabs; per batch
     // the two node lists (int4), three sums (shared and source in T order, super in S' order) and the TX_BINS + 1
     // bin lists per leaf, and per tree the lengths of all those lists
@@ -3250,23 +3309,14 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
     auto *d_dsup = d_dsrc + c.max_lb;
     auto *d_zbin = (int32_t *)(d_dsup + c.max_lb);
     auto *d_ycnt = d_zbin + (TX_BINS + 1) * c.max_lb;
-    // per batch: W words per bitset row (largest tree of the batch) and the plan of its bins; blk: per bin the first
-    // pair workgroup of every tree, ceil((n - 2) / zb) of them (n - 2 bounds the nodes of any list)
+    // per batch: W words per bitset row, the plan of its bins and whether the slab kernel runs; blk: per bin the first
+    // pair workgroup of every tree
     const size_t n_batches = c.bstart.size() - 1;
-    std::vector<int> words(n_batches);
-    std::vector<sc_tx_plan> plans(n_batches);
-    std::vector<int64_t> blk(((size_t)M + 1) * TX_BINS, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        plans[b] = sc_tx_plan_of(words[b], lds_cap);
-        for (int i = 0; i < TX_BINS; ++i) {
-            int64_t *bl = blk.data() + (size_t)i * (M + 1);
-            for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
-                bl[t + 1] = bl[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + plans[b].zb[i] - 1) / plans[b].zb[i];
-        }
-    }
+    std::vector<int> words;
+    std::vector<sc_tx_plan> plans;
+    std::vector<char> slab_launches;
+    std::vector<int64_t> blk;
+    sc_tx_batches(off.data(), c.bstart, tc, words, plans, slab_launches, blk);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_tx, 0, (size_t)n_out * 40, s);
     if (e == hipSuccess)
@@ -3314,7 +3364,7 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
         if (e != hipSuccess) break;
         int32_t *d_zbcnt = d_ycnt + 2 * nb;
         const sc_tx_plan &pl = plans[b];
-        const bool slab_launch = slab_wgs > 0 && 2 * ((int64_t)words[b] * 32) > pl.dcap_max;
+        const bool slab_launch = slab_launches[b] != 0;
         k_tx_single<<<grid_of(Lb), SC_THREADS, 0, s>>>(a.off, nb, d_ylist, d_zlist, a.ycnt, a.zcnt, pl.bins, Lb, d_zbin,
                                                        d_zbcnt, d_dsrc, d_dsup, slab_launch, c.d_flag);
         if (!sc_launched(e)) break;
@@ -3332,7 +3382,7 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
         // and dcap_max only grows when W shrinks (bin 2 holds one node: (cap - 64 - 16 W) / 8, capped by 64 W), so a
         // batch lists such a node only if need_slab held for m_max, that is only if the slabs exist
         if (slab_launch) {
-            k_tx_pairs<true><<<(unsigned)slab_wgs, SC_THREADS, (size_t)16 * words[b], s>>>(
+            k_tx_pairs<true><<<(unsigned)slab_wgs, SC_THREADS, sc_tx_slab_lds(words[b]), s>>>(
                 nullptr, nb, a.off, d_ylist, d_zlist, a.ycnt, d_zbin + (int64_t)TX_BINS * Lb,
                 d_zbcnt + (int64_t)TX_BINS * nb, c.d_mm, 1, words[b], d_slab, slab_stride, d_acc);
             if (!sc_launched(e)) break;
@@ -3348,6 +3398,66 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
     for (int i = 0; i < 5 && e == hipSuccess; ++i)
         if (outs[i] && n_out) e = hipMemcpyAsync(outs[i], d_tx + i * n_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, s);
     SCS_TRY(sc_end(ctx, c, e, bad));
+    return SCS_OK;
+}
+
+// the plans of scs_score_branch_triplets / scs_score_branch_resample and of scs_score_taxon_triplets on the host, by
+// the functions those exports call
+extern "C" int scs_debug_branch_plan(const scs_tables *src, int32_t n_trees, const int64_t *tree_off,
+                                     int32_t super_leaves, int32_t max_batch_trees, int64_t extra_per_leaf,
+                                     int64_t extra_per_tree, int32_t max_lds_bytes, int32_t *n_batches_out,
+                                     int32_t *bstart_out, int64_t *bt_out, int64_t *tx_out, int64_t *call_out) {
+    SCS_REQUIRE((src || tree_off) && n_batches_out && bstart_out && bt_out && tx_out && call_out,
+                "scs_debug_branch_plan: null argument");
+    SCS_REQUIRE(!src || n_trees == src->n_trees, "scs_debug_branch_plan: the tables hold %d trees, not %d",
+                src ? src->n_trees : 0, n_trees);
+    SCS_REQUIRE(n_trees >= 0 && super_leaves >= 0 && extra_per_leaf >= 0 && extra_per_tree >= 0 && max_lds_bytes >= 0,
+                "scs_debug_branch_plan: negative argument");
+    const int64_t *off = src ? src->h_tree_off.data() : tree_off;
+    int64_t max_leaves = src ? src->max_leaves : 0;
+    if (!src)
+        for (int32_t t = 0; t < n_trees; ++t) {
+            SCS_REQUIRE(off[t + 1] >= off[t], "scs_debug_branch_plan: tree_off decreases at tree %d", t);
+            max_leaves = std::max(max_leaves, off[t + 1] - off[t]);
+        }
+    int levels = 0;
+    int64_t row_stride = 0;
+    std::vector<int32_t> bstart;
+    sc_plan_batches(off, n_trees, max_leaves, super_leaves, max_batch_trees, (uint64_t)extra_per_leaf,
+                    (uint64_t)extra_per_tree, levels, row_stride, bstart);
+    const size_t n_batches = bstart.size() - 1;
+    *n_batches_out = (int32_t)n_batches;
+    std::copy(bstart.begin(), bstart.end(), bstart_out);
+    std::vector<int> words, zbs;
+    std::vector<size_t> ldss;
+    std::vector<int64_t> blk;
+    sc_bt_plan(off, bstart, words, zbs, ldss, blk);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t *o = bt_out + 4 * b;
+        o[0] = words[b];
+        o[1] = zbs[b];
+        o[2] = (int64_t)ldss[b];
+        o[3] = blk[bstart[b + 1]] - blk[bstart[b]];
+    }
+    const sc_tx_call tc = sc_tx_call_of(std::max<int64_t>(max_leaves, 0), max_lds_bytes);
+    std::vector<sc_tx_plan> plans;
+    std::vector<char> slab_launches;
+    sc_tx_batches(off, bstart, tc, words, plans, slab_launches, blk);
+    for (size_t b = 0; b < n_batches; ++b) {
+        int64_t *o = tx_out + (4 * TX_BINS + 2) * b;
+        for (int i = 0; i < TX_BINS; ++i) {
+            const int64_t *bl = blk.data() + (size_t)i * (n_trees + 1);
+            o[4 * i] = plans[b].zb[i];
+            o[4 * i + 1] = plans[b].bins.dcap[i];
+            o[4 * i + 2] = plans[b].lds[i];
+            o[4 * i + 3] = bl[bstart[b + 1]] - bl[bstart[b]];
+        }
+        o[4 * TX_BINS] = slab_launches[b];
+        o[4 * TX_BINS + 1] = (int64_t)sc_tx_slab_lds(words[b]);
+    }
+    call_out[0] = tc.need_slab;
+    call_out[1] = tc.slab_wgs;
+    call_out[2] = tc.slab_stride;
     return SCS_OK;
 }
 
@@ -4425,17 +4535,11 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
     for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
     for (int32_t v = 1; v < n_nodes; ++v)
         if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
-    // W, zb and blk per batch as in scs_score_branch_triplets
-    std::vector<int> words(n_batches), zbs(n_batches);
-    std::vector<int64_t> blk((size_t)M + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t)
-            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
-    }
+    // W, zb, the launch's LDS and blk per batch as in scs_score_branch_triplets
+    std::vector<int> words, zbs;
+    std::vector<size_t> ldss;
+    std::vector<int64_t> blk;
+    sc_bt_plan(off.data(), c.bstart, words, zbs, ldss, blk);
     const int n_ub = grid_of((int64_t)nn), n_tiles = (n_rep + RS_TILE - 1) / RS_TILE;
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
@@ -4474,9 +4578,7 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
         if (!sc_launched(e)) break;
         const int64_t n_wg = blk[t0 + nb] - blk[t0];
         if (n_wg > 0) {
-            const size_t lds = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b],
-                                                (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
-            k_rs_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
+            k_rs_pairs<<<(unsigned)n_wg, SC_THREADS, ldss[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
                                                                c.d_mm, zbs[b], words[b], d_slab, (int64_t)nn, nullptr,
                                                                nullptr);
             if (!sc_launched(e)) break;
