@@ -792,7 +792,7 @@ int scs_debug_score_plan(const scs_tables *sources, int32_t n_trees, const int64
                          int32_t *n_batches_out, int32_t *bstart_out, int64_t *info_out, int32_t *words_out,
                          int32_t *zb_out, int64_t *wg_out);
 
-/* The same for scs_score_branch_triplets / scs_score_branch_resample (one plan: both call sc_bt_plan) and for
+/* The same for scs_score_branch_triplets / scs_score_branch_resample (one plan: both call sc_plan_pairs) and for
  * scs_score_taxon_triplets, on the host, by the functions those exports call.  Inputs as for scs_debug_score_plan
  * (extra_per_leaf / extra_per_tree: 40 / 8 for the branch export, 40 / 8 + 32 x supertree nodes for the resample,
  * 72 / 24 for the taxon export) and max_lds_bytes as for scs_score_taxon_triplets (0: no cap).  *n_batches_out and

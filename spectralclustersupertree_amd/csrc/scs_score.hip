@@ -218,19 +218,25 @@ __global__ void k_score_restrict(const int64_t *__restrict__ off, int nb, const 
     node[q] = s_gap_node[(uint32_t)m];
 }
 
-struct sc_nodes_args {
+// one prepared batch as the kernels see it (sc_batch_of fills it on the host): every kernel argument struct below
+// derives from it and adds its own members, so a kernel may be handed a few pointers it does not read
+struct sc_batch {
     const int64_t *off;          // tree_off + t0 (global leaf offsets of the batch's trees)
     int nb;                      // trees in the batch
     const int32_t *sp;           // [Lb] S positions in S order
-    const int32_t *dep, *node;   // [Lb] D and U of the restricted tree
-    const int2 *mm;              // min-max table of tp: level j at mm[j * Lb]
+    const int32_t *dep, *node;   // [Lb] D and U of the restricted tree S'
+    const int2 *mm;              // min-max table of tp (.x of level 0 is tp itself): level j at mm[j * Lb]
     const int32_t *adj;          // T's adj_depth of the batch (level 0 of the min table)
     const int32_t *amin;         // levels >= 1 of the min table of adj: level j at amin[(j - 1) * Lb]
     int levels;                  // levels of the batch's tables (2^levels > largest tree)
-    int64_t Lb;
+    int64_t Lb;                  // leaves of the batch
     const uint64_t *s_tab;       // S's packed gap table
-    int64_t s_stride;
+    int64_t s_stride;            // entries per level of it (S's gaps)
+    int s_levels;                // its levels (2^s_levels > S's gaps)
     const int32_t *s_lo, *s_hi;  // leaf range of every S node
+};
+
+struct sc_nodes_args : sc_batch {
     int32_t *mark_inf, *mark_sup;                   // [S nodes]
     unsigned long long *c_super, *c_source, *c_shared;  // [nb] of the batch
 };
@@ -368,17 +374,8 @@ constexpr int TP_ZMAX = 8;                // S' nodes per workgroup
 constexpr int TP_LDS_BUDGET = 40 << 10;   // LDS bytes a workgroup aims at (4 workgroups per CU) ...
 constexpr int TP_LDS_MAX = 160 << 10;     // ... and may take for one S' node: trees of up to 327 679 leaves
 
-struct sc_trip_args {
-    const int64_t *off;                     // tree_off + t0
-    int nb;
-    const int32_t *sp, *dep, *node;         // [Lb] S positions in S order, D and U of S'
-    const int32_t *adj, *amin;              // T's min table of adj_depth (as in sc_nodes_args)
-    int levels;
-    int64_t Lb;
-    const uint64_t *s_tab;                  // S's packed gap table
-    int64_t s_stride;
-    const int32_t *s_lo, *s_hi;             // leaf range of every S node
-    int4 *ylist, *zlist;                    // [Lb]: the nodes of a tree from its first leaf on
+struct sc_trip_args : sc_batch {
+    int4 *ylist, *zlist;                   // [Lb]: the nodes of a tree from its first leaf on
     int32_t *ycnt, *zcnt;                   // [nb] list lengths
     unsigned long long *c_super, *c_source; // [nb] of the batch
 };
@@ -573,18 +570,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_trip_pairs(const int64_t *__rest
 //   k_conf_nodes, one thread per gap: every non-root node at its first gap reads its sum; a flagged S' node marks the
 //     S path [u, w) of its cluster for `conflicting`, as k_score_nodes does for `supported`.
 
-struct sc_conf_args {
-    const int64_t *off;          // tree_off + t0
-    int nb;
-    const int32_t *sp, *dep, *node;  // [Lb] S positions in S order, D and U of S'
-    const int2 *mm;              // min-max table of tp (S' order): level j at mm[j * Lb]
+struct sc_conf_args : sc_batch {
     const int2 *im;              // min-max table of ip (T order): level j at im[j * Lb]
-    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
-    int levels;
-    int64_t Lb;
-    const uint64_t *s_tab;       // S's packed gap table
-    int64_t s_stride;
-    const int32_t *s_lo, *s_hi;  // leaf range of every S node
     int32_t *mark_s, *mark_t;    // [Lb] marks on S''s / T's gaps, then their per-tree inclusive prefix sums
     int32_t *mark_node;          // [S nodes]
     unsigned long long *c_super, *c_source;  // [nb] of the batch
@@ -893,12 +880,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_conf_nodes(sc_conf_args a) {
 // exactly its size and the LCA of that span has no further leaf (step 4 of section 14).  Every result belongs to C
 // alone: the counts go straight onto per-node counters, no path marks and no prefix pass.
 
+// (not over sc_batch: with the view's unread members between its own, k_conc_branches fetches its arguments in four
+// pieces where it fetched them in one, and scs_score_concordance, which is this one launch a batch, came out 0.06 ms
+// behind in two of four comparisons; alone, the struct leaves the kernel as it was, instruction for instruction)
 struct sc_conc_args {
     const int64_t *off;          // tree_off + t0
     int nb;
     const int32_t *sp, *node;    // [Lb] S positions in S order, U of S'
     const int2 *mm;              // min-max table of tp: level j at mm[j * Lb]
-    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
+    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_batch)
     int64_t Lb;
     const int32_t *s_lo, *s_hi;  // leaf range of every S node
     const int32_t *q_parent;     // [S nodes] the parent of a quartet branch, -1 for every other node
@@ -995,15 +985,8 @@ struct sc_bt_rec {
     int32_t dlo, dhi;      // D' = [dlo, dhi]
 };
 
-struct sc_bt_args {
-    const int64_t *off;          // tree_off + t0
-    int nb;
-    const int32_t *sp, *node;    // [Lb] S positions in S order, U of S'
-    const int32_t *adj, *amin;   // T's min table of adj_depth (as in sc_nodes_args)
-    int levels;
-    int64_t Lb;
-    const int32_t *s_lo, *s_hi;  // leaf range of every S node
-    const int32_t *q_parent;     // [S nodes] the parent of a quartet branch, -1 for every other node
+struct sc_bt_args : sc_batch {
+    const int32_t *q_parent;    // [S nodes] the parent of a quartet branch, -1 for every other node
     int4 *ylist;                 // [Lb] T's nodes of a tree from its first leaf on
     sc_bt_rec *recs;             // [Lb] the tree's records likewise
     int32_t *ycnt, *rcnt;        // [nb] list lengths
@@ -1620,17 +1603,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_pl_queries(const int64_t *__rest
     gcnt[idx] = 0;
 }
 
-struct sc_pl_args {
-    const int64_t *off;                     // tree_off + t0
-    int nb;
-    const int32_t *sp, *dep, *node;         // [Lb] S positions in S order, D and U of S'
-    const int32_t *adj, *amin;              // T's min table of adj_depth (as in sc_nodes_args)
-    int levels;
-    int64_t Lb;
-    const uint64_t *s_tab;                  // S's packed gap table
-    int64_t s_stride;
-    int s_levels;
-    const int32_t *s_lo, *s_hi;             // leaf range of every S node
+struct sc_pl_args : sc_batch {
     const int32_t *tip_node, *tip_depth;    // [S leaves] preorder index and depth of the tip at an S position
     int4 *zlist, *zmeta;                    // [2 Lb]: the nodes of a tree from twice its first leaf on
     int32_t *zcnt;                          // [nb]
@@ -1984,16 +1957,9 @@ __global__ void __launch_bounds__(1024) k_pl_prefix(const unsigned long long *__
 
 constexpr int CP_QMAX = 64;  // sub-queries (tips of query clades) per pass over a batch
 
-struct sc_cp_args {
-    const int64_t *off;             // tree_off + t0
-    int nb;
-    const int32_t *sp;              // [Lb] S positions in S order
-    const int2 *tp;                 // [Lb] T position of every S' leaf (.x)
+struct sc_cp_args : sc_batch {    // (mm: .x of its level 0 is the T position of every S' leaf)
     const int32_t *rows;            // [nb][row_stride] T position by S position
     int64_t row_stride;
-    const int32_t *adj, *amin;      // T's min table of adj_depth
-    int levels;
-    int64_t Lb;
     const int32_t *c_lo, *c_hi;     // [ncl] S leaf range of the pass's clades
     const int32_t *q_spos, *q_slot; // [qc] S position and clade (slot in the pass) of the pass's sub-queries
     int ncl, qc;
@@ -2025,7 +1991,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_cp_clades(sc_cp_args a) {
     const int W = (int)(n >> 5) + 1;
     unsigned *bits = reinterpret_cast<unsigned *>(row);  // (zeroed by the host before the launch)
     for (int64_t k = ka + threadIdx.x; k < kb; k += SC_THREADS) {
-        const int x = a.tp[base + k].x;
+        const int x = a.mm[base + k].x;
         atomicOr(bits + 2 * (x >> 5), 1u << (x & 31));
     }
     __threadfence();
@@ -2452,11 +2418,13 @@ bool sc_launched(hipError_t &e) {
 
 // what both exports share: the supertree's host layout, the batches and the device block with S's arrays, the rows and
 // the per-batch tables of steps 1 - 2.  The caller's own arrays: extra_bytes once (d_extra) and extra_per_leaf /
-// extra_per_tree bytes per leaf / tree of the largest batch (d_extra_batch), both counted in the batch budget.
+// extra_per_tree bytes per leaf / tree of the largest batch (d_extra_batch: max_lb leaves, max_rows trees), both
+// counted in the batch budget.
 struct sc_call {
     const char *who = nullptr;
     int32_t n_taxa = 0, n_leaves = 0, M = 0;
-    int64_t n_gaps = 0, row_stride = 0, max_lb = 0;
+    int64_t n_gaps = 0, row_stride = 0, max_lb = 0, max_rows = 0;
+    size_t extra_bytes = 0, extra_batch_bytes = 0;
     int levels = 0;
     std::vector<int32_t> s_lo, s_hi, sub_end, s_pos, s_gap_node, bstart;
     std::vector<uint64_t> s_gap;
@@ -2496,45 +2464,141 @@ void sc_plan_batches(const int64_t *off, int32_t M, int64_t max_leaves, int64_t 
     bstart.push_back(M);
 }
 
-// the pair kernel's plan per batch, for scs_score_triplets and scs_debug_score_plan alike: W words per bitset row
-// (largest tree of the batch), zb S' nodes per workgroup; blk: the first pair workgroup of every tree, ceil((n - 2) /
-// zb) of them (n - 2 bounds the non-root internal nodes)
-void sc_trip_plan(const int64_t *off, const std::vector<int32_t> &bstart, std::vector<int> &words,
-                  std::vector<int> &zbs, std::vector<int64_t> &blk) {
-    const size_t n_batches = bstart.size() - 1;
-    words.assign(n_batches, 0);
-    zbs.assign(n_batches, 0);
-    blk.assign((size_t)bstart.back() + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        zbs[b] = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (16 * words[b])));
-        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t)
-            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
-    }
+// the largest tree among [t0, t1), and the words W of a bitset row over its T positions (one word per 32, one more
+// than the last position needs: the pair kernels' rows)
+int64_t sc_largest_tree(const int64_t *off, int32_t t0, int32_t t1) {
+    int64_t nmax = 0;
+    for (int32_t t = t0; t < t1; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
+    return nmax;
 }
 
-// the same for k_bt_pairs / k_rs_pairs, for scs_score_branch_triplets, scs_score_branch_resample and
-// scs_debug_branch_plan alike: zb records per workgroup (three rows of int2 each), lds the launch's dynamic LDS (at
-// least the 768 bytes of the workgroup's wave sums); blk: ceil((n - 2) / zb) workgroups a tree (a tree is decisive for
-// at most n - 2 branches)
-void sc_bt_plan(const int64_t *off, const std::vector<int32_t> &bstart, std::vector<int> &words,
-                std::vector<int> &zbs, std::vector<size_t> &lds, std::vector<int64_t> &blk) {
+int sc_row_words(const int64_t *off, int32_t t0, int32_t t1) { return (int)(sc_largest_tree(off, t0, t1) >> 5) + 1; }
+
+// what differs between the pair kernels' plans
+struct sc_pair_rule {
+    int word_bytes;          // LDS bytes of one node's (record's) rows per word of a row
+    int zmax;                // nodes per workgroup at most
+    int aux_node, aux_pass;  // LDS bytes beside the rows, per node and per launch (0, 0: the kernel keeps none) ...
+    int lds_cap;             // ... and what the rows and those bytes may take together
+    size_t lds_floor;        // the least dynamic LDS of a launch
+    bool leaves_too;         // a tree's workgroups: ceil(2 n / zb) for n >= 3 (S' has n leaves and at most n - 1 other
+                             // nodes), else ceil((n - 2) / zb) (n - 2 bounds the non-root internal nodes)
+};
+
+// k_trip_pairs: two rows (cl(z), cl(pz)) of int2 a node; a launch asks for 32 bytes at least
+const sc_pair_rule SC_TRIP_RULE = {16, TP_ZMAX, 0, 0, 0, 32, false};
+// k_bt_pairs / k_rs_pairs: three rows a record; at least the 768 bytes of the workgroup's wave sums
+const sc_pair_rule SC_BT_RULE = {BT_ROW_BYTES, BT_ZMAX, 0, 0, 0, (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8, false};
+
+// k_pl_pairs / k_cp_pairs with qc queries in a pass keep sums in LDS beside the rows, where they fit: these bytes a
+// node, and these a pass
+constexpr int sc_pl_node_bytes(int qc) { return 16 * qc + 32; }
+constexpr int sc_pl_pass_bytes(int qc) { return 4 * ((qc + 4) & ~3); }
+
+// their plan with up to qcap queries in a pass: the rows of k_trip_pairs and those sums, under the caller's cap
+sc_pair_rule sc_pl_rule(int qcap, int lds_cap) {
+    return {16, TP_ZMAX, sc_pl_node_bytes(qcap), sc_pl_pass_bytes(qcap), lds_cap, 0, true};
+}
+
+// the plan per batch, for the exports and the debug entries alike: W words per bitset row (largest tree of the
+// batch), zb nodes per workgroup -- as many as TP_LDS_BUDGET holds rows of, fewer while the bytes beside the rows
+// take them past the cap; sums: those bytes fit (with zb = 1 they may not: the kernel then adds straight to memory);
+// lds: the rows' bytes of a launch, at least the floor; blk: the first pair workgroup of every tree
+struct sc_pair_plan {
+    std::vector<int> words, zbs, sums;
+    std::vector<size_t> lds;
+    std::vector<int64_t> blk;
+};
+
+sc_pair_plan sc_plan_pairs(const int64_t *off, const std::vector<int32_t> &bstart, const sc_pair_rule &r) {
     const size_t n_batches = bstart.size() - 1;
-    words.assign(n_batches, 0);
-    zbs.assign(n_batches, 0);
-    lds.assign(n_batches, 0);
-    blk.assign((size_t)bstart.back() + 1, 0);
+    sc_pair_plan p;
+    p.words.assign(n_batches, 0);
+    p.zbs.assign(n_batches, 0);
+    p.sums.assign(n_batches, 0);
+    p.lds.assign(n_batches, 0);
+    p.blk.assign((size_t)bstart.back() + 1, 0);
     for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        zbs[b] = (int)std::min<int64_t>(BT_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / (BT_ROW_BYTES * words[b])));
-        lds[b] = std::max<size_t>((size_t)zbs[b] * BT_ROW_BYTES * words[b], (size_t)(SC_THREADS / 64) * BT_ZMAX * 3 * 8);
-        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t)
-            blk[t + 1] = blk[t] + (std::max<int64_t>(off[t + 1] - off[t] - 2, 0) + zbs[b] - 1) / zbs[b];
+        p.words[b] = sc_row_words(off, bstart[b], bstart[b + 1]);
+        const int rowb = r.word_bytes * p.words[b];
+        int zb = (int)std::min<int64_t>(r.zmax, std::max<int64_t>(1, TP_LDS_BUDGET / rowb));
+        if (r.aux_node) {
+            while (zb > 1 && zb * (rowb + r.aux_node) + r.aux_pass > r.lds_cap) --zb;
+            p.sums[b] = zb * (rowb + r.aux_node) + r.aux_pass <= r.lds_cap;
+        }
+        p.zbs[b] = zb;
+        p.lds[b] = std::max<size_t>((size_t)zb * rowb, r.lds_floor);
+        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) {
+            const int64_t n = off[t + 1] - off[t];
+            const int64_t nodes = r.leaves_too ? (n >= 3 ? 2 * n : 0) : std::max<int64_t>(n - 2, 0);
+            p.blk[t + 1] = p.blk[t] + (nodes + zb - 1) / zb;
+        }
     }
+    return p;
+}
+
+// the dynamic LDS of a k_pl_pairs / k_cp_pairs launch of batch b with qc queries in the pass
+size_t sc_pl_lds(const sc_pair_plan &p, size_t b, int qc) {
+    return p.lds[b] + (p.sums[b] ? (size_t)p.zbs[b] * sc_pl_node_bytes(qc) + sc_pl_pass_bytes(qc) : 0);
+}
+
+// A bump allocator over one block of a call's workspace: typed pointers, `step` bytes apart at least.  An export
+// declares its d_extra arrays once, as a function of the carver, and runs it twice: over nothing for the size it asks
+// sc_begin for, then over the block for the pointers.  d_extra_batch is carved with step 1 for max_lb leaves and
+// max_rows trees: its arrays are packed, because the per-leaf and per-tree byte counts an export gives sc_begin are
+// the contract -- they decide the batch split -- and the carver checks the export against them.  An array that does
+// not fit gets the block's start, never an address past it, and sets `over`: the export then ends the call with an
+// internal error (SC_BAD_LAYOUT) before it launches anything of its own.  That check is the one over d_extra_batch:
+// over d_extra the second run is bounded by the size the first run gave, so it cannot fail while both runs are the
+// same code, and the exports test it only because the pass is the same function
+struct sc_carver {
+    char *base = nullptr;
+    size_t cap = SIZE_MAX, step = 256, at = 0;
+    bool over = false;
+    template <typename T>
+    T *take(size_t n) {
+        const size_t bytes = (n * sizeof(T) + step - 1) / step * step;
+        over = over || bytes > cap - at;
+        if (over) return (T *)base;
+        at += bytes;
+        return base ? (T *)(base + at - bytes) : nullptr;
+    }
+};
+
+// batch b as the kernels see it, and for the host its first tree and its first leaf
+struct sc_bview : sc_batch {
+    int32_t t0;
+    int64_t L0;
+};
+
+sc_bview sc_batch_of(const scs_tables *src, const sc_call &c, size_t b) {
+    sc_bview v;
+    v.t0 = c.bstart[b];
+    v.nb = c.bstart[b + 1] - v.t0;
+    v.L0 = src->h_tree_off[v.t0];
+    v.Lb = src->h_tree_off[v.t0 + v.nb] - v.L0;
+    v.off = src->d_tree_off + v.t0;
+    v.sp = c.d_sp;
+    v.dep = c.d_dep;
+    v.node = c.d_node;
+    v.mm = c.d_mm;
+    v.adj = src->d_adj_depth + v.L0;
+    v.amin = c.d_amin;
+    v.levels = c.levels;
+    v.s_tab = c.d_stab;
+    v.s_stride = c.n_gaps;
+    v.s_levels = sc_levels_host(c.n_gaps);
+    v.s_lo = c.d_slo;
+    v.s_hi = c.d_shi;
+    return v;
+}
+
+// a kernel's argument struct over a batch view; its own members start as zero
+template <typename A>
+A sc_args(const sc_batch &v) {
+    A a{};
+    static_cast<sc_batch &>(a) = v;
+    return a;
 }
 
 // checks, host layout, block, uploads (their errors in e); SCS_OK or the code of a failure before the block exists
@@ -2616,42 +2680,33 @@ int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nod
         max_lb = std::max<int64_t>(max_lb, off[bstart[b + 1]] - off[bstart[b]]);
     }
     c.max_lb = max_lb;
+    c.max_rows = max_rows;
+    c.extra_bytes = extra_bytes;
+    c.extra_batch_bytes = (size_t)(max_lb * extra_per_leaf + max_rows * extra_per_tree);
     const int s_levels = sc_levels_host(n_gaps);
-    // persistent part: S arrays, flags, the caller's arrays
-    size_t o = 0;
-    const size_t o_spos = o; o += sc_up256((size_t)std::max(n_taxa, 1) * 4);
-    const size_t o_gnode = o; o += sc_up256((size_t)n_gaps * 4);
-    const size_t o_stab = o; o += sc_up256((size_t)n_gaps * 8 * s_levels);
-    const size_t o_slo = o; o += sc_up256((size_t)n_nodes * 4);
-    const size_t o_shi = o; o += sc_up256((size_t)n_nodes * 4);
-    const size_t o_end = o; o += sc_up256((size_t)n_nodes * 4);
-    const size_t o_flag = o; o += 256;
-    const size_t o_extra = o; o += sc_up256(extra_bytes);
-    // batch part
-    const size_t o_rows = o; o += sc_up256((size_t)max_rows * row_stride * 4);
-    const size_t o_sp = o; o += sc_up256((size_t)max_lb * 4);
-    const size_t o_dep = o; o += sc_up256((size_t)max_lb * 4);
-    const size_t o_node = o; o += sc_up256((size_t)max_lb * 4);
-    const size_t o_mm = o; o += sc_up256((size_t)max_lb * 8 * levels);
-    const size_t o_amin = o; o += sc_up256((size_t)max_lb * 4 * std::max(levels - 1, 1));
-    const size_t o_xb = o; o += sc_up256((size_t)(max_lb * extra_per_leaf + max_rows * extra_per_tree));
-    SCS_TRY(scs_block_alloc(ctx, o, &c.block));
-    char *bp = (char *)c.block;
-    c.d_spos = (int32_t *)(bp + o_spos);
-    c.d_gnode = (int32_t *)(bp + o_gnode);
-    c.d_stab = (uint64_t *)(bp + o_stab);
-    c.d_slo = (int32_t *)(bp + o_slo);
-    c.d_shi = (int32_t *)(bp + o_shi);
-    c.d_end = (int32_t *)(bp + o_end);
-    c.d_flag = (unsigned *)(bp + o_flag);
-    c.d_extra = bp + o_extra;
-    c.d_rows = (int32_t *)(bp + o_rows);
-    c.d_sp = (int32_t *)(bp + o_sp);
-    c.d_dep = (int32_t *)(bp + o_dep);
-    c.d_node = (int32_t *)(bp + o_node);
-    c.d_mm = (int2 *)(bp + o_mm);
-    c.d_amin = (int32_t *)(bp + o_amin);
-    c.d_extra_batch = bp + o_xb;
+    const auto layout = [&](sc_carver w) {
+        // persistent part: S arrays, flags, the caller's arrays
+        c.d_spos = w.take<int32_t>((size_t)std::max(n_taxa, 1));
+        c.d_gnode = w.take<int32_t>((size_t)n_gaps);
+        c.d_stab = w.take<uint64_t>((size_t)n_gaps * s_levels);
+        c.d_slo = w.take<int32_t>((size_t)n_nodes);
+        c.d_shi = w.take<int32_t>((size_t)n_nodes);
+        c.d_end = w.take<int32_t>((size_t)n_nodes);
+        c.d_flag = w.take<unsigned>(1);
+        c.d_extra = w.take<char>(extra_bytes);
+        // batch part
+        c.d_rows = w.take<int32_t>((size_t)max_rows * row_stride);
+        c.d_sp = w.take<int32_t>((size_t)max_lb);
+        c.d_dep = w.take<int32_t>((size_t)max_lb);
+        c.d_node = w.take<int32_t>((size_t)max_lb);
+        c.d_mm = w.take<int2>((size_t)max_lb * levels);
+        c.d_amin = w.take<int32_t>((size_t)max_lb * std::max(levels - 1, 1));
+        c.d_extra_batch = w.take<char>(c.extra_batch_bytes);
+        return w.at;
+    };
+    const size_t bytes = layout(sc_carver());
+    SCS_TRY(scs_block_alloc(ctx, bytes, &c.block));
+    layout(sc_carver{(char *)c.block, bytes});
 
     e = hipMemcpyAsync(c.d_spos, s_pos.data(), (size_t)std::max(n_taxa, 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
@@ -2672,9 +2727,9 @@ int sc_begin(scs_ctx *ctx, const scs_tables *src, const char *who, int32_t n_nod
 // steps 1 - 2 for batch b: sp, the tp min-max table, T's min table of adj, D and U.  False (stop) on an error or on a
 // bad source taxon (`bad`): a row left short must not be read
 bool sc_prepare_batch(const scs_tables *src, hipStream_t s, sc_call &c, size_t b, hipError_t &e, unsigned &bad) {
-    const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-    const int64_t *d_off = src->d_tree_off + t0;
-    const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
+    const sc_bview v = sc_batch_of(src, c, b);
+    const int64_t *d_off = v.off, Lb = v.Lb;
+    const int32_t nb = v.nb;
     e = hipMemsetAsync(c.d_rows, 0xff, (size_t)nb * c.row_stride * 4, s);
     if (e != hipSuccess) return false;
     k_score_scatter<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, src->d_leaf_taxon, c.n_taxa, c.d_spos, c.d_rows,
@@ -2685,9 +2740,8 @@ bool sc_prepare_batch(const scs_tables *src, hipStream_t s, sc_call &c, size_t b
     if (e != hipSuccess || bad) return false;
     k_score_compact<<<nb, SC_THREADS, 0, s>>>(d_off, c.d_rows, c.row_stride, c.d_sp, c.d_mm);
     if (!sc_launched(e)) return false;
-    const int32_t *adj = src->d_adj_depth + L0;
     for (int j = 1; j < c.levels && e == hipSuccess; ++j) {
-        k_score_level_tree<<<grid_of(Lb), SC_THREADS, 0, s>>>(j == 1 ? adj : c.d_amin + (int64_t)(j - 2) * Lb,
+        k_score_level_tree<<<grid_of(Lb), SC_THREADS, 0, s>>>(j == 1 ? v.adj : c.d_amin + (int64_t)(j - 2) * Lb,
                                                                c.d_amin + (int64_t)(j - 1) * Lb, c.d_mm + (j - 1) * Lb,
                                                                c.d_mm + j * Lb, Lb, (int64_t)1 << (j - 1));
         sc_launched(e);
@@ -2698,9 +2752,20 @@ bool sc_prepare_batch(const scs_tables *src, hipStream_t s, sc_call &c, size_t b
     return sc_launched(e);
 }
 
-// waits for the stream (after the caller's copies), releases the block, reports
+constexpr unsigned SC_BAD_LAYOUT = 16u;  // host only: an export carved more than it budgeted (the device flag has 1 - 8)
+
+// the call's sc_carver over d_extra (the bytes the export asked sc_begin for) ...
+sc_carver sc_carve_extra(const sc_call &c) { return sc_carver{c.d_extra, c.extra_bytes}; }
+
+// ... and over d_extra_batch: packed, for max_lb leaves and max_rows trees
+sc_carver sc_carve_batch(const sc_call &c) { return sc_carver{c.d_extra_batch, c.extra_batch_bytes, 1}; }
+
+// reads the device flag (it only gathers bits: `bad` is an earlier reading of it, or SC_BAD_LAYOUT), waits for the
+// stream (after the caller's copies), releases the block, reports
 int sc_end(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad) {
     hipStream_t s = ctx->stream;
+    unsigned flag = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, c.d_flag, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) (void)hipStreamSynchronize(s);  // (nothing may still write into the block)
     scs_block_release(ctx, c.block);
@@ -2708,64 +2773,42 @@ int sc_end(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad) {
         scs_set_error("%s: %s", c.who, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? SCS_ENOMEM : SCS_EHIP;
     }
+    bad |= flag;
     if (bad) {
-        scs_set_error("%s: %s", c.who, (bad & 8u)   ? "internal: a node was listed for a slab launch that is not made"
-                                       : (bad & 1u) ? "a leaf_taxon entry is out of range [0, n_taxa)"
-                                       : (bad & 2u) ? "a source tree has a taxon the supertree lacks"
-                                                    : "a source tree has a taxon twice");
+        scs_set_error("%s: %s", c.who,
+                      (bad & SC_BAD_LAYOUT) ? "internal: the export's arrays do not fit the bytes it budgeted for them"
+                      : (bad & 8u)          ? "internal: a node was listed for a slab launch that is not made"
+                      : (bad & 1u)          ? "a leaf_taxon entry is out of range [0, n_taxa)"
+                      : (bad & 2u)          ? "a source tree has a taxon the supertree lacks"
+                                            : "a source tree has a taxon twice");
         return SCS_EINVAL;
     }
     return SCS_OK;
 }
 
-}  // namespace
+// the tail of an export with k counters per tree (d_cnt [k][M]): they come down, sc_end, and row i goes to outs[i]
+// where that is not null
+int sc_end_counted(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad, const unsigned long long *d_cnt, int k,
+                   int64_t *const *outs) {
+    const size_t M = (size_t)c.M;
+    std::vector<unsigned long long> cnt(M * k);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, M * k * 8, hipMemcpyDeviceToHost, ctx->stream);
+    SCS_TRY(sc_end(ctx, c, e, bad));
+    for (int i = 0; i < k; ++i)
+        for (size_t t = 0; t < M && outs[i]; ++t) outs[i][t] = (int64_t)cnt[i * M + t];
+    return SCS_OK;
+}
 
-extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
-                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super,
-                                   int64_t *n_source, int64_t *shared, int64_t *informative, int64_t *supported) {
-    // own arrays: marks, prefix sums, outputs per S node; three counters per tree
-    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
-    const size_t o_mark = 0, o_pref = o_mark + sc_up256(nn * 8), o_out = o_pref + sc_up256((nn + 1) * 16),
-                 o_cnt = o_out + sc_up256(nn * 16), own = o_cnt + sc_up256(mt * 24);
-    sc_call c;
-    hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_supertree", n_nodes, parent, taxon, max_batch_trees, own, 0, 0, c, e));
-    const int32_t M = c.M;
-    hipStream_t s = ctx->stream;
-    auto *d_mark = (int32_t *)(c.d_extra + o_mark);
-    auto *d_pref = (int64_t *)(c.d_extra + o_pref);
-    auto *d_out = (int64_t *)(c.d_extra + o_out);
-    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
-    unsigned bad = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, nn * 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
-    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
-        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
-        sc_nodes_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.dep = c.d_dep;
-        a.node = c.d_node;
-        a.mm = c.d_mm;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_tab = c.d_stab;
-        a.s_stride = c.n_gaps;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
-        a.mark_inf = d_mark;
-        a.mark_sup = d_mark + n_nodes;
-        a.c_super = d_cnt + t0;
-        a.c_source = d_cnt + M + t0;
-        a.c_shared = d_cnt + 2 * (int64_t)M + t0;
-        k_score_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
-        if (!sc_launched(e)) break;
-    }
+// k rows of n 64-bit entries each, from d on, come down into the outputs that are not null
+void sc_fetch_rows(hipStream_t s, const void *d, size_t n, int k, int64_t *const *outs, hipError_t &e) {
+    for (int i = 0; i < k && e == hipSuccess; ++i)
+        if (outs[i] && n) e = hipMemcpyAsync(outs[i], (const char *)d + i * n * 8, n * 8, hipMemcpyDeviceToHost, s);
+}
+
+// the marks of the S nodes (two rows) become every node's sum over its subtree: d_pref two rows of n_nodes + 1 prefix
+// sums, d_out the two rows of results
+void sc_subtree_sums(hipStream_t s, const sc_call &c, int32_t n_nodes, const int32_t *d_mark, int64_t *d_pref,
+                     int64_t *d_out, hipError_t &e, unsigned bad) {
     if (e == hipSuccess && !bad) {
         k_score_prefix<<<1, 1024, 0, s>>>(d_mark, d_mark + n_nodes, n_nodes, d_pref, d_pref + n_nodes + 1);
         sc_launched(e);
@@ -2775,22 +2818,171 @@ extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t 
                                                                 d_out + n_nodes);
         sc_launched(e);
     }
-    std::vector<unsigned long long> cnt((size_t)M * 3);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && informative)
-        e = hipMemcpyAsync(informative, d_out, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && supported)
-        e = hipMemcpyAsync(supported, d_out + n_nodes, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    const std::vector<int64_t> &off = src->h_tree_off;
-    for (int32_t t = 0; t < M; ++t) {
-        const int64_t n = off[t + 1] - off[t];
-        const int64_t ns = (int64_t)cnt[t], nt = n >= 2 ? (int64_t)cnt[M + t] - 1 : 0, sh = (int64_t)cnt[2 * M + t];
-        if (n_super) n_super[t] = ns;
-        if (n_source) n_source[t] = nt;
-        if (shared) shared[t] = sh;
+}
+
+int64_t sc_max_leaves(const scs_tables *src) { return src ? std::max<int64_t>(src->max_leaves, 0) : 0; }
+
+// the LDS a workgroup may take: the caller's max_lds_bytes (0: no wish), TP_LDS_MAX at most
+int sc_lds_cap(int32_t max_lds_bytes) {
+    return max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+}
+
+// the rows of one node (row_bytes per word) of the largest tree must fit one workgroup's LDS -- and, where the caller
+// names its wish, under that
+int sc_rows_fit(const char *who, const scs_tables *src, int row_bytes, int32_t max_lds_bytes = 0) {
+    const int64_t m_max = sc_max_leaves(src), need = row_bytes * ((m_max >> 5) + 1);
+    if (max_lds_bytes > 0) {
+        SCS_REQUIRE(need <= sc_lds_cap(max_lds_bytes),
+                    "%s: max_lds_bytes = %d does not hold the rows of a source tree of %lld leaves", who,
+                    max_lds_bytes, (long long)m_max);
+        return SCS_OK;
     }
+    SCS_REQUIRE(need <= TP_LDS_MAX,
+                "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
+                (long long)m_max, TP_LDS_MAX / row_bytes * 32 - 1);
+    return SCS_OK;
+}
+
+// a sum over nodes of triples is at most sum_t (m_t / 3)^3: it must fit int64
+int sc_cubes_fit(const char *who, const scs_tables *src) {
+    if (!src) return SCS_OK;
+    unsigned __int128 cubes = 0;
+    for (int32_t t = 0; t < src->n_trees; ++t) {
+        const unsigned __int128 m = (unsigned __int128)(src->h_tree_off[t + 1] - src->h_tree_off[t]);
+        cubes += m * m * m;
+    }
+    SCS_REQUIRE(cubes / 27 <= (unsigned __int128)INT64_MAX,
+                "%s: the triple counts of %d source trees may not fit 64 bits", who, src->n_trees);
+    return SCS_OK;
+}
+
+// quartet branches: two children, below a parent of two children -- their parent, -1 for every other node (sc_begin
+// has checked `parent`)
+std::vector<int32_t> sc_quartet_parents(int32_t n_nodes, const int32_t *parent) {
+    const size_t nn = (size_t)std::max(n_nodes, 0);
+    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
+    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
+    for (int32_t v = 1; v < n_nodes; ++v)
+        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    return q_parent;
+}
+
+// The supertree as an export needs it for its own refusals, before sc_begin has checked it: every node's children,
+// depth and -- with `ranges` -- leaf range (tips counted in preorder), the tips' nodes and depths by leaf position.  A
+// parent entry that is not an earlier node is passed over, not refused: sc_begin refuses it afterwards, and the
+// export's own refusals come first
+struct sc_walk {
+    std::vector<int32_t> n_kids, depth, lo, hi, tip_node, tip_depth;
+};
+
+sc_walk sc_walk_super(int32_t n_nodes, const int32_t *parent, bool ranges) {
+    sc_walk w;
+    w.n_kids.assign((size_t)n_nodes, 0);
+    w.depth.assign((size_t)n_nodes, 0);
+    if (ranges) {
+        w.lo.assign((size_t)n_nodes, INT32_MAX);
+        w.hi.assign((size_t)n_nodes, -1);
+    }
+    const auto linked = [&](int32_t v) { return parent[v] >= 0 && parent[v] < v; };
+    for (int32_t v = 1; v < n_nodes; ++v)
+        if (linked(v)) {
+            w.n_kids[parent[v]]++;
+            w.depth[v] = w.depth[parent[v]] + 1;
+        }
+    for (int32_t v = 0; v < n_nodes; ++v)
+        if (!w.n_kids[v]) {
+            if (ranges) w.lo[v] = w.hi[v] = (int32_t)w.tip_node.size();
+            w.tip_node.push_back(v);
+            w.tip_depth.push_back(w.depth[v]);
+        }
+    for (int32_t v = n_nodes - 1; v >= 1 && ranges; --v)
+        if (linked(v)) {
+            w.lo[parent[v]] = std::min(w.lo[parent[v]], w.lo[v]);
+            w.hi[parent[v]] = std::max(w.hi[parent[v]], w.hi[v]);
+        }
+    return w;
+}
+
+// what the two debug plan entries share: off (the tables' or the caller's) with its largest tree, and the batches by
+// sc_plan_batches
+struct sc_debug_plan {
+    const int64_t *off = nullptr;
+    int64_t max_leaves = 0, row_stride = 0;
+    int levels = 0;
+    std::vector<int32_t> bstart;
+};
+
+// ... after their checks (outs_given: the entry's own outputs are there); the batches are written out as well
+int sc_debug_batches(const char *who, const scs_tables *src, int32_t n_trees, const int64_t *tree_off,
+                     int32_t super_leaves, int32_t max_batch_trees, int64_t extra_per_leaf, int64_t extra_per_tree,
+                     int32_t max_lds_bytes, bool outs_given, int32_t *n_batches_out, int32_t *bstart_out,
+                     sc_debug_plan &d) {
+    SCS_REQUIRE((src || tree_off) && n_batches_out && bstart_out && outs_given, "%s: null argument", who);
+    SCS_REQUIRE(!src || n_trees == src->n_trees, "%s: the tables hold %d trees, not %d", who, src ? src->n_trees : 0,
+                n_trees);
+    SCS_REQUIRE(n_trees >= 0 && super_leaves >= 0 && extra_per_leaf >= 0 && extra_per_tree >= 0 && max_lds_bytes >= 0,
+                "%s: negative argument", who);
+    d.off = src ? src->h_tree_off.data() : tree_off;
+    d.max_leaves = src ? src->max_leaves : 0;
+    if (!src)
+        for (int32_t t = 0; t < n_trees; ++t) {
+            SCS_REQUIRE(d.off[t + 1] >= d.off[t], "%s: tree_off decreases at tree %d", who, t);
+            d.max_leaves = std::max(d.max_leaves, d.off[t + 1] - d.off[t]);
+        }
+    sc_plan_batches(d.off, n_trees, d.max_leaves, super_leaves, max_batch_trees, (uint64_t)extra_per_leaf,
+                    (uint64_t)extra_per_tree, d.levels, d.row_stride, d.bstart);
+    *n_batches_out = (int32_t)d.bstart.size() - 1;
+    std::copy(d.bstart.begin(), d.bstart.end(), bstart_out);
+    return SCS_OK;
+}
+
+}  // namespace
+
+extern "C" int scs_score_supertree(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
+                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super,
+                                   int64_t *n_source, int64_t *shared, int64_t *informative, int64_t *supported) {
+    // own arrays: marks, prefix sums, outputs per S node (two rows each); three counters per tree
+    const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
+    int32_t *d_mark;
+    int64_t *d_pref, *d_out;
+    unsigned long long *d_cnt;
+    const auto own = [&](sc_carver w) {
+        d_mark = w.take<int32_t>(2 * nn);
+        d_pref = w.take<int64_t>(2 * (nn + 1));
+        d_out = w.take<int64_t>(2 * nn);
+        d_cnt = w.take<unsigned long long>(3 * mt);
+        return w;
+    };
+    sc_call c;
+    hipError_t e = hipSuccess;
+    SCS_TRY(sc_begin(ctx, src, "scs_score_supertree", n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at, 0,
+                     0, c, e));
+    if (own(sc_carve_extra(c)).over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
+    const int32_t M = c.M;
+    hipStream_t s = ctx->stream;
+    unsigned bad = 0;
+    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, nn * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
+        if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
+        const sc_bview v = sc_batch_of(src, c, b);
+        auto a = sc_args<sc_nodes_args>(v);
+        a.mark_inf = d_mark;
+        a.mark_sup = d_mark + n_nodes;
+        a.c_super = d_cnt + v.t0;
+        a.c_source = d_cnt + M + v.t0;
+        a.c_shared = d_cnt + 2 * (int64_t)M + v.t0;
+        k_score_nodes<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
+        if (!sc_launched(e)) break;
+    }
+    sc_subtree_sums(s, c, n_nodes, d_mark, d_pref, d_out, e, bad);
+    int64_t *const node_outs[2] = {informative, supported};
+    sc_fetch_rows(s, d_out, nn, 2, node_outs, e);
+    int64_t *const outs[3] = {n_super, n_source, shared};
+    SCS_TRY(sc_end_counted(ctx, c, e, bad, d_cnt, 3, outs));
+    // n_source is the kernel's count less one for a tree of two leaves or more, 0 for the others
+    const std::vector<int64_t> &off = src->h_tree_off;
+    for (int32_t t = 0; t < M && n_source; ++t) n_source[t] = off[t + 1] - off[t] >= 2 ? n_source[t] - 1 : 0;
     return SCS_OK;
 }
 
@@ -2798,81 +2990,60 @@ extern "C" int scs_score_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n
                                   const int32_t *taxon, int32_t max_batch_trees, int64_t *t_super, int64_t *t_source,
                                   int64_t *t_shared) {
     // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "scs_score_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS",
-                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_TRY(sc_rows_fit("scs_score_triplets", src, 16));
     // own arrays: three counters and the first pair workgroup per tree (+ 1); per batch two node lists (int4 per
     // leaf) and their two lengths per tree
     const size_t mt = src ? (size_t)src->n_trees : 0;
-    const size_t o_cnt = 0, o_blk = sc_up256(mt * 24), own = o_blk + sc_up256((mt + 1) * 8);
+    unsigned long long *d_cnt;
+    int64_t *d_blk;
+    const auto own = [&](sc_carver w) {
+        d_cnt = w.take<unsigned long long>(3 * mt);
+        d_blk = w.take<int64_t>(mt + 1);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_triplets", n_nodes, parent, taxon, max_batch_trees, own, 32, 8, c, e));
+    SCS_TRY(sc_begin(ctx, src, "scs_score_triplets", n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at, 32,
+                     8, c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_ylist = wb.take<int4>(c.max_lb);
+    auto *d_zlist = wb.take<int4>(c.max_lb);
+    auto *d_ycnt = wb.take<int32_t>(2 * c.max_rows);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
     hipStream_t s = ctx->stream;
-    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    auto *d_ylist = (int4 *)c.d_extra_batch;
-    auto *d_zlist = d_ylist + c.max_lb;
-    auto *d_ycnt = (int32_t *)(d_zlist + c.max_lb);
     // per batch: W words per bitset row, zb S' nodes per workgroup; blk: the first pair workgroup of every tree
-    const size_t n_batches = c.bstart.size() - 1;
-    std::vector<int> words, zbs;
-    std::vector<int64_t> blk;
-    sc_trip_plan(off.data(), c.bstart, words, zbs, blk);
+    const sc_pair_plan pl = sc_plan_pairs(src->h_tree_off.data(), c.bstart, SC_TRIP_RULE);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, pl.blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
     // (the attribute is per function and device: set on every call)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_trip_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
         e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
         if (e != hipSuccess) break;
-        sc_trip_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.dep = c.d_dep;
-        a.node = c.d_node;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_tab = c.d_stab;
-        a.s_stride = c.n_gaps;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        auto a = sc_args<sc_trip_args>(v);
         a.ylist = d_ylist;
         a.zlist = d_zlist;
         a.ycnt = d_ycnt;
         a.zcnt = d_ycnt + nb;
         a.c_super = d_cnt + t0;
         a.c_source = d_cnt + M + t0;
-        k_trip_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        k_trip_nodes<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t n_wg = pl.blk[t0 + nb] - pl.blk[t0];
         if (n_wg == 0) continue;
-        const size_t lds = std::max<size_t>((size_t)zbs[b] * 16 * words[b], 32);
-        k_trip_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(d_blk + t0, nb, a.off, d_ylist, d_zlist, a.ycnt, a.zcnt,
-                                                             c.d_mm, zbs[b], words[b], d_cnt + 2 * (int64_t)M + t0);
+        k_trip_pairs<<<(unsigned)n_wg, SC_THREADS, pl.lds[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_zlist, a.ycnt,
+                                                                   a.zcnt, c.d_mm, pl.zbs[b], pl.words[b],
+                                                                   d_cnt + 2 * (int64_t)M + t0);
         if (!sc_launched(e)) break;
     }
-    std::vector<unsigned long long> cnt((size_t)M * 3);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    for (int32_t t = 0; t < M; ++t) {
-        if (t_super) t_super[t] = (int64_t)cnt[t];
-        if (t_source) t_source[t] = (int64_t)cnt[M + t];
-        if (t_shared) t_shared[t] = (int64_t)cnt[2 * M + t];
-    }
-    return SCS_OK;
+    int64_t *const outs[3] = {t_super, t_source, t_shared};
+    return sc_end_counted(ctx, c, e, bad, d_cnt, 3, outs);
 }
 
 // the plan of one scoring call on the host: what sc_begin and scs_score_triplets decide, by their own functions
@@ -2880,36 +3051,18 @@ extern "C" int scs_debug_score_plan(const scs_tables *src, int32_t n_trees, cons
                                     int32_t super_leaves, int32_t max_batch_trees, int64_t extra_per_leaf,
                                     int64_t extra_per_tree, int32_t *n_batches_out, int32_t *bstart_out,
                                     int64_t *info_out, int32_t *words_out, int32_t *zb_out, int64_t *wg_out) {
-    SCS_REQUIRE((src || tree_off) && n_batches_out && bstart_out && info_out && words_out && zb_out && wg_out,
-                "scs_debug_score_plan: null argument");
-    SCS_REQUIRE(!src || n_trees == src->n_trees, "scs_debug_score_plan: the tables hold %d trees, not %d",
-                src ? src->n_trees : 0, n_trees);
-    SCS_REQUIRE(n_trees >= 0 && super_leaves >= 0 && extra_per_leaf >= 0 && extra_per_tree >= 0,
-                "scs_debug_score_plan: negative argument");
-    const int64_t *off = src ? src->h_tree_off.data() : tree_off;
-    int64_t max_leaves = src ? src->max_leaves : 0;
-    if (!src)
-        for (int32_t t = 0; t < n_trees; ++t) {
-            SCS_REQUIRE(off[t + 1] >= off[t], "scs_debug_score_plan: tree_off decreases at tree %d", t);
-            max_leaves = std::max(max_leaves, off[t + 1] - off[t]);
-        }
-    int levels = 0;
-    int64_t row_stride = 0;
-    std::vector<int32_t> bstart;
-    sc_plan_batches(off, n_trees, max_leaves, super_leaves, max_batch_trees, (uint64_t)extra_per_leaf,
-                    (uint64_t)extra_per_tree, levels, row_stride, bstart);
-    std::vector<int> words, zbs;
-    std::vector<int64_t> blk;
-    sc_trip_plan(off, bstart, words, zbs, blk);
-    const size_t n_batches = bstart.size() - 1;
-    *n_batches_out = (int32_t)n_batches;
-    std::copy(bstart.begin(), bstart.end(), bstart_out);
-    info_out[0] = levels;
-    info_out[1] = row_stride;
-    for (size_t b = 0; b < n_batches; ++b) {
-        words_out[b] = words[b];
-        zb_out[b] = zbs[b];
-        wg_out[b] = blk[bstart[b + 1]] - blk[bstart[b]];
+    sc_debug_plan d;
+    SCS_TRY(sc_debug_batches("scs_debug_score_plan", src, n_trees, tree_off, super_leaves, max_batch_trees,
+                             extra_per_leaf, extra_per_tree, 0, info_out && words_out && zb_out && wg_out,
+                             n_batches_out, bstart_out, d));
+    const std::vector<int32_t> &bstart = d.bstart;
+    const sc_pair_plan pl = sc_plan_pairs(d.off, bstart, SC_TRIP_RULE);
+    info_out[0] = d.levels;
+    info_out[1] = d.row_stride;
+    for (size_t b = 0; b + 1 < bstart.size(); ++b) {
+        words_out[b] = pl.words[b];
+        zb_out[b] = pl.zbs[b];
+        wg_out[b] = pl.blk[bstart[b + 1]] - pl.blk[bstart[b]];
     }
     return SCS_OK;
 }
@@ -2921,32 +3074,37 @@ extern "C" int scs_score_conflicts(scs_ctx *ctx, const scs_tables *src, int32_t 
     // two counters per tree; per batch leaf ip's min-max table (the levels sc_begin gives the batch) and two mark rows
     const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
     const int levels = sc_levels_host(std::max<int64_t>(src ? src->max_leaves : 1, 1));
-    const size_t o_mark = 0, o_pref = o_mark + sc_up256(nn * 8), o_out = o_pref + sc_up256((nn + 1) * 16),
-                 o_cnt = o_out + sc_up256(nn * 16), own = o_cnt + sc_up256(mt * 16);
+    int32_t *d_mark;
+    int64_t *d_pref, *d_out;
+    unsigned long long *d_cnt;
+    const auto own = [&](sc_carver w) {
+        d_mark = w.take<int32_t>(2 * nn);
+        d_pref = w.take<int64_t>(2 * (nn + 1));
+        d_out = w.take<int64_t>(2 * nn);
+        d_cnt = w.take<unsigned long long>(2 * mt);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_conflicts", n_nodes, parent, taxon, max_batch_trees, own,
+    SCS_TRY(sc_begin(ctx, src, "scs_score_conflicts", n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
                      8 * (uint64_t)levels + 8, 0, c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_im = wb.take<int2>((size_t)c.levels * c.max_lb);
+    auto *d_ms = wb.take<int32_t>(2 * c.max_lb);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
     hipStream_t s = ctx->stream;
-    auto *d_mark = (int32_t *)(c.d_extra + o_mark);
-    auto *d_pref = (int64_t *)(c.d_extra + o_pref);
-    auto *d_out = (int64_t *)(c.d_extra + o_out);
-    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
-    auto *d_im = (int2 *)c.d_extra_batch;
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, nn * 8, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 16, s);
     for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
-        const int64_t *d_off = src->d_tree_off + t0;
-        int32_t *d_ms = (int32_t *)(d_im + (int64_t)c.levels * Lb), *d_mt = d_ms + Lb;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int64_t Lb = v.Lb;
+        int32_t *d_mt = d_ms + Lb;
         e = hipMemsetAsync(d_ms, 0, (size_t)Lb * 8, s);
         if (e != hipSuccess) break;
-        k_conf_ip<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_off, nb, c.d_mm, d_im);
+        k_conf_ip<<<grid_of(Lb), SC_THREADS, 0, s>>>(v.off, v.nb, c.d_mm, d_im);
         if (!sc_launched(e)) break;
         for (int j = 1; j < c.levels && e == hipSuccess; ++j) {
             k_conf_level<<<grid_of(Lb), SC_THREADS, 0, s>>>(d_im + (j - 1) * Lb, d_im + j * Lb, Lb,
@@ -2954,54 +3112,24 @@ extern "C" int scs_score_conflicts(scs_ctx *ctx, const scs_tables *src, int32_t 
             sc_launched(e);
         }
         if (e != hipSuccess) break;
-        sc_conf_args a;
-        a.off = d_off;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.dep = c.d_dep;
-        a.node = c.d_node;
-        a.mm = c.d_mm;
+        auto a = sc_args<sc_conf_args>(v);
         a.im = d_im;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_tab = c.d_stab;
-        a.s_stride = c.n_gaps;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
         a.mark_s = d_ms;
         a.mark_t = d_mt;
         a.mark_node = d_mark;
-        a.c_super = d_cnt + t0;
-        a.c_source = d_cnt + M + t0;
+        a.c_super = d_cnt + v.t0;
+        a.c_source = d_cnt + M + v.t0;
         k_conf_marks<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        k_conf_scan<<<nb, SC_THREADS, 0, s>>>(d_off, d_ms, d_mt);
+        k_conf_scan<<<v.nb, SC_THREADS, 0, s>>>(v.off, d_ms, d_mt);
         if (!sc_launched(e)) break;
         k_conf_nodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
     }
-    if (e == hipSuccess && !bad) {
-        k_score_prefix<<<1, 1024, 0, s>>>(d_mark, d_mark + n_nodes, n_nodes, d_pref, d_pref + n_nodes + 1);
-        sc_launched(e);
-    }
-    if (e == hipSuccess && !bad) {
-        k_score_subtree<<<grid_of(n_nodes), SC_THREADS, 0, s>>>(d_pref, d_pref + n_nodes + 1, c.d_end, n_nodes, d_out,
-                                                                d_out + n_nodes);
-        sc_launched(e);
-    }
-    std::vector<unsigned long long> cnt((size_t)M * 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 16, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && conflicting)
-        e = hipMemcpyAsync(conflicting, d_out, (size_t)n_nodes * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    for (int32_t t = 0; t < M; ++t) {
-        if (n_super_conflict) n_super_conflict[t] = (int64_t)cnt[t];
-        if (n_source_conflict) n_source_conflict[t] = (int64_t)cnt[M + t];
-    }
-    return SCS_OK;
+    sc_subtree_sums(s, c, n_nodes, d_mark, d_pref, d_out, e, bad);
+    sc_fetch_rows(s, d_out, nn, 1, &conflicting, e);
+    int64_t *const outs[2] = {n_super_conflict, n_source_conflict};
+    return sc_end_counted(ctx, c, e, bad, d_cnt, 2, outs);
 }
 
 extern "C" int scs_score_concordance(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
@@ -3010,141 +3138,107 @@ extern "C" int scs_score_concordance(scs_ctx *ctx, const scs_tables *src, int32_
                                      int64_t *concordant, int64_t *alt1, int64_t *alt2) {
     // own arrays: four counters and the quartet-branch record per S node, three counters per tree; nothing per leaf
     const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
-    const size_t o_node = 0, o_qp = o_node + sc_up256(nn * 32), o_cnt = o_qp + sc_up256(nn * 4),
-                 own = o_cnt + sc_up256(mt * 24);
+    unsigned long long *d_node, *d_cnt;
+    int32_t *d_qp;
+    const auto own = [&](sc_carver w) {
+        d_node = w.take<unsigned long long>(4 * nn);
+        d_qp = w.take<int32_t>(nn);
+        d_cnt = w.take<unsigned long long>(3 * mt);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_concordance", n_nodes, parent, taxon, max_batch_trees, own, 0, 0, c, e));
+    SCS_TRY(sc_begin(ctx, src, "scs_score_concordance", n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
+                     0, 0, c, e));
+    if (own(sc_carve_extra(c)).over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const int32_t M = c.M;
     hipStream_t s = ctx->stream;
-    auto *d_node = (unsigned long long *)(c.d_extra + o_node);
-    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
-    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
-    // quartet branches: two children, below a parent of two children (sc_begin has checked `parent`)
-    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
-    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
-    for (int32_t v = 1; v < n_nodes; ++v)
-        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    const std::vector<int32_t> q_parent = sc_quartet_parents(n_nodes, parent);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_node, 0, nn * 32, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
     for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = src->h_tree_off[t0], Lb = src->h_tree_off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
         sc_conc_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.node = c.d_node;
-        a.mm = c.d_mm;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.Lb = Lb;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        a.off = v.off;
+        a.nb = v.nb;
+        a.sp = v.sp;
+        a.node = v.node;
+        a.mm = v.mm;
+        a.adj = v.adj;
+        a.amin = v.amin;
+        a.Lb = v.Lb;
+        a.s_lo = v.s_lo;
+        a.s_hi = v.s_hi;
         a.q_parent = d_qp;
         a.n_dec = d_node;
         a.n_con = d_node + nn;
         a.n_alt1 = d_node + 2 * nn;
         a.n_alt2 = d_node + 3 * nn;
-        a.c_dec = d_cnt + t0;
-        a.c_con = d_cnt + M + t0;
-        a.c_alt = d_cnt + 2 * (int64_t)M + t0;
-        k_conc_branches<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        a.c_dec = d_cnt + v.t0;
+        a.c_con = d_cnt + M + v.t0;
+        a.c_alt = d_cnt + 2 * (int64_t)M + v.t0;
+        k_conc_branches<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
     }
-    std::vector<unsigned long long> cnt((size_t)M * 3);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
-    int64_t *const outs[4] = {decisive, concordant, alt1, alt2};
-    for (int i = 0; i < 4 && e == hipSuccess; ++i)
-        if (outs[i]) e = hipMemcpyAsync(outs[i], d_node + i * nn, nn * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    for (int32_t t = 0; t < M; ++t) {
-        if (n_decisive) n_decisive[t] = (int64_t)cnt[t];
-        if (n_concordant) n_concordant[t] = (int64_t)cnt[M + t];
-        if (n_alternative) n_alternative[t] = (int64_t)cnt[2 * M + t];
-    }
-    return SCS_OK;
+    int64_t *const node_outs[4] = {decisive, concordant, alt1, alt2};
+    sc_fetch_rows(s, d_node, nn, 4, node_outs, e);
+    int64_t *const outs[3] = {n_decisive, n_concordant, n_alternative};
+    return sc_end_counted(ctx, c, e, bad, d_cnt, 3, outs);
 }
 
 extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
                                          const int32_t *taxon, int32_t max_batch_trees, int64_t *n_bt_total,
                                          int64_t *n_bt_concordant, int64_t *n_bt_alternative, int64_t *bt_total,
                                          int64_t *bt_concordant, int64_t *bt_alt1, int64_t *bt_alt2) {
-    // the three rows of one record of the largest tree must fit one workgroup's LDS
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
-    SCS_REQUIRE(BT_ROW_BYTES * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "scs_score_branch_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in "
-                "LDS", (long long)m_max, TP_LDS_MAX / BT_ROW_BYTES * 32 - 1);
-    // a node's sum is at most sum_t (m_t / 3)^3: it must fit int64
-    if (src) {
-        unsigned __int128 cubes = 0;
-        for (int32_t t = 0; t < src->n_trees; ++t) {
-            const unsigned __int128 m = (unsigned __int128)(src->h_tree_off[t + 1] - src->h_tree_off[t]);
-            cubes += m * m * m;
-        }
-        SCS_REQUIRE(cubes / 27 <= (unsigned __int128)INT64_MAX,
-                    "scs_score_branch_triplets: the triple counts of %d source trees may not fit 64 bits",
-                    src->n_trees);
-    }
+    // the three rows of one record of the largest tree must fit one workgroup's LDS, and a node's sum int64
+    SCS_TRY(sc_rows_fit("scs_score_branch_triplets", src, BT_ROW_BYTES));
+    SCS_TRY(sc_cubes_fit("scs_score_branch_triplets", src));
     // own arrays: four counters and the quartet-branch record per S node, three counters and the first pair workgroup
     // per tree (+ 1); per batch T's node list (int4) and the record list per leaf, their two lengths per tree
     const size_t nn = (size_t)std::max(n_nodes, 0), mt = src ? (size_t)src->n_trees : 0;
-    const size_t o_node = 0, o_qp = o_node + sc_up256(nn * 32), o_cnt = o_qp + sc_up256(nn * 4),
-                 o_blk = o_cnt + sc_up256(mt * 24), own = o_blk + sc_up256((mt + 1) * 8);
+    unsigned long long *d_node, *d_cnt;
+    int32_t *d_qp;
+    int64_t *d_blk;
+    const auto own = [&](sc_carver w) {
+        d_node = w.take<unsigned long long>(4 * nn);
+        d_qp = w.take<int32_t>(nn);
+        d_cnt = w.take<unsigned long long>(3 * mt);
+        d_blk = w.take<int64_t>(mt + 1);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_branch_triplets", n_nodes, parent, taxon, max_batch_trees, own,
-                     16 + sizeof(sc_bt_rec), 8, c, e));
+    SCS_TRY(sc_begin(ctx, src, "scs_score_branch_triplets", n_nodes, parent, taxon, max_batch_trees,
+                     own(sc_carver()).at, 16 + sizeof(sc_bt_rec), 8, c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_ylist = wb.take<int4>(c.max_lb);
+    auto *d_recs = wb.take<sc_bt_rec>(c.max_lb);
+    auto *d_ycnt = wb.take<int32_t>(2 * c.max_rows);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
     hipStream_t s = ctx->stream;
-    auto *d_node = (unsigned long long *)(c.d_extra + o_node);
-    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
-    auto *d_cnt = (unsigned long long *)(c.d_extra + o_cnt);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    auto *d_ylist = (int4 *)c.d_extra_batch;
-    auto *d_recs = (sc_bt_rec *)(d_ylist + c.max_lb);
-    auto *d_ycnt = (int32_t *)(d_recs + c.max_lb);
-    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
-    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
-    for (int32_t v = 1; v < n_nodes; ++v)
-        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    const std::vector<int32_t> q_parent = sc_quartet_parents(n_nodes, parent);
     // per batch: W words per bitset row, zb records per workgroup and the launch's LDS; blk: the first pair workgroup
     // of every tree
-    const size_t n_batches = c.bstart.size() - 1;
-    std::vector<int> words, zbs;
-    std::vector<size_t> ldss;
-    std::vector<int64_t> blk;
-    sc_bt_plan(off.data(), c.bstart, words, zbs, ldss, blk);
+    const sc_pair_plan pl = sc_plan_pairs(src->h_tree_off.data(), c.bstart, SC_BT_RULE);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_node, 0, nn * 32, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 24, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, pl.blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
     // (the attribute is per function and device: set on every call)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_bt_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
         e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
         if (e != hipSuccess) break;
-        sc_bt_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.node = c.d_node;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        auto a = sc_args<sc_bt_args>(v);
         a.q_parent = d_qp;
         a.ylist = d_ylist;
         a.recs = d_recs;
@@ -3153,28 +3247,20 @@ extern "C" int scs_score_branch_triplets(scs_ctx *ctx, const scs_tables *src, in
         a.n_tot = d_node;
         a.c_tot = d_cnt + t0;
         a.nn = (int64_t)nn;
-        k_bt_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        k_bt_records<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t n_wg = pl.blk[t0 + nb] - pl.blk[t0];
         if (n_wg == 0) continue;
-        k_bt_pairs<<<(unsigned)n_wg, SC_THREADS, ldss[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
-                                                           c.d_mm, zbs[b], words[b], d_node + nn, (int64_t)nn,
-                                                           d_cnt + M + t0, d_cnt + 2 * (int64_t)M + t0);
+        k_bt_pairs<<<(unsigned)n_wg, SC_THREADS, pl.lds[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt,
+                                                                 a.rcnt, c.d_mm, pl.zbs[b], pl.words[b], d_node + nn,
+                                                                 (int64_t)nn, d_cnt + M + t0,
+                                                                 d_cnt + 2 * (int64_t)M + t0);
         if (!sc_launched(e)) break;
     }
-    std::vector<unsigned long long> cnt((size_t)M * 3);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, (size_t)M * 24, hipMemcpyDeviceToHost, s);
-    int64_t *const outs[4] = {bt_total, bt_concordant, bt_alt1, bt_alt2};
-    for (int i = 0; i < 4 && e == hipSuccess; ++i)
-        if (outs[i]) e = hipMemcpyAsync(outs[i], d_node + i * nn, nn * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    for (int32_t t = 0; t < M; ++t) {
-        if (n_bt_total) n_bt_total[t] = (int64_t)cnt[t];
-        if (n_bt_concordant) n_bt_concordant[t] = (int64_t)cnt[M + t];
-        if (n_bt_alternative) n_bt_alternative[t] = (int64_t)cnt[2 * M + t];
-    }
-    return SCS_OK;
+    int64_t *const node_outs[4] = {bt_total, bt_concordant, bt_alt1, bt_alt2};
+    sc_fetch_rows(s, d_node, nn, 4, node_outs, e);
+    int64_t *const outs[3] = {n_bt_total, n_bt_concordant, n_bt_alternative};
+    return sc_end_counted(ctx, c, e, bad, d_cnt, 3, outs);
 }
 
 namespace {
@@ -3219,7 +3305,7 @@ struct sc_tx_call {
 
 sc_tx_call sc_tx_call_of(int64_t m_max, int32_t max_lds_bytes) {
     sc_tx_call tc;
-    tc.lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    tc.lds_cap = sc_lds_cap(max_lds_bytes);
     tc.slab_stride = 2 * m_max + 2 + TX_SLAB_PAD;
     tc.need_slab = 2 * m_max + 1 > sc_tx_plan_of((int)(m_max >> 5) + 1, tc.lds_cap).dcap_max;
     tc.slab_wgs = !tc.need_slab ? 0
@@ -3244,9 +3330,7 @@ void sc_tx_batches(const int64_t *off, const std::vector<int32_t> &bstart, const
     slab_launch.assign(n_batches, 0);
     blk.assign(((size_t)M + 1) * TX_BINS, 0);
     for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = bstart[b]; t < bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
+        words[b] = sc_row_words(off, bstart[b], bstart[b + 1]);
         plans[b] = sc_tx_plan_of(words[b], tc.lds_cap);
         slab_launch[b] = tc.slab_wgs > 0 && 2 * ((int64_t)words[b] * 32) > plans[b].dcap_max;
         for (int i = 0; i < TX_BINS; ++i) {
@@ -3265,12 +3349,11 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
                                         int64_t *tx_shared) {
     // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS, as for scs_score_triplets; every
     // count of one tree is then below m^3 < 2^63
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "scs_score_taxon_triplets: a source tree of %lld leaves is more than the %d the pair kernel holds in "
-                "LDS", (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_TRY(sc_rows_fit("scs_score_taxon_triplets", src, 16));
     SCS_REQUIRE(max_lds_bytes >= 0, "scs_score_taxon_triplets: max_lds_bytes = %d is negative", max_lds_bytes);
-    // the outputs have one entry per supertree tip: the tips' taxon ids must be below their number
+    // the outputs have one entry per supertree tip: the tips' taxon ids must be below their number.  (Not
+    // sc_walk_super: this export has always taken any parent entry in range for a link here, and what it refuses for
+    // an array sc_begin would refuse later follows from that)
     int64_t n_out = 0;
     if (parent && taxon && n_nodes >= 1) {
         std::vector<char> has_kid((size_t)n_nodes, 0);
@@ -3283,40 +3366,43 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
                         taxon[v], (long long)n_out);
     }
     // the LDS cap and the slab path
-    const sc_tx_call tc = sc_tx_call_of(m_max, max_lds_bytes);
+    const sc_tx_call tc = sc_tx_call_of(sc_max_leaves(src), max_lds_bytes);
     const int64_t slab_stride = tc.slab_stride;
     const int slab_wgs = tc.slab_wgs;
     // own arrays: the five outputs per taxon, the first pair workgroup per tree (+ 1) and bin, the slabs; per batch
     // the two node lists (int4), three sums (shared and source in T order, super in S' order) and the TX_BINS + 1
     // bin lists per leaf, and per tree the lengths of all those lists
     const size_t mt = src ? (size_t)src->n_trees : 0;
-    const size_t o_tx = 0, o_blk = sc_up256((size_t)n_out * 40), o_slab = o_blk + sc_up256((mt + 1) * 8 * TX_BINS),
-                 own = o_slab + sc_up256((size_t)slab_wgs * slab_stride * 8);
+    unsigned long long *d_tx, *d_slab;
+    int64_t *d_blk;
+    const auto own = [&](sc_carver w) {
+        d_tx = w.take<unsigned long long>(5 * (size_t)n_out);
+        d_blk = w.take<int64_t>((mt + 1) * TX_BINS);
+        d_slab = w.take<unsigned long long>((size_t)slab_wgs * slab_stride);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_taxon_triplets", n_nodes, parent, taxon, max_batch_trees, own,
-                     32 + 24 + 4 * (TX_BINS + 1), 8 + 4 * (TX_BINS + 1), c, e));
+    SCS_TRY(sc_begin(ctx, src, "scs_score_taxon_triplets", n_nodes, parent, taxon, max_batch_trees,
+                     own(sc_carver()).at, 32 + 24 + 4 * (TX_BINS + 1), 8 + 4 * (TX_BINS + 1), c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_ylist = wb.take<int4>(c.max_lb);
+    auto *d_zlist = wb.take<int4>(c.max_lb);
+    auto *d_acc = wb.take<unsigned long long>(c.max_lb);
+    auto *d_dsrc = wb.take<unsigned long long>(c.max_lb);
+    auto *d_dsup = wb.take<unsigned long long>(c.max_lb);
+    auto *d_zbin = wb.take<int32_t>((TX_BINS + 1) * c.max_lb);
+    auto *d_ycnt = wb.take<int32_t>((2 + TX_BINS + 1) * c.max_rows);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
     hipStream_t s = ctx->stream;
-    auto *d_tx = (unsigned long long *)(c.d_extra + o_tx);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    auto *d_slab = (unsigned long long *)(c.d_extra + o_slab);
-    auto *d_ylist = (int4 *)c.d_extra_batch;
-    auto *d_zlist = d_ylist + c.max_lb;
-    auto *d_acc = (unsigned long long *)(d_zlist + c.max_lb);
-    auto *d_dsrc = d_acc + c.max_lb;
-    auto *d_dsup = d_dsrc + c.max_lb;
-    auto *d_zbin = (int32_t *)(d_dsup + c.max_lb);
-    auto *d_ycnt = d_zbin + (TX_BINS + 1) * c.max_lb;
     // per batch: W words per bitset row, the plan of its bins and whether the slab kernel runs; blk: per bin the first
     // pair workgroup of every tree
-    const size_t n_batches = c.bstart.size() - 1;
     std::vector<int> words;
     std::vector<sc_tx_plan> plans;
     std::vector<char> slab_launches;
     std::vector<int64_t> blk;
-    sc_tx_batches(off.data(), c.bstart, tc, words, plans, slab_launches, blk);
+    sc_tx_batches(src->h_tree_off.data(), c.bstart, tc, words, plans, slab_launches, blk);
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_tx, 0, (size_t)n_out * 40, s);
     if (e == hipSuccess)
@@ -3328,27 +3414,15 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_tx_pairs<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
+        const int64_t Lb = v.Lb;
         e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * (8 + 4 * (TX_BINS + 1)), s);
         if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, (size_t)c.max_lb * 8, s);
         if (e != hipSuccess) break;
-        sc_trip_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.dep = c.d_dep;
-        a.node = c.d_node;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_tab = c.d_stab;
-        a.s_stride = c.n_gaps;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        auto a = sc_args<sc_trip_args>(v);
         a.ylist = d_ylist;
         a.zlist = d_zlist;
         a.ycnt = d_ycnt;
@@ -3393,12 +3467,9 @@ extern "C" int scs_score_taxon_triplets(scs_ctx *ctx, const scs_tables *src, int
                                                      n_out);
         if (!sc_launched(e)) break;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
     int64_t *const outs[5] = {tx_trees, tx_total, tx_super, tx_source, tx_shared};
-    for (int i = 0; i < 5 && e == hipSuccess; ++i)
-        if (outs[i] && n_out) e = hipMemcpyAsync(outs[i], d_tx + i * n_out, (size_t)n_out * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    return SCS_OK;
+    sc_fetch_rows(s, d_tx, (size_t)n_out, 5, outs, e);
+    return sc_end(ctx, c, e, bad);
 }
 
 // the plans of scs_score_branch_triplets / scs_score_branch_resample and of scs_score_taxon_triplets on the host, by
@@ -3407,41 +3478,26 @@ extern "C" int scs_debug_branch_plan(const scs_tables *src, int32_t n_trees, con
                                      int32_t super_leaves, int32_t max_batch_trees, int64_t extra_per_leaf,
                                      int64_t extra_per_tree, int32_t max_lds_bytes, int32_t *n_batches_out,
                                      int32_t *bstart_out, int64_t *bt_out, int64_t *tx_out, int64_t *call_out) {
-    SCS_REQUIRE((src || tree_off) && n_batches_out && bstart_out && bt_out && tx_out && call_out,
-                "scs_debug_branch_plan: null argument");
-    SCS_REQUIRE(!src || n_trees == src->n_trees, "scs_debug_branch_plan: the tables hold %d trees, not %d",
-                src ? src->n_trees : 0, n_trees);
-    SCS_REQUIRE(n_trees >= 0 && super_leaves >= 0 && extra_per_leaf >= 0 && extra_per_tree >= 0 && max_lds_bytes >= 0,
-                "scs_debug_branch_plan: negative argument");
-    const int64_t *off = src ? src->h_tree_off.data() : tree_off;
-    int64_t max_leaves = src ? src->max_leaves : 0;
-    if (!src)
-        for (int32_t t = 0; t < n_trees; ++t) {
-            SCS_REQUIRE(off[t + 1] >= off[t], "scs_debug_branch_plan: tree_off decreases at tree %d", t);
-            max_leaves = std::max(max_leaves, off[t + 1] - off[t]);
-        }
-    int levels = 0;
-    int64_t row_stride = 0;
-    std::vector<int32_t> bstart;
-    sc_plan_batches(off, n_trees, max_leaves, super_leaves, max_batch_trees, (uint64_t)extra_per_leaf,
-                    (uint64_t)extra_per_tree, levels, row_stride, bstart);
+    sc_debug_plan d;
+    SCS_TRY(sc_debug_batches("scs_debug_branch_plan", src, n_trees, tree_off, super_leaves, max_batch_trees,
+                             extra_per_leaf, extra_per_tree, max_lds_bytes, bt_out && tx_out && call_out,
+                             n_batches_out, bstart_out, d));
+    const int64_t *off = d.off;
+    const std::vector<int32_t> &bstart = d.bstart;
     const size_t n_batches = bstart.size() - 1;
-    *n_batches_out = (int32_t)n_batches;
-    std::copy(bstart.begin(), bstart.end(), bstart_out);
-    std::vector<int> words, zbs;
-    std::vector<size_t> ldss;
-    std::vector<int64_t> blk;
-    sc_bt_plan(off, bstart, words, zbs, ldss, blk);
+    const sc_pair_plan bt = sc_plan_pairs(off, bstart, SC_BT_RULE);
     for (size_t b = 0; b < n_batches; ++b) {
         int64_t *o = bt_out + 4 * b;
-        o[0] = words[b];
-        o[1] = zbs[b];
-        o[2] = (int64_t)ldss[b];
-        o[3] = blk[bstart[b + 1]] - blk[bstart[b]];
+        o[0] = bt.words[b];
+        o[1] = bt.zbs[b];
+        o[2] = (int64_t)bt.lds[b];
+        o[3] = bt.blk[bstart[b + 1]] - bt.blk[bstart[b]];
     }
-    const sc_tx_call tc = sc_tx_call_of(std::max<int64_t>(max_leaves, 0), max_lds_bytes);
+    const sc_tx_call tc = sc_tx_call_of(std::max<int64_t>(d.max_leaves, 0), max_lds_bytes);
+    std::vector<int> words;
     std::vector<sc_tx_plan> plans;
     std::vector<char> slab_launches;
+    std::vector<int64_t> blk;
     sc_tx_batches(off, bstart, tc, words, plans, slab_launches, blk);
     for (size_t b = 0; b < n_batches; ++b) {
         int64_t *o = tx_out + (4 * TX_BINS + 2) * b;
@@ -3465,141 +3521,95 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
                                     const int32_t *taxon, int32_t max_batch_trees, int32_t max_lds_bytes,
                                     int32_t n_queries, const int32_t *queries, int64_t *pl_trees, int64_t *pl_total,
                                     int64_t *pl_source, int64_t *pl_super, int64_t *pl_shared) {
+    const char *const who = "scs_score_placements";
     // a row pair (cl(z), cl(pz)) of the largest tree must fit one workgroup's LDS, as for scs_score_triplets; every
     // count of one tree is then below m^2 < 2^63
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "scs_score_placements: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS",
-                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
-    SCS_REQUIRE(max_lds_bytes >= 0, "scs_score_placements: max_lds_bytes = %d is negative", max_lds_bytes);
-    SCS_REQUIRE(n_queries >= 1 && queries, "scs_score_placements: no query taxon");
-    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= lds_cap,
-                "scs_score_placements: max_lds_bytes = %d does not hold the rows of a source tree of %lld leaves",
-                max_lds_bytes, (long long)m_max);
+    SCS_TRY(sc_rows_fit(who, src, 16));
+    SCS_REQUIRE(max_lds_bytes >= 0, "%s: max_lds_bytes = %d is negative", who, max_lds_bytes);
+    SCS_REQUIRE(n_queries >= 1 && queries, "%s: no query taxon", who);
+    SCS_TRY(sc_rows_fit(who, src, 16, max_lds_bytes));
     // the queries are tips of the supertree, each once; the tips' preorder index and depth by leaf position
-    std::vector<int32_t> tip_node, tip_depth;
+    sc_walk sw;
     if (parent && taxon && n_nodes >= 1) {
-        std::vector<char> has_kid((size_t)n_nodes, 0);
-        std::vector<int32_t> depth((size_t)n_nodes, 0);
-        for (int32_t v = 1; v < n_nodes; ++v)
-            if (parent[v] >= 0 && parent[v] < v) {
-                has_kid[parent[v]] = 1;
-                depth[v] = depth[parent[v]] + 1;
-            }
+        sw = sc_walk_super(n_nodes, parent, false);
         std::vector<int32_t> tips;
-        for (int32_t v = 0; v < n_nodes; ++v)
-            if (!has_kid[v]) {
-                tip_node.push_back(v);
-                tip_depth.push_back(depth[v]);
-                tips.push_back(taxon[v]);
-            }
+        for (const int32_t v : sw.tip_node) tips.push_back(taxon[v]);
         std::sort(tips.begin(), tips.end());
         std::vector<int32_t> qs(queries, queries + n_queries);
         std::sort(qs.begin(), qs.end());
         for (int32_t i = 0; i < n_queries; ++i) {
             SCS_REQUIRE(std::binary_search(tips.begin(), tips.end(), qs[i]),
-                        "scs_score_placements: query taxon %d is not a tip of the supertree", qs[i]);
-            SCS_REQUIRE(i == 0 || qs[i] != qs[i - 1], "scs_score_placements: query taxon %d is given twice", qs[i]);
+                        "%s: query taxon %d is not a tip of the supertree", who, qs[i]);
+            SCS_REQUIRE(i == 0 || qs[i] != qs[i - 1], "%s: query taxon %d is given twice", who, qs[i]);
         }
     }
     // own arrays: three rows of n_nodes + 1 sums per query and output (`sub`, later the values; `strict`; the
-    // difference row), the two common rows per pass, three sums per query, the queries' S positions, S's parents and tips, the first pair workgroup
-    // per tree (+ 1).  Per batch: a group list entry per leaf and query of a pass, two node lists of two entries per
-    // leaf; per tree and query the query's positions and its list's length, per tree the node list's length and the
-    // number of queries it holds
+    // difference row), the two common rows per pass, three sums per query, the queries' S positions, S's parents and
+    // tips, the first pair workgroup per tree (+ 1).  Per batch: a group list entry per leaf and query of a pass, two
+    // node lists of two entries per leaf; per tree and query the query's positions and its list's length, per tree
+    // the node list's length and the number of queries it holds
     const size_t nn = (size_t)std::max(n_nodes, 0), nq = (size_t)n_queries, mt = src ? (size_t)src->n_trees : 0;
     const size_t row_bytes = sc_up256(2 * nq * (nn + 1) * 8);
     const int qcap = std::min<int>(std::max(n_queries, 1), PL_QMAX);
     const size_t n_pass = (nq + qcap - 1) / qcap, common_bytes = sc_up256(2 * n_pass * nn * 8);
     SCS_REQUIRE(3 * (uint64_t)row_bytes + common_bytes <= SC_BUDGET,
-                "scs_score_placements: %d query taxa x %d supertree nodes need %llu bytes of rows, more than the %llu "
-                "of the call's workspace", n_queries, n_nodes,
-                (unsigned long long)(3 * (uint64_t)row_bytes + common_bytes), (unsigned long long)SC_BUDGET);
-    const size_t o_sub = 0, o_strict = row_bytes, o_diff = 2 * row_bytes, o_common = 3 * row_bytes,
-                 o_qs = o_common + common_bytes, o_qpos = o_qs + sc_up256(nq * 24), o_par = o_qpos + sc_up256(nq * 4), o_tipn = o_par + sc_up256(nn * 4),
-                 o_tipd = o_tipn + sc_up256(nn * 4), o_blk = o_tipd + sc_up256(nn * 4),
-                 own = o_blk + sc_up256((mt + 1) * 8);
+                "%s: %d query taxa x %d supertree nodes need %llu bytes of rows, more than the %llu of the call's "
+                "workspace", who, n_queries, n_nodes, (unsigned long long)(3 * (uint64_t)row_bytes + common_bytes),
+                (unsigned long long)SC_BUDGET);
+    unsigned long long *d_sub, *d_strict, *d_diff, *d_common, *d_qs;
+    int32_t *d_qpos, *d_par, *d_tipn, *d_tipd;
+    int64_t *d_blk;
+    const auto own = [&](sc_carver w) {
+        d_sub = w.take<unsigned long long>(2 * nq * (nn + 1));  // (row_bytes each; zeroed up to d_qpos in one go)
+        d_strict = w.take<unsigned long long>(2 * nq * (nn + 1));
+        d_diff = w.take<unsigned long long>(2 * nq * (nn + 1));
+        d_common = w.take<unsigned long long>(2 * n_pass * nn);
+        d_qs = w.take<unsigned long long>(3 * nq);
+        d_qpos = w.take<int32_t>(nq);
+        d_par = w.take<int32_t>(nn);
+        d_tipn = w.take<int32_t>(nn);
+        d_tipd = w.take<int32_t>(nn);
+        d_blk = w.take<int64_t>(mt + 1);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, "scs_score_placements", n_nodes, parent, taxon, max_batch_trees, own,
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
                      16 * (uint64_t)qcap + 64, 12 * (uint64_t)qcap + 8, c, e));
-    const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_glist = wb.take<int4>(c.max_lb * qcap);
+    auto *d_zlist = wb.take<int4>(2 * c.max_lb);
+    auto *d_zmeta = wb.take<int4>(2 * c.max_lb);
+    auto *d_qinfo = wb.take<int2>(c.max_rows * qcap);
+    auto *d_gcnt = wb.take<int32_t>(c.max_rows * qcap);
+    auto *d_zcnt = wb.take<int32_t>(c.max_rows);
+    auto *d_qheld = wb.take<int32_t>(c.max_rows);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     hipStream_t s = ctx->stream;
-    auto *d_sub = (unsigned long long *)(c.d_extra + o_sub);
-    auto *d_strict = (unsigned long long *)(c.d_extra + o_strict);
-    auto *d_diff = (unsigned long long *)(c.d_extra + o_diff);
-    auto *d_common = (unsigned long long *)(c.d_extra + o_common);
-    auto *d_qs = (unsigned long long *)(c.d_extra + o_qs);
-    auto *d_qpos = (int32_t *)(c.d_extra + o_qpos);
-    auto *d_par = (int32_t *)(c.d_extra + o_par);
-    auto *d_tipn = (int32_t *)(c.d_extra + o_tipn);
-    auto *d_tipd = (int32_t *)(c.d_extra + o_tipd);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    const size_t n_batches = c.bstart.size() - 1;
-    int64_t max_rows = 0;
-    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
-    auto *d_glist = (int4 *)c.d_extra_batch;
-    auto *d_zlist = d_glist + c.max_lb * qcap;
-    auto *d_zmeta = d_zlist + 2 * c.max_lb;
-    auto *d_qinfo = (int2 *)(d_zmeta + 2 * c.max_lb);
-    auto *d_gcnt = (int32_t *)(d_qinfo + max_rows * qcap);
-    auto *d_zcnt = d_gcnt + max_rows * qcap;
-    auto *d_qheld = d_zcnt + max_rows;
     std::vector<int32_t> q_spos(nq);
     for (size_t i = 0; i < nq; ++i) q_spos[i] = queries[i] < c.n_taxa ? c.s_pos[queries[i]] : -1;
     // per batch: W words per bitset row, zb S' nodes per workgroup and whether the sums of a pass fit beside the rows;
-    // blk: the first pair workgroup of every tree, ceil(2 n / zb) of them for a tree of n >= 3 leaves (its S' has n
-    // leaves and at most n - 1 other nodes)
-    const int aux1 = 16 * qcap + 32, auxq = 4 * ((qcap + 4) & ~3);  // LDS bytes beside the rows: per node, per pass
-    std::vector<int> words(n_batches), zbs(n_batches), sums(n_batches);
-    std::vector<int64_t> blk((size_t)M + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        const int rowb = 16 * words[b];
-        int zb = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / rowb));
-        while (zb > 1 && zb * (rowb + aux1) + auxq > lds_cap) --zb;
-        sums[b] = zb * (rowb + aux1) + auxq <= lds_cap;
-        zbs[b] = zb;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) {
-            const int64_t n = off[t + 1] - off[t];
-            blk[t + 1] = blk[t] + (n >= 3 ? (2 * n + zb - 1) / zb : 0);
-        }
-    }
+    // blk: the first pair workgroup of every tree
+    const sc_pair_plan pl = sc_plan_pairs(src->h_tree_off.data(), c.bstart, sc_pl_rule(qcap, sc_lds_cap(max_lds_bytes)));
     unsigned bad = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, 3 * row_bytes + common_bytes + sc_up256(nq * 24), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, (size_t)((char *)d_qpos - (char *)d_sub), s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_qpos, q_spos.data(), nq * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_par, parent, nn * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tipn, tip_node.data(), tip_node.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tipd, tip_depth.data(), tip_depth.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_tipn, sw.tip_node.data(), sw.tip_node.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_tipd, sw.tip_depth.data(), sw.tip_depth.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, pl.blk.data(), (mt + 1) * 8, hipMemcpyHostToDevice, s);
     // (the attribute is per function and device: set on every call)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_pl_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
         e = hipMemsetAsync(d_zcnt, 0, (size_t)nb * 4, s);
         if (e != hipSuccess) break;
-        sc_pl_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.dep = c.d_dep;
-        a.node = c.d_node;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_tab = c.d_stab;
-        a.s_stride = c.n_gaps;
-        a.s_levels = sc_levels_host(c.n_gaps);
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        auto a = sc_args<sc_pl_args>(v);
         a.tip_node = d_tipn;
         a.tip_depth = d_tipd;
         a.zlist = d_zlist;
@@ -3608,9 +3618,9 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
         a.qinfo = d_qinfo;
         a.glist = d_glist;
         a.gcnt = d_gcnt;
-        k_pl_znodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        k_pl_znodes<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t n_wg = pl.blk[t0 + nb] - pl.blk[t0];
         for (int32_t q0 = 0; q0 < n_queries && n_wg > 0; q0 += qcap) {
             const int qc = std::min<int>(qcap, n_queries - q0);
             a.qc = qc;
@@ -3621,7 +3631,7 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
                                                                           c.row_stride, c.d_sp, d_qinfo, d_gcnt,
                                                                           d_qheld, d_qs + q0, d_qs + nq + q0);
             if (!sc_launched(e)) break;
-            k_pl_groups<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+            k_pl_groups<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
             if (!sc_launched(e)) break;
             sc_pl_pair_args pa;
             pa.blk = d_blk + t0;
@@ -3636,18 +3646,16 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
             pa.zmeta = d_zmeta;
             pa.zcnt = d_zcnt;
             pa.tp = c.d_mm;
-            pa.zb = zbs[b];
-            pa.W = words[b];
-            pa.lds_sums = sums[b];
+            pa.zb = pl.zbs[b];
+            pa.W = pl.words[b];
+            pa.lds_sums = pl.sums[b];
             pa.sub = d_sub + (size_t)q0 * nn;
             pa.strict = d_strict + (size_t)q0 * nn;
             pa.row_stride = (int64_t)nn;
             pa.super_off = (int64_t)(nq * nn);
             pa.csub = d_common + (size_t)(q0 / qcap) * nn;
             pa.cstrict = d_common + (n_pass + (size_t)(q0 / qcap)) * nn;
-            const size_t lds = (size_t)zbs[b] * 16 * words[b] + (sums[b] ? (size_t)zbs[b] * (16 * qc + 32) +
-                                                                              4 * ((qc + 4) & ~3) : 0);
-            k_pl_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(pa);
+            k_pl_pairs<<<(unsigned)n_wg, SC_THREADS, sc_pl_lds(pl, b, qc), s>>>(pa);
             if (!sc_launched(e)) break;
         }
     }
@@ -3661,15 +3669,10 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
         k_pl_prefix<<<(unsigned)(2 * nq), 1024, 0, s>>>(d_diff, (int64_t)nn, d_sub);
         sc_launched(e);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    int64_t *const scal[3] = {pl_trees, pl_total, pl_source};
-    for (int i = 0; i < 3 && e == hipSuccess; ++i)
-        if (scal[i]) e = hipMemcpyAsync(scal[i], d_qs + i * nq, nq * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && pl_shared) e = hipMemcpyAsync(pl_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && pl_super)
-        e = hipMemcpyAsync(pl_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    return SCS_OK;
+    int64_t *const scal[3] = {pl_trees, pl_total, pl_source}, *const rows[2] = {pl_shared, pl_super};
+    sc_fetch_rows(s, d_qs, nq, 3, scal, e);
+    sc_fetch_rows(s, d_sub, nq * nn, 2, rows, e);
+    return sc_end(ctx, c, e, bad);
 }
 
 // what scs_score_clade_placements and scs_score_clade_moves share: the checks, the sweep and the rows in the call's
@@ -3681,47 +3684,25 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
                          int64_t *cp_total, int64_t *cp_source, int64_t *cp_super, int64_t *cp_shared,
                          int64_t *mv_own_super, int64_t *mv_own_shared, int32_t *mv_node, int64_t *mv_super,
                          int64_t *mv_shared) {
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
-                (long long)m_max, TP_LDS_MAX / 16 * 32 - 1);
+    SCS_TRY(sc_rows_fit(who, src, 16));
     SCS_REQUIRE(max_lds_bytes >= 0, "%s: max_lds_bytes = %d is negative", who, max_lds_bytes);
     SCS_REQUIRE(n_queries >= 1 && query_nodes, "%s: no query node", who);
-    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
-    SCS_REQUIRE(16 * ((m_max >> 5) + 1) <= lds_cap,
-                "%s: max_lds_bytes = %d does not hold the rows of a source tree of %lld leaves", who, max_lds_bytes,
-                (long long)m_max);
+    SCS_TRY(sc_rows_fit(who, src, 16, max_lds_bytes));
     // the query nodes: not the root, in range, each once; their leaf ranges; the tips' preorder index and depth by
     // leaf position; the sub-queries (the S positions of every clade's tips, clade by clade)
-    std::vector<int32_t> tip_node, tip_depth, c_lo, c_hi, q_spos, q_clade;
+    sc_walk sw;
+    std::vector<int32_t> c_lo, c_hi, q_spos, q_clade;
     if (parent && taxon && n_nodes >= 1) {
-        std::vector<char> has_kid((size_t)n_nodes, 0);
-        std::vector<int32_t> depth((size_t)n_nodes, 0), lo((size_t)n_nodes, INT32_MAX), hi((size_t)n_nodes, -1);
-        for (int32_t v = 1; v < n_nodes; ++v)
-            if (parent[v] >= 0 && parent[v] < v) {
-                has_kid[parent[v]] = 1;
-                depth[v] = depth[parent[v]] + 1;
-            }
-        for (int32_t v = 0; v < n_nodes; ++v)
-            if (!has_kid[v]) {
-                lo[v] = hi[v] = (int32_t)tip_node.size();
-                tip_node.push_back(v);
-                tip_depth.push_back(depth[v]);
-            }
-        for (int32_t v = n_nodes - 1; v >= 1; --v)
-            if (parent[v] >= 0 && parent[v] < v) {
-                lo[parent[v]] = std::min(lo[parent[v]], lo[v]);
-                hi[parent[v]] = std::max(hi[parent[v]], hi[v]);
-            }
+        sw = sc_walk_super(n_nodes, parent, true);
         std::vector<char> seen((size_t)n_nodes, 0);
         for (int32_t i = 0; i < n_queries; ++i) {
             const int32_t q = query_nodes[i];
             SCS_REQUIRE(q >= 1 && q < n_nodes, "%s: query node %d is the root or out of range [1, %d)", who, q, n_nodes);
             SCS_REQUIRE(!seen[q], "%s: query node %d is given twice", who, q);
             seen[q] = 1;
-            c_lo.push_back(lo[q]);
-            c_hi.push_back(hi[q]);
-            for (int32_t p = lo[q]; p <= hi[q]; ++p) {
+            c_lo.push_back(sw.lo[q]);
+            c_hi.push_back(sw.hi[q]);
+            for (int32_t p = sw.lo[q]; p <= sw.hi[q]; ++p) {
                 q_spos.push_back(p);
                 q_clade.push_back(i);
             }
@@ -3740,102 +3721,81 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
                 "workspace", who, n_queries, n_nodes, (unsigned long long)(3 * (uint64_t)row_bytes),
                 (unsigned long long)SC_BUDGET);
     const int qcap = (int)std::min<size_t>(std::max<size_t>(ns, 1), CP_QMAX);
-    const size_t o_sub = 0, o_strict = row_bytes, o_diff = 2 * row_bytes, o_cs = 3 * row_bytes,
-                 o_clo = o_cs + sc_up256(nq * 24), o_chi = o_clo + sc_up256(nq * 4), o_qpos = o_chi + sc_up256(nq * 4),
-                 o_qslot = o_qpos + sc_up256(ns * 4), o_par = o_qslot + sc_up256(ns * 4),
-                 o_tipn = o_par + sc_up256(nn * 4), o_tipd = o_tipn + sc_up256(nn * 4),
-                 o_blk = o_tipd + sc_up256(nn * 4), o_mv = o_blk + sc_up256((mt + 1) * 8);
-    // the reduced rows (top_k >= 1): the query nodes, then per query its own pair and top_k (node, super, shared)
-    const size_t kk = (size_t)top_k, o_mvn = o_mv + (kk ? sc_up256(nq * 4) : 0), o_mvs = o_mvn + sc_up256(nq * kk * 4),
-                 o_mvh = o_mvs + sc_up256(nq * kk * 8), o_own = o_mvh + sc_up256(nq * kk * 8),
-                 own = o_own + (kk ? sc_up256(2 * nq * 8) : 0);
+    // (after the sweep's arrays the reduced rows, top_k >= 1: the query nodes, then per query top_k (node, super,
+    // shared) and its own pair)
+    const size_t kk = (size_t)top_k;
+    unsigned long long *d_sub, *d_strict, *d_diff, *d_cs;
+    int32_t *d_clo, *d_chi, *d_qpos, *d_qslot, *d_par, *d_tipn, *d_tipd, *d_qnode = nullptr, *d_mvn;
+    int64_t *d_blk;
+    long long *d_mvs, *d_mvh, *d_own = nullptr;
+    const auto own = [&](sc_carver w) {
+        d_sub = w.take<unsigned long long>(2 * nq * (nn + 1));  // (row_bytes each; zeroed up to d_clo in one go)
+        d_strict = w.take<unsigned long long>(2 * nq * (nn + 1));
+        d_diff = w.take<unsigned long long>(2 * nq * (nn + 1));
+        d_cs = w.take<unsigned long long>(3 * nq);
+        d_clo = w.take<int32_t>(nq);
+        d_chi = w.take<int32_t>(nq);
+        d_qpos = w.take<int32_t>(ns);
+        d_qslot = w.take<int32_t>(ns);
+        d_par = w.take<int32_t>(nn);
+        d_tipn = w.take<int32_t>(nn);
+        d_tipd = w.take<int32_t>(nn);
+        d_blk = w.take<int64_t>(mt + 1);
+        if (kk) d_qnode = w.take<int32_t>(nq);
+        d_mvn = w.take<int32_t>(nq * kk);
+        d_mvs = w.take<long long>(nq * kk);
+        d_mvh = w.take<long long>(nq * kk);
+        if (kk) d_own = w.take<long long>(2 * nq);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 25 * (uint64_t)qcap + 64,
-                     36 * (uint64_t)qcap + 8, c, e));
-    const int32_t M = c.M;
-    const std::vector<int64_t> &off = src->h_tree_off;
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
+                     25 * (uint64_t)qcap + 64, 36 * (uint64_t)qcap + 8, c, e));
+    const int64_t max_rstride = (c.max_lb >> 5) + c.max_rows;
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_glist = wb.take<int4>(c.max_lb * qcap);
+    auto *d_zlist = wb.take<int4>(2 * c.max_lb);
+    auto *d_zmeta = wb.take<int4>(2 * c.max_lb);
+    auto *d_cinfo = wb.take<int4>(c.max_rows * qcap);
+    auto *d_gq = wb.take<int2>(c.max_lb * qcap);
+    auto *d_qrow = wb.take<int2>(max_rstride * qcap);
+    auto *d_qinfo = wb.take<int2>(c.max_rows * qcap);
+    auto *d_gcnt = wb.take<int32_t>(c.max_rows * qcap);
+    auto *d_zcnt = wb.take<int32_t>(c.max_rows);
+    auto *d_qheld = wb.take<int32_t>(c.max_rows);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     hipStream_t s = ctx->stream;
-    auto *d_sub = (unsigned long long *)(c.d_extra + o_sub);
-    auto *d_strict = (unsigned long long *)(c.d_extra + o_strict);
-    auto *d_diff = (unsigned long long *)(c.d_extra + o_diff);
-    auto *d_cs = (unsigned long long *)(c.d_extra + o_cs);
-    auto *d_clo = (int32_t *)(c.d_extra + o_clo);
-    auto *d_chi = (int32_t *)(c.d_extra + o_chi);
-    auto *d_qpos = (int32_t *)(c.d_extra + o_qpos);
-    auto *d_qslot = (int32_t *)(c.d_extra + o_qslot);
-    auto *d_par = (int32_t *)(c.d_extra + o_par);
-    auto *d_tipn = (int32_t *)(c.d_extra + o_tipn);
-    auto *d_tipd = (int32_t *)(c.d_extra + o_tipd);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    const size_t n_batches = c.bstart.size() - 1;
-    int64_t max_rows = 0;
-    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
-    const int64_t max_rstride = (c.max_lb >> 5) + max_rows;
-    auto *d_glist = (int4 *)c.d_extra_batch;
-    auto *d_zlist = d_glist + c.max_lb * qcap;
-    auto *d_zmeta = d_zlist + 2 * c.max_lb;
-    auto *d_cinfo = d_zmeta + 2 * c.max_lb;
-    auto *d_gq = (int2 *)(d_cinfo + max_rows * qcap);
-    auto *d_qrow = d_gq + c.max_lb * qcap;
-    auto *d_qinfo = d_qrow + max_rstride * qcap;
-    auto *d_gcnt = (int32_t *)(d_qinfo + max_rows * qcap);
-    auto *d_zcnt = d_gcnt + max_rows * qcap;
-    auto *d_qheld = d_zcnt + max_rows;
     // the sub-queries' slots: the clade's index less the first clade of the sub-query's pass
     std::vector<int32_t> q_slot(ns);
     for (size_t i = 0; i < ns; ++i) q_slot[i] = q_clade[i] - q_clade[i / qcap * qcap];
-    const int aux1 = 16 * qcap + 32, auxq = 4 * ((qcap + 4) & ~3);  // LDS bytes beside the rows: per node, per pass
-    std::vector<int> words(n_batches), zbs(n_batches), sums(n_batches);
-    std::vector<int64_t> blk((size_t)M + 1, 0);
-    for (size_t b = 0; b < n_batches; ++b) {
-        int64_t nmax = 0;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        words[b] = (int)(nmax >> 5) + 1;
-        const int rowb = 16 * words[b];
-        int zb = (int)std::min<int64_t>(TP_ZMAX, std::max<int64_t>(1, TP_LDS_BUDGET / rowb));
-        while (zb > 1 && zb * (rowb + aux1) + auxq > lds_cap) --zb;
-        sums[b] = zb * (rowb + aux1) + auxq <= lds_cap;
-        zbs[b] = zb;
-        for (int32_t t = c.bstart[b]; t < c.bstart[b + 1]; ++t) {
-            const int64_t n = off[t + 1] - off[t];
-            blk[t + 1] = blk[t] + (n >= 3 ? (2 * n + zb - 1) / zb : 0);
-        }
-    }
+    // per batch W, zb and whether the sums fit, and blk, as in scs_score_placements
+    const sc_pair_plan pl = sc_plan_pairs(src->h_tree_off.data(), c.bstart, sc_pl_rule(qcap, sc_lds_cap(max_lds_bytes)));
     unsigned bad = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, 3 * row_bytes + sc_up256(nq * 24), s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_sub, 0, (size_t)((char *)d_clo - (char *)d_sub), s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_clo, c_lo.data(), nq * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_chi, c_hi.data(), nq * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_qpos, q_spos.data(), ns * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_qslot, q_slot.data(), ns * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_par, parent, nn * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tipn, tip_node.data(), tip_node.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tipd, tip_depth.data(), tip_depth.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_tipn, sw.tip_node.data(), sw.tip_node.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_tipd, sw.tip_depth.data(), sw.tip_depth.size() * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, pl.blk.data(), (mt + 1) * 8, hipMemcpyHostToDevice, s);
     // (the attribute is per function and device: set on every call)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_cp_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
+        const int64_t Lb = v.Lb;
         e = hipMemsetAsync(d_zcnt, 0, (size_t)nb * 4, s);
         if (e != hipSuccess) break;
-        sc_pl_args za;
-        za.off = src->d_tree_off + t0;
-        za.nb = nb;
-        za.sp = c.d_sp;
-        za.dep = c.d_dep;
-        za.node = c.d_node;
-        za.adj = src->d_adj_depth + L0;
-        za.amin = c.d_amin;
-        za.levels = c.levels;
-        za.Lb = Lb;
-        za.s_tab = c.d_stab;
-        za.s_stride = c.n_gaps;
-        za.s_levels = sc_levels_host(c.n_gaps);
-        za.s_lo = c.d_slo;
-        za.s_hi = c.d_shi;
+        // k_pl_znodes, the one kernel launched with these arguments here, reads nothing of a query: those members of
+        // sc_pl_args stay null (the clades' own lists go through sc_cp_args below)
+        auto za = sc_args<sc_pl_args>(v);
         za.tip_node = d_tipn;
         za.tip_depth = d_tipd;
         za.zlist = d_zlist;
@@ -3848,22 +3808,14 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
         za.q_source = nullptr;
         k_pl_znodes<<<grid_of(Lb), SC_THREADS, 0, s>>>(za);
         if (!sc_launched(e)) break;
-        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t n_wg = pl.blk[t0 + nb] - pl.blk[t0];
         const int64_t rstride = (Lb >> 5) + nb;
         for (size_t i0 = 0; i0 < ns && n_wg > 0; i0 += qcap) {
             const int qc = (int)std::min<size_t>(qcap, ns - i0);
             const int32_t c0 = q_clade[i0], c1 = q_clade[i0 + qc - 1];
-            sc_cp_args a;
-            a.off = za.off;
-            a.nb = nb;
-            a.sp = c.d_sp;
-            a.tp = c.d_mm;
+            auto a = sc_args<sc_cp_args>(v);
             a.rows = c.d_rows;
             a.row_stride = c.row_stride;
-            a.adj = za.adj;
-            a.amin = c.d_amin;
-            a.levels = c.levels;
-            a.Lb = Lb;
             a.c_lo = d_clo + c0;
             a.c_hi = d_chi + c0;
             a.q_spos = d_qpos + i0;
@@ -3915,16 +3867,14 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
             pa.zmeta = d_zmeta;
             pa.zcnt = d_zcnt;
             pa.tp = c.d_mm;
-            pa.zb = zbs[b];
-            pa.W = words[b];
-            pa.lds_sums = sums[b];
+            pa.zb = pl.zbs[b];
+            pa.W = pl.words[b];
+            pa.lds_sums = pl.sums[b];
             pa.sub = a.sub;
             pa.strict = d_strict + (size_t)c0 * nn;
             pa.row_stride = (int64_t)nn;
             pa.super_off = a.super_off;
-            const size_t lds = (size_t)zbs[b] * 16 * words[b] + (sums[b] ? (size_t)zbs[b] * (16 * qc + 32) +
-                                                                              4 * ((qc + 4) & ~3) : 0);
-            k_cp_pairs<<<(unsigned)n_wg, SC_THREADS, lds, s>>>(pa);
+            k_cp_pairs<<<(unsigned)n_wg, SC_THREADS, sc_pl_lds(pl, b, qc), s>>>(pa);
             if (!sc_launched(e)) break;
         }
     }
@@ -3937,19 +3887,10 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
         k_pl_prefix<<<(unsigned)(2 * nq), 1024, 0, s>>>(d_diff, (int64_t)nn, d_sub);
         sc_launched(e);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
-    int64_t *const scal[3] = {cp_trees, cp_total, cp_source};
-    for (int i = 0; i < 3 && e == hipSuccess; ++i)
-        if (scal[i]) e = hipMemcpyAsync(scal[i], d_cs + i * nq, nq * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cp_shared) e = hipMemcpyAsync(cp_shared, d_sub, nq * nn * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && cp_super)
-        e = hipMemcpyAsync(cp_super, d_sub + nq * nn, nq * nn * 8, hipMemcpyDeviceToHost, s);
+    int64_t *const scal[3] = {cp_trees, cp_total, cp_source}, *const rows[2] = {cp_shared, cp_super};
+    sc_fetch_rows(s, d_cs, nq, 3, scal, e);
+    sc_fetch_rows(s, d_sub, nq * nn, 2, rows, e);
     if (top_k > 0 && e == hipSuccess && !bad) {
-        auto *d_qnode = (int32_t *)(c.d_extra + o_mv);
-        auto *d_mvn = (int32_t *)(c.d_extra + o_mvn);
-        auto *d_mvs = (long long *)(c.d_extra + o_mvs);
-        auto *d_mvh = (long long *)(c.d_extra + o_mvh);
-        auto *d_own = (long long *)(c.d_extra + o_own);
         e = hipMemcpyAsync(d_qnode, query_nodes, nq * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             k_cp_best<<<(unsigned)nq, SC_THREADS, 0, s>>>((const long long *)d_sub, (const long long *)(d_sub + nq * nn),
@@ -3960,13 +3901,10 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
         if (e == hipSuccess && mv_node) e = hipMemcpyAsync(mv_node, d_mvn, nq * kk * 4, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && mv_super) e = hipMemcpyAsync(mv_super, d_mvs, nq * kk * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && mv_shared) e = hipMemcpyAsync(mv_shared, d_mvh, nq * kk * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && mv_own_super)
-            e = hipMemcpyAsync(mv_own_super, d_own, nq * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && mv_own_shared)
-            e = hipMemcpyAsync(mv_own_shared, d_own + nq, nq * 8, hipMemcpyDeviceToHost, s);
+        int64_t *const owns[2] = {mv_own_super, mv_own_shared};
+        sc_fetch_rows(s, d_own, nq, 2, owns, e);
     }
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    return SCS_OK;
+    return sc_end(ctx, c, e, bad);
 }
 
 extern "C" int scs_score_clade_placements(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
@@ -4010,13 +3948,8 @@ namespace {
 
 constexpr int PY_KMAX = 64;  // children of a query node: one lane each
 
-struct sc_py_rec_args {
-    const int64_t *off;         // tree_off + t0
-    int nb;
-    const int32_t *adj, *amin;  // T's min table of adj_depth (as in sc_nodes_args)
-    int levels;
-    int64_t Lb;
-    int4 *ylist;                // [Lb] T's nodes of a tree from its first leaf on
+struct sc_py_rec_args : sc_batch {
+    int4 *ylist;               // [Lb] T's nodes of a tree from its first leaf on
     int32_t *ycnt;              // [nb] list lengths
 };
 
@@ -4055,22 +3988,20 @@ __global__ void __launch_bounds__(SC_THREADS) k_py_records(sc_py_rec_args a) {
 // what the colour, total and sweep kernels share: query q has k = coff[q + 1] - coff[q] - 1 children, its k + 1
 // boundaries (S positions: the first leaf of every child, then one past the node's last) at bnd[coff[q] ...], the same
 // slots in a tree's row of cidx (S' indices), and its k^3 output entries at ooff[q]
-struct sc_py_args {
-    const int64_t *off;       // tree_off + t0
-    int nb, nq, totb;         // trees of the batch, queries, boundaries of all queries
-    const int32_t *sp;        // [Lb] S positions in S order
-    const int32_t *coff;      // [nq + 1]
+struct sc_py_args : sc_batch {
+    int nq, totb;             // queries, boundaries of all queries
+    const int32_t *coff;     // [nq + 1]
     const int64_t *ooff;      // [nq + 1]
     const int32_t *bnd;       // [totb]
     int32_t *cidx;            // [nb][totb]
     int32_t *dec;             // [nb][nq] 1: the tree is decisive at the query
     unsigned long long *trees, *total, *joint;  // py_trees [nq], py_total / py_joint [ooff[nq]]
-    // the sweep alone: the queries of one degree k, T's node lists, tp, the words of a row and its stride in LDS
+    // the sweep alone: the queries of one degree k, T's node lists, the words of a row and its stride in LDS (and of
+    // the batch view off and mm, moved to the launch's first tree)
     const int32_t *gq;
     int ngq, k, W, Ws, acc_lds;
     const int4 *ylist;
     const int32_t *ycnt;
-    const int2 *tp;
 };
 
 // one thread per (tree, query): the colour boundaries in the tree's S' order; decisive trees counted
@@ -4141,7 +4072,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_py_sweep(sc_py_args a) {
     unsigned *bits = reinterpret_cast<unsigned *>(rows);  // (word i of the image: .x of entry i / 2)
     for (int c = wave; c < k; c += SC_THREADS / 64)
         for (int s = cx[c] + lane; s < cx[c + 1]; s += 64) {
-            const int x = a.tp[base + s].x;
+            const int x = a.mm[base + s].x;
             atomicOr(bits + 2 * (c * Ws + (x >> 5)), 1u << (x & 31));
         }
     __syncthreads();
@@ -4204,19 +4135,18 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
                                     int32_t n_queries, const int32_t *query_nodes, int32_t *py_degree,
                                     int64_t *py_trees, int64_t *py_total, int64_t *py_joint) {
     const char *const who = "scs_score_polytomies";
-    const int64_t m_max = src ? std::max<int64_t>(src->max_leaves, 0) : 0;
+    const int64_t m_max = sc_max_leaves(src);
     SCS_REQUIRE(max_lds_bytes >= 0, "%s: max_lds_bytes = %d is negative", who, max_lds_bytes);
     SCS_REQUIRE(n_queries >= 1 && query_nodes, "%s: no query node", who);
-    const int lds_cap = max_lds_bytes > 0 ? std::min<int>(max_lds_bytes, TP_LDS_MAX) : TP_LDS_MAX;
+    const int lds_cap = sc_lds_cap(max_lds_bytes);
     // the query nodes: nodes, each once, 3 to PY_KMAX children; their children in child order
     const size_t nq = (size_t)n_queries;
     std::vector<int32_t> coff(nq + 1, 0), kid_of;  // kid_of: the children of query i at coff[i] - i ...
     std::vector<int64_t> ooff(nq + 1, 0);
     int k_max = 0;
     if (parent && taxon && n_nodes >= 1) {
-        std::vector<int32_t> n_kids((size_t)n_nodes, 0), slot((size_t)n_nodes, -1);
-        for (int32_t v = 1; v < n_nodes; ++v)
-            if (parent[v] >= 0 && parent[v] < v) n_kids[parent[v]]++;
+        const std::vector<int32_t> n_kids = sc_walk_super(n_nodes, parent, false).n_kids;
+        std::vector<int32_t> slot((size_t)n_nodes, -1);
         for (size_t i = 0; i < nq; ++i) {
             const int32_t q = query_nodes[i];
             SCS_REQUIRE(q >= 0 && q < n_nodes, "%s: query node %d is not in [0, %d)", who, q, n_nodes);
@@ -4247,41 +4177,35 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
                 "%s: the tensors of %d query nodes need %llu bytes, more than the %llu of the call's workspace", who,
                 n_queries, (unsigned long long)ooff[nq] * 16, (unsigned long long)SC_BUDGET);
     // an entry is at most sum_t (m_t / 3)^3: it must fit int64
-    if (src) {
-        unsigned __int128 cubes = 0;
-        for (int32_t t = 0; t < src->n_trees; ++t) {
-            const unsigned __int128 m = (unsigned __int128)(src->h_tree_off[t + 1] - src->h_tree_off[t]);
-            cubes += m * m * m;
-        }
-        SCS_REQUIRE(cubes / 27 <= (unsigned __int128)INT64_MAX,
-                    "%s: the triple counts of %d source trees may not fit 64 bits", who, src->n_trees);
-    }
+    SCS_TRY(sc_cubes_fit(who, src));
     // own arrays: the two tensors, py_trees, the offsets, the boundaries and the queries by degree; per batch T's node
     // list (int4) per leaf, its length per tree, and per tree the boundaries in S' order and the decisive flags
     const size_t totb = (size_t)coff[nq], n_out = (size_t)ooff[nq];
-    const size_t o_total = 0, o_joint = o_total + sc_up256(n_out * 8), o_trees = o_joint + sc_up256(n_out * 8),
-                 o_coff = o_trees + sc_up256(nq * 8), o_ooff = o_coff + sc_up256((nq + 1) * 4),
-                 o_bnd = o_ooff + sc_up256((nq + 1) * 8), o_gq = o_bnd + sc_up256(totb * 4),
-                 own = o_gq + sc_up256(nq * 4);
+    unsigned long long *d_total, *d_joint, *d_trees;
+    int32_t *d_coff, *d_bnd, *d_gq;
+    int64_t *d_ooff;
+    const auto own = [&](sc_carver w) {
+        d_total = w.take<unsigned long long>(n_out);  // (both tensors and py_trees are zeroed in one go)
+        d_joint = w.take<unsigned long long>(n_out);
+        d_trees = w.take<unsigned long long>(nq);
+        d_coff = w.take<int32_t>(nq + 1);
+        d_ooff = w.take<int64_t>(nq + 1);
+        d_bnd = w.take<int32_t>(totb);
+        d_gq = w.take<int32_t>(nq);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 16, 4 + 4 * (totb + nq), c, e));
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at, 16,
+                     4 + 4 * (totb + nq), c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_ylist = wb.take<int4>(c.max_lb);
+    auto *d_ycnt = wb.take<int32_t>(c.max_rows);
+    auto *d_cidx = wb.take<int32_t>(c.max_rows * totb);
+    auto *d_dec = wb.take<int32_t>(c.max_rows * nq);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     const std::vector<int64_t> &off = src->h_tree_off;
     hipStream_t s = ctx->stream;
-    auto *d_total = (unsigned long long *)(c.d_extra + o_total);
-    auto *d_joint = (unsigned long long *)(c.d_extra + o_joint);
-    auto *d_trees = (unsigned long long *)(c.d_extra + o_trees);
-    auto *d_coff = (int32_t *)(c.d_extra + o_coff);
-    auto *d_ooff = (int64_t *)(c.d_extra + o_ooff);
-    auto *d_bnd = (int32_t *)(c.d_extra + o_bnd);
-    auto *d_gq = (int32_t *)(c.d_extra + o_gq);
-    const size_t n_batches = c.bstart.size() - 1;
-    int64_t max_rows = 0;
-    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
-    auto *d_ylist = (int4 *)c.d_extra_batch;
-    auto *d_ycnt = (int32_t *)(d_ylist + c.max_lb);
-    auto *d_cidx = d_ycnt + max_rows;
-    auto *d_dec = d_cidx + max_rows * (int64_t)totb;
     // the boundaries (S positions, sc_begin's leaf ranges) and the queries grouped by degree
     std::vector<int32_t> bnd(totb), gq(nq), g_first(PY_KMAX + 2, 0);
     for (size_t i = 0; i < nq; ++i) {
@@ -4297,7 +4221,7 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
         for (size_t i = 0; i < nq; ++i) gq[at[coff[i + 1] - coff[i] - 1]++] = (int32_t)i;
     }
     unsigned bad = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, o_coff, s);  // (both tensors and py_trees)
+    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, (size_t)((char *)d_coff - (char *)d_total), s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_coff, coff.data(), (nq + 1) * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ooff, ooff.data(), (nq + 1) * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_bnd, bnd.data(), totb * 4, hipMemcpyHostToDevice, s);
@@ -4305,29 +4229,20 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
     // (the attribute is per function and device: set on every call)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_py_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
         e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 4, s);
         if (e != hipSuccess) break;
-        sc_py_rec_args r;
-        r.off = src->d_tree_off + t0;
-        r.nb = nb;
-        r.adj = src->d_adj_depth + L0;
-        r.amin = c.d_amin;
-        r.levels = c.levels;
-        r.Lb = Lb;
+        auto r = sc_args<sc_py_rec_args>(v);
         r.ylist = d_ylist;
         r.ycnt = d_ycnt;
-        k_py_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(r);
+        k_py_records<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(r);
         if (!sc_launched(e)) break;
-        sc_py_args a;
-        a.off = r.off;
-        a.nb = nb;
+        auto a = sc_args<sc_py_args>(v);  // (the sweep's own members: zero until its launches)
         a.nq = n_queries;
         a.totb = (int)totb;
-        a.sp = c.d_sp;
         a.coff = d_coff;
         a.ooff = d_ooff;
         a.bnd = d_bnd;
@@ -4337,19 +4252,15 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
         a.total = d_total;
         a.joint = d_joint;
         a.gq = d_gq;
-        a.ngq = a.k = a.W = a.Ws = a.acc_lds = 0;
         a.ylist = d_ylist;
         a.ycnt = d_ycnt;
-        a.tp = c.d_mm;
         k_py_colours<<<grid_of((int64_t)nb * n_queries), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
         k_py_total<<<grid_of((int64_t)n_out), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
         // the sweep, one launch per degree (and chunk of 65535 trees): W words per row; the rows' stride is odd where
         // that fits (lane = row: an even stride puts the lanes' reads on few banks); the sums in LDS where they fit
-        int64_t nmax = 0;
-        for (int32_t t = t0; t < t0 + nb; ++t) nmax = std::max(nmax, off[t + 1] - off[t]);
-        a.W = (int)std::max<int64_t>((nmax + 31) >> 5, 1);
+        a.W = (int)std::max<int64_t>((sc_largest_tree(off.data(), t0, t0 + nb) + 31) >> 5, 1);
         for (int k = 3; k <= PY_KMAX && e == hipSuccess; ++k) {
             const int ng = g_first[k + 1] - g_first[k];
             if (ng == 0) continue;
@@ -4368,21 +4279,19 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
                 ac.dec = d_dec + (int64_t)ty * n_queries;
                 ac.ycnt = d_ycnt + ty;
                 // (lists and tp are indexed from the batch's first leaf: off[t] - off[0] of the chunk's own off)
-                const int64_t shift = off[t0 + ty] - L0;
+                const int64_t shift = off[t0 + ty] - v.L0;
                 ac.ylist = d_ylist + shift;
-                ac.tp = c.d_mm + shift;
+                ac.mm = c.d_mm + shift;
                 k_py_sweep<<<dim3((unsigned)(ng * (k - 1)), (unsigned)std::min<int32_t>(nb - ty, 65535)), SC_THREADS,
                              lds, s>>>(ac);
                 sc_launched(e);
             }
         }
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_trees) e = hipMemcpyAsync(py_trees, d_trees, nq * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_total) e = hipMemcpyAsync(py_total, d_total, n_out * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_joint) e = hipMemcpyAsync(py_joint, d_joint, n_out * 8, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    return SCS_OK;
+    return sc_end(ctx, c, e, bad);
 }
 
 // ---- resampled and weighted branch triplet support (scs_score_branch_resample) ----
@@ -4482,11 +4391,9 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
     const int32_t M = src->n_trees;
     const std::vector<int64_t> &off = src->h_tree_off;
     // the three rows of one record of the largest tree must fit one workgroup's LDS (section 18)
-    const int64_t m_max = std::max<int64_t>(src->max_leaves, 0);
-    SCS_REQUIRE(BT_ROW_BYTES * ((m_max >> 5) + 1) <= TP_LDS_MAX,
-                "%s: a source tree of %lld leaves is more than the %d the pair kernel holds in LDS", who,
-                (long long)m_max, TP_LDS_MAX / BT_ROW_BYTES * 32 - 1);
-    // a row's entry is at most sum_t w[r][t] floor(m_t^3 / 27): it must fit int64
+    SCS_TRY(sc_rows_fit(who, src, BT_ROW_BYTES));
+    // a row's entry is at most sum_t w[r][t] floor(m_t^3 / 27): it must fit int64 (the bound of sc_cubes_fit tree by
+    // tree, each floored before its weight: not that sum)
     {
         std::vector<unsigned __int128> cube((size_t)M);
         for (int32_t t = 0; t < M; ++t) {
@@ -4511,61 +4418,47 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
                 "workspace", who, n_rep, n_nodes, (unsigned long long)(32 * R * nn), (unsigned long long)SC_BUDGET);
     // own arrays: the accumulators [4][R][nn], the wins [4][nn], the weights, the quartet-branch record per S node and
     // the first pair workgroup per tree (+ 1); per batch the lists of section 18 and the slab [tree][4][nn]
-    const size_t o_acc = 0, o_wins = o_acc + sc_up256(32 * R * nn), o_w = o_wins + sc_up256(nn * 16),
-                 o_qp = o_w + sc_up256(R * mt * 4), o_blk = o_qp + sc_up256(nn * 4),
-                 own = o_blk + sc_up256((mt + 1) * 8);
+    unsigned long long *d_acc;
+    int32_t *d_wins, *d_w, *d_qp;
+    int64_t *d_blk;
+    const auto own = [&](sc_carver w) {
+        d_acc = w.take<unsigned long long>(4 * R * nn);
+        d_wins = w.take<int32_t>(4 * nn);
+        d_w = w.take<int32_t>(R * mt);
+        d_qp = w.take<int32_t>(nn);
+        d_blk = w.take<int64_t>(mt + 1);
+        return w;
+    };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own, 16 + sizeof(sc_bt_rec),
-                     8 + 32 * (uint64_t)nn, c, e));
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
+                     16 + sizeof(sc_bt_rec), 8 + 32 * (uint64_t)nn, c, e));
+    sc_carver wb = sc_carve_batch(c);
+    auto *d_ylist = wb.take<int4>(c.max_lb);
+    auto *d_recs = wb.take<sc_bt_rec>(c.max_lb);
+    auto *d_ycnt = wb.take<int32_t>(2 * c.max_rows);
+    auto *d_slab = wb.take<unsigned long long>(c.max_rows * 4 * nn);
+    if (own(sc_carve_extra(c)).over || wb.over) return sc_end(ctx, c, e, SC_BAD_LAYOUT);
     hipStream_t s = ctx->stream;
-    auto *d_acc = (unsigned long long *)(c.d_extra + o_acc);
-    auto *d_wins = (int32_t *)(c.d_extra + o_wins);
-    auto *d_w = (int32_t *)(c.d_extra + o_w);
-    auto *d_qp = (int32_t *)(c.d_extra + o_qp);
-    auto *d_blk = (int64_t *)(c.d_extra + o_blk);
-    const size_t n_batches = c.bstart.size() - 1;
-    int64_t max_rows = 0;
-    for (size_t b = 0; b < n_batches; ++b) max_rows = std::max<int64_t>(max_rows, c.bstart[b + 1] - c.bstart[b]);
-    auto *d_ylist = (int4 *)c.d_extra_batch;
-    auto *d_recs = (sc_bt_rec *)(d_ylist + c.max_lb);
-    auto *d_ycnt = (int32_t *)(d_recs + c.max_lb);
-    auto *d_slab = (unsigned long long *)(d_ycnt + 2 * max_rows);
-    std::vector<int32_t> n_kids(nn, 0), q_parent(nn, -1);
-    for (int32_t v = 1; v < n_nodes; ++v) n_kids[parent[v]]++;
-    for (int32_t v = 1; v < n_nodes; ++v)
-        if (n_kids[v] == 2 && n_kids[parent[v]] == 2) q_parent[v] = parent[v];
+    const std::vector<int32_t> q_parent = sc_quartet_parents(n_nodes, parent);
     // W, zb, the launch's LDS and blk per batch as in scs_score_branch_triplets
-    std::vector<int> words, zbs;
-    std::vector<size_t> ldss;
-    std::vector<int64_t> blk;
-    sc_bt_plan(off.data(), c.bstart, words, zbs, ldss, blk);
+    const sc_pair_plan pl = sc_plan_pairs(off.data(), c.bstart, SC_BT_RULE);
     const int n_ub = grid_of((int64_t)nn), n_tiles = (n_rep + RS_TILE - 1) / RS_TILE;
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(d_qp, q_parent.data(), nn * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_w, weights, R * mt * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, 32 * R * nn, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blk, pl.blk.data(), ((size_t)M + 1) * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void *)k_rs_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_MAX);
-    for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+    for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
-        const int32_t t0 = c.bstart[b], nb = c.bstart[b + 1] - t0;
-        const int64_t L0 = off[t0], Lb = off[t0 + nb] - L0;
+        const sc_bview v = sc_batch_of(src, c, b);
+        const int32_t t0 = v.t0, nb = v.nb;
         e = hipMemsetAsync(d_ycnt, 0, (size_t)nb * 8, s);
         if (e == hipSuccess) e = hipMemsetAsync(d_slab, 0, (size_t)nb * 32 * nn, s);
         if (e != hipSuccess) break;
-        sc_bt_args a;
-        a.off = src->d_tree_off + t0;
-        a.nb = nb;
-        a.sp = c.d_sp;
-        a.node = c.d_node;
-        a.adj = src->d_adj_depth + L0;
-        a.amin = c.d_amin;
-        a.levels = c.levels;
-        a.Lb = Lb;
-        a.s_lo = c.d_slo;
-        a.s_hi = c.d_shi;
+        auto a = sc_args<sc_bt_args>(v);
         a.q_parent = d_qp;
         a.ylist = d_ylist;
         a.recs = d_recs;
@@ -4574,13 +4467,13 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
         a.n_tot = d_slab;
         a.c_tot = nullptr;
         a.nn = (int64_t)nn;
-        k_rs_records<<<grid_of(Lb), SC_THREADS, 0, s>>>(a);
+        k_rs_records<<<grid_of(v.Lb), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        const int64_t n_wg = blk[t0 + nb] - blk[t0];
+        const int64_t n_wg = pl.blk[t0 + nb] - pl.blk[t0];
         if (n_wg > 0) {
-            k_rs_pairs<<<(unsigned)n_wg, SC_THREADS, ldss[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt, a.rcnt,
-                                                               c.d_mm, zbs[b], words[b], d_slab, (int64_t)nn, nullptr,
-                                                               nullptr);
+            k_rs_pairs<<<(unsigned)n_wg, SC_THREADS, pl.lds[b], s>>>(d_blk + t0, nb, a.off, d_ylist, d_recs, a.ycnt,
+                                                                     a.rcnt, c.d_mm, pl.zbs[b], pl.words[b], d_slab,
+                                                                     (int64_t)nn, nullptr, nullptr);
             if (!sc_launched(e)) break;
         }
         k_rs_reduce<<<dim3((unsigned)n_ub * (unsigned)n_tiles, 4), SC_THREADS, 0, s>>>(d_slab, nb, (int64_t)nn, n_ub,
@@ -4592,11 +4485,9 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
         k_rs_wins<<<n_ub, SC_THREADS, 0, s>>>(d_acc, (int64_t)nn, n_rep, d_wins);
         sc_launched(e);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c.d_flag, 4, hipMemcpyDeviceToHost, s);
     for (size_t x = 0; x < 4 && e == hipSuccess; ++x)  // (row 0 of every counter)
         e = hipMemcpyAsync(rs_point + x * nn, d_acc + x * R * nn, nn * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(rs_wins, d_wins, nn * 16, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && rs_rows) e = hipMemcpyAsync(rs_rows, d_acc, 32 * R * nn, hipMemcpyDeviceToHost, s);
-    SCS_TRY(sc_end(ctx, c, e, bad));
-    return SCS_OK;
+    return sc_end(ctx, c, e, bad);
 }

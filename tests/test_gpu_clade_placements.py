@@ -145,12 +145,27 @@ def test_batches_of_seven_trees(dev, monkeypatch):
     _same(score_supertree(sup, trees, clade_placements=queries, device=dev), ref, "batches of 7")
 
 
-@pytest.mark.parametrize("lds_bytes", [4096, 64])
+@pytest.mark.parametrize("lds_bytes", [4096, 64, 3488])
 def test_less_lds_than_the_sums_need(dev, passes, monkeypatch, lds_bytes):
     # a row pair takes 80 bytes here (150 leaves: five words), the sums of one node and 64 sub-queries 1 056: 4 096
     # bytes leave room for three nodes per workgroup; 64 bytes are less than one row pair and are refused
     sup, trees, queries, ref = passes
     monkeypatch.setattr(score_mod, "CLADE_PLACEMENT_LDS_BYTES", lds_bytes)
+    if lds_bytes == 3488:
+        # two batches of one call with different plans: rows of one word (trees of up to 31 leaves) leave room for
+        # three nodes (272 + 3 (16 + 1 056) = 3 488), rows of three words (64 to 95 leaves) for two
+        # (zb = 3 and 2, W = 1 and 3, the sums in LDS in both: the host plan worked out off the device for these six
+        # sizes, by the loop this test was written against and by the library's; the results here do not show it)
+        rs = np.random.RandomState(3488)
+        names = _names(100)
+        trees = [sr.random_tree(rs, [names[i] for i in rs.choice(100, size=n, replace=False)])
+                 for n in (20, 31, 29, 64, 95, 70)]
+        sup = sr.random_tree(rs, names, binary=True)
+        size = _sizes(sup)
+        queries = [int(q) for q in np.flatnonzero((size >= 2) & (size <= 12))[::2][:20]]
+        assert size[queries].sum() >= 64  # (a full pass of sub-queries: the sums of a node take 1 056 bytes)
+        ref = cr.composed(sup, trees, queries)
+        monkeypatch.setattr(score_mod, "BATCH_TREES", 3)
     if lds_bytes < 80:
         with pytest.raises(ValueError, match="max_lds_bytes"):
             score_supertree(sup, trees, clade_placements=queries, device=dev)
