@@ -807,6 +807,23 @@ int scs_debug_branch_plan(const scs_tables *sources, int32_t n_trees, const int6
                           int32_t max_lds_bytes, int32_t *n_batches_out, int32_t *bstart_out, int64_t *bt_out,
                           int64_t *tx_out, int64_t *call_out);
 
+/* The same for scs_score_placements, scs_score_clade_placements / scs_score_clade_moves (one plan) and
+ * scs_score_polytomies, on the host, by the functions those exports call.  Trees, super_leaves, max_batch_trees and
+ * max_lds_bytes as for scs_debug_branch_plan; the workspace bytes per leaf and per tree are the exports' own, from
+ * n_queries (query taxa of the placements), n_sub_queries (tips of all query clades) and degrees[n_degrees] (the
+ * children, 3 to 64, of every query node of the polytomies; n_degrees may be 0).  Export x = 0 placements, 1 clades,
+ * 2 polytomies: n_batches_out[x] batches, bstart_out[x * (n_trees + 1) ...] the first tree of every batch and n_trees.
+ * pl_out / cp_out[6 x batch] = {words, zb, 1 when the sums of a pass lie in LDS beside the rows, dynamic LDS bytes of
+ * k_pl_pairs / k_cp_pairs for a full pass, the same for the last pass, workgroups of one launch};
+ * blk_out[x * (n_trees + 1) + t], x = 0, 1: the first pair workgroup of tree t (and the total at n_trees).
+ * py_out[4 x (batch * n_degrees + i)] = {W words per row, Ws the rows' stride in LDS, 1 when the k^2 sums lie in LDS,
+ * dynamic LDS bytes of k_py_sweep} for degrees[i] (whether they fit the cap is scs_score_polytomies' own refusal).
+ * Room for max(n_trees, 1) batches in pl_out, cp_out and py_out. */
+int scs_debug_placement_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t super_leaves,
+                             int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
+                             int32_t n_sub_queries, int32_t n_degrees, const int32_t *degrees, int32_t *n_batches_out,
+                             int32_t *bstart_out, int64_t *pl_out, int64_t *cp_out, int64_t *blk_out, int64_t *py_out);
+
 #ifdef __cplusplus
 }
 #endif

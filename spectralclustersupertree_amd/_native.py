@@ -201,6 +201,8 @@ SIGNATURES = {
     "scs_debug_graph_raw": (C.c_int, [_P, _P, _I32, _P, _IP]),
     "scs_debug_score_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, C.c_int64, C.c_int64, _P, _IP, _LP, _IP, _IP, _LP]),
     "scs_debug_branch_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, C.c_int64, C.c_int64, _I32, _P, _IP, _LP, _LP, _LP]),
+    "scs_debug_placement_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, _I32, _I32, _I32, _I32, _IP, _IP, _IP, _LP, _LP,
+                                           _LP, _LP]),
 }
 
 _lib = None

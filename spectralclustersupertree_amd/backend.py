@@ -465,6 +465,11 @@ class Device:
         """``debug_branch_plan`` (below) for tables on this device."""
         return debug_branch_plan(sources, super_leaves, batch_trees, extra_per_leaf, extra_per_tree, lds_bytes)
 
+    def debug_placement_plan(self, sources, super_leaves: int, batch_trees: int = 0, lds_bytes: int = 0,
+                             n_queries: int = 1, n_sub_queries: int = 1, degrees=()) -> dict:
+        """``debug_placement_plan`` (below) for tables on this device."""
+        return debug_placement_plan(sources, super_leaves, batch_trees, lds_bytes, n_queries, n_sub_queries, degrees)
+
 
 class DeviceForest:
     """A source forest resident in HBM (``scs_forest``): preorder node arrays, and -- for the
@@ -676,6 +681,45 @@ def debug_branch_plan(sources, super_leaves: int, batch_trees: int = 0, extra_pe
             "tx_slab_launch": tx[:k, 12].copy(), "tx_slab_lds": tx[:k, 13].copy(), "need_slab": int(call[0]),
             "slab_wgs": int(call[1]),
             "slab_stride": int(call[2])}
+
+
+def debug_placement_plan(sources, super_leaves: int, batch_trees: int = 0, lds_bytes: int = 0, n_queries: int = 1,
+                         n_sub_queries: int = 1, degrees=()) -> dict:
+    """``scs_debug_placement_plan``: the plans of ``scs_score_placements`` (``n_queries`` query taxa), of
+    ``scs_score_clade_placements`` / ``scs_score_clade_moves`` (``n_sub_queries`` tips of all query clades) and of
+    ``scs_score_polytomies`` (``degrees``: the children of every query node) for ``sources`` (as for
+    ``debug_score_plan``) -- per export x in ``pl``, ``cp``, ``py`` the batches ``x_bstart`` under the export's own
+    workspace bytes; for ``pl`` and ``cp`` per batch ``x_words``, ``x_zb``, ``x_sums``, ``x_lds_full``, ``x_lds_last``
+    (the pair kernel's launch bytes for a full and for the last pass), ``x_workgroups``, and per tree ``x_blk`` (its
+    workgroups); for ``py`` per batch and degree ``py_words``, ``py_stride``, ``py_acc_lds``, ``py_lds``.  The
+    library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    deg = np.ascontiguousarray(degrees, dtype=np.int32)
+    nb = np.zeros(3, dtype=np.int32)
+    bstart = np.zeros((3, m + 1), dtype=np.int32)
+    pair = np.zeros((2, max(m, 1), 6), dtype=np.int64)
+    blk = np.zeros((2, m + 1), dtype=np.int64)
+    py = np.zeros((max(m, 1), max(len(deg), 1), 4), dtype=np.int64)
+    nv.check(nv.load_library().scs_debug_placement_plan(
+        handle, m, None if off is None else nv.lptr(off), int(super_leaves), int(batch_trees), int(lds_bytes),
+        int(n_queries), int(n_sub_queries), len(deg), nv.iptr(deg) if len(deg) else None, nv.iptr(nb),
+        nv.iptr(bstart), nv.lptr(pair[0]), nv.lptr(pair[1]), nv.lptr(blk), nv.lptr(py)))
+    out = {}
+    for x, name in enumerate(("pl", "cp")):
+        k = int(nb[x])
+        out[f"{name}_bstart"] = bstart[x, : k + 1].astype(np.int64)
+        for i, key in enumerate(("words", "zb", "sums", "lds_full", "lds_last", "workgroups")):
+            out[f"{name}_{key}"] = pair[x, :k, i].copy()
+        out[f"{name}_blk"] = np.diff(blk[x])
+    k = int(nb[2])
+    out["py_bstart"] = bstart[2, : k + 1].astype(np.int64)
+    rows = py.reshape(-1)[: k * len(deg) * 4].reshape(k, len(deg), 4)
+    for i, key in enumerate(("words", "stride", "acc_lds", "lds")):
+        out[f"py_{key}"] = rows[:, :, i].copy()
+    return out
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

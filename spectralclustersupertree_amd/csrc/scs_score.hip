@@ -2542,6 +2542,16 @@ size_t sc_pl_lds(const sc_pair_plan &p, size_t b, int qc) {
     return p.lds[b] + (p.sums[b] ? (size_t)p.zbs[b] * sc_pl_node_bytes(qc) + sc_pl_pass_bytes(qc) : 0);
 }
 
+// the workspace bytes per leaf and per tree of a batch that scs_score_placements, the clade exports and
+// scs_score_polytomies give sc_begin (they decide the batch split), for the exports and scs_debug_placement_plan
+// alike: qcap queries (sub-queries) in a pass; totb boundaries of nq polytomies
+struct sc_extras {
+    uint64_t per_leaf, per_tree;
+};
+sc_extras sc_pl_extras(int qcap) { return {16 * (uint64_t)qcap + 64, 12 * (uint64_t)qcap + 8}; }
+sc_extras sc_cp_extras(int qcap) { return {25 * (uint64_t)qcap + 64, 36 * (uint64_t)qcap + 8}; }
+sc_extras sc_py_extras(size_t totb, size_t nq) { return {16, 4 + 4 * ((uint64_t)totb + nq)}; }
+
 // A bump allocator over one block of a call's workspace: typed pointers, `step` bytes apart at least.  An export
 // declares its d_extra arrays once, as a function of the carver, and runs it twice: over nothing for the size it asks
 // sc_begin for, then over the block for the pointers.  d_extra_batch is carved with step 1 for max_lb leaves and
@@ -3575,7 +3585,7 @@ extern "C" int scs_score_placements(scs_ctx *ctx, const scs_tables *src, int32_t
     sc_call c;
     hipError_t e = hipSuccess;
     SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
-                     16 * (uint64_t)qcap + 64, 12 * (uint64_t)qcap + 8, c, e));
+                     sc_pl_extras(qcap).per_leaf, sc_pl_extras(qcap).per_tree, c, e));
     sc_carver wb = sc_carve_batch(c);
     auto *d_glist = wb.take<int4>(c.max_lb * qcap);
     auto *d_zlist = wb.take<int4>(2 * c.max_lb);
@@ -3751,7 +3761,7 @@ static int sc_clade_rows(const char *const who, scs_ctx *ctx, const scs_tables *
     sc_call c;
     hipError_t e = hipSuccess;
     SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
-                     25 * (uint64_t)qcap + 64, 36 * (uint64_t)qcap + 8, c, e));
+                     sc_cp_extras(qcap).per_leaf, sc_cp_extras(qcap).per_tree, c, e));
     const int64_t max_rstride = (c.max_lb >> 5) + c.max_rows;
     sc_carver wb = sc_carve_batch(c);
     auto *d_glist = wb.take<int4>(c.max_lb * qcap);
@@ -4128,6 +4138,27 @@ __global__ void __launch_bounds__(SC_THREADS) k_py_sweep(sc_py_args a) {
     }
 }
 
+// the sweep's plan for one batch and degree k, for scs_score_polytomies and scs_debug_placement_plan alike: W words per
+// row (largest tree of the batch, ceil(n / 32)); the rows' stride Ws is odd where that fits (lane = row: an even stride
+// puts the lanes' reads on few banks); the k^2 sums in LDS where they fit beside the rows; lds: the launch's bytes
+struct sc_py_plan {
+    int W, Ws, acc_lds;
+    size_t lds;
+};
+
+int sc_py_words(int64_t n_max) { return (int)std::max<int64_t>((n_max + 31) >> 5, 1); }
+
+sc_py_plan sc_py_plan_of(int W, int k, int lds_cap) {
+    sc_py_plan p;
+    const int64_t accb = (int64_t)k * k * 8, odd = W | 1;
+    const bool acc_odd = k * odd * 8 + accb <= lds_cap, acc_even = (int64_t)k * W * 8 + accb <= lds_cap;
+    p.W = W;
+    p.acc_lds = acc_odd || acc_even;
+    p.Ws = (p.acc_lds ? acc_odd : k * odd * 8 <= lds_cap) ? (int)odd : W;
+    p.lds = (size_t)k * p.Ws * 8 + (p.acc_lds ? (size_t)accb : 0);
+    return p;
+}
+
 }  // namespace
 
 extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t n_nodes, const int32_t *parent,
@@ -4168,7 +4199,7 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
                 kid_of[coff[i] + fill[i]++] = v;
             }
     }
-    const int64_t w_max = std::max<int64_t>((m_max + 31) >> 5, 1);
+    const int64_t w_max = sc_py_words(m_max);
     SCS_REQUIRE((int64_t)k_max * w_max * 8 <= lds_cap,
                 "%s: the %d rows of a source tree of %lld leaves take %lld bytes, more than the %d of a workgroup's "
                 "LDS%s", who, k_max, (long long)m_max, (long long)k_max * w_max * 8, lds_cap,
@@ -4196,8 +4227,8 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
     };
     sc_call c;
     hipError_t e = hipSuccess;
-    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at, 16,
-                     4 + 4 * (totb + nq), c, e));
+    SCS_TRY(sc_begin(ctx, src, who, n_nodes, parent, taxon, max_batch_trees, own(sc_carver()).at,
+                     sc_py_extras(totb, nq).per_leaf, sc_py_extras(totb, nq).per_tree, c, e));
     sc_carver wb = sc_carve_batch(c);
     auto *d_ylist = wb.take<int4>(c.max_lb);
     auto *d_ycnt = wb.take<int32_t>(c.max_rows);
@@ -4258,20 +4289,18 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
         if (!sc_launched(e)) break;
         k_py_total<<<grid_of((int64_t)n_out), SC_THREADS, 0, s>>>(a);
         if (!sc_launched(e)) break;
-        // the sweep, one launch per degree (and chunk of 65535 trees): W words per row; the rows' stride is odd where
-        // that fits (lane = row: an even stride puts the lanes' reads on few banks); the sums in LDS where they fit
-        a.W = (int)std::max<int64_t>((sc_largest_tree(off.data(), t0, t0 + nb) + 31) >> 5, 1);
+        // the sweep, one launch per degree (and chunk of 65535 trees), by sc_py_plan_of
+        a.W = sc_py_words(sc_largest_tree(off.data(), t0, t0 + nb));
         for (int k = 3; k <= PY_KMAX && e == hipSuccess; ++k) {
             const int ng = g_first[k + 1] - g_first[k];
             if (ng == 0) continue;
-            const int64_t accb = (int64_t)k * k * 8, odd = a.W | 1;
-            const bool acc_odd = k * odd * 8 + accb <= lds_cap, acc_even = (int64_t)k * a.W * 8 + accb <= lds_cap;
-            a.acc_lds = acc_odd || acc_even;
-            a.Ws = (a.acc_lds ? acc_odd : k * odd * 8 <= lds_cap) ? (int)odd : a.W;
+            const sc_py_plan pp = sc_py_plan_of(a.W, k, lds_cap);
+            a.acc_lds = pp.acc_lds;
+            a.Ws = pp.Ws;
             a.k = k;
             a.gq = d_gq + g_first[k];
             a.ngq = ng;
-            const size_t lds = (size_t)k * a.Ws * 8 + (a.acc_lds ? (size_t)accb : 0);
+            const size_t lds = pp.lds;
             for (int32_t ty = 0; ty < nb && e == hipSuccess; ty += 65535) {
                 sc_py_args ac = a;
                 ac.off = a.off + ty;
@@ -4292,6 +4321,65 @@ extern "C" int scs_score_polytomies(scs_ctx *ctx, const scs_tables *src, int32_t
     if (e == hipSuccess && py_total) e = hipMemcpyAsync(py_total, d_total, n_out * 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && py_joint) e = hipMemcpyAsync(py_joint, d_joint, n_out * 8, hipMemcpyDeviceToHost, s);
     return sc_end(ctx, c, e, bad);
+}
+
+// the plans of scs_score_placements, scs_score_clade_placements / scs_score_clade_moves and scs_score_polytomies on the
+// host, by the functions those exports call
+extern "C" int scs_debug_placement_plan(const scs_tables *src, int32_t n_trees, const int64_t *tree_off,
+                                        int32_t super_leaves, int32_t max_batch_trees, int32_t max_lds_bytes,
+                                        int32_t n_queries, int32_t n_sub_queries, int32_t n_degrees,
+                                        const int32_t *degrees, int32_t *n_batches_out, int32_t *bstart_out,
+                                        int64_t *pl_out, int64_t *cp_out, int64_t *blk_out, int64_t *py_out) {
+    const char *const who = "scs_debug_placement_plan";
+    SCS_REQUIRE(n_queries >= 1 && n_sub_queries >= 1 && n_degrees >= 0 && (n_degrees == 0 || degrees),
+                "%s: no query, no sub-query or no degrees", who);
+    size_t totb = 0;
+    for (int32_t i = 0; i < n_degrees; ++i) {
+        SCS_REQUIRE(degrees[i] >= 3 && degrees[i] <= PY_KMAX, "%s: degree %d is not in [3, %d]", who, degrees[i],
+                    PY_KMAX);
+        totb += (size_t)degrees[i] + 1;
+    }
+    const bool outs = pl_out && cp_out && blk_out && (py_out || n_degrees == 0);
+    const size_t m1 = (size_t)std::max(n_trees, 0) + 1;
+    const int lds_cap = sc_lds_cap(max_lds_bytes);
+    const int counts[2] = {n_queries, n_sub_queries}, qmax[2] = {PL_QMAX, CP_QMAX};
+    int64_t *const pair_out[2] = {pl_out, cp_out};
+    for (int x = 0; x < 2; ++x) {
+        const int qcap = std::min(counts[x], qmax[x]), q_last = counts[x] - (counts[x] - 1) / qcap * qcap;
+        const sc_extras ex = x == 0 ? sc_pl_extras(qcap) : sc_cp_extras(qcap);
+        sc_debug_plan d;
+        SCS_TRY(sc_debug_batches(who, src, n_trees, tree_off, super_leaves, max_batch_trees, (int64_t)ex.per_leaf,
+                                 (int64_t)ex.per_tree, max_lds_bytes, outs, n_batches_out ? n_batches_out + x : nullptr,
+                                 bstart_out ? bstart_out + x * m1 : nullptr, d));
+        const sc_pair_plan pl = sc_plan_pairs(d.off, d.bstart, sc_pl_rule(qcap, lds_cap));
+        for (size_t b = 0; b + 1 < d.bstart.size(); ++b) {
+            int64_t *o = pair_out[x] + 6 * b;
+            o[0] = pl.words[b];
+            o[1] = pl.zbs[b];
+            o[2] = pl.sums[b];
+            o[3] = (int64_t)sc_pl_lds(pl, b, qcap);
+            o[4] = (int64_t)sc_pl_lds(pl, b, q_last);
+            o[5] = pl.blk[d.bstart[b + 1]] - pl.blk[d.bstart[b]];
+        }
+        std::copy(pl.blk.begin(), pl.blk.end(), blk_out + x * m1);
+    }
+    const sc_extras ex = sc_py_extras(totb, (size_t)n_degrees);
+    sc_debug_plan d;
+    SCS_TRY(sc_debug_batches(who, src, n_trees, tree_off, super_leaves, max_batch_trees, (int64_t)ex.per_leaf,
+                             (int64_t)ex.per_tree, max_lds_bytes, outs, n_batches_out ? n_batches_out + 2 : nullptr,
+                             bstart_out ? bstart_out + 2 * m1 : nullptr, d));
+    for (size_t b = 0; b + 1 < d.bstart.size(); ++b) {
+        const int W = sc_py_words(sc_largest_tree(d.off, d.bstart[b], d.bstart[b + 1]));
+        for (int32_t i = 0; i < n_degrees; ++i) {
+            const sc_py_plan pp = sc_py_plan_of(W, degrees[i], lds_cap);
+            int64_t *o = py_out + 4 * (b * (size_t)n_degrees + i);
+            o[0] = pp.W;
+            o[1] = pp.Ws;
+            o[2] = pp.acc_lds;
+            o[3] = (int64_t)pp.lds;
+        }
+    }
+    return SCS_OK;
 }
 
 // ---- resampled and weighted branch triplet support (scs_score_branch_resample) ----
