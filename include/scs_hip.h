@@ -326,6 +326,29 @@ int scs_score_supertree(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes
                         const int32_t *taxon, int32_t max_batch_trees, int64_t *n_super, int64_t *n_source,
                         int64_t *shared, int64_t *informative, int64_t *supported);
 
+/* MRP parsimony scores per source tree and per source clade, same inputs and SCS_EINVAL cases,
+ * in the same order, as scs_score_supertree.  For a source tree T on leaf set L with m = |L| >= 3 and S' = S|L:
+ *   characters: T's nontrivial clusters C(T), 2 <= |C| < m, each once, in the order of the clusters' first gaps in
+ *     T's DFS order (the gap between the first and second child in the flattened table).  Character C gives state 1
+ *     to the taxa of C, 0 to L - C, and "missing" to every other tip of S (the Baum-Ragan matrix of the sources).
+ *   len(C): the least number of state changes of that character on S with an all-zero outgroup attached above the
+ *     root (rooted coding), polytomies taken as hard; it equals the length on S' with the outgroup.  len(C) >= 1;
+ *     len(C) = 1 iff C is a cluster of S'; len(C) <= gmax(C) = min(|C|, m - |C| + 1), the length on a star.
+ * Per source tree t (n_trees entries; trees of fewer than 3 leaves give zeros):
+ *   mrp_chars[t] = |C(T)| (= n_source[t]), mrp_length[t] = sum of len, mrp_perfect[t] = #{len = 1} (= shared[t]),
+ *   mrp_max[t] = sum of gmax.
+ * Per character, in tree order and within a tree in character order: char_off[n_trees + 1] the first character of
+ * every tree (and the total), char_len its length, char_lo / char_hi the first and last leaf position of its cluster
+ * in T's DFS order, relative to the tree.  char_len, char_lo and char_hi are buffers the caller sizes: sum of
+ * mrp_chars entries, which a first call with the three null returns (char_off[n_trees]), as does n_source of
+ * scs_score_supertree.  Any output pointer may be null; the per-character lengths cost a second kernel variant that
+ * runs only when char_len is given.  max_pass_words > 0 lowers the 64-character words of a tree one pass covers (at
+ * most 64; tests); a tree of more characters takes several passes. */
+int scs_score_parsimony(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes, const int32_t *parent,
+                        const int32_t *taxon, int32_t max_batch_trees, int32_t max_pass_words, int64_t *mrp_chars,
+                        int64_t *mrp_length, int64_t *mrp_perfect, int64_t *mrp_max, int64_t *char_off,
+                        int32_t *char_len, int32_t *char_lo, int32_t *char_hi);
+
 /* Rooted triplet terms per source tree, same inputs and SCS_EINVAL cases as
  * scs_score_supertree.  For a source tree T on the leaf set L and S' = S|L, a triple {a, b, c} of L is resolved
  * ab|c in a tree when one of its clusters holds a and b but not c, and a fan when no cluster separates one pair:
@@ -823,6 +846,18 @@ int scs_debug_placement_plan(const scs_tables *sources, int32_t n_trees, const i
                              int32_t max_batch_trees, int32_t max_lds_bytes, int32_t n_queries,
                              int32_t n_sub_queries, int32_t n_degrees, const int32_t *degrees, int32_t *n_batches_out,
                              int32_t *bstart_out, int64_t *pl_out, int64_t *cp_out, int64_t *blk_out, int64_t *py_out);
+
+/* The plan of one scs_score_parsimony call on the host, by the functions the export calls.  Trees and
+ * max_batch_trees as for scs_debug_score_plan; chars[n_trees]: the characters of every tree (NULL: leaves - 2, the
+ * most a tree can have); parent[n_nodes]: the supertree (root -1, every other parent an earlier node; SCS_EINVAL
+ * otherwise); max_pass_words as for the export.  *n_batches_out and bstart_out as there.  info_out[8] = {words of a
+ * tree one pass covers, frames a fold may open on the supertree laid out largest child first, slices of a frame's
+ * counter, dynamic LDS bytes of a fold workgroup (0 when the frames lie in the call's block), 1 when they do,
+ * workspace bytes per leaf, per tree, the supertree's tips}; batch_out[2 x batch] = {passes, words of the batch's
+ * largest character set}.  Room for max(n_trees, 1) batches in batch_out. */
+int scs_debug_parsimony_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, const int64_t *chars,
+                             int32_t n_nodes, const int32_t *parent, int32_t max_batch_trees, int32_t max_pass_words,
+                             int32_t *n_batches_out, int32_t *bstart_out, int64_t *info_out, int64_t *batch_out);
 
 #ifdef __cplusplus
 }

@@ -297,6 +297,28 @@ class Device:
                          for e, c, k in zip(ends, cubes, out["py_degree"])]
         return out
 
+    def score_parsimony(self, sources, parent: np.ndarray, taxon: np.ndarray, chars: bool = False,
+                        batch_trees: int = 0, pass_words: int = 0, n_chars: int | None = None) -> dict:
+        """``scs_score_parsimony``: the MRP parsimony scores, with the inputs of ``score``.  Returns int64 arrays
+        ``mrp_chars``, ``mrp_length``, ``mrp_perfect``, ``mrp_max`` (per tree) and, with ``chars``, per character
+        ``char_off`` (int64, trees + 1) and ``char_len``, ``char_lo``, ``char_hi`` (int32; None otherwise), sized by
+        ``n_chars`` (the sum of ``n_source`` of ``score``) or, without it, by a first call.  ``pass_words`` > 0 lowers
+        the 64-character words of a tree one pass covers (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        ints = (batch_trees, pass_words)
+        per_tree = (("mrp_chars", "mrp_length", "mrp_perfect", "mrp_max"), _M)
+        per_char = ("char_len", "char_lo", "char_hi")
+        sizes = {"m1": tabs.n_trees + 1}
+        if not chars or n_chars is None:
+            out = self._score_call("scs_score_parsimony", tabs, parent, taxon, ints,
+                                   (per_tree, (("char_off",), ("m1",) if chars else None), (per_char, None)), sizes=sizes)
+            if not chars:
+                return out
+            n_chars = int(out["char_off"][-1])
+        sizes["total"] = int(n_chars)
+        return self._score_call("scs_score_parsimony", tabs, parent, taxon, ints,
+                                (per_tree, (("char_off",), ("m1",)), (per_char, ("total",), np.int32, 0)), sizes=sizes)
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.
@@ -720,6 +742,37 @@ def debug_placement_plan(sources, super_leaves: int, batch_trees: int = 0, lds_b
     for i, key in enumerate(("words", "stride", "acc_lds", "lds")):
         out[f"py_{key}"] = rows[:, :, i].copy()
     return out
+
+
+def debug_parsimony_plan(sources, parent, chars=None, batch_trees: int = 0, pass_words: int = 0) -> dict:
+    """``scs_debug_parsimony_plan``: the plan of ``scs_score_parsimony`` for ``sources`` (as for ``debug_score_plan``)
+    whose trees have ``chars`` characters (None: leaves - 2 each) and the supertree ``parent`` -- ``bstart``; per batch
+    ``passes`` and ``words``; once ``pass_words``, ``frame_depth``, ``counter_bits``, ``lds_bytes`` (of a fold
+    workgroup; 0 with ``frames_in_block``), ``frames_in_block``, ``extra_per_leaf``, ``extra_per_tree``,
+    ``super_tips``.  The library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    parent = np.ascontiguousarray(parent, dtype=np.int32)
+    if chars is not None:
+        chars = np.ascontiguousarray(chars, dtype=np.int64)
+        if chars.shape != (m,):
+            msg = f"chars must have one entry per source tree ({m}), not shape {chars.shape}"
+            raise ValueError(msg)
+    nb = C.c_int32(0)
+    bstart = np.zeros(m + 1, dtype=np.int32)
+    info = np.zeros(8, dtype=np.int64)
+    rows = np.zeros((max(m, 1), 2), dtype=np.int64)
+    nv.check(nv.load_library().scs_debug_parsimony_plan(
+        handle, m, None if off is None else nv.lptr(off), None if chars is None else nv.lptr(chars), len(parent),
+        nv.iptr(parent), int(batch_trees), int(pass_words), C.byref(nb), nv.iptr(bstart), nv.lptr(info),
+        nv.lptr(rows)))
+    k = int(nb.value)
+    keys = ("pass_words", "frame_depth", "counter_bits", "lds_bytes", "frames_in_block", "extra_per_leaf",
+            "extra_per_tree", "super_tips")
+    return {"bstart": bstart[: k + 1].astype(np.int64), "passes": rows[:k, 0].copy(), "words": rows[:k, 1].copy(),
+            **{key: int(info[i]) for i, key in enumerate(keys)}}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

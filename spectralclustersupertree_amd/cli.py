@@ -108,6 +108,12 @@ from spectralclustersupertree_amd import __version__
               help="The least gain in triplet distance a merge of --resolved-out must have.")
 @click.option("--resolve-polytomies", "resolve_first", default=False, is_flag=True,
               help="With --refined-out: resolve the polytomies before the first round (refine_supertree(resolve=True)).")
+@click.option("--parsimony", default=False, is_flag=True,
+              help="Add the MRP parsimony scores to --scores-out (mrp_chars, mrp_length, mrp_perfect, mrp_max): the "
+                   "length of the supertree on the matrix representation of every source tree.")
+@click.option("--source-clades-out", default=None,
+              help="Also write a TSV with one row per clade of every source tree (tree, tips, size, length, gmax): its "
+                   "parsimony length on the supertree, the worst-fitting clades first.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
@@ -118,7 +124,8 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         refined_out: str | None = None, refine_rounds: int = 50, refine_log: str | None = None,
         polytomies_out: str | None = None, resolved_out: str | None = None, resolve_min_gain: int = 1,
         resolve_first: bool = False, branch_resample: int = 0, resample_seed: int = 0, jackknife: bool = False,
-        branch_support_out: str | None = None) -> None:
+        branch_support_out: str | None = None, parsimony: bool = False,
+        source_clades_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if branch_resample and not (branches_out or branch_support_out):
         msg = "--branch-resample needs --branches-out or --branch-support-out"
@@ -144,6 +151,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if branch_triplets and not (scores_out or branches_out):
         msg = "--branch-triplets needs --scores-out or --branches-out"
         raise click.UsageError(msg)
+    if parsimony and not scores_out:
+        msg = "--parsimony needs --scores-out"
+        raise click.UsageError(msg)
     if taxon_triplets and not taxa_out:
         msg = "--taxon-triplets needs --taxa-out"
         raise click.UsageError(msg)
@@ -161,7 +171,8 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     if team is None or team.rank == 0:  # a launched job: every rank holds the tree, one writes it
         supertree.write(out_file)
         if (scores_out or support_out or conflict_out or concordance_out or branches_out or branch_triplets_out
-                or taxa_out or placements_out or clade_placements_out or polytomies_out or branch_support_out):
+                or taxa_out or placements_out or clade_placements_out or polytomies_out or branch_support_out
+                or source_clades_out):
             from spectralclustersupertree_amd.score import score_supertree
 
             result = score_supertree(supertree, load_tree_arrays(in_file), triplets=triplets,
@@ -174,8 +185,13 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                                      clade_placements=place_clades if clade_placements_out else None,
                                      clade_max_tips=clade_max_tips, polytomies=True if polytomies_out else None,
                                      branch_resample=branch_resample or None, resample_seed=resample_seed,
-                                     resample="jackknife" if jackknife else "bootstrap")
+                                     resample="jackknife" if jackknife else "bootstrap",
+                                     parsimony=parsimony or source_clades_out is not None,
+                                     parsimony_chars=source_clades_out is not None)
             resampled = result._rs  # (a non-field attribute: the copies made below do not carry it)
+            mrp = result._mrp       # (likewise)
+            if source_clades_out:
+                Path(source_clades_out).write_text(result.source_clade_table())
             if branch_support_out:
                 Path(branch_support_out).write_text(
                     result.annotate_branch_support().get_newick(with_node_names=True) + "\n")
@@ -194,7 +210,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
                 result = _without_branch_triplets(result)  # (the tables keep their columns of before)
             if scores_out:
                 shown = result if conflicts else _without_conflicts(result)
-                Path(scores_out).write_text((shown if concordance else _without_concordance(shown)).table())
+                shown = shown if concordance else _without_concordance(shown)
+                shown._mrp = mrp if parsimony else None  # (--source-clades-out alone adds no column)
+                Path(scores_out).write_text(shown.table())
             if support_out:
                 Path(support_out).write_text(result.annotate().get_newick(with_node_names=True) + "\n")
             if conflict_out:

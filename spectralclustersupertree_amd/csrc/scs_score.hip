@@ -2762,7 +2762,8 @@ bool sc_prepare_batch(const scs_tables *src, hipStream_t s, sc_call &c, size_t b
     return sc_launched(e);
 }
 
-constexpr unsigned SC_BAD_LAYOUT = 16u;  // host only: an export carved more than it budgeted (the device flag has 1 - 8)
+constexpr unsigned SC_BAD_LAYOUT = 16u;  // host only: an export carved more than it budgeted (the device flag has 1 - 8
+                                         // and 32, SC_BAD_FRAMES of scs_score_parsimony.h)
 
 // the call's sc_carver over d_extra (the bytes the export asked sc_begin for) ...
 sc_carver sc_carve_extra(const sc_call &c) { return sc_carver{c.d_extra, c.extra_bytes}; }
@@ -2787,6 +2788,7 @@ int sc_end(scs_ctx *ctx, sc_call &c, hipError_t e, unsigned bad) {
     if (bad) {
         scs_set_error("%s: %s", c.who,
                       (bad & SC_BAD_LAYOUT) ? "internal: the export's arrays do not fit the bytes it budgeted for them"
+                      : (bad & 32u)         ? "internal: a parsimony fold opened more frames than were planned"
                       : (bad & 8u)          ? "internal: a node was listed for a slab launch that is not made"
                       : (bad & 1u)          ? "a leaf_taxon entry is out of range [0, n_taxa)"
                       : (bad & 2u)          ? "a source tree has a taxon the supertree lacks"
@@ -4579,3 +4581,5 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
     if (e == hipSuccess && rs_rows) e = hipMemcpyAsync(rs_rows, d_acc, 32 * R * nn, hipMemcpyDeviceToHost, s);
     return sc_end(ctx, c, e, bad);
 }
+
+#include "scs_score_parsimony.h"

@@ -139,10 +139,24 @@ replicate with rs_total > 0 at a branch is counted once there: for the arrangeme
 (``win_concordant``, ``win_alt1``, ``win_alt2``) or as ``win_tie``; ``branch_support`` = win_concordant over the four
 together.  Only this pass is weighted; every other count of this module ignores tree weights.
 
+MRP parsimony (``parsimony=True``): the length of the supertree on the Baum-Ragan matrix of its sources, the
+criterion matrix-representation-with-parsimony supertrees minimise.  For a source tree T on leaf set L with m = |L| >= 3
+and S' = S|L, the characters of T are its nontrivial clusters C(T) (2 <= |C| < m, each once, in the order of the
+clusters' first gaps in T's DFS order); character C gives state 1 to the taxa of C, 0 to L - C and "missing" to every
+other tip of S.  len(C) is the least number of state changes of that character on S with an all-zero outgroup attached
+above the root (rooted coding), polytomies taken as hard; it equals the length on S' with the outgroup.  len(C) >= 1,
+len(C) = 1 iff C is a cluster of S', and len(C) <= gmax(C) = min(|C|, m - |C| + 1), the length on a star.  Per source
+tree (zeros for trees of fewer than 3 leaves): ``mrp_chars`` = |C(T)| (= ``n_source``), ``mrp_length`` = Σ len,
+``mrp_perfect`` = #{len = 1} (= ``shared``), ``mrp_max`` = Σ gmax; ``mrp_extra`` = length - chars,
+``consistency_index`` = Σ chars / Σ length, ``retention_index`` = (Σ max - Σ length) / (Σ max - Σ chars).  With
+``parsimony_chars=True`` also the length of every single source clade (``mrp_char_length``, ``mrp_char_clusters``,
+``worst_source_clades``, ``annotate_source``): a graded form of ``shared`` / ``n_source_conflict``, as the triplet
+distance is a graded form of RF.
+
 Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_score_triplets``,
 ``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_branch_resample``,
-``scs_score_taxon_triplets``, ``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies`` and
-(for ``refine_supertree``) ``scs_score_clade_moves``; the host only validates and lays out.
+``scs_score_taxon_triplets``, ``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies``,
+``scs_score_parsimony`` and (for ``refine_supertree``) ``scs_score_clade_moves``; the host only validates and lays out.
 """
 
 from __future__ import annotations
@@ -170,6 +184,11 @@ CLADE_PLACEMENT_LDS_BYTES: int | None = None
 POLYTOMY_LDS_BYTES: int | None = None
 
 
+# 64-character words of a source tree one pass of the parsimony fold covers; None: the default, 64 (a test sets a small
+# value to reach the pass loop)
+PARSIMONY_PASS_WORDS: int | None = None
+
+
 @dataclass
 class SupertreeScore:
     """Scores of ``supertree`` against its sources; int64 arrays."""
@@ -187,7 +206,8 @@ class SupertreeScore:
     # "concordance" (scs_score_concordance, when requested), "branch_triplets" (scs_score_branch_triplets, when
     # requested), "taxon_triplets" (scs_score_taxon_triplets, when requested), "placements" (scs_score_placements,
     # when requested), "clade_placements" (scs_score_clade_placements, when requested), "polytomies"
-    # (scs_score_polytomies, when requested), "branch_resample" (scs_score_branch_resample, when requested)
+    # (scs_score_polytomies, when requested), "branch_resample" (scs_score_branch_resample, when requested),
+    # "parsimony" (scs_score_parsimony, when requested)
     timings: dict = field(default_factory=dict)
     # rooted triplet terms per source tree (``triplets=True``; None otherwise)
     t_super: np.ndarray | None = None
@@ -818,11 +838,152 @@ class SupertreeScore:
             rows.append(row)
         return "\n".join(rows) + "\n"
 
+    # MRP parsimony (``parsimony=True``; None otherwise), kept beside the dataclass fields like ``_py``: a dict with the
+    # four per-tree counts, ``chars`` (None, or per source tree the ``len``, ``lo``, ``hi`` arrays of its characters) and
+    # ``source`` (index -> that source tree as a tree object)
+    _mrp = None
+
+    def _mrp_count(self, key: str) -> np.ndarray | None:
+        return None if self._mrp is None else self._mrp[key]
+
+    @property
+    def mrp_chars(self) -> np.ndarray | None:
+        """Per source tree: its characters, the nontrivial clusters (= ``n_source``)."""
+        return self._mrp_count("mrp_chars")
+
+    @property
+    def mrp_length(self) -> np.ndarray | None:
+        """Per source tree: the parsimony length of the supertree on its characters."""
+        return self._mrp_count("mrp_length")
+
+    @property
+    def mrp_perfect(self) -> np.ndarray | None:
+        """Per source tree: its characters of length 1, the clusters the supertree displays (= ``shared``)."""
+        return self._mrp_count("mrp_perfect")
+
+    @property
+    def mrp_max(self) -> np.ndarray | None:
+        """Per source tree: the length of its characters on a star, the most any supertree can need."""
+        return self._mrp_count("mrp_max")
+
+    def _need_parsimony(self, chars: bool = False) -> None:
+        if self._mrp is None:
+            msg = "parsimony scores were not computed: score_supertree(..., parsimony=True)"
+            raise ValueError(msg)
+        if chars and self._mrp["chars"] is None:
+            msg = "per-clade lengths were not computed: score_supertree(..., parsimony=True, parsimony_chars=True)"
+            raise ValueError(msg)
+
+    @property
+    def mrp_extra(self) -> np.ndarray:
+        """Per source tree: the changes beyond one per character (0: the supertree displays the whole tree)."""
+        self._need_parsimony()
+        return self.mrp_length - self.mrp_chars
+
+    @property
+    def total_mrp_length(self) -> int:
+        """The MRP supertree score: the length over every source's characters."""
+        self._need_parsimony()
+        return int(self.mrp_length.sum())
+
+    @property
+    def consistency_index(self) -> float:
+        """Σ chars / Σ length over all sources (NaN without a character)."""
+        self._need_parsimony()
+        return consistency(int(self.mrp_chars.sum()), int(self.mrp_length.sum()))
+
+    @property
+    def tree_consistency_index(self) -> np.ndarray:
+        """``mrp_chars / mrp_length`` per source tree (NaN where it has no character)."""
+        self._need_parsimony()
+        return consistency(self.mrp_chars, self.mrp_length)
+
+    @property
+    def retention_index(self) -> float:
+        """(Σ max - Σ length) / (Σ max - Σ chars) over all sources (NaN where no character can take two changes)."""
+        self._need_parsimony()
+        return retention(int(self.mrp_chars.sum()), int(self.mrp_length.sum()), int(self.mrp_max.sum()))
+
+    @property
+    def tree_retention_index(self) -> np.ndarray:
+        """The same per source tree."""
+        self._need_parsimony()
+        return retention(self.mrp_chars, self.mrp_length, self.mrp_max)
+
+    def parsimony_table(self) -> str:
+        """One TSV row per source tree: index, n_leaves, mrp_chars, mrp_length, mrp_perfect, mrp_max, mrp_extra,
+        consistency_index, retention_index.  ``ValueError`` unless the parsimony scores were computed."""
+        ci, ri = self.tree_consistency_index, self.tree_retention_index
+        rows = ["index\tn_leaves\tmrp_chars\tmrp_length\tmrp_perfect\tmrp_max\tmrp_extra\tconsistency_index"
+                "\tretention_index"]
+        for t in range(len(ci)):
+            rows.append(f"{t}\t{self.n_leaves[t]}\t{self.mrp_chars[t]}\t{self.mrp_length[t]}\t{self.mrp_perfect[t]}"
+                        f"\t{self.mrp_max[t]}\t{self.mrp_extra[t]}\t{ci[t]:.4f}\t{ri[t]:.4f}")
+        return "\n".join(rows) + "\n"
+
+    def mrp_char_length(self, i: int) -> np.ndarray:
+        """The length of every character of source tree ``i`` (as given), in the order of the clusters' first gaps
+        in the tree's DFS order."""
+        self._need_parsimony(chars=True)
+        return self._mrp["chars"][int(i)]["len"]
+
+    def mrp_char_clusters(self, i: int) -> list:
+        """The clusters behind ``mrp_char_length(i)``: one list of tip names each, in the tree's DFS order."""
+        self._need_parsimony(chars=True)
+        got = self._mrp["chars"][int(i)]
+        if len(got["len"]) == 0:
+            return []
+        names = self._mrp["source"](int(i)).get_tip_names()
+        return [names[lo:hi + 1] for lo, hi in zip(got["lo"], got["hi"])]
+
+    def worst_source_clades(self, n: int | None = None) -> list[dict]:
+        """Every source clade with its length: one dict per character with ``tree`` (index as given), ``tips`` (its
+        names), ``size``, ``length`` and ``gmax``; largest length first, then the larger gmax, then tree and character
+        order.  The first ``n`` when given."""
+        self._need_parsimony(chars=True)
+        rows = []
+        for i, got in enumerate(self._mrp["chars"]):
+            if len(got["len"]) == 0:
+                continue
+            m = int(self.n_leaves[i])
+            size = got["hi"].astype(np.int64) - got["lo"] + 1
+            gmax = np.minimum(size, m - size + 1)
+            rows += [(-int(got["len"][j]), -int(gmax[j]), i, j) for j in range(len(size))]
+        rows.sort()
+        out, clusters = [], {}
+        for length, gmax, i, j in rows if n is None else rows[:n]:
+            if i not in clusters:
+                clusters[i] = self.mrp_char_clusters(i)
+            tips = clusters[i][j]
+            out.append({"tree": i, "tips": tips, "size": len(tips), "length": -length, "gmax": -gmax})
+        return out
+
+    def source_clade_table(self, n: int | None = None) -> str:
+        """``worst_source_clades`` as TSV: tree, tips (comma-separated), size, length, gmax."""
+        rows = ["tree\ttips\tsize\tlength\tgmax"]
+        for r in self.worst_source_clades(n):
+            rows.append(f"{r['tree']}\t{','.join(r['tips'])}\t{r['size']}\t{r['length']}\t{r['gmax']}")
+        return "\n".join(rows) + "\n"
+
+    def annotate_source(self, i: int) -> TreeNode:
+        """A copy of source tree ``i`` whose inner nodes with a nontrivial cluster are named by that cluster's length
+        on the supertree (no name elsewhere), so that ``get_newick(with_node_names=True)`` writes it."""
+        self._need_parsimony(chars=True)
+        out = self._mrp["source"](int(i)).copy()
+        length = {frozenset(c): int(x) for c, x in zip(self.mrp_char_clusters(i), self.mrp_char_length(i))}
+        for node in _preorder(out):
+            if not node.is_tip():
+                got = length.get(frozenset(node.get_tip_names()))
+                node.name = None if got is None else str(got)
+        return out
+
     def table(self) -> str:
         """One TSV row per source tree: index, n_leaves, n_super, n_source, shared, rf, then t_super, t_source,
         t_shared, triplet_distance when the triplet terms were computed, n_super_conflict, n_source_conflict
         when the conflicts were, n_decisive, n_concordant, n_alternative when the concordance was and n_bt_total,
-        n_bt_concordant, n_bt_alternative when the branch triplet counts were."""
+        n_bt_concordant, n_bt_alternative when the branch triplet counts were and mrp_chars, mrp_length, mrp_perfect,
+        mrp_max when the parsimony scores were."""
+        mrp = self._mrp is not None
         trip = self.t_shared is not None
         bt = self.n_bt_total is not None
         conf = self.n_super_conflict is not None
@@ -836,6 +997,8 @@ class SupertreeScore:
             head += "\tn_decisive\tn_concordant\tn_alternative"
         if bt:
             head += "\tn_bt_total\tn_bt_concordant\tn_bt_alternative"
+        if mrp:
+            head += "\tmrp_chars\tmrp_length\tmrp_perfect\tmrp_max"
         rows = [head]
         rf = self.rf
         td = self.triplet_distance if trip else None
@@ -849,6 +1012,8 @@ class SupertreeScore:
                 row += f"\t{self.n_decisive[t]}\t{self.n_concordant[t]}\t{self.n_alternative[t]}"
             if bt:
                 row += f"\t{self.n_bt_total[t]}\t{self.n_bt_concordant[t]}\t{self.n_bt_alternative[t]}"
+            if mrp:
+                row += f"\t{self.mrp_chars[t]}\t{self.mrp_length[t]}\t{self.mrp_perfect[t]}\t{self.mrp_max[t]}"
             rows.append(row)
         return "\n".join(rows) + "\n"
 
@@ -862,6 +1027,21 @@ def _preorder(tree: TreeNode) -> list[TreeNode]:
         out.append(node)
         stack.extend(reversed(node.children))
     return out
+
+
+def consistency(chars, length):
+    """chars / length (a float for ints, an array for arrays); NaN where the length is 0."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = np.where(np.asarray(length) > 0, np.asarray(chars) / np.maximum(length, 1), np.nan)
+    return float(out) if out.ndim == 0 else out
+
+
+def retention(chars, length, most):
+    """(most - length) / (most - chars); NaN where most = chars (no character can take a second change)."""
+    room = np.asarray(most) - np.asarray(chars)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = np.where(room > 0, (np.asarray(most) - np.asarray(length)) / np.maximum(room, 1), np.nan)
+    return float(out) if out.ndim == 0 else out
 
 
 def _at(children: list, node: TreeNode) -> int:
@@ -973,7 +1153,7 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
                     placements=None, clade_placements=None, clade_max_tips: int = 64, polytomies=None,
                     polytomy_max_degree: int = 64, branch_resample=None, tree_weights=None,
                     resample: str = "bootstrap", resample_seed: int = 0, resample_rows: bool = False,
-                    device=None) -> SupertreeScore:
+                    parsimony: bool = False, parsimony_chars: bool = False, device=None) -> SupertreeScore:
     """RF distance of ``supertree`` to every source tree and the support of every clade (module docstring);
     ``triplets=True`` adds the rooted triplet terms (``t_super``, ``t_source``, ``t_shared``) and
     ``conflicts=True`` the clade conflict counts (``n_super_conflict``, ``n_source_conflict``, ``conflicting``) and
@@ -1006,6 +1186,10 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
     ``resample_rows=True``; ``annotate_branch_support``, ``nni_candidates(by="triplets", min_support=p)``).  The
     replicates of a count are drawn by ``resample_weights`` (``resample``: ``"bootstrap"`` or ``"jackknife"``, from
     ``numpy.random.RandomState(resample_seed)``).  With ``tree_weights`` alone there is row 0 and no replicate.
+    ``parsimony=True``: the MRP parsimony scores (``mrp_chars``, ``mrp_length``, ``mrp_perfect``, ``mrp_max`` per tree;
+    ``mrp_extra``, ``total_mrp_length``, ``consistency_index``, ``retention_index``, ``parsimony_table``);
+    ``parsimony_chars=True`` (which implies it) also the length of every source clade (``mrp_char_length``,
+    ``mrp_char_clusters``, ``worst_source_clades``, ``annotate_source``).
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped, as in ``construct_supertree``) or a
     ``TreeArrays`` (``load_tree_arrays``), whose tables are then built on the device.  Tree weights are accepted
@@ -1026,12 +1210,13 @@ def score_supertree(supertree: TreeNode, trees, *, triplets: bool = False, confl
                    int(polytomy_max_degree),
                    resample=None if branch_resample is None and tree_weights is None else resample_weights(
                        _n_given(trees), branch_resample, tree_weights, resample, resample_seed),
-                   resample_rows=bool(resample_rows))
+                   resample_rows=bool(resample_rows), parsimony=bool(parsimony or parsimony_chars),
+                   parsimony_chars=bool(parsimony_chars))
     with _resident_tables(device, trees, tips, index) as src:
         timings = {"prepare": 0.0, "tables": src.seconds}
         res = _run_passes(src, parent, taxon, req, timings)
     timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
-    return _result(supertree, src.n_leaves, res, timings)
+    return _result(supertree, src.n_leaves, res, timings, trees)
 
 
 _COUNTS = tuple(f.name for f in fields(SupertreeScore) if f.name not in ("supertree", "n_leaves", "timings"))
@@ -1040,9 +1225,21 @@ _COUNTS = tuple(f.name for f in fields(SupertreeScore) if f.name not in ("supert
 _PY_KEYS = ("py_nodes", "py_degree", "py_trees", "py_total", "py_joint", "py_skipped")
 
 
-def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
+def _source_getter(trees):
+    """index -> the source tree of that index as a tree object, for either input of ``score_supertree``."""
+    if isinstance(trees, TreeArrays):
+        return trees.to_tree
+    kept = [t for t in trees if not is_not_completed(t)]
+    return kept.__getitem__
+
+
+def _result(supertree, n_leaves, res: dict, timings: dict, trees=None) -> SupertreeScore:
     out = SupertreeScore(supertree=supertree, n_leaves=n_leaves, timings=timings,
                          **{k: res.get(k) for k in _COUNTS})
+    if "mrp_chars" in res:
+        out._mrp = {k: res[k] for k in _MRP_KEYS}
+        out._mrp["chars"] = res.get("mrp_char_rows")
+        out._mrp["source"] = None if trees is None else _source_getter(trees)
     if "py_nodes" in res:
         out._py = {k: res[k] for k in _PY_KEYS}
     if "rs_point" in res:
@@ -1051,6 +1248,7 @@ def _result(supertree, n_leaves, res: dict, timings: dict) -> SupertreeScore:
 
 
 _RS_KEYS = ("rs_weights", "rs_point", "rs_wins", "rs_rows")
+_MRP_KEYS = ("mrp_chars", "mrp_length", "mrp_perfect", "mrp_max")
 _WIN_KEYS = ("win_concordant", "win_alt1", "win_alt2", "win_tie")
 
 
@@ -1458,6 +1656,9 @@ class _Request:
     resample: object = None         # None or the R x trees weight matrix, columns in the order of the trees as given
     resample_rows: bool = False
     tree_index: object = None       # the given tree behind every tree of the tables (set by ``_run_passes``)
+    parsimony: bool = False
+    parsimony_chars: bool = False
+    n_given: int = 0                # the source trees as given (set by ``_run_passes``)
 
 
 @dataclass(frozen=True)
@@ -1499,6 +1700,25 @@ def _branch_resample(dev, tabs, parent, taxon, res: dict, req) -> dict:
     return out
 
 
+def _parsimony(dev, tabs, parent, taxon, res: dict, req) -> dict:
+    """The four per-tree counts and, with ``parsimony_chars``, ``mrp_char_rows``: per source tree as given a dict of
+    its characters' ``len``, ``lo``, ``hi`` (empty for a tree the tables do not hold).  The character buffers are sized
+    by ``n_source`` of the first pass."""
+    out = dev.score_parsimony(tabs, parent, taxon, chars=req.parsimony_chars, batch_trees=BATCH_TREES or 0,
+                              pass_words=PARSIMONY_PASS_WORDS or 0,
+                              n_chars=int(res["n_source"].sum()) if req.parsimony_chars else None)
+    got = {k: out[k] for k in _MRP_KEYS}
+    if req.parsimony_chars:
+        none = {k: np.zeros(0, dtype=np.int32) for k in ("len", "lo", "hi")}
+        rows = [none] * req.n_given
+        off = out["char_off"]
+        for j in range(len(off) - 1):
+            i = j if req.tree_index is None else int(req.tree_index[j])
+            rows[i] = {k: out["char_" + k][off[j]:off[j + 1]] for k in ("len", "lo", "hi")}
+        got["mrp_char_rows"] = rows
+    return got
+
+
 # in call order (the query passes read the per-taxon counts)
 _PASSES = (
     _Pass("score", lambda req: True, _on_tables("score"),
@@ -1516,6 +1736,7 @@ _PASSES = (
     _Pass("clade_placements", lambda req: req.clades is not None, _clade_placements, queries=True),
     _Pass("polytomies", lambda req: req.polytomies is not None, _polytomies, queries=True),
     _Pass("branch_resample", lambda req: req.resample is not None, _branch_resample, queries=True),
+    _Pass("parsimony", lambda req: req.parsimony, _parsimony, _MRP_KEYS),
 )
 
 
@@ -1524,7 +1745,7 @@ def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> d
     go back to the places of the trees as given (``src.tree_index``); without tables every output is zeros."""
     m = len(src.n_leaves)
     tree_index = None if src.tabs is None else src.tree_index()
-    req = replace(req, max_leaves=int(np.max(src.n_leaves)) if m else 0, tree_index=tree_index)
+    req = replace(req, max_leaves=int(np.max(src.n_leaves)) if m else 0, tree_index=tree_index, n_given=m)
     res: dict = {}
     for p in _PASSES:
         if not p.wanted(req):
@@ -1544,4 +1765,6 @@ def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> d
         res.update(out)
     if req.taxon_triplets or req.placements is not None:
         res["taxa"] = list(req.tips)
+    if req.parsimony_chars and "mrp_char_rows" not in res:  # (no tables: no tree has a character)
+        res["mrp_char_rows"] = [{k: np.zeros(0, dtype=np.int32) for k in ("len", "lo", "hi")}] * m
     return res

@@ -21,6 +21,8 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
     python tools/score_bench.py --branch-resample 100 --size 10000x500   # scs_score_branch_resample with 100 weight
                                                      # rows (repeatable) beside one scs_score_branch_triplets call
                                                      # 
+    python tools/score_bench.py --parsimony --size 10000x500   # scs_score_parsimony with and without the per-clade
+                                                     # lengths beside one scs_score_triplets call
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -39,7 +41,7 @@ import numpy as np  # noqa: E402
 
 from spectralclustersupertree_amd import refine_supertree, score_supertree, synthetic  # noqa: E402
 from spectralclustersupertree_amd import refine as refine_mod  # noqa: E402
-from spectralclustersupertree_amd.backend import Device  # noqa: E402
+from spectralclustersupertree_amd.backend import Device, debug_parsimony_plan  # noqa: E402
 from spectralclustersupertree_amd.score import (_leaf_ranges, _resident_tables, resample_weights,  # noqa: E402
                                                 select_clades, supertree_arrays)
 from spectralclustersupertree_amd.tree import TreeNode  # noqa: E402
@@ -424,6 +426,54 @@ def run_resample(dev: Device, size: str, n_rows, repeats: int = 5) -> dict:
     return out
 
 
+def run_parsimony(dev: Device, size: str, repeats: int = 5) -> dict:
+    """``scs_score_parsimony`` on resident tables, a warm-up and ``repeats`` timed calls without and with the
+    per-character lengths; beside it one ``scs_score_triplets`` call, the other pass that is quadratic per tree, and
+    the bytes of the membership tiles the fold reads (8 bytes per leaf and 64-character word of its tree) and all
+    tile traffic (the clearing of every pass, the scan's two reads and one write, the fold's read)."""
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    sup = random_binary_tree(2, n_taxa)
+    parent, taxon, tips = supertree_arrays(sup)
+    index = {x: i for i, x in enumerate(tips)}
+    out = {"size": size, "parsimony": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "supertree_nodes": len(parent), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        out["triplets_s_min_median_max"], _ = timed(lambda: dev.score_triplets(tabs, parent, taxon))
+        out["parsimony_s_min_median_max"], res = timed(lambda: dev.score_parsimony(tabs, parent, taxon))
+        total = int(res["mrp_chars"].sum())
+        out["parsimony_chars_s_min_median_max"], full = timed(
+            lambda: dev.score_parsimony(tabs, parent, taxon, chars=True, n_chars=total))
+        plan = debug_parsimony_plan(tabs, parent, chars=res["mrp_chars"])
+    leaves = arrays.leaf_counts().astype(np.int64)
+    leaves = leaves[leaves >= 2]  # (the tables hold the trees of two leaves and more, in order)
+    words = (res["mrp_chars"] + 63) // 64
+    fold = int((leaves * words).sum()) * 8
+    cleared = sum(int(leaves[a:b].sum()) * int(p) for a, b, p in zip(plan["bstart"][:-1], plan["bstart"][1:],
+                                                                     plan["passes"])) * 8 * plan["pass_words"]
+    med = out["parsimony_s_min_median_max"][1]
+    out.update({"characters": total, "mrp_length": int(res["mrp_length"].sum()),
+                "same_per_tree_numbers": all(np.array_equal(res[k], full[k]) for k in res if res[k] is not None),
+                "batches": len(plan["bstart"]) - 1, "passes": [int(x) for x in plan["passes"]],
+                "frame_depth": plan["frame_depth"], "counter_bits": plan["counter_bits"],
+                "fold_lds_bytes": plan["lds_bytes"], "tile_bytes_fold": fold, "tile_bytes_all": cleared + 4 * fold,
+                "tile_gb_per_s_of_call": round((cleared + 4 * fold) / med / 1e9, 2),
+                "over_triplets": round(med / out["triplets_s_min_median_max"][1], 3)})
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -461,6 +511,8 @@ def main() -> None:
     ap.add_argument("--collapse", type=int, default=4, help="how many nodes --polytomies collapses to each degree")
     ap.add_argument("--branch-resample", type=int, action="append", metavar="R",
                     help="time scs_score_branch_resample instead, with R weight rows (repeatable)")
+    ap.add_argument("--parsimony", action="store_true",
+                    help="time scs_score_parsimony instead, without and with the per-clade lengths")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -471,6 +523,12 @@ def main() -> None:
             run_resample(dev, "200x6", [3], repeats=1)  # warm-up
             for size in args.size or SIZES[:1]:
                 print(json.dumps(run_resample(dev, size, args.branch_resample)), flush=True)
+        return
+    if args.parsimony:
+        with Device(0) as dev:
+            run_parsimony(dev, "200x6", repeats=1)  # warm-up
+            for size in args.size or SIZES[:1]:
+                print(json.dumps(run_parsimony(dev, size, max(args.repeats, 5))), flush=True)
         return
     if args.polytomies:
         with Device(0) as dev:
