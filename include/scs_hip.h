@@ -84,7 +84,9 @@ typedef struct scs_build_stats {
     int32_t spec_batches;       /* of them walked by the producer / consumer tile kernel
                                    (k_accumulate_spec; the others by the 4-wave kernels)   */
     double cell_trees;          /* (matrix cell, tree) evaluations performed         */
-    double prep_ms;             /* position / sparse-table / block-record kernels    */
+    double prep_ms;             /* position fill, position / sparse-table / argmin / block-record kernels, and --
+                                   tables still on their way, prepared piece by piece as their chunks arrive --
+                                   whatever the stream waited for a chunk in between */
     double accumulate_ms;       /* the tile accumulate kernel(s)                     */
     double exchange_ms;         /* shared build: tile all-gather + unpack            */
     double total_ms;            /* whole call, device time                           */
@@ -97,10 +99,11 @@ typedef struct scs_build_stats {
     int32_t spec_trees;            /* trees the spec_batches walked (the rest: 4-wave kernels)       */
     double spec_ms;                /* device time of the k_accumulate_spec launches (of accumulate_ms) */
     int32_t listed_batches;        /* batches walked through per-tile tree lists (partial-coverage forests) */
-    int32_t reserved;
+    int32_t prep_pieces;           /* pieces the batches were prepared in: a batch is cut where a late chunk of the
+                                      table upload begins, one piece per batch when the tables are resident */
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements, scs_score_clade_placements and scs_score_clade_moves added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_block_records added, and scs_build_stats' `reserved` slot became prep_pieces.  (The rule for a reserved slot: the version changes when a struct's size or a field's offset or meaning changes for a caller that follows the older header of the same number.  A slot that header called `reserved` was written as 0 and promised nothing; naming it, with size and offsets as they were, leaves every such caller correct -- it reads a count it ignores -- so the number stays.  The earlier reuses, 100 -> 101 and 101 -> 102, also made their structs longer.)  scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements, scs_score_clade_placements and scs_score_clade_moves added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -792,6 +795,20 @@ int scs_debug_scan(scs_ctx *ctx, int32_t op, int32_t n_parts, int64_t n, const i
  * made).  SCS_EUNSUP, never something else, where the library makes no image: a matrix-free graph (what = 0 as
  * well: it has no matrix), an SCS_BUILD_UPPER graph, a row block on one rank, no memory. */
 int scs_debug_graph_raw(scs_ctx *ctx, scs_graph *graph, int32_t what, void *out, int32_t *info_out);
+
+/* The block records of the trees [t_begin, t_end) for the 64-row blocks of rows [row_begin, row_end), made by the
+ * build's own preparation (positions, range-minimum and argmin tables, one record kernel) as ONE batch in one piece
+ * (tests/test_gpu_prep_records.py).  kind: 0 k_block_records_mono, 1 k_block_records_wide, 2 k_block_records_gen
+ * (pair tables); 0 and 1 take the tables as monotone, whatever they are.  With B = ceil((row_end - row_begin) / 64)
+ * blocks and T trees, per (block b, tree t) at index b * T + t: spos_out 64 x int32, the sorted DFS positions of the
+ * block's rows (INT32_MAX beyond the count); gap_out 64 x double, entry k the value of the shallowest gap in
+ * [spos[k], spos[k + 1]) (0 beyond count - 1); argpos_out 64 x int32, the position the record names for that gap --
+ * the LEFTMOST one that attains the minimum (W cannot show which: every position of the minimum gives the same
+ * cells); depth_out 64 x int32, kind 2 only (else untouched, may be NULL): the gap's depth; cnt_out one int32, the
+ * rows of the block the tree holds. */
+int scs_debug_block_records(scs_ctx *ctx, const scs_tables *tables, int32_t t_begin, int32_t t_end, int32_t row_begin,
+                            int32_t row_end, int32_t kind, int32_t *spos_out, double *gap_out, int32_t *argpos_out,
+                            int32_t *depth_out, int32_t *cnt_out);
 
 /* The plan of the thread-per-tree split kernels for a forest's offsets (node_off[n_trees + 1]), by the launcher's
  * rule and the kernels' predicate, on the host (no device): *tpb_out trees per workgroup (64 ... 8),

@@ -110,7 +110,7 @@ class BuildStats(C.Structure):
         ("spec_trees", C.c_int32),
         ("spec_ms", C.c_double),
         ("listed_batches", C.c_int32),
-        ("reserved", C.c_int32),
+        ("prep_pieces", C.c_int32),
     ]
 
     def as_dict(self) -> dict:
@@ -200,6 +200,7 @@ SIGNATURES = {
     "scs_debug_scan": (C.c_int, [_P, _I32, _I32, C.c_int64, _IP, _IP]),
     "scs_debug_split_plan": (C.c_int, [_I32, _LP, _P, _P, _P]),
     "scs_debug_graph_raw": (C.c_int, [_P, _P, _I32, _P, _IP]),
+    "scs_debug_block_records": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _IP, _DP, _IP, _IP, _IP]),
     "scs_debug_score_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, C.c_int64, C.c_int64, _P, _IP, _LP, _IP, _IP, _LP]),
     "scs_debug_branch_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, C.c_int64, C.c_int64, _I32, _P, _IP, _LP, _LP, _LP]),
     "scs_debug_placement_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, _I32, _I32, _I32, _I32, _IP, _IP, _IP, _LP, _LP,

@@ -944,6 +944,27 @@ class DeviceTables:
         graph.upper = bool(upper)
         return graph
 
+    def block_records(self, kind: str, t_begin: int = 0, t_end: int | None = None, row_begin: int = 0,
+                      row_end: int | None = None) -> dict:
+        """``scs_debug_block_records``: what the build's preparation leaves per (64-row block, tree) for the trees
+        [t_begin, t_end) and the blocks of rows [row_begin, row_end), through the record kernel ``kind`` (``mono``,
+        ``wide`` or ``general``).  Arrays of shape (blocks, trees, 64): ``spos`` the sorted DFS positions of the
+        block's rows, ``gap`` the value of the shallowest gap between neighbours, ``argpos`` the position named for
+        it, ``depth`` its depth (``general`` only, else None); ``cnt`` (blocks, trees) the rows present."""
+        t_end = self.n_trees if t_end is None else t_end
+        row_end = self.n_taxa if row_end is None else row_end
+        code = {"mono": 0, "wide": 1, "general": 2}[kind]
+        nb, nt = (max(row_end - row_begin, 0) + 63) // 64, max(t_end - t_begin, 0)
+        spos = np.empty((nb, nt, 64), dtype=np.int32)
+        gap = np.empty((nb, nt, 64), dtype=np.float64)
+        argpos = np.empty((nb, nt, 64), dtype=np.int32)
+        depth = np.empty((nb, nt, 64), dtype=np.int32) if code == 2 else None
+        cnt = np.empty((nb, nt), dtype=np.int32)
+        nv.check(self.dev._lib.scs_debug_block_records(
+            self.dev._ctx, self._h, int(t_begin), int(t_end), int(row_begin), int(row_end), code, nv.iptr(spos),
+            nv.dptr(gap), nv.iptr(argpos), nv.iptr(depth) if depth is not None else None, nv.iptr(cnt)))
+        return {"spos": spos, "gap": gap, "argpos": argpos, "depth": depth, "cnt": cnt}
+
 
     def matrix_free_graph(self, max_block: int = 8) -> "DeviceGraph":
         """A graph WITHOUT its matrix (``scs_graph_matrix_free``): ``fiedler`` on it applies W straight

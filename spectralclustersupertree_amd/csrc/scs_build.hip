@@ -62,16 +62,61 @@ __device__ __forceinline__ K rmq_min(const K *__restrict__ base, int m, int a, i
     return x < y ? x : y;
 }
 
+// ---- argmin tables ------------------------------------------------------------
+// Beside a tree's value (or pair) table, in an array of its own: for every level 1 <= k <= ARGMIN_MAX_LEVEL
+// the offset of the LEFTMOST minimum inside the window [p, p + 2^k), 16 bits an entry, level k at
+// [(k - 1) m, k m) from the tree's own offset (level 0 would be all zeros and is not stored).  The block
+// records take the position of a gap's minimum from it -- one more gather behind the query's two instead of
+// a halving search of log2(gap) rounds of two dependent gathers each.  Offsets inside a window of 2^16 fit
+// an entry; a query of level 17 and more (two tile rows 2^17 positions apart) keeps the halving search.
+typedef unsigned short argmin_t;
+constexpr int ARGMIN_MAX_LEVEL = 16;
+__host__ __device__ inline int argmin_levels(int levels) {  // stored levels of a table of `levels` levels
+    return levels - 1 < ARGMIN_MAX_LEVEL ? (levels > 1 ? levels - 1 : 0) : ARGMIN_MAX_LEVEL;
+}
+// the two entries x at a and y at b - 2^k of a query over [a, b), k >= 1: the minimum is on the right
+// only when y is STRICTLY smaller (ties go left: the leftmost position overall)
+__device__ __forceinline__ int argmin_position(const argmin_t *__restrict__ am, int m, int k, int a, int b,
+                                               bool right_smaller) {
+    const int q = right_smaller ? b - (1 << k) : a;
+    return q + (int)am[(int64_t)(k - 1) * m + q];
+}
+// minimum over gaps [a, b) of a value table, bit for bit rmq_min's, and in `at` the leftmost position that
+// attains it: three gathers.  (Level 17 and up: halve the range, keeping a half whose minimum is still the
+// value -- the left one when both are.)
+__device__ __forceinline__ double rmq_min_at(const double *__restrict__ st, const argmin_t *__restrict__ am, int m,
+                                             int a, int b, int &at) {
+    int o[2];
+    rmq_offsets(m, a, b, o);
+    const int k = 31 - __clz(b - a);
+    const double x = st[o[0]], y = st[o[1]];
+    const double g = x < y ? x : y;
+    if (k == 0) {
+        at = a;
+    } else if (k <= ARGMIN_MAX_LEVEL) {
+        at = argmin_position(am, m, k, a, b, y < x);
+    } else {
+        int lo = a, hi = b;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rmq_min<double>(st, m, lo, mid) == g) hi = mid;
+            else lo = mid;
+        }
+        at = lo;
+    }
+    return g;
+}
+
 // monotone builds: the range-minimum table is over the gap VALUES themselves (the value of
 // the shallowest LCA of a range is the smallest value in it), level 0 = value * w per gap
 __global__ void k_positions_values(const int64_t *__restrict__ tree_off,
                                    const int32_t *__restrict__ leaf_taxon,
                                    const int32_t *__restrict__ adj_depth,
                                    const double *__restrict__ adj_val,
-                                   const double *__restrict__ tree_w, int t0,
+                                   const double *__restrict__ tree_w, int t0, int tl0,
                                    int32_t *__restrict__ pos, int64_t npad,
                                    const int64_t *__restrict__ st_off, double *__restrict__ stv) {
-    const int tl = blockIdx.y;
+    const int tl = tl0 + blockIdx.y;  // tree in batch: a prep piece starts at tl0
     const int t = t0 + tl;
     const int64_t off = tree_off[t];
     const int n = (int)(tree_off[t + 1] - off);
@@ -86,43 +131,93 @@ __global__ void k_positions_values(const int64_t *__restrict__ tree_off,
         stv[st_off[tl] + p] = adj_depth[off + p] ? adj_val[off + p] * tree_w[t] : 0.0;
 }
 
-// level k >= 1 of every tree's sparse table; grid as k_positions
-template <typename K>
-__global__ void k_sparse_level(const int64_t *__restrict__ tree_off, int t0, int k,
-                               const int64_t *__restrict__ st_off, K *__restrict__ st) {
-    const int tl = blockIdx.y;
+// level k >= 1 of every tree's sparse table and of its argmin table; grid as k_positions.  PICK: the smaller
+// of two entries as the tile kernels expect it (pick_smaller_value, pick_shallower_pair) and `right_less`,
+// the strict comparison the argmin goes by.
+template <typename K, typename PICK>
+__global__ void k_sparse_level(const int64_t *__restrict__ tree_off, int t0, int tl0, int k,
+                               const int64_t *__restrict__ st_off, K *__restrict__ st,
+                               const int64_t *__restrict__ am_off, argmin_t *__restrict__ am_all, PICK pick) {
+    const int tl = tl0 + blockIdx.y;
     const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (m < (1 << k) || p > m - (1 << k)) return;
     K *base = st + st_off[tl];
-    const K a = base[(int64_t)(k - 1) * m + p], b = base[(int64_t)(k - 1) * m + p + (1 << (k - 1))];
-    base[(int64_t)k * m + p] = a < b ? a : b;
+    const int half = 1 << (k - 1);
+    const K a = base[(int64_t)(k - 1) * m + p], b = base[(int64_t)(k - 1) * m + p + half];
+    base[(int64_t)k * m + p] = pick(a, b);
+    if (k > ARGMIN_MAX_LEVEL) return;
+    argmin_t *am = am_all + am_off[tl];
+    const bool right = pick.right_less(a, b);
+    int off = right ? half : 0;
+    if (k > 1) off += (int)am[(int64_t)(k - 2) * m + p + (right ? half : 0)];
+    am[(int64_t)(k - 1) * m + p] = (argmin_t)off;
 }
 
-// ALL levels k >= 1 of a tree's sparse table by ONE workgroup per tree (grid = trees in the batch):
+// ALL levels k >= 1 of a tree's sparse table by ONE workgroup per tree (grid = trees of the piece):
 // a launch per level is a dozen launches of a few microseconds of work each for trees of up to a
 // few 10^4 leaves -- 0.56 ms of a 19 ms step at configs[2] (profiles/r04_bench_cfg2_kernel_stats.csv:
 // 63 launches of k_sparse_level per pass).  Level k reads what the same workgroup wrote as level
 // k - 1: __syncthreads() orders that (workgroup-scope release / acquire on global memory: the
-// workgroup's waves share one L1).  MIN(a, b) is `a < b ? a : b` on values, gap_min on pairs.
-template <typename K, typename MIN>
-__global__ __launch_bounds__(1024) void k_sparse_levels_fused(const int64_t *__restrict__ tree_off, int t0,
+// workgroup's waves share one L1).
+// Previous and current level come from one pointer, so no load moves above a store by itself: a thread
+// loads FUSED_UNROLL entries' worth of a level -- both halves and, from level 2 on, both argmin
+// candidates of each, not the chosen one behind the comparison -- before it stores any of them.  The
+// argmin level rides in the same pass; all levels of a fused table are below ARGMIN_MAX_LEVEL.
+// (Measured, profiles/prep_argmin_arrival.md: no faster than one entry at a time.  A workgroup takes
+// 85-120 us for a tree of 10 000 leaves with the argmin levels -- a quarter more bytes, two 2-byte loads
+// and one 2-byte store more per entry through the CU's one L1 -- against 73 us without them; longer
+// unrolls and hand-placed waits made no difference beyond the run-to-run spread and are not kept.)
+constexpr int FUSED_UNROLL = 4;
+template <typename K, typename PICK>
+__global__ __launch_bounds__(1024) void k_sparse_levels_fused(const int64_t *__restrict__ tree_off, int t0, int tl0,
                                                                const int64_t *__restrict__ st_off,
-                                                               K *__restrict__ st, MIN pick) {
-    const int tl = blockIdx.x;
+                                                               K *__restrict__ st,
+                                                               const int64_t *__restrict__ am_off,
+                                                               argmin_t *__restrict__ am_all, PICK pick) {
+    const int tl = tl0 + blockIdx.x;
     const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
     K *base = st + st_off[tl];
+    argmin_t *am = am_all + am_off[tl];
     for (int k = 1; (1 << k) <= m; ++k) {
         const K *prev = base + (int64_t)(k - 1) * m;
         K *cur = base + (int64_t)k * m;
         const int half = 1 << (k - 1), last = m - (1 << k);
-        for (int p = threadIdx.x; p <= last; p += 1024) cur[p] = pick(prev[p], prev[p + half]);
+        const argmin_t *am_prev = am + (int64_t)(k - 2) * m;  // (read from level 2 on)
+        argmin_t *am_cur = am + (int64_t)(k - 1) * m;
+        for (int p0 = threadIdx.x; p0 <= last; p0 += 1024 * FUSED_UNROLL) {
+            K a[FUSED_UNROLL], b[FUSED_UNROLL];
+            int oa[FUSED_UNROLL], ob[FUSED_UNROLL];
+#pragma unroll
+            for (int u = 0; u < FUSED_UNROLL; ++u) {
+                const int p = p0 + u * 1024;
+                oa[u] = ob[u] = 0;
+                if (p <= last) {
+                    a[u] = prev[p];
+                    b[u] = prev[p + half];
+                    if (k > 1) {
+                        oa[u] = (int)am_prev[p];
+                        ob[u] = (int)am_prev[p + half];
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FUSED_UNROLL; ++u) {
+                const int p = p0 + u * 1024;
+                if (p <= last) {
+                    cur[p] = pick(a[u], b[u]);
+                    am_cur[p] = (argmin_t)(pick.right_less(a[u], b[u]) ? half + ob[u] : oa[u]);
+                }
+            }
+        }
         __syncthreads();
     }
 }
 constexpr int SPARSE_FUSED_MAX_LEAVES = 32768;  // beyond: a launch per level has real work and more parallelism
+static_assert(SPARSE_FUSED_MAX_LEAVES <= (1 << ARGMIN_MAX_LEVEL), "every level of a fused table has an argmin level");
 struct pick_smaller_value {
     __device__ double operator()(double a, double b) const { return a < b ? a : b; }
+    __device__ bool right_less(double a, double b) const { return b < a; }
 };
 
 // one v_min_f64 (the builtin fmin adds a canonicalising v_max_f64 in front of it);
@@ -142,6 +237,7 @@ __device__ __forceinline__ double min_f64(double a, double b) {
 #include "scs_gen.h"   // general path on the same tile structure: k_block_records_gen, k_accumulate_gen
 struct pick_shallower_pair {
     __device__ gap_entry operator()(const gap_entry a, const gap_entry b) const { return gap_min(a, b); }
+    __device__ bool right_less(const gap_entry a, const gap_entry b) const { return b.d < a.d; }
 };
 
 // ---------------------------------------------------------------------------
@@ -626,6 +722,97 @@ __global__ void k_tile_lists(const int2 *__restrict__ tiles, int n_tiles, const 
     list_cnt[i] = c;
 }
 
+// ---- preparation of a tree batch: positions, range-minimum and argmin tables, block records
+constexpr int PIPE_NG = 2;  // tiles of one row block per producer / consumer workgroup (scs_mono_wide.h)
+
+namespace {
+
+enum { PREP_MONO = 0, PREP_WIDE = 1, PREP_GEN = 2, PREP_NO_RECORDS = 3 };  // (the last: the scatter variant)
+
+// what the prep kernels of one batch share; everything indexed by tree-in-batch
+struct prep_batch {
+    const scs_tables *tb;
+    int t0, nb;                // the batch: trees [t0, t0 + nb)
+    int kind;                  // PREP_*: which record kernel; PREP_GEN also selects the pair tables
+    int32_t *pos;
+    int64_t npad;
+    const int64_t *st_off;     // [nb + 1] entries of the value / pair tables
+    const int64_t *am_off;     // [nb + 1] entries of the argmin tables
+    void *st;
+    argmin_t *am;
+    unsigned char *rec;
+    int n_blocks, row_begin, row_end;
+};
+
+int64_t table_entries(int64_t m) { return (int64_t)levels_for(m) * m; }
+int64_t argmin_entries(int64_t m) { return (int64_t)argmin_levels(levels_for(m)) * m; }
+
+// positions, levels and records of the trees [tl0, tl0 + np) of the batch, on `s`.  The pieces of a batch write
+// disjoint parts of the batch's buffers; `pos` has been set to -1 ("absent") for the whole batch.
+int prep_piece(const prep_batch &b, int tl0, int np, hipStream_t s) {
+    if (np <= 0) return SCS_OK;
+    const scs_tables *tb = b.tb;
+    int max_levels = 0;
+    int64_t max_n = 0;
+    for (int t = b.t0 + tl0; t < b.t0 + tl0 + np; ++t) {
+        const int64_t nt = tb->h_tree_off[t + 1] - tb->h_tree_off[t];
+        max_levels = std::max(max_levels, levels_for(nt - 1));
+        max_n = std::max(max_n, nt);
+    }
+    const dim3 grid_l((unsigned)((max_n + 255) / 256), (unsigned)np);
+    const dim3 grid_r((unsigned)b.n_blocks, (unsigned)np);
+    const bool fused = max_n <= SPARSE_FUSED_MAX_LEAVES && max_levels > 1;
+    if (b.kind != PREP_GEN) {
+        double *st = (double *)b.st;
+        k_positions_values<<<grid_l, 256, 0, s>>>(tb->d_tree_off, tb->d_leaf_taxon, tb->d_adj_depth, tb->d_adj_val,
+                                                  tb->d_tree_w, b.t0, tl0, b.pos, b.npad, b.st_off, st);
+        if (fused)
+            k_sparse_levels_fused<double><<<(unsigned)np, 1024, 0, s>>>(tb->d_tree_off, b.t0, tl0, b.st_off, st, b.am_off,
+                                                                        b.am, pick_smaller_value{});
+        else
+            for (int k = 1; k < max_levels; ++k)
+                k_sparse_level<double><<<grid_l, 256, 0, s>>>(tb->d_tree_off, b.t0, tl0, k, b.st_off, st, b.am_off, b.am,
+                                                              pick_smaller_value{});
+        if (b.kind == PREP_WIDE)
+            k_block_records_wide<PIPE_NG><<<grid_r, 64, 0, s>>>(tb->d_tree_off, b.t0, tl0, b.nb, b.pos, b.npad, b.st_off, st,
+                                                          b.am_off, b.am, b.row_begin, b.row_end, b.rec);
+        else if (b.kind == PREP_MONO)
+            k_block_records_mono<<<grid_r, 64, 0, s>>>(tb->d_tree_off, b.t0, tl0, b.nb, b.pos, b.npad, b.st_off, st,
+                                                       b.am_off, b.am, b.row_begin, b.row_end, b.rec);
+    } else {
+        gap_entry *st = (gap_entry *)b.st;
+        k_positions_pairs<<<grid_l, 256, 0, s>>>(tb->d_tree_off, tb->d_leaf_taxon, tb->d_adj_depth, tb->d_adj_val,
+                                                 tb->d_tree_w, b.t0, tl0, b.pos, b.npad, b.st_off, st);
+        if (fused)
+            k_sparse_levels_fused<gap_entry><<<(unsigned)np, 1024, 0, s>>>(tb->d_tree_off, b.t0, tl0, b.st_off, st,
+                                                                           b.am_off, b.am, pick_shallower_pair{});
+        else
+            for (int k = 1; k < max_levels; ++k)
+                k_sparse_level<gap_entry><<<grid_l, 256, 0, s>>>(tb->d_tree_off, b.t0, tl0, k, b.st_off, st, b.am_off,
+                                                                 b.am, pick_shallower_pair{});
+        k_block_records_gen<<<grid_r, 64, 0, s>>>(tb->d_tree_off, b.t0, tl0, b.nb, b.pos, b.npad, b.st_off, st, b.am_off,
+                                                  b.am, b.row_begin, b.row_end, b.rec);
+    }
+    SCS_HIP_CHECK(hipGetLastError());
+    return SCS_OK;
+}
+
+// a page-locked block of the context for as long as a copy out of it may be in flight
+struct pinned_ref {
+    scs_ctx *ctx;
+    hipStream_t stream;
+    void *p = nullptr;
+    bool in_flight = false;
+    pinned_ref(scs_ctx *c, hipStream_t s) : ctx(c), stream(s) {}
+    ~pinned_ref() {
+        if (!p) return;
+        if (in_flight) hipStreamSynchronize(stream);  // (an error return: the copy may still read the block)
+        scs_pinned_release(ctx, p);
+    }
+};
+
+}  // namespace
+
 extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_begin,
                              int32_t row_end, int32_t flags, scs_graph **out,
                              scs_build_stats *stats) {
@@ -786,7 +973,6 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
     // measured with the long tree batches it prefers (below): -11 % at 10 000 leaves per tree, -12 %
     // at 50 000; a handful of tiles -- a node of the deep recursion -- keeps one workgroup per tile.
     // SCS_WIDE=0 / 1 force either kernel (A/B runs, tests).
-    constexpr int PIPE_NG = 2;
     // (Round 4, later: it also pays on a few dozen tiles -- a node of 1 000 to 5 000 taxa in the
     // recursion, where the walk is bound by the latency of a tree's step, not by the chip:
     // 1 000 taxa x 5 000 trees 11.1 -> 9.5 ms, 3 000 x 5 000 15.5 -> 11.2, 3 000 x 300 1.03 -> 0.78;
@@ -841,8 +1027,6 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
         SCS_HIP_CHECK(hipMemcpyAsync(d_groups.p, groups.data(), groups.size() * sizeof(int4),
                                      hipMemcpyHostToDevice, s));
     }
-
-    auto table_entries = [](int64_t m) -> int64_t { return (int64_t)levels_for(m) * m; };
 
     // ---- batch plan: bound range-minimum tables + records + positions by the workspace
     const int M = tb->n_trees;
@@ -900,8 +1084,8 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
         for (int t = 0; t < M; ++t) {
             const int64_t nt = tb->h_tree_off[t + 1] - tb->h_tree_off[t];
             const int64_t m = nt - 1;
-            const size_t need =
-                (size_t)table_entries(m) * entry_bytes + (size_t)npad * 4 + (size_t)n_blocks * rec_bytes;
+            const size_t need = (size_t)table_entries(m) * entry_bytes + (size_t)argmin_entries(m) * sizeof(argmin_t) +
+                                (size_t)npad * 4 + (size_t)n_blocks * rec_bytes;
             if ((used + need > ctx->ws_limit || t - batch_start.back() >= max_batch_trees ||
                  (t == arrived && batch_start.size() == 1)) &&
                 t > batch_start.back()) {
@@ -929,26 +1113,47 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
     int spec_batches = 0, spec_trees = 0;
     float spec_ms = 0.f;
     bool single_batch_spec = false;
-    pooled_buf d_pos(ctx, 1), d_st(ctx, 3), d_stoff(ctx, 4), d_rec(ctx, 5), d_cells(ctx, 6);
+    pooled_buf d_pos(ctx, 1), d_am(ctx, 2), d_st(ctx, 3), d_stoff(ctx, 4), d_rec(ctx, 5), d_cells(ctx, 6);
     dev_buf d_pcol(ctx), d_lists(ctx), d_list_cnt(ctx);  // (partial-coverage forests: per-tile tree lists)
     int listed_batches = 0;
+    // ---- table offsets of ALL batches, sent once: batch bi has nb + 1 offsets into its value / pair tables at
+    // off_at[bi] and nb + 1 into its argmin tables behind them.  The copy leaves a page-locked block that lives
+    // until the build's final synchronisation: a copy per batch out of pageable memory made the host wait for
+    // the stream -- and with it for a table chunk still on its way -- before it could enqueue anything else.
+    std::vector<size_t> off_at((size_t)n_batches + 1, 0);
+    for (int bi = 0; bi < n_batches; ++bi)
+        off_at[bi + 1] = off_at[bi] + 2 * (size_t)(batch_start[bi + 1] - batch_start[bi] + 1);
+    pinned_ref h_off(ctx, s);
+    SCS_TRY(scs_pinned_get(ctx, std::max<size_t>(off_at[n_batches], 2) * 8, &h_off.p));
+    {
+        int64_t *h = (int64_t *)h_off.p;
+        for (int bi = 0; bi < n_batches; ++bi) {
+            const int t0 = batch_start[bi], nb = batch_start[bi + 1] - t0;
+            int64_t *st_off = h + off_at[bi], *am_off = st_off + nb + 1;
+            st_off[0] = am_off[0] = 0;
+            for (int t = 0; t < nb; ++t) {
+                const int64_t m = tb->h_tree_off[t0 + t + 1] - tb->h_tree_off[t0 + t] - 1;
+                st_off[t + 1] = st_off[t] + table_entries(m);
+                am_off[t + 1] = am_off[t] + argmin_entries(m);
+            }
+        }
+        SCS_TRY(d_stoff.alloc(off_at[n_batches] * 8));
+        h_off.in_flight = true;
+        SCS_HIP_CHECK(hipMemcpyAsync(d_stoff.p, h, off_at[n_batches] * 8, hipMemcpyHostToDevice, s));
+    }
+    // SCS_PREP_BY_ARRIVAL=0: one prep piece per batch, behind the batch's last table chunk (A/B runs, tests)
+    const bool by_arrival = !(scs_dbg("SCS_PREP_BY_ARRIVAL") && atoi(scs_dbg("SCS_PREP_BY_ARRIVAL")) == 0);
+    int prep_pieces = 0;
     for (int bi = 0; bi < n_batches; ++bi) {
         const int t0 = batch_start[bi], t1 = batch_start[bi + 1];
         const int nb = t1 - t0;
-        std::vector<int64_t> st_off(nb + 1);
-        int max_levels = 0;
+        const int64_t *h_st_off = (const int64_t *)h_off.p + off_at[bi], *h_am_off = h_st_off + nb + 1;
         int64_t max_n = 0;
-        st_off[0] = 0;
-        for (int t = t0; t < t1; ++t) {
-            const int64_t nt = tb->h_tree_off[t + 1] - tb->h_tree_off[t];
-            st_off[t - t0 + 1] = st_off[t - t0] + table_entries(nt - 1);
-            max_levels = std::max(max_levels, levels_for(nt - 1));
-            max_n = std::max(max_n, nt);
-        }
+        for (int t = t0; t < t1; ++t) max_n = std::max(max_n, tb->h_tree_off[t + 1] - tb->h_tree_off[t]);
         const size_t need_pos = (size_t)nb * npad * 4;
         // +64: a tree without gaps may be probed at entry 0
-        const size_t need_st = (size_t)st_off[nb] * entry_bytes + 64;
-        const size_t need_stoff = (size_t)(nb + 1) * 8;
+        const size_t need_st = (size_t)h_st_off[nb] * entry_bytes + 64;
+        const size_t need_am = (size_t)h_am_off[nb] * sizeof(argmin_t) + 64;
         const size_t need_rec = (size_t)n_blocks * nb * rec_bytes;
         // A short batch (the first 64 trees of tables still on their way, a forest's last few trees)
         // is the 4-wave kernel's: a twelve-wave workgroup has a CU to itself, nothing hides its
@@ -967,51 +1172,38 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
         }
         SCS_TRY(d_pos.alloc(need_pos));
         SCS_TRY(d_st.alloc(need_st));
-        SCS_TRY(d_stoff.alloc(need_stoff));
+        SCS_TRY(d_am.alloc(need_am));
         SCS_TRY(d_rec.alloc(need_rec));
 
         SCS_HIP_CHECK(hipEventRecord(ev_prep.a, s));
-        SCS_TRY(scs_tables_wait(ctx, tb, t1, s));  // (leaf arrays still on their way: scs_tables_upload)
-        SCS_HIP_CHECK(hipMemcpyAsync(d_stoff.p, st_off.data(), need_stoff, hipMemcpyHostToDevice, s));
-        SCS_HIP_CHECK(hipMemsetAsync(d_pos.p, 0xFF, need_pos, s));
-        dim3 grid_l((unsigned)((max_n + 255) / 256), (unsigned)nb);
-        if (monotone) {
-            k_positions_values<<<grid_l, 256, 0, s>>>(tb->d_tree_off, tb->d_leaf_taxon,
-                                                      tb->d_adj_depth, tb->d_adj_val, tb->d_tree_w,
-                                                      t0, (int32_t *)d_pos.p, npad,
-                                                      (const int64_t *)d_stoff.p, (double *)d_st.p);
-            if (max_n <= SPARSE_FUSED_MAX_LEAVES && max_levels > 1)
-                k_sparse_levels_fused<double><<<(unsigned)nb, 1024, 0, s>>>(
-                    tb->d_tree_off, t0, (const int64_t *)d_stoff.p, (double *)d_st.p, pick_smaller_value{});
-            else
-            for (int k = 1; k < max_levels; ++k)
-                k_sparse_level<double><<<grid_l, 256, 0, s>>>(tb->d_tree_off, t0, k,
-                                                              (const int64_t *)d_stoff.p,
-                                                              (double *)d_st.p);
-            if (wide_b)
-                k_block_records_wide<PIPE_NG><<<dim3((unsigned)n_blocks, (unsigned)nb), 64, 0, s>>>(
-                    tb->d_tree_off, t0, nb, (const int32_t *)d_pos.p, npad, (const int64_t *)d_stoff.p,
-                    (const double *)d_st.p, b_row_begin, b_row_end, (unsigned char *)d_rec.p);
-            else if (!scatter)
-            k_block_records_mono<<<dim3((unsigned)n_blocks, (unsigned)nb), 64, 0, s>>>(
-                tb->d_tree_off, t0, nb, (const int32_t *)d_pos.p, npad, (const int64_t *)d_stoff.p,
-                (const double *)d_st.p, b_row_begin, b_row_end, (unsigned char *)d_rec.p);
-        } else {
-            k_positions_pairs<<<grid_l, 256, 0, s>>>(tb->d_tree_off, tb->d_leaf_taxon,
-                                                     tb->d_adj_depth, tb->d_adj_val, tb->d_tree_w,
-                                                     t0, (int32_t *)d_pos.p, npad,
-                                                     (const int64_t *)d_stoff.p, (gap_entry *)d_st.p);
-            if (max_n <= SPARSE_FUSED_MAX_LEAVES && max_levels > 1)
-                k_sparse_levels_fused<gap_entry><<<(unsigned)nb, 1024, 0, s>>>(
-                    tb->d_tree_off, t0, (const int64_t *)d_stoff.p, (gap_entry *)d_st.p, pick_shallower_pair{});
-            else
-            for (int k = 1; k < max_levels; ++k)
-                k_sparse_level_pairs<<<grid_l, 256, 0, s>>>(tb->d_tree_off, t0, k,
-                                                            (const int64_t *)d_stoff.p,
-                                                            (gap_entry *)d_st.p);
-            k_block_records_gen<<<dim3((unsigned)n_blocks, (unsigned)nb), 64, 0, s>>>(
-                tb->d_tree_off, t0, nb, (const int32_t *)d_pos.p, npad, (const int64_t *)d_stoff.p,
-                (const gap_entry *)d_st.p, b_row_begin, b_row_end, (unsigned char *)d_rec.p);
+        SCS_HIP_CHECK(hipMemsetAsync(d_pos.p, 0xFF, need_pos, s));  // (before any wait: it reads no table)
+        prep_batch pb;
+        pb.tb = tb;
+        pb.t0 = t0;
+        pb.nb = nb;
+        pb.kind = !monotone ? PREP_GEN : wide_b ? PREP_WIDE : scatter ? PREP_NO_RECORDS : PREP_MONO;
+        pb.pos = (int32_t *)d_pos.p;
+        pb.npad = npad;
+        pb.st_off = (const int64_t *)d_stoff.p + off_at[bi];
+        pb.am_off = pb.st_off + nb + 1;
+        pb.st = d_st.p;
+        pb.am = (argmin_t *)d_am.p;
+        pb.rec = (unsigned char *)d_rec.p;
+        pb.n_blocks = n_blocks;
+        pb.row_begin = b_row_begin;
+        pb.row_end = b_row_end;
+        // Prep by arrival: the batch is cut where a late table chunk begins (scs_tables_upload), and every piece
+        // is prepared as soon as ITS chunk is there -- the stream waits for the piece's chunk, not the batch's last.
+        // All on the build's one stream, in tree order.  Resident tables: one piece.
+        for (int p0 = t0; p0 < t1;) {
+            int p1 = t1;
+            if (by_arrival)
+                for (const int32_t c : tb->late_start)
+                    if (c > p0 && c < p1) p1 = c;
+            SCS_TRY(scs_tables_wait(ctx, tb, p1, s));  // (leaf arrays still on their way: scs_tables_upload)
+            SCS_TRY(prep_piece(pb, p0 - t0, p1 - p0, s));
+            ++prep_pieces;
+            p0 = p1;
         }
         SCS_HIP_CHECK(hipEventRecord(ev_prep.b, s));
 
@@ -1020,7 +1212,7 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
         if (scatter) {
             const int64_t nbk = (max_n + 63) / 64;
             k_scatter_atomic<<<dim3((unsigned)(nbk * (nbk + 1) / 2), (unsigned)nb), 256, 0, s>>>(
-                tb->d_tree_off, tb->d_leaf_taxon, t0, (const int64_t *)d_stoff.p, (const double *)d_st.p,
+                tb->d_tree_off, tb->d_leaf_taxon, t0, pb.st_off, (const double *)d_st.p,
                 g->d_w, g->ld);
         } else if (monotone) {
             mono_params mp;
@@ -1248,6 +1440,7 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
     }
     SCS_HIP_CHECK(hipEventRecord(ev_total.b, s));
     SCS_HIP_CHECK(hipEventSynchronize(ev_total.b));
+    h_off.in_flight = false;
     SCS_TRY(scs_tables_finish(ctx, tb));  // the range check of the chunks that arrived meanwhile
     float total_ms = 0.f;
     SCS_HIP_CHECK(hipEventElapsedTime(&total_ms, ev_total.a, ev_total.b));
@@ -1272,6 +1465,7 @@ extern "C" int scs_pcg_build(scs_ctx *ctx, const scs_tables *tb, int32_t row_beg
         stats->tree_parallel_batches = tree_par ? n_batches : 0;
         stats->spec_trees = spec_trees;
         stats->listed_batches = listed_batches;
+        stats->prep_pieces = prep_pieces;
         stats->spec_ms = spec_ms;
         stats->cell_trees = (double)tiles.size() * SCS_TR * cols_per_tile * (double)M;
         stats->prep_ms = prep_ms;
@@ -1567,5 +1761,76 @@ extern "C" int scs_debug_graph_raw(scs_ctx *ctx, scs_graph *g, int32_t what, voi
         SCS_HIP_CHECK(hipMemcpy(out, g->d_w32, (size_t)rows * (size_t)g->ld * 4, hipMemcpyDeviceToHost));
     else
         SCS_HIP_CHECK(hipMemcpy(out, g->d_w, (size_t)rows * (size_t)g->ld * 8, hipMemcpyDeviceToHost));
+    return SCS_OK;
+}
+
+// The build's own preparation for the trees [t_begin, t_end) as one batch in one piece, and what the record kernel
+// of `kind` left per (row block, tree) (tests/test_gpu_prep_records.py).  No kernel of its own.
+extern "C" int scs_debug_block_records(scs_ctx *ctx, const scs_tables *tb, int32_t t_begin, int32_t t_end,
+                                       int32_t row_begin, int32_t row_end, int32_t kind, int32_t *spos_out,
+                                       double *gap_out, int32_t *argpos_out, int32_t *depth_out, int32_t *cnt_out) {
+    SCS_REQUIRE(ctx && tb && spos_out && gap_out && argpos_out && cnt_out, "scs_debug_block_records: null argument");
+    SCS_REQUIRE(kind == PREP_MONO || kind == PREP_WIDE || kind == PREP_GEN,
+                "scs_debug_block_records: kind must be 0 (mono), 1 (wide) or 2 (general), not %d", kind);
+    SCS_REQUIRE(t_begin >= 0 && t_begin < t_end && t_end <= tb->n_trees,
+                "scs_debug_block_records: bad tree range [%d, %d) of %d", t_begin, t_end, tb->n_trees);
+    SCS_REQUIRE(row_begin >= 0 && row_begin < row_end && row_end <= tb->n_taxa,
+                "scs_debug_block_records: bad row range [%d, %d) for %d taxa", row_begin, row_end, tb->n_taxa);
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int n = tb->n_taxa, nb = t_end - t_begin;
+    const int n_blocks = (row_end - row_begin + SCS_TR - 1) / SCS_TR;
+    const int n_cgroups = (n + MONO_TCW - 1) / MONO_TCW;
+    const int64_t npad = scs_round_up((int64_t)n_cgroups * MONO_TCW, SCS_NPAD);
+    const size_t entry_bytes = kind == PREP_GEN ? sizeof(gap_entry) : 8;
+    const size_t rec_bytes = kind == PREP_GEN ? G3_BYTES : kind == PREP_WIDE ? wide_layout<PIPE_NG>::BYTES : R3_BYTES;
+    std::vector<int64_t> off(2 * (size_t)(nb + 1), 0);
+    int64_t *st_off = off.data(), *am_off = off.data() + nb + 1;
+    for (int t = 0; t < nb; ++t) {
+        const int64_t m = tb->h_tree_off[t_begin + t + 1] - tb->h_tree_off[t_begin + t] - 1;
+        st_off[t + 1] = st_off[t] + table_entries(m);
+        am_off[t + 1] = am_off[t] + argmin_entries(m);
+    }
+    dev_buf d_pos(ctx), d_st(ctx), d_am(ctx), d_off(ctx), d_rec(ctx);
+    const size_t need_pos = (size_t)nb * npad * 4, need_rec = (size_t)n_blocks * nb * rec_bytes;
+    SCS_TRY(d_pos.alloc(need_pos));
+    SCS_TRY(d_st.alloc((size_t)st_off[nb] * entry_bytes + 64));
+    SCS_TRY(d_am.alloc((size_t)am_off[nb] * sizeof(argmin_t) + 64));
+    SCS_TRY(d_off.alloc(off.size() * 8));
+    SCS_TRY(d_rec.alloc(need_rec));
+    SCS_HIP_CHECK(hipMemcpy(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+    SCS_HIP_CHECK(hipMemsetAsync(d_pos.p, 0xFF, need_pos, s));
+    prep_batch pb;
+    pb.tb = tb;
+    pb.t0 = t_begin;
+    pb.nb = nb;
+    pb.kind = kind;
+    pb.pos = (int32_t *)d_pos.p;
+    pb.npad = npad;
+    pb.st_off = (const int64_t *)d_off.p;
+    pb.am_off = pb.st_off + nb + 1;
+    pb.st = d_st.p;
+    pb.am = (argmin_t *)d_am.p;
+    pb.rec = (unsigned char *)d_rec.p;
+    pb.n_blocks = n_blocks;
+    pb.row_begin = row_begin;
+    pb.row_end = row_end;
+    SCS_TRY(scs_tables_wait(ctx, tb, t_end, s));
+    SCS_TRY(prep_piece(pb, 0, nb, s));
+    std::vector<unsigned char> rec(need_rec);
+    SCS_HIP_CHECK(hipMemcpyAsync(rec.data(), d_rec.p, need_rec, hipMemcpyDeviceToHost, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
+    const int o_spos = kind == PREP_GEN ? G3_SPOS : kind == PREP_WIDE ? wide_layout<PIPE_NG>::SPOS : R3_SPOS;
+    const int o_gap = kind == PREP_GEN ? G3_GV : kind == PREP_WIDE ? wide_layout<PIPE_NG>::G : R3_G;
+    const int o_arg = kind == PREP_GEN ? G3_ARGPOS : kind == PREP_WIDE ? wide_layout<PIPE_NG>::ARGPOS : R3_ARGPOS;
+    const int o_cnt = kind == PREP_GEN ? G3_CNT : kind == PREP_WIDE ? wide_layout<PIPE_NG>::CNT : R3_CNT;
+    for (size_t i = 0; i < (size_t)n_blocks * nb; ++i) {
+        const unsigned char *r = rec.data() + i * rec_bytes;
+        memcpy(spos_out + i * 64, r + o_spos, 256);
+        memcpy(gap_out + i * 64, r + o_gap, 512);
+        memcpy(argpos_out + i * 64, r + o_arg, 256);
+        if (kind == PREP_GEN && depth_out) memcpy(depth_out + i * 64, r + G3_GD, 256);
+        memcpy(cnt_out + i, r + o_cnt, 4);
+    }
     return SCS_OK;
 }

@@ -69,10 +69,10 @@ __global__ void k_positions_pairs(const int64_t *__restrict__ tree_off,
                                   const int32_t *__restrict__ leaf_taxon,
                                   const int32_t *__restrict__ adj_depth,
                                   const double *__restrict__ adj_val,
-                                  const double *__restrict__ tree_w, int t0,
+                                  const double *__restrict__ tree_w, int t0, int tl0,
                                   int32_t *__restrict__ pos, int64_t npad,
                                   const int64_t *__restrict__ st_off, gap_entry *__restrict__ ste) {
-    const int tl = blockIdx.y;
+    const int tl = tl0 + blockIdx.y;
     const int t = t0 + tl;
     const int64_t off = tree_off[t];
     const int n = (int)(tree_off[t + 1] - off);
@@ -91,26 +91,14 @@ __global__ void k_positions_pairs(const int64_t *__restrict__ tree_off,
     }
 }
 
-// level k >= 1 of every tree's pair table; grid as k_positions_pairs
-__global__ void k_sparse_level_pairs(const int64_t *__restrict__ tree_off, int t0, int k,
-                                     const int64_t *__restrict__ st_off,
-                                     gap_entry *__restrict__ ste) {
-    const int tl = blockIdx.y;
-    const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < (1 << k) || p > m - (1 << k)) return;
-    gap_entry *base = ste + st_off[tl];
-    base[(int64_t)k * m + p] =
-        gap_min(base[(int64_t)(k - 1) * m + p], base[(int64_t)(k - 1) * m + p + (1 << (k - 1))]);
-}
-
 // one wave per (local row block, tree): grid (n_blocks, trees in batch), 64 threads
 __global__ __launch_bounds__(64) void k_block_records_gen(
-    const int64_t *__restrict__ tree_off, int t0, int n_batch, const int32_t *__restrict__ pos,
+    const int64_t *__restrict__ tree_off, int t0, int tl0, int n_batch, const int32_t *__restrict__ pos,
     int64_t npad, const int64_t *__restrict__ st_off, const gap_entry *__restrict__ ste,
+    const int64_t *__restrict__ am_off, const argmin_t *__restrict__ am_all,
     int row_begin, int row_end, unsigned char *__restrict__ rec_all) {
     const int blk = blockIdx.x;
-    const int tl = blockIdx.y;
+    const int tl = tl0 + blockIdx.y;
     const int lane = threadIdx.x;
     const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
     const int row = row_begin + blk * SCS_TR + lane;
@@ -138,18 +126,29 @@ __global__ __launch_bounds__(64) void k_block_records_gen(
     double gv = 0.0;
     int argpos = 0;
     if (lane < cnt - 1) {
-        const gap_entry g = rmq_gap(st, m, spos, next_pos);
+        // the query's two entries, and the leftmost position in [spos, next_pos) where the depth is
+        // smallest from the tree's argmin table (level 17 and up: halve the range, keeping a half whose
+        // minimum is still gd)
+        int o[2];
+        rmq_offsets(m, spos, next_pos, o);
+        const int k = 31 - __clz(next_pos - spos);
+        const gap_entry x = st[o[0]], y = st[o[1]];
+        const gap_entry g = gap_min(x, y);
         gd = g.d;
         gv = g.v();
-        // a position in [spos, next_pos) where the depth is smallest: halve the range, keeping
-        // a half whose minimum is still gd
-        int lo = spos, hi = next_pos;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rmq_gap(st, m, lo, mid).d == gd) hi = mid;
-            else lo = mid;
+        if (k == 0) {
+            argpos = spos;
+        } else if (k <= ARGMIN_MAX_LEVEL) {
+            argpos = argmin_position(am_all + am_off[tl], m, k, spos, next_pos, y.d < x.d);
+        } else {
+            int lo = spos, hi = next_pos;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (rmq_gap(st, m, lo, mid).d == gd) hi = mid;
+                else lo = mid;
+            }
+            argpos = lo;
         }
-        argpos = lo;
     }
     unsigned char *rec = rec_all + ((int64_t)blk * n_batch + tl) * G3_BYTES;
     ((int *)(rec + G3_SPOS))[lane] = spos;

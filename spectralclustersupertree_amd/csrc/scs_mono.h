@@ -85,11 +85,12 @@ static_assert(R3_STOFF + 8 <= R3_BYTES && R3_PIECE <= 1024, "record layout");
 
 // one wave per (local row block, tree): grid (n_blocks, trees in batch), 64 threads
 __global__ __launch_bounds__(64) void k_block_records_mono(
-    const int64_t *__restrict__ tree_off, int t0, int n_batch, const int32_t *__restrict__ pos,
+    const int64_t *__restrict__ tree_off, int t0, int tl0, int n_batch, const int32_t *__restrict__ pos,
     int64_t npad, const int64_t *__restrict__ st_off, const double *__restrict__ stv,
+    const int64_t *__restrict__ am_off, const argmin_t *__restrict__ am_all,
     int row_begin, int row_end, unsigned char *__restrict__ rec_all) {
     const int blk = blockIdx.x;
-    const int tl = blockIdx.y;
+    const int tl = tl0 + blockIdx.y;
     const int lane = threadIdx.x;
     const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
     const int row = row_begin + blk * SCS_TR + lane;
@@ -117,21 +118,13 @@ __global__ __launch_bounds__(64) void k_block_records_mono(
     // table entry that involves an absent row comes out 0
     double g = 0.0;
     int argpos = 0;
-    if (lane < cnt - 1) {
-        g = rmq_min<double>(st, m, spos, next_pos);
-        // a position in [spos, next_pos) where the minimum is attained: halve the range,
-        // keeping a half whose minimum is still g.  (Eight sub-ranges a step -- seven prefix minima
-        // in flight together, a third of the dependent round trips -- was measured: 587 us
-        // against 450 for the 436-tree batch of 10 000 leaves: the kernel is bound by the number
-        // of table gathers, not by their latency.)
-        int lo = spos, hi = next_pos;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rmq_min<double>(st, m, lo, mid) == g) hi = mid;
-            else lo = mid;
-        }
-        argpos = lo;
-    }
+    // the leftmost position in [spos, next_pos) where the minimum is attained comes from the tree's
+    // argmin table (scs_build.hip), one gather behind the query's two.  (Until the table existed the
+    // range was halved, keeping a half whose minimum was still g: log2(gap) rounds of two dependent
+    // gathers, about 17 gathers a lane at 10 000 leaves.  Eight sub-ranges a round -- a third of the
+    // round trips, more gathers -- took 587 us against 450 for the 436-tree batch: the kernel is bound
+    // by the NUMBER of table gathers, not by their latency, and the table takes them away.)
+    if (lane < cnt - 1) g = rmq_min_at(st, am_all + am_off[tl], m, spos, next_pos, argpos);
     unsigned char *rec = rec_all + ((int64_t)blk * n_batch + tl) * R3_BYTES;
     ((int *)(rec + R3_SPOS))[lane] = spos;
     ((double *)(rec + R3_G))[lane] = g;

@@ -51,12 +51,13 @@ struct wide_layout {
 // k_block_records_mono with the seeds of 4 NG expansion segments.
 template <int NG>
 __global__ __launch_bounds__(64) void k_block_records_wide(
-    const int64_t *__restrict__ tree_off, int t0, int n_batch, const int32_t *__restrict__ pos,
+    const int64_t *__restrict__ tree_off, int t0, int tl0, int n_batch, const int32_t *__restrict__ pos,
     int64_t npad, const int64_t *__restrict__ st_off, const double *__restrict__ stv,
+    const int64_t *__restrict__ am_off, const argmin_t *__restrict__ am_all,
     int row_begin, int row_end, unsigned char *__restrict__ rec_all) {
     using L = wide_layout<NG>;
     const int blk = blockIdx.x;
-    const int tl = blockIdx.y;
+    const int tl = tl0 + blockIdx.y;
     const int lane = threadIdx.x;
     const int m = (int)(tree_off[t0 + tl + 1] - tree_off[t0 + tl]) - 1;
     const int row = row_begin + blk * SCS_TR + lane;
@@ -81,16 +82,7 @@ __global__ __launch_bounds__(64) void k_block_records_wide(
     const double *st = stv + st_off[tl];
     double g = 0.0;
     int argpos = 0;
-    if (lane < cnt - 1) {
-        g = rmq_min<double>(st, m, spos, next_pos);
-        int lo = spos, hi = next_pos;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rmq_min<double>(st, m, lo, mid) == g) hi = mid;
-            else lo = mid;
-        }
-        argpos = lo;
-    }
+    if (lane < cnt - 1) g = rmq_min_at(st, am_all + am_off[tl], m, spos, next_pos, argpos);
     unsigned char *rec = rec_all + ((int64_t)blk * n_batch + tl) * L::BYTES;
     ((int *)(rec + L::SPOS))[lane] = spos;
     ((double *)(rec + L::G))[lane] = g;
