@@ -352,6 +352,24 @@ int scs_score_parsimony(scs_ctx *ctx, const scs_tables *sources, int32_t n_nodes
                         int64_t *mrp_length, int64_t *mrp_perfect, int64_t *mrp_max, int64_t *char_off,
                         int32_t *char_len, int32_t *char_lo, int32_t *char_hi);
 
+/* Pairwise source-tree distances on shared taxa: the Robinson-Foulds terms between every two
+ * source trees, each pair restricted to the taxa both hold.  `sources` as for scs_score_supertree (adj_val and tree_w
+ * are not read).  For a row tree A and a column tree B, with L = L(A) ∩ L(B), c = |L| and C(X|L) the set of DISTINCT
+ * leaf sets {cl(v) ∩ L : v a node of X} with 2 <= size < c (a set counts once however many nodes carry it):
+ *   common[A][B] = c, clusters[A][B] = |C(A|L)|, clusters_other[A][B] = |C(B|L)|, shared[A][B] = |C(A|L) ∩ C(B|L)|
+ *   (RF = clusters + clusters_other - 2 shared).  c < 3: common = c, the other three 0.  A against itself: c = its
+ *   leaves, all three counts its n_source.  Every count is exact and unweighted.
+ * rows: n_rows tree ids, in any order, repeats allowed; NULL: every tree, and n_rows must be the tables' tree count.
+ * Outputs: n_rows x n_trees int32, row-major (every count is below a tree's leaf count); any of them may be null.
+ * max_batch_trees > 0 caps the trees of a row batch and of a column batch of the tiled pair matrix (tests); 0: sized
+ * by workspace.  max_lds_bytes > 0 caps the LDS of a pair workgroup (tests): a pair whose arrays need more runs from
+ * a slab in the call's block, as does every pair past the 160 KiB of a workgroup -- no tree size is refused.
+ * SCS_EINVAL: a row id out of range, n_rows < 0, rows NULL with n_rows != n_trees, max_lds_bytes < 0, or (checked on
+ * the device before any pair kernel runs) a source taxon out of range or twice in one tree. */
+int scs_score_source_pairs(scs_ctx *ctx, const scs_tables *sources, int32_t n_rows, const int32_t *rows,
+                           int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *common, int32_t *clusters,
+                           int32_t *clusters_other, int32_t *shared);
+
 /* Rooted triplet terms per source tree, same inputs and SCS_EINVAL cases as
  * scs_score_supertree.  For a source tree T on the leaf set L and S' = S|L, a triple {a, b, c} of L is resolved
  * ab|c in a tree when one of its clusters holds a and b but not c, and a fan when no cluster separates one pair:
@@ -875,6 +893,27 @@ int scs_debug_placement_plan(const scs_tables *sources, int32_t n_trees, const i
 int scs_debug_parsimony_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, const int64_t *chars,
                              int32_t n_nodes, const int32_t *parent, int32_t max_batch_trees, int32_t max_pass_words,
                              int32_t *n_batches_out, int32_t *bstart_out, int64_t *info_out, int64_t *batch_out);
+
+/* The plan of one scs_score_source_pairs call on the host, by the functions the export calls.  Trees as for
+ * scs_debug_score_plan (n_taxa is read when `sources` is NULL); n_rows, max_batch_trees and max_lds_bytes as for the
+ * export.  *n_batches_out batches, the same on both axes of the pair matrix; bstart_out[n_batches + 1] (room for
+ * n_trees + 1).
+ * info_out[6] = {levels of the per-tree min tables, stride of a dense position row in entries, bytes of one slab (0:
+ * no pair of the call needs one), persistent workgroups of a slab launch, workspace bytes of the call with all four
+ * outputs asked for, the LDS bytes a pair workgroup may take}.
+ * tile_out (may be NULL; room for n_batches x n_batches x 7), per row batch I and column batch J:
+ *   {entry width in bytes (2: both batches' trees have fewer than 65 536 leaves, else 4),
+ *    dynamic LDS bytes of the pair launch,
+ *    1 when the tile also launches the slab kernel,
+ *    the bytes the tile's largest pair needs,
+ *    threads of a pair workgroup (256, or more while the LDS leaves a CU room for fewer than 32 waves),
+ *    the workgroups one launch may have (2^30, and no more work-items than a dispatch counts in 32 bits),
+ *    the rows of the tile one launch takes under that limit (at least 1: a longer row is strided over)}.
+ * A pair goes to the slab when its own bytes exceed the launch's; the fourth entry of a tile of one tree by one tree
+ * is a pair's bytes. */
+int scs_debug_source_pairs_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
+                                int32_t n_rows, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *n_batches_out,
+                                int32_t *bstart_out, int64_t *info_out, int64_t *tile_out);
 
 #ifdef __cplusplus
 }

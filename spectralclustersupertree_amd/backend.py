@@ -319,6 +319,33 @@ class Device:
         return self._score_call("scs_score_parsimony", tabs, parent, taxon, ints,
                                 (per_tree, (("char_off",), ("m1",)), (per_char, ("total",), np.int32, 0)), sizes=sizes)
 
+    def score_source_pairs(self, sources, rows=None, batch_trees: int = 0, lds_bytes: int = 0,
+                           outputs=("common", "clusters", "clusters_other", "shared")) -> dict:
+        """``scs_score_source_pairs``: the Robinson-Foulds terms between every two source trees, each pair restricted
+        to the taxa both hold.  ``sources`` as for ``score``; ``rows``: the tree ids of the rows wanted (any order,
+        repeats allowed; None: every tree).  Returns int32 arrays ``common``, ``clusters``, ``clusters_other``,
+        ``shared``, rows x trees (None for a name ``outputs`` leaves out).  ``batch_trees`` > 0 caps the trees of a row
+        and of a column batch, ``lds_bytes`` > 0 the LDS of a pair workgroup (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        m = tabs.n_trees
+        if rows is None:
+            n_rows, row_ptr = m, None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.ndim != 1:
+                msg = "rows must be a list of tree ids"
+                raise ValueError(msg)
+            n_rows, row_ptr = len(rows), nv.iptr(rows)
+        names = ("common", "clusters", "clusters_other", "shared")
+        out = {k: np.zeros((n_rows, m), dtype=np.int32) if k in outputs else None for k in names}
+        rc = self._lib.scs_score_source_pairs(self._ctx, tabs._h, n_rows, row_ptr, int(batch_trees), int(lds_bytes),
+                                              *(None if v is None else v.ctypes.data for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_source_pairs: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.
@@ -773,6 +800,36 @@ def debug_parsimony_plan(sources, parent, chars=None, batch_trees: int = 0, pass
             "extra_per_tree", "super_tips")
     return {"bstart": bstart[: k + 1].astype(np.int64), "passes": rows[:k, 0].copy(), "words": rows[:k, 1].copy(),
             **{key: int(info[i]) for i, key in enumerate(keys)}}
+
+
+def debug_source_pairs_plan(sources, n_taxa: int = 0, n_rows: int | None = None, batch_trees: int = 0,
+                            lds_bytes: int = 0) -> dict:
+    """``scs_debug_source_pairs_plan``: the plan of ``scs_score_source_pairs`` for ``sources`` (as for
+    ``debug_score_plan``; ``n_taxa`` is read with a ``tree_off`` array) and ``n_rows`` rows (None: every tree) --
+    ``bstart`` (the batches, the same on both axes); per tile (row batch x column batch) ``width`` (bytes of a list
+    entry), ``lds`` (dynamic LDS of the pair launch), ``slab`` (the tile also launches the slab kernel), ``need``
+    (bytes of its largest pair), ``threads`` (of a pair workgroup), ``grid_limit`` (workgroups one launch may have)
+    and ``rows_per_launch``; once ``levels``, ``row_stride``, ``slab_stride``, ``slab_wgs``, ``workspace`` (bytes of the
+    call's block), ``lds_cap``.  The library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    lib = nv.load_library()
+    nb = C.c_int32(0)
+    bstart = np.zeros(m + 1, dtype=np.int32)
+    info = np.zeros(6, dtype=np.int64)
+    args = (handle, m, None if off is None else nv.lptr(off), int(n_taxa), m if n_rows is None else int(n_rows),
+            int(batch_trees), int(lds_bytes), C.byref(nb), nv.iptr(bstart), nv.lptr(info))
+    nv.check(lib.scs_debug_source_pairs_plan(*args, None))  # (the batches first: they size the tiles)
+    k = int(nb.value)
+    tiles = np.zeros((k, k, 7), dtype=np.int64)
+    nv.check(lib.scs_debug_source_pairs_plan(*args, nv.lptr(tiles)))
+    keys = ("levels", "row_stride", "slab_stride", "slab_wgs", "workspace", "lds_cap")
+    return {"bstart": bstart[: k + 1].astype(np.int64), **{key: int(info[i]) for i, key in enumerate(keys)},
+            "width": tiles[:, :, 0].copy(), "lds": tiles[:, :, 1].copy(), "slab": tiles[:, :, 2].copy(),
+            "need": tiles[:, :, 3].copy(), "threads": tiles[:, :, 4].copy(), "grid_limit": tiles[:, :, 5].copy(),
+            "rows_per_launch": tiles[:, :, 6].copy()}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

@@ -114,6 +114,13 @@ from spectralclustersupertree_amd import __version__
 @click.option("--source-clades-out", default=None,
               help="Also write a TSV with one row per clade of every source tree (tree, tips, size, length, gmax): its "
                    "parsimony length on the supertree, the worst-fitting clades first.")
+@click.option("--source-distances-out", default=None,
+              help="Also write a TSV with one row per pair of source trees that share 3 taxa or more (tree_a, tree_b, "
+                   "common, clusters_a, clusters_b, shared, rf, normalized_rf): the Robinson-Foulds terms between the "
+                   "two trees restricted to the taxa both hold.")
+@click.option("--min-common", default=3, type=click.IntRange(min=3), show_default=True,
+              help="The fewest shared taxa of a pair --source-distances-out lists (3: every pair that has a cluster to "
+                   "compare; the library's mean_distance and outlier_sources start at 4, where two trees can differ).")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
@@ -125,7 +132,8 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         polytomies_out: str | None = None, resolved_out: str | None = None, resolve_min_gain: int = 1,
         resolve_first: bool = False, branch_resample: int = 0, resample_seed: int = 0, jackknife: bool = False,
         branch_support_out: str | None = None, parsimony: bool = False,
-        source_clades_out: str | None = None) -> None:
+        source_clades_out: str | None = None, source_distances_out: str | None = None,
+        min_common: int = 3) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if branch_resample and not (branches_out or branch_support_out):
         msg = "--branch-resample needs --branches-out or --branch-support-out"
@@ -160,8 +168,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
     from spectralclustersupertree_amd import construct_supertree
     from spectralclustersupertree_amd.load import load_tree_arrays
 
+    sources = load_tree_arrays(in_file)
     supertree = construct_supertree(
-        load_tree_arrays(in_file),
+        sources,
         pcg_weighting=pcg_weighting.lower(),
         contract_edges=not disable_contraction,
     )
@@ -223,6 +232,10 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
             if branches_out:
                 result._rs = resampled
                 Path(branches_out).write_text(result.branch_table())
+        if source_distances_out:
+            from spectralclustersupertree_amd.score import source_distances
+
+            Path(source_distances_out).write_text(source_distances(sources).table(min_common))
         if resolved_out:
             from spectralclustersupertree_amd.resolve import resolve_polytomies
 

@@ -4583,3 +4583,4 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
 }
 
 #include "scs_score_parsimony.h"
+#include "scs_score_pairs.h"

@@ -157,6 +157,9 @@ Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_sco
 ``scs_score_conflicts``, ``scs_score_concordance``, ``scs_score_branch_triplets``, ``scs_score_branch_resample``,
 ``scs_score_taxon_triplets``, ``scs_score_placements``, ``scs_score_clade_placements``, ``scs_score_polytomies``,
 ``scs_score_parsimony`` and (for ``refine_supertree``) ``scs_score_clade_moves``; the host only validates and lays out.
+
+``source_distances`` measures the sources against one another instead: the same RF terms between every two source
+trees, each pair restricted to the taxa both hold (``scs_score_source_pairs``).
 """
 
 from __future__ import annotations
@@ -1768,3 +1771,135 @@ def _run_passes(src: _Sources, parent, taxon, req: _Request, timings: dict) -> d
     if req.parsimony_chars and "mrp_char_rows" not in res:  # (no tables: no tree has a character)
         res["mrp_char_rows"] = [{k: np.zeros(0, dtype=np.int32) for k in ("len", "lo", "hi")}] * m
     return res
+
+
+# ------------------------------------------------------------------------------------- the sources against one another
+def _normalized(rf: np.ndarray, total: np.ndarray) -> np.ndarray:
+    out = np.full(rf.shape, np.nan, dtype=np.float64)
+    np.divide(rf, total, out=out, where=total > 0)
+    return out
+
+
+@dataclass
+class SourceDistances:
+    """The Robinson-Foulds terms between source trees, every pair restricted to the taxa both trees hold
+    (``source_distances``).  Row i is tree ``rows[i]`` of the trees as given, column j tree j.
+    With L the taxa both trees hold and C(X|L) the distinct sets cl(v) ∩ L of 2 <= size < |L| over the nodes v of X:
+    ``common`` = |L|, ``clusters`` = |C(row|L)|, ``clusters_other`` = |C(column|L)|, ``shared`` = the sets in both
+    (int32, rows x trees; fewer than 3 common taxa: zeros beside ``common``)."""
+
+    common: np.ndarray
+    clusters: np.ndarray
+    clusters_other: np.ndarray
+    shared: np.ndarray
+    rows: np.ndarray
+    n_leaves: np.ndarray
+    timings: dict = field(default_factory=dict)
+
+    @property
+    def rf(self) -> np.ndarray:
+        """Robinson-Foulds distance of every pair on its common taxa (int64)."""
+        return self.clusters.astype(np.int64) + self.clusters_other - 2 * self.shared.astype(np.int64)
+
+    @property
+    def normalized_rf(self) -> np.ndarray:
+        """``rf`` / (``clusters`` + ``clusters_other``); NaN where neither restricted tree has a cluster."""
+        return _normalized(self.rf, self.clusters.astype(np.int64) + self.clusters_other)
+
+    def _comparable(self, min_common: int) -> np.ndarray:
+        ok = (self.common >= int(min_common)) & ~np.isnan(self.normalized_rf)
+        ok[np.arange(len(self.rows)), self.rows] = False  # (a tree is not compared with itself)
+        return ok
+
+    def mean_distance(self, min_common: int = 4) -> tuple[np.ndarray, np.ndarray]:
+        """``(mean, comparable)`` per row: the mean normalized RF to the other trees that share at least
+        ``min_common`` taxa with it (and have a cluster to compare; NaN when there is none) and how many those are."""
+        ok = self._comparable(min_common)
+        comparable = ok.sum(axis=1).astype(np.int64)
+        total = np.where(ok, np.nan_to_num(self.normalized_rf), 0.0).sum(axis=1)
+        return _normalized(total, comparable), comparable
+
+    def outlier_sources(self, n: int | None = None, min_common: int = 4) -> list[dict]:
+        """The rows by ``mean_distance``, the worst first (ties by tree; trees with nothing to compare left out):
+        dicts ``tree``, ``mean_distance``, ``comparable``; the first ``n`` of them."""
+        mean, comparable = self.mean_distance(min_common)
+        order = sorted((i for i in range(len(self.rows)) if comparable[i] > 0),
+                       key=lambda i: (-mean[i], int(self.rows[i])))
+        out = [{"tree": int(self.rows[i]), "mean_distance": float(mean[i]), "comparable": int(comparable[i])}
+               for i in order]
+        return out if n is None else out[: max(int(n), 0)]
+
+    def table(self, min_common: int = 3) -> str:
+        """TSV, one row per unordered pair of trees a < b with at least ``min_common`` (>= 3) common taxa that a row
+        of the matrices holds: tree_a, tree_b, common, clusters_a, clusters_b, shared, rf, normalized_rf."""
+        floor = max(int(min_common), 3)
+        lines = ["tree_a\ttree_b\tcommon\tclusters_a\tclusters_b\tshared\trf\tnormalized_rf"]
+        first = {}
+        for i, r in enumerate(self.rows.tolist()):
+            first.setdefault(r, i)
+        found = {}
+        for r, i in first.items():
+            for j in np.flatnonzero(self.common[i] >= floor).tolist():
+                if j == r or (j < r and j in first):
+                    continue  # (itself, or the pair is listed from the other tree's row)
+                mine, other = int(self.clusters[i, j]), int(self.clusters_other[i, j])
+                a, b, ca, cb = (r, j, mine, other) if r < j else (j, r, other, mine)
+                found[(a, b)] = (int(self.common[i, j]), ca, cb, int(self.shared[i, j]))
+        for (a, b), (c, ca, cb, sh) in sorted(found.items()):
+            rf = ca + cb - 2 * sh
+            nrf = f"{rf / (ca + cb):.4f}" if ca + cb else "nan"
+            lines.append(f"{a}\t{b}\t{c}\t{ca}\t{cb}\t{sh}\t{rf}\t{nrf}")
+        return "\n".join(lines) + "\n"
+
+
+def _source_names(trees) -> list[str]:
+    """The taxon names of the sources, each once, in order of first appearance."""
+    if isinstance(trees, TreeArrays):
+        return [trees.name(int(x)) for x in trees.present_taxa()]
+    seen: dict = {}
+    for tree in trees:
+        if not is_not_completed(tree):
+            for name in tree.get_tip_names():
+                seen.setdefault(name, None)
+    return list(seen)
+
+
+def source_distances(trees, rows=None, device=None) -> SourceDistances:
+    """The Robinson-Foulds terms between every two source trees, each pair restricted to the taxa both trees hold:
+    which sources disagree with the rest, which pairs overlap too little to say anything (``SourceDistances``).
+
+    ``trees``: a list of tree objects (``NotCompleted`` entries dropped) or a ``TreeArrays``, as for
+    ``score_supertree``; the taxon ids are the union of their names.  ``rows``: the trees (indices into ``trees`` as
+    given) whose rows are wanted, in any order; None: all of them.  Trees of fewer than two leaves of a ``TreeArrays``
+    have no tables: their rows and columns are zeros.  Every count comes from ``scs_score_source_pairs``."""
+    t0 = time.perf_counter()
+    names = _source_names(trees)
+    index = {name: i for i, name in enumerate(names)}
+    keys = ("common", "clusters", "clusters_other", "shared")
+    with _resident_tables(device, trees, names, index) as src:
+        m = len(src.n_leaves)
+        given = np.arange(m, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
+        if given.ndim != 1 or (given.size and (given.min() < 0 or given.max() >= m)):
+            msg = f"rows must be indices of the {m} source trees"
+            raise ValueError(msg)
+        out = {k: np.zeros((len(given), m), dtype=np.int32) for k in keys}
+        timings = {"prepare": 0.0, "tables": src.seconds, "pairs": 0.0}
+        if src.tabs is not None and len(given):
+            tree_index = src.tree_index()
+            t1 = time.perf_counter()
+            if tree_index is None:
+                res = src.dev.score_source_pairs(src.tabs, None if rows is None else given.astype(np.int32))
+                out = {k: res[k] for k in keys}
+            else:
+                at = np.full(m, -1, dtype=np.int64)
+                at[tree_index] = np.arange(len(tree_index))
+                have = np.flatnonzero(at[given] >= 0)
+                ask = at[given[have]].astype(np.int32)
+                everything = len(ask) == len(tree_index) and np.array_equal(ask, np.arange(len(tree_index)))
+                if len(ask):
+                    res = src.dev.score_source_pairs(src.tabs, None if everything else ask)
+                    for k in keys:
+                        out[k][np.ix_(have, tree_index)] = res[k]
+            timings["pairs"] = time.perf_counter() - t1
+    timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
+    return SourceDistances(rows=given, n_leaves=np.asarray(src.n_leaves, dtype=np.int64), timings=timings, **out)

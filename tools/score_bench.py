@@ -23,6 +23,10 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
                                                      # 
     python tools/score_bench.py --parsimony --size 10000x500   # scs_score_parsimony with and without the per-clade
                                                      # lengths beside one scs_score_triplets call
+    python tools/score_bench.py --source-pairs --size 10000x500   # scs_score_source_pairs, every pair of sources,
+                                                     # beside scs_score_supertree and scs_score_triplets on the same
+                                                     # tables and the host reference on a sample of the pairs
+                                                     # 
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -474,6 +478,75 @@ def run_parsimony(dev: Device, size: str, repeats: int = 5) -> dict:
     return out
 
 
+def run_source_pairs(dev: Device, size: str, repeats: int = 7, sample: int = 40) -> dict:
+    """``scs_score_source_pairs`` for every pair of sources on resident tables, a warm-up and ``repeats`` timed calls;
+    for scale ``scs_score_supertree`` and ``scs_score_triplets`` on the same tables, and the host's linear reference
+    (``tests/source_pairs_reference.py``) on ``sample`` of the pairs, which must give the device's numbers."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import source_pairs_reference as sp
+
+    from spectralclustersupertree_amd.backend import debug_source_pairs_plan
+
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    sup = random_binary_tree(2, n_taxa)
+    parent, taxon, tips = supertree_arrays(sup)
+    index = {x: i for i, x in enumerate(tips)}
+    out = {"size": size, "source_pairs": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        m = tabs.n_trees
+        out["supertree_s_min_median_max"], rf = timed(lambda: dev.score(tabs, parent, taxon))
+        out["triplets_s_min_median_max"], _ = timed(lambda: dev.score_triplets(tabs, parent, taxon))
+        out["source_pairs_s_min_median_max"], res = timed(lambda: dev.score_source_pairs(tabs))
+        out["one_row_s_min_median_max"], row = timed(lambda: dev.score_source_pairs(tabs, rows=[m // 2]))
+        plan = debug_source_pairs_plan(tabs)
+        off, leaf, adj = (np.array(x) for x in src.forest.tables()[:3])
+    rs = np.random.RandomState(3)
+    pairs = [(int(a), int(b)) for a, b in rs.randint(0, m, size=(sample, 2))]
+    t0 = time.perf_counter()
+    same = True
+    for a, b in pairs:
+        want = sp.pair_linear(leaf[off[a]:off[a + 1]].astype(np.int64), adj[off[a]:off[a + 1]].astype(np.int64),
+                              leaf[off[b]:off[b + 1]].astype(np.int64), adj[off[b]:off[b + 1]].astype(np.int64), n_taxa)
+        same = same and tuple(int(res[k][a, b]) for k in sp.KEYS) == tuple(int(x) for x in want)
+    host = (time.perf_counter() - t0) / max(len(pairs), 1)
+    med = out["source_pairs_s_min_median_max"][1]
+    unordered = m * (m + 1) // 2
+    common = res["common"].astype(np.int64)
+    out.update({"tables_trees": m, "pairs_computed": unordered, "cells": m * m,
+                "pairs_per_s": round(unordered / med), "us_per_pair": round(med / unordered * 1e6, 3),
+                "common_leaves_mean": round(float(common.mean()), 1), "common_leaves_max": int(common.max()),
+                "common_leaves_per_s": round(float(np.triu(common).sum()) / med),
+                "pairs_with_3_common": int((np.triu(common, 1) >= 3).sum()),
+                "mean_normalized_rf": round(float(np.nanmean(np.where(
+                    res["clusters"] + res["clusters_other"] > 0,
+                    (res["clusters"] + res["clusters_other"] - 2.0 * res["shared"])
+                    / np.maximum(res["clusters"] + res["clusters_other"], 1), np.nan))), 4),
+                "diagonal_equals_n_source": bool(np.array_equal(np.diagonal(res["shared"]), rf["n_source"])),
+                "one_row_equals_its_row": all(np.array_equal(row[k][0], res[k][m // 2]) for k in sp.KEYS),
+                "host_reference_sample": len(pairs), "host_reference_s_per_pair": round(host, 6),
+                "host_reference_agrees": bool(same), "host_over_device_per_pair": round(host / (med / unordered), 1),
+                "batches": len(plan["bstart"]) - 1, "entry_width": int(plan["width"].max()),
+                "pair_lds_bytes": int(plan["lds"].max()), "slab_launch": bool(plan["slab"].any()),
+                "workspace_bytes": plan["workspace"],
+                "over_supertree": round(med / out["supertree_s_min_median_max"][1], 2),
+                "over_triplets": round(med / out["triplets_s_min_median_max"][1], 2)})
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -513,6 +586,8 @@ def main() -> None:
                     help="time scs_score_branch_resample instead, with R weight rows (repeatable)")
     ap.add_argument("--parsimony", action="store_true",
                     help="time scs_score_parsimony instead, without and with the per-clade lengths")
+    ap.add_argument("--source-pairs", action="store_true",
+                    help="time scs_score_source_pairs instead: every pair of the synthetic sources")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -529,6 +604,12 @@ def main() -> None:
             run_parsimony(dev, "200x6", repeats=1)  # warm-up
             for size in args.size or SIZES[:1]:
                 print(json.dumps(run_parsimony(dev, size, max(args.repeats, 5))), flush=True)
+        return
+    if args.source_pairs:
+        with Device(0) as dev:
+            run_source_pairs(dev, "200x6", repeats=1, sample=4)  # warm-up
+            for size in args.size or SIZES[:1]:
+                print(json.dumps(run_source_pairs(dev, size, args.repeats)), flush=True)
         return
     if args.polytomies:
         with Device(0) as dev:
