@@ -103,7 +103,7 @@ typedef struct scs_build_stats {
                                       table upload begins, one piece per batch when the tables are resident */
 } scs_build_stats;
 
-/* ABI version of this header: 109.  Still 109: scs_debug_block_records added, and scs_build_stats' `reserved` slot became prep_pieces.  (The rule for a reserved slot: the version changes when a struct's size or a field's offset or meaning changes for a caller that follows the older header of the same number.  A slot that header called `reserved` was written as 0 and promised nothing; naming it, with size and offsets as they were, leaves every such caller correct -- it reads a count it ignores -- so the number stays.  The earlier reuses, 100 -> 101 and 101 -> 102, also made their structs longer.)  scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements, scs_score_clade_placements and scs_score_clade_moves added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
+/* ABI version of this header: 109.  Still 109: scs_debug_matrix_free_plan added (a new symbol breaks no caller).  Still 109: scs_debug_block_records added, and scs_build_stats' `reserved` slot became prep_pieces.  (The rule for a reserved slot: the version changes when a struct's size or a field's offset or meaning changes for a caller that follows the older header of the same number.  A slot that header called `reserved` was written as 0 and promised nothing; naming it, with size and offsets as they were, leaves every such caller correct -- it reads a count it ignores -- so the number stays.  The earlier reuses, 100 -> 101 and 101 -> 102, also made their structs longer.)  scs_debug_apply_ex, scs_debug_gram_ex and scs_debug_update added; scs_score_branch_triplets, scs_score_taxon_triplets, scs_score_placements, scs_score_clade_placements and scs_score_clade_moves added (a new symbol breaks no caller).  108 -> 109: scs_score_concordance added.  107 -> 108: scs_score_conflicts added.  106 -> 107: scs_score_triplets added.  105 -> 106: scs_score_supertree added.  104 -> 105: scs_debug_arena_stats and scs_ctx_reserve added; scs_ctx_trim's keep_bytes counts the
  * free bytes of the device's arena.  103 -> 104: scs_forest_split_level, scs_forest_analyze,
  * scs_forest_tables_download_range, scs_tables_from_forest_range, scs_small_solve_begin_level added;
  * scs_forest_upload checks the arrays.  102 -> 103: scs_stats ends with event_pair_ms.  101 -> 102: scs_stats is
@@ -667,6 +667,15 @@ int scs_fiedler(scs_ctx *ctx, scs_graph *graph, const double *x_init, double tol
  * made for); the tables must outlive the graph; no contraction, no download.  Results agree with the dense
  * path to rounding, not bit for bit.  Free with scs_graph_free. */
 int scs_graph_matrix_free(scs_ctx *ctx, const scs_tables *tables, int32_t max_block, scs_graph **out);
+
+/* What scs_graph_matrix_free planned for a matrix-free graph and where the graph stands, from host fields alone: no
+ * launch, nothing on the device changes (tests/test_gpu_matrix_free_edges.py).  info_out[6]: [0] chunks a tree's
+ * leaves are cut into per direction, [1] stack_total, the entries of all strips of one (direction, column, chunk) --
+ * the sum over the trees of (deepest separator + 1), [2] the widest block the buffers are made for, [3] the block
+ * width the slabs were last written with (0: never), [4] operator applications so far (the degrees count as one),
+ * [5] the number of trees.  maxd_out (n_trees x int32, may be NULL): per tree the deepest separator the device found
+ * at creation, which sizes that tree's strips.  SCS_EINVAL for a graph that has a matrix. */
+int scs_debug_matrix_free_plan(const scs_graph *graph, int64_t *info_out, int32_t *maxd_out);
 
 /* ---- batched small nodes ----------------------------------------------- */
 

@@ -177,6 +177,7 @@ SIGNATURES = {
     "scs_pcg_build": (C.c_int, [_P, _P, _I32, _I32, _I32, _PP, C.POINTER(BuildStats)]),
     "scs_graph_contract": (C.c_int, [_P, _P, _IP, _I32, _PP]),
     "scs_graph_matrix_free": (C.c_int, [_P, _P, _I32, _PP]),
+    "scs_debug_matrix_free_plan": (C.c_int, [_P, _LP, _IP]),
     "scs_graph_shape": (C.c_int, [_P, _IP, _IP, _IP]),
     "scs_graph_download": (C.c_int, [_P, _P, _DP]),
     "scs_graph_download_rows": (C.c_int, [_P, _P, _I32, _I32, _DP]),

@@ -1124,6 +1124,17 @@ class DeviceGraph:
                  else (rb + np.arange(rows, dtype=np.int64)) // 512 * 512)
         return out, {"rows": rows, "ld": ld, "col0": int(info[2]), "first_col": first}
 
+    def matrix_free_plan(self) -> dict:
+        """``scs_debug_matrix_free_plan``: what ``scs_graph_matrix_free`` planned (``chunks``, ``stack_total``,
+        ``b_cap``), where the graph stands (``slabs_b``, ``n_apply``) and ``maxd``, per tree the deepest separator
+        the device found.  Host fields only: nothing is launched.  ``ScsError`` (``EINVAL``) on a graph with a matrix."""
+        info = np.zeros(6, dtype=np.int64)
+        nv.check(self.dev._lib.scs_debug_matrix_free_plan(self._h, nv.lptr(info), None))
+        maxd = np.zeros(int(info[5]), dtype=np.int32)
+        nv.check(self.dev._lib.scs_debug_matrix_free_plan(self._h, nv.lptr(info), nv.iptr(maxd)))
+        return {"chunks": int(info[0]), "stack_total": int(info[1]), "b_cap": int(info[2]), "slabs_b": int(info[3]),
+                "n_apply": int(info[4]), "maxd": maxd}
+
     def degrees_all(self) -> np.ndarray:
         """The degrees of ALL vertices as this rank holds them (``scs_debug_graph_raw``, mode 2)."""
         info = np.zeros(4, dtype=np.int32)

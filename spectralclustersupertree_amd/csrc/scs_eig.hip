@@ -1679,7 +1679,8 @@ extern "C" int scs_graph_matrix_free(scs_ctx *ctx, const scs_tables *tb, int32_t
     hipMemsetAsync(d_maxd, 0, (size_t)M * 4, s);
     k_mf_maxdepth<<<(unsigned)(((tb->n_leaves + 63) / 64 + 255) / 256), 256, 0, s>>>(tb->d_tree_off, M, tb->d_adj_depth,
                                                                                      tb->n_leaves, d_maxd);
-    std::vector<int32_t> maxd((size_t)M);
+    std::vector<int32_t> &maxd = m->maxd;  // kept: scs_debug_matrix_free_plan reports it
+    maxd.assign((size_t)M, 0);
     hipError_t e = hipMemcpyAsync(maxd.data(), d_maxd, (size_t)M * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     scs_dev_free(d_maxd);
@@ -1695,25 +1696,39 @@ extern "C" int scs_graph_matrix_free(scs_ctx *ctx, const scs_tables *tb, int32_t
     const size_t strips = (size_t)2 * max_block * (size_t)m->chunks * (size_t)m->stack_total;
     const size_t slots = (size_t)2 * max_block * (size_t)m->chunks * (size_t)M;
     const size_t slab_bytes = (size_t)2 * M * (size_t)n * max_block * 8;
-    if (scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->d_stack_off, (size_t)(M + 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->st_val, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->st_sum, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->st_dep, std::max<size_t>(strips, 1) * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->sm_val, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->sm_sum, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->sm_dep, std::max<size_t>(strips, 1) * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->cy_pa, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->cy_ps, std::max<size_t>(strips, 1) * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->cy_dep, std::max<size_t>(strips, 1) * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->sm_cnt, slots * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->sm_root, slots * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->cy_cnt, slots * 4) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->x, (size_t)n * max_block * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->y, (size_t)n * max_block * 8) != hipSuccess ||
-        scs_dev_malloc((scs_ctx *)nullptr, (void **)&m->slabs, slab_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        scs_set_error("scs_graph_matrix_free: cannot allocate %.1f GB of slabs", slab_bytes / 1073741824.0);
-        return fail(SCS_ENOMEM);
+    // (every request by name and size: the message of a failure quotes the bytes that were asked for)
+    const size_t strip_n = std::max<size_t>(strips, 1);
+    const struct {
+        void **p;
+        size_t bytes;
+        const char *what;
+    } want[] = {{(void **)&m->d_stack_off, (size_t)(M + 1) * 8, "strip offsets"},
+                {(void **)&m->st_val, strip_n * 8, "stack strips (values)"},
+                {(void **)&m->st_sum, strip_n * 8, "stack strips (sums)"},
+                {(void **)&m->st_dep, strip_n * 4, "stack strips (depths)"},
+                {(void **)&m->sm_val, strip_n * 8, "summary strips (values)"},
+                {(void **)&m->sm_sum, strip_n * 8, "summary strips (sums)"},
+                {(void **)&m->sm_dep, strip_n * 4, "summary strips (depths)"},
+                {(void **)&m->cy_pa, strip_n * 8, "carry strips (value prefix sums)"},
+                {(void **)&m->cy_ps, strip_n * 8, "carry strips (prefix sums)"},
+                {(void **)&m->cy_dep, strip_n * 4, "carry strips (depths)"},
+                {(void **)&m->sm_cnt, slots * 4, "summary counts"},
+                {(void **)&m->sm_root, slots * 4, "root flags"},
+                {(void **)&m->cy_cnt, slots * 4, "carry counts"},
+                {(void **)&m->x, (size_t)n * max_block * 8, "operand"},
+                {(void **)&m->y, (size_t)n * max_block * 8, "result"},
+                {(void **)&m->slabs, slab_bytes, "slabs"}};
+    size_t asked = 0;
+    for (const auto &w : want) {
+        asked += w.bytes;
+        if (scs_dev_malloc((scs_ctx *)nullptr, w.p, w.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            scs_set_error("scs_graph_matrix_free: cannot allocate %.3f GB of %s (%.3f GB asked for so far; the nine "
+                          "strip arrays take %.3f GB, the slabs %.3f GB)",
+                          w.bytes / 1073741824.0, w.what, asked / 1073741824.0,
+                          (6.0 * 8 + 3.0 * 4) * strip_n / 1073741824.0, slab_bytes / 1073741824.0);
+            return fail(SCS_ENOMEM);
+        }
     }
     e = hipMemcpyAsync(m->d_stack_off, soff.data(), (size_t)(M + 1) * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(m->slabs, 0, slab_bytes, s);  // taxa a tree does not hold stay zero
@@ -1789,6 +1804,21 @@ int scs_matfree_apply(scs_ctx *ctx, scs_graph *g, const double *zt, int64_t ldz,
     if (!zt) k_mf_column0<<<(n + 255) / 256, 256, 0, s>>>(y, n, b, g->d_deg);
     SCS_HIP_CHECK(hipGetLastError());
     ++m->n_apply;
+    return SCS_OK;
+}
+
+// what scs_graph_matrix_free planned and where the graph stands: host fields only, no launch
+extern "C" int scs_debug_matrix_free_plan(const scs_graph *g, int64_t *info_out, int32_t *maxd_out) {
+    SCS_REQUIRE(g && info_out, "scs_debug_matrix_free_plan: null argument");
+    SCS_REQUIRE(g->mf, "scs_debug_matrix_free_plan: the graph has a matrix (only scs_graph_matrix_free plans a walk)");
+    const mf_data *m = g->mf;
+    info_out[0] = m->chunks;
+    info_out[1] = m->stack_total;
+    info_out[2] = m->b_cap;
+    info_out[3] = m->slabs_b;
+    info_out[4] = m->n_apply;
+    info_out[5] = (int64_t)m->maxd.size();
+    if (maxd_out && !m->maxd.empty()) memcpy(maxd_out, m->maxd.data(), m->maxd.size() * sizeof(int32_t));
     return SCS_OK;
 }
 

@@ -234,6 +234,7 @@ struct mf_data {
     double *slabs = nullptr;         // [2][n_trees][n][b_cap]
     int slabs_b = 0;                 // block width the slabs were last written with (absent taxa stay zero)
     int64_t n_apply = 0;
+    std::vector<int32_t> maxd;       // per tree: the deepest separator k_mf_maxdepth found (the strips' sizes)
 };
 
 struct scs_graph {

@@ -147,7 +147,9 @@ def forest(seed: int, n_taxa: int, trees: Sequence[tuple[str, Sequence[int]]], l
         order = np.asarray(order, dtype=np.int32)
         assert len(np.unique(order)) == len(order) and len(order) >= 1
         assert order.min() >= 0 and order.max() < n_taxa
-        par, leaf = shape(kind, len(order), rng)
+        # (a ``(parent, is_leaf)`` pair in place of a kind: a shape made elsewhere, tests/matrix_free_reference.py)
+        par, leaf = kind if isinstance(kind, tuple) else shape(kind, len(order), rng)
+        assert int(np.count_nonzero(leaf)) == len(order)
         tax = np.full(len(par), -1, dtype=np.int32)
         tax[leaf] = order
         parents.append(par)
