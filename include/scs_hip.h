@@ -776,6 +776,27 @@ int scs_debug_apply(scs_ctx *ctx, scs_graph *graph, const double *x, int32_t b, 
 int scs_debug_apply_ex(scs_ctx *ctx, scs_graph *graph, const double *x, int32_t b, int32_t image,
                        int32_t reps, double *y_out, int32_t *info_out);
 
+/* The operator as a multi-rank solve assembles it.  COLLECTIVE: every rank of the job calls it with the same
+ * arguments.  A solver is set up exactly as scs_fiedler sets it up for this graph (row splits gathered, chunk =
+ * the longest slice x b, receive buffer, the SCS_BUILD_UPPER rank's tile lists) and S is applied `reps` times
+ * on that one object to the R block (columns 2b ... 3b-1) of the host panel q (V x 3b, row-major; aq likewise)
+ * by path 0, solver::apply (scale, SYMM, all-gather, unpack -- SCS_BUILD_UPPER: sum of the ranks' partial
+ * products --, store into AQ's R slot; b = 4, 8, 12, 16, SCS_BUILD_UPPER graphs 4 and 8), or path 1, the
+ * fused loop's back half with the second pass in front (SYMM, all-gather, the Gram kernel that assembles AQ's
+ * R slot on its way, the reduction of its partials; b = 4, 8).  y_out (reps x V x b): AQ's R slot after every
+ * application, ALL V rows as this rank holds them.  qaq_out (reps x 3b x 3b; path 1, else may be null): Q^T AQ.
+ * part_out (reps x V x b; SCS_BUILD_UPPER graphs, else may be null): this rank's own unscaled partial product.
+ * image != 0: the ranks stream the single-precision image of their rows -- only where scs_fiedler does
+ * (more than one rank, not SCS_BUILD_UPPER, V >= 4096, b = 4); refused with SCS_EUNSUP otherwise, on every
+ * rank alike and behind the same collectives, never served from W.  info_out[8]: [0] layout (0 row slices,
+ * 1 partial products), [1] path, [2] ranks, [3] chunk in doubles, [4] column segments (partial products:
+ * ranks) of the last SYMM, [5] tiles per application (0 for k_symm), [6] applications that streamed the
+ * image, [7] all-gathers made.  Every buffer an application adds up or unpacks, and AQ's R slot, is filled
+ * with NaN patterns before it: what no rank wrote shows in the product. */
+int scs_debug_team_apply(scs_ctx *ctx, scs_graph *graph, const double *q, const double *aq, int32_t b,
+                         int32_t path, int32_t image, int32_t reps, double *y_out, double *qaq_out,
+                         double *part_out, int64_t *info_out);
+
 /* scs_debug_gram on column blocks of wider panels, as the solver calls it: out (ka x kb) = A^T B with
  * A = columns [a_col0, a_col0 + ka) of the host panel a (n x lda, row-major), B likewise; a == b with
  * lda == ldb is ONE device panel (two blocks of Q).  gram_blocks (1 ... 1024) caps the number of

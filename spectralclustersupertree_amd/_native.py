@@ -194,6 +194,7 @@ SIGNATURES = {
     "scs_debug_gram": (C.c_int, [_P, _DP, _DP, _I32, _I32, _I32, _I32, _DP]),
     "scs_debug_apply": (C.c_int, [_P, _P, _DP, _I32, _DP]),
     "scs_debug_apply_ex": (C.c_int, [_P, _P, _DP, _I32, _I32, _I32, _DP, _IP]),
+    "scs_debug_team_apply": (C.c_int, [_P, _P, _DP, _DP, _I32, _I32, _I32, _I32, _DP, _DP, _DP, _LP]),
     "scs_debug_gram_ex": (C.c_int, [_P, _DP, _I32, _I32, _I32, _DP, _I32, _I32, _I32, _I32, _I32, _I32, _DP]),
     "scs_debug_update": (C.c_int, [_P, _DP, _I32, _I32, _I32, C.c_double, _DP, _I32, _I32, _I32, _DP, _I32,
                                    C.c_double, _I32]),

@@ -1105,6 +1105,30 @@ class DeviceGraph:
                                                   int(reps), nv.dptr(y), nv.iptr(info)))
         return y, dict(zip(self.APPLY_INFO, (int(v) for v in info)))
 
+    TEAM_INFO = ("partial", "path", "world", "chunk", "segments", "tiles", "n_apply32", "n_allgather")
+
+    def team_apply(self, q: np.ndarray, aq: np.ndarray, path: int = 0, image: bool = False, reps: int = 1):
+        """``scs_debug_team_apply`` (collective: every rank, the same arguments): S applied ``reps`` times to the
+        R block of the panel ``q`` (V x 3b) as a multi-rank solve assembles it -- ``path`` 0 ``solver::apply``, 1 the
+        fused loop's back half.  Returns ``(y, qaq, part, info)``: AQ's R slot after every application (reps x V x b,
+        all V rows as this rank holds them), Q^T AQ (reps x 3b x 3b; path 1, else None), this rank's own partial
+        product (reps x V x b; upper-triangle graphs, else None) and a dict of what ran (``TEAM_INFO``)."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        aq = np.ascontiguousarray(aq, dtype=np.float64)
+        n = self.shape[0]
+        if q.ndim != 2 or q.shape[0] != n or q.shape[1] % 3 or aq.shape != q.shape:
+            msg = f"team_apply: q and aq must both have shape ({n}, 3b)"
+            raise ValueError(msg)
+        b = q.shape[1] // 3
+        y = np.empty((reps, n, b))
+        qaq = np.empty((reps, 3 * b, 3 * b)) if path == 1 else None
+        part = np.empty((reps, n, b)) if self.upper else None
+        info = np.zeros(8, dtype=np.int64)
+        nv.check(self.dev._lib.scs_debug_team_apply(
+            self.dev._ctx, self._h, nv.dptr(q), nv.dptr(aq), b, int(path), int(image), int(reps), nv.dptr(y),
+            nv.dptr(qaq) if qaq is not None else None, nv.dptr(part) if part is not None else None, nv.lptr(info)))
+        return y, qaq, part, dict(zip(self.TEAM_INFO, (int(v) for v in info)))
+
     def raw(self, what: int = 0):
         """``scs_debug_graph_raw``: the stored block with all ``ld`` columns -- ``what`` 0 the rows of W (float64),
         1 the single-precision image (float32; made by the solver's degree pass if missing) -- and a dict with

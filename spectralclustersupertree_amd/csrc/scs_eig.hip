@@ -4052,6 +4052,121 @@ extern "C" int scs_debug_apply_ex(scs_ctx *ctx, scs_graph *g, const double *x, i
     return SCS_OK;
 }
 
+// The operator as a multi-rank solve assembles it (collective): the solver is set up as scs_fiedler sets it up,
+// S is applied to the R block of the host panel q by solver::apply (path 0) or solver::fused_back with
+// fold_pass2 off (path 1), `reps` times on one solver object, and every application returns the R slot of AQ
+// -- all V rows, as THIS rank holds them after the gather
+extern "C" int scs_debug_team_apply(scs_ctx *ctx, scs_graph *g, const double *q, const double *aq, int32_t b,
+                                    int32_t path, int32_t image, int32_t reps, double *y_out, double *qaq_out,
+                                    double *part_out, int64_t *info_out) {
+    // (argument checks: the same verdict on every rank, before the first collective)
+    SCS_REQUIRE(ctx && g && q && aq && y_out && info_out, "scs_debug_team_apply: null argument");
+    SCS_REQUIRE(!g->mf, "scs_debug_team_apply: a matrix-free graph is solved on one rank");
+    SCS_REQUIRE(path == 0 || path == 1, "scs_debug_team_apply: path must be 0 (apply) or 1 (fused_back)");
+    SCS_REQUIRE(b == 4 || b == 8 || b == 12 || b == 16, "scs_debug_team_apply: b must be 4, 8, 12 or 16");
+    SCS_REQUIRE(path == 0 || b == 4 || b == 8, "scs_debug_team_apply: the fused loop takes block widths 4 and 8 (asked: %d)", b);
+    SCS_REQUIRE(path == 0 || qaq_out, "scs_debug_team_apply: path 1 returns Q^T AQ");
+    SCS_REQUIRE(!g->upper || part_out, "scs_debug_team_apply: an SCS_BUILD_UPPER graph returns its partial product");
+    SCS_REQUIRE(reps >= 1 && reps <= 64, "scs_debug_team_apply: reps must be in [1, 64]");
+    SCS_REQUIRE(!image || b == 4, "scs_debug_team_apply: the image is streamed at block width 4 (asked: %d)", b);
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    hipStream_t s = ctx->stream;
+    const int n = g->n, q3 = 3 * b;
+    // scs_fiedler's own condition for a row-partitioned rank to stream the image of its rows
+    const bool image_rows = ctx->comm.world > 1 && !g->upper && n >= 4096 && b == 4;
+    SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, image && image_rows));
+    SCS_TRY(scs_graph_prepare_degrees(ctx, g));
+
+    solver sv;
+    sv.ctx = ctx;
+    sv.g = g;
+    sv.s = s;
+    sv.n = n;
+    sv.b = b;
+    sv.rows = g->row_end - g->row_begin;
+    sv.world = ctx->comm.world;
+    sv.gram_blocks = 256;
+    SCS_TRY(gather_full_rows(ctx, g, sv.splits));
+    int max_rows = 0;
+    for (int r = 0; r < sv.world; ++r) max_rows = std::max(max_rows, sv.splits[r + 1] - sv.splits[r]);
+    sv.chunk = g->upper ? (int64_t)n * b : (int64_t)max_rows * b;
+    // (from here on every refusal is the same on all ranks and no collective lies behind it)
+    SCS_TRY(sv.alloc_symm_buffers());
+    if (image) {
+        if (!image_rows || !g->have_w32) {
+            scs_set_error("scs_debug_team_apply: no image for this graph (%s)",
+                          image_rows ? "it could not be made" : "the solver does not stream one in this layout or at this size");
+            return SCS_EUNSUP;
+        }
+        sv.use32 = true;
+    }
+    SCS_TRY(sv.q.alloc((size_t)n * q3 * 8));
+    SCS_TRY(sv.aq.alloc((size_t)n * q3 * 8));
+    SCS_TRY(sv.yloc.alloc((size_t)sv.chunk * 8));
+    SCS_TRY(sv.part2.alloc((size_t)1024 * q3 * q3 * 8));
+    SCS_TRY(sv.small.alloc((size_t)SM_TOTAL * 8));
+    const bool rows_mode = sv.world > 1 && !sv.part_mode;
+    if (rows_mode) {
+        SCS_TRY(sv.yfull.alloc((size_t)n * b * 8));
+        SCS_TRY(sv.recv.alloc((size_t)sv.chunk * sv.world * 8));
+        SCS_TRY(sv.splits_d.alloc((size_t)(sv.world + 1) * 4));
+        SCS_HIP_CHECK(hipMemcpyAsync(sv.splits_d.p, sv.splits.data(), (size_t)(sv.world + 1) * 4,
+                                     hipMemcpyHostToDevice, s));
+    }
+    SCS_HIP_CHECK(hipMemcpyAsync(sv.q.p, q, (size_t)n * q3 * 8, hipMemcpyHostToDevice, s));
+    SCS_HIP_CHECK(hipMemcpyAsync(sv.aq.p, aq, (size_t)n * q3 * 8, hipMemcpyHostToDevice, s));
+    double *G = sv.small_at(SM_G);
+    const size_t slab = (size_t)n * b * 8;
+    for (int r = 0; r < reps; ++r) {
+        // whatever an application adds up or unpacks it has to have written itself: a tail of a chunk, a slab or
+        // a row that nobody wrote is NaN in the product, not what the application before left there
+        if (sv.tri) {  // (the sizes alloc_symm_buffers gave them)
+            const size_t n_rb = sv.part_mode ? (size_t)(sv.tri_rb_hi - sv.tri_rb_lo) : (size_t)((n + TRI_TH - 1) / TRI_TH);
+            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_pdir.p, 0xFF, (size_t)std::max(sv.tri_nct, sv.tri32_nct) * slab, s));
+            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_ptr.p, 0xFF, n_rb * slab, s));
+        }
+        if (sv.ysend.p) SCS_HIP_CHECK(hipMemsetAsync(sv.ysend.p, 0xFF, slab, s));
+        if (sv.recv.p) SCS_HIP_CHECK(hipMemsetAsync(sv.recv.p, 0xFF, (size_t)sv.chunk * sv.world * 8, s));
+        if (sv.yfull.p) SCS_HIP_CHECK(hipMemsetAsync(sv.yfull.p, 0xFF, slab, s));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.ypart.p, 0xFF, sv.ypart_cap * 8, s));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0xFF, (size_t)sv.chunk * 8, s));
+        SCS_HIP_CHECK(hipMemset2DAsync(sv.aq.d() + 2 * b, (size_t)q3 * 8, 0xFF, (size_t)b * 8, (size_t)n, s));
+        if (path == 0) {
+            SCS_TRY(sv.apply(sv.q.d(), 2 * b, sv.aq.d(), 2 * b));
+        } else {
+            int nparts = 0;
+            k_scale_rows<<<(n * b + 255) / 256, 256, 0, s>>>(sv.q.d(), q3, 2 * b, b, n, g->d_dinv, sv.z.d(), sv.ldz);
+            if (b == 4) {
+                SCS_TRY(sv.fused_back<4>(&nparts, sv.part2.d()));
+            } else {
+                SCS_TRY(sv.fused_back<8>(&nparts, sv.part2.d()));
+            }
+            k_reduce_partials<<<(q3 * q3 + 3) / 4, 256, 0, s>>>(sv.part2.d(), nparts, q3 * q3, G);
+            SCS_HIP_CHECK(hipGetLastError());
+            SCS_HIP_CHECK(hipMemcpyAsync(qaq_out + (size_t)r * q3 * q3, G, (size_t)q3 * q3 * 8,
+                                         hipMemcpyDeviceToHost, s));
+        }
+        SCS_HIP_CHECK(hipGetLastError());
+        SCS_HIP_CHECK(hipMemcpy2DAsync(y_out + (size_t)r * n * b, (size_t)b * 8, sv.aq.d() + 2 * b, (size_t)q3 * 8,
+                                       (size_t)b * 8, (size_t)n, hipMemcpyDeviceToHost, s));
+        if (sv.part_mode)
+            SCS_HIP_CHECK(hipMemcpyAsync(part_out + (size_t)r * n * b, sv.ysend.p, slab, hipMemcpyDeviceToHost, s));
+        // (a peer reads this rank's send buffer inside the gather: nothing is refilled before all have met there,
+        // and the in-process gather ends with such a meeting)
+        SCS_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    info_out[0] = sv.part_mode ? 1 : 0;
+    info_out[1] = path;
+    info_out[2] = sv.world;
+    info_out[3] = sv.chunk;
+    info_out[4] = sv.last_nseg;
+    info_out[5] = sv.tri ? sv.tri_ntiles : 0;
+    info_out[6] = sv.n_apply32;
+    info_out[7] = sv.n_allgather;
+    return SCS_OK;
+}
+
 // scs_debug_gram on column sub-blocks of wider host panels, with the caller's count of partials
 extern "C" int scs_debug_gram_ex(scs_ctx *ctx, const double *a, int32_t lda, int32_t a_col0, int32_t ka,
                                  const double *b, int32_t ldb, int32_t b_col0, int32_t kb, int32_t n,
