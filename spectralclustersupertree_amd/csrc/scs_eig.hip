@@ -177,11 +177,18 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restric
 // y and a may alias (in-place y = y*c): every thread of a row reads the row's inputs
 // before any thread of that row writes, because a row lives inside one workgroup
 // and a barrier separates the two phases.
+// (y2, a2: a second pair of panels that takes the same transform in the same launch -- X and S X under
+// one rotation; the workgroups with blockIdx.y == 1 work on it, every element as in a launch of its own)
 __global__ __launch_bounds__(256) void k_update(double *y, int ldy, int kc, double alpha_y,
                                                  const double *a, int lda, int ka,
                                                  const double *__restrict__ c, int ldc,
-                                                 double sign, int n) {
+                                                 double sign, int n, double *y2 = nullptr,
+                                                 const double *a2 = nullptr) {
     __shared__ double sc[3 * MAXB][MAXB];
+    if (blockIdx.y) {
+        y = y2;
+        a = a2;
+    }
     for (int e = threadIdx.x; e < ka * kc; e += 256) {
         const int i = e / kc, j = e - i * kc;
         sc[i][j] = c[i * ldc + j];
@@ -287,11 +294,6 @@ __global__ void k_init_block(double *__restrict__ q, int b, int n, const double 
     double v = hash_uniform((unsigned long long)i, (unsigned long long)k + 1);
     if (k == 0 && x0) v = x0[i];
     q[(int64_t)i * (3 * b) + k] = v;
-}
-
-__global__ void k_fill_int(int *p, int n, int v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
 }
 
 // u[i] = sqrt(deg[i]) / ||sqrt(deg)||   (trivial eigenvector of S when no row is isolated)
@@ -1345,6 +1347,19 @@ __global__ __launch_bounds__(256) void k_small_rr(const double *__restrict__ tm,
     small_rr_body(tm, nparts, nq, b, mask, c, d, theta, mask_p, drop_tol);
 }
 
+// The b x b rotation of X that closes start-up and a confirmation, with the masks it needs and leaves set
+// here instead of by two launches of their own: all 48 slots live going in, P's slots dead coming out
+// (no search directions yet).  mask: the 48 ints; the solve itself is k_small_rr's with nq = b.
+__global__ __launch_bounds__(256) void k_small_rr_start(const double *__restrict__ tm, int b, int *mask,
+                                                         double *__restrict__ c, double *__restrict__ d,
+                                                         double *__restrict__ theta, double drop_tol) {
+    if (threadIdx.x < 48) mask[threadIdx.x] = 1;
+    __syncthreads();
+    small_rr_body(tm, 0, b, b, mask, c, d, theta, mask + b, drop_tol);
+    __syncthreads();
+    if ((int)threadIdx.x < b) mask[b + threadIdx.x] = 0;
+}
+
 // Projected SVQB (fused path, b <= 8).  Input: per-workgroup partials of
 //   Cxp = [x p]^T r (2b x b),  G = r^T r (b x b),  cu = u^T r (1 x b)
 // for an orthonormal [u x p].  With M = G - Cxp^T Cxp - cu^T cu (the Gram matrix of r
@@ -1491,6 +1506,9 @@ __global__ __launch_bounds__(256) void k_panel_rr_solve(double *q, double *aq,
     __shared__ double c_s[3 * B * B], d_s[3 * B * B], th_s[B + 4];
     __shared__ int live_s[3 * B], mp_s[B];
     const int tid = threadIdx.x;
+    // the rows' operands are on their way while the solve runs (scs_panel.h: load part / compute part)
+    panel_rr_ops<B> pre[PANEL_PRE];
+    panel_rr_prefetch<B>(pre, q, aq, u, dinv, zt != nullptr, n);
     if (solve) {
         if (tid < 3 * B) live_s[tid] = tid < B ? 1 : (tid < 2 * B ? maskp_in[tid - B] : mask_r[tid - 2 * B]);
         __syncthreads();
@@ -1509,7 +1527,7 @@ __global__ __launch_bounds__(256) void k_panel_rr_solve(double *q, double *aq,
         if (solve && tid <= B) theta_g[tid] = th_s[tid];
         if (tid < B) maskp_out[tid] = mp_s[tid];
     }
-    panel_rr_body<B>(q, aq, u, c_s, d_s, th_s, n, partial, dinv, zt, ldz);
+    panel_rr_run<B>(pre, q, aq, u, c_s, d_s, th_s, n, partial, dinv, zt, ldz);
 }
 
 template <int B, bool GRAM, bool WRITE_Z>
@@ -1523,10 +1541,12 @@ __global__ __launch_bounds__(256) void k_panel_tf_solve(double *q, const double 
                                                          double *__restrict__ zt, int64_t ldz) {
     __shared__ double coef_s[PANEL_COEF_ROWS<B> * B];
     const bool lead = blockIdx.x == 0;
+    panel_tf_ops<B> pre[PANEL_PRE];
+    panel_tf_prefetch<B, GRAM, WRITE_Z>(pre, q, u, dinv, n);
     small_orth_body(part_in, nparts_in, B, drop_tol, coef_s, lead ? mask_r : nullptr, theta_g,
                     lead ? report : nullptr, -1.0);
     __syncthreads();
-    panel_tf_body<B, GRAM, WRITE_Z>(q, u, coef_s, n, partial, dinv, zt, ldz);
+    panel_tf_run<B, GRAM, WRITE_Z>(pre, q, u, coef_s, n, partial, dinv, zt, ldz);
     if (lead && report) {
         // the report's sequence number, after the rows (the end of the kernel makes it visible)
         __threadfence_system();
@@ -1549,6 +1569,8 @@ __global__ __launch_bounds__(256) void k_panel_gram_tf_solve(double *q, double *
     constexpr int NC = PANEL_COEF_ROWS<B> * B;
     __shared__ double coef_s[NC], coefa_s[NC];
     const bool lead = blockIdx.x == 0;
+    panel_gram_tf_ops<B> pre[PANEL_PRE];
+    panel_gram_tf_prefetch<B, FINISH>(pre, q, aq, u, n, ypart, nseg, dinv, chunk, splits);
     small_orth_body(part_in, nparts_in, B, 0.0, coef_s, lead ? mask_r : nullptr, theta_g, nullptr, -1.0);
     __syncthreads();
     // coef1 (overlapped loop, k_symm_tri_tf): the operator was applied to the RAW residual block R~, and
@@ -1564,7 +1586,7 @@ __global__ __launch_bounds__(256) void k_panel_gram_tf_solve(double *q, double *
         coefa_s[e] = v;
     }
     __syncthreads();
-    panel_gram_tf_body<B, FINISH>(q, aq, u, coef_s, coefa_s, n, ypart, nseg, dinv, partial, chunk, splits);
+    panel_gram_tf_body<B, FINISH>(pre, q, aq, u, coef_s, coefa_s, n, ypart, nseg, dinv, partial, chunk, splits);
 }
 
 // Pass 1 of that orthonormalisation INSIDE the SYMM launch (round 5): the first n_tf workgroups run it
@@ -1593,12 +1615,19 @@ __global__ __launch_bounds__(256, 2) void k_symm_tri_tf(const WT *__restrict__ w
         return;
     }
     const bool lead = bid == 0;
+    // the rows' operands ahead of the solve (scs_panel.h) at width 4 only: at width 8 the solve's
+    // registers and two groups of operands do not fit the 256 VGPRs that two workgroups per CU leave
+    // (measured on the code object: 44 registers spilled to scratch), so there the loads follow it
+    constexpr bool AHEAD = B == 4;
+    panel_tf_ops<B> pre[PANEL_PRE];
+    if (AHEAD) panel_tf_prefetch<B, true, false>(pre, q, u, nullptr, n, bid, n_tf);
     small_orth_core(lds.tf, part_in, nparts_in, B, drop_tol, lds.tf.coef, lead ? mask_r : nullptr, theta_g,
                     lead ? report : nullptr, -1.0);
     __syncthreads();
+    if (!AHEAD) panel_tf_prefetch<B, true, false>(pre, q, u, nullptr, n, bid, n_tf);
     if (lead)
         for (int e = threadIdx.x; e < PANEL_COEF_ROWS<B> * B; e += 256) coef_out[e] = lds.tf.coef[e];
-    panel_tf_body<B, true, false>(q, u, lds.tf.coef, n, partial, nullptr, nullptr, 0, bid, n_tf, &lds.tf.red);
+    panel_tf_run<B, true, false>(pre, q, u, lds.tf.coef, n, partial, nullptr, nullptr, 0, bid, n_tf, &lds.tf.red);
     if (lead && report) {
         __threadfence_system();
         __syncthreads();
@@ -2212,6 +2241,13 @@ struct solver {
         return SCS_OK;
     }
 
+    // Y <- Y C and Y2 <- Y2 C (both n x kc blocks of panels with leading dimension ld) in one launch
+    int rotate2(double *y, double *y2, int ld, int kc, const double *c, int ldc) {
+        k_update<<<dim3((n + 15) / 16, 2), 256, 0, s>>>(y, ld, kc, 0.0, y, ld, kc, c, ldc, 1.0, n, y2, y2);
+        SCS_HIP_CHECK(hipGetLastError());
+        return SCS_OK;
+    }
+
     // ---- fused iteration (scs_panel.h), block widths 4 and 8 ----
     static int panel_cap() {
         static const int cap = PANEL_BLOCKS_MAX;
@@ -2661,11 +2697,10 @@ extern "C" int scs_fiedler(scs_ctx *ctx, scs_graph *g, const double *x_init, dou
     // rotate X so that X^T A X is diagonal
     SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
     {
-        k_fill_int<<<1, 64, 0, s>>>(MASK, 48, 1);
-        k_small_rr<<<1, 256, 0, s>>>(G, 0, b, b, MASK, T, D, TH, MASK + b, drop_tol);
-        SCS_TRY(sv.update(X, q3, b, 0.0, X, q3, b, T, b, 1.0));
-        SCS_TRY(sv.update(AX, q3, b, 0.0, AX, q3, b, T, b, 1.0));
-        k_fill_int<<<1, 64, 0, s>>>(MASK + b, b, 0);  // no search directions yet
+        // (masks: all live going in, no search directions yet coming out -- set by the kernel itself;
+        // X and S X rotated in one launch)
+        k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
+        SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
     }
 
     const int res_blocks = (n + 255) / 256;
@@ -2807,12 +2842,9 @@ extern "C" int scs_fiedler(scs_ctx *ctx, scs_graph *g, const double *x_init, dou
             if (policy.begin_confirmation()) {
                 SCS_TRY(sv.apply(Q, 0, AQ, 0));
                 SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
-                k_fill_int<<<1, 64, 0, s>>>(MASK, 48, 1);
-                k_small_rr<<<1, 256, 0, s>>>(G, 0, b, b, MASK, T, D, TH, MASK + b, drop_tol);
-                SCS_TRY(sv.update(X, q3, b, 0.0, X, q3, b, T, b, 1.0));
-                SCS_TRY(sv.update(AX, q3, b, 0.0, AX, q3, b, T, b, 1.0));
-                // restart the search directions after the refresh: P slot dead and zero
-                k_fill_int<<<1, 64, 0, s>>>(MASK + b, b, 0);
+                // (the kernel leaves the P slots dead: the search directions restart after the refresh)
+                k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
+                SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
                 k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
                 k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
                 SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
