@@ -814,6 +814,52 @@ int scs_debug_update(scs_ctx *ctx, double *y, int32_t ldy, int32_t y_col0, int32
                      const double *a, int32_t lda, int32_t a_col0, int32_t ka, const double *c,
                      int32_t ldc, double sign, int32_t n);
 
+/* The small solves and tall panel kernels of the LOBPCG loop, ONE launch of the product code each on host
+ * arrays.  Every output and scratch buffer is filled with 0xFF bytes before the launch:
+ * an entry nobody wrote comes back as NaN (doubles) or -1 (ints).
+ *
+ * scs_debug_small_svqb: one k_small_svqb launch on g (k x k, row-major), 1 <= k <= 64: t_out (k x k), mask_out (k). */
+int scs_debug_small_svqb(scs_ctx *ctx, const double *g, int32_t k, double drop_tol, double *t_out,
+                         int32_t *mask_out);
+
+/* The Rayleigh-Ritz solve (small_rr_body) through the product kernels.  tm: nq x nq, or with nparts > 0 (nq <= 24
+ * only) nparts partials of it that the kernel sums; mask: nq ints (live basis slots); 1 <= b <= 16, b <= nq <= 3b.
+ * start = 0: k_small_rr, with exact_from handed through (-1: none).  start = 1: k_small_rr_start (nq = b, nparts = 0;
+ * mask is not read).  start = 2: the same body with the one-wave direction path of nq = 3b, b = 4 or 8 switched off,
+ * so that these sizes run the general path too (a debug kernel; the product never takes this switch).
+ * c_out, d_out: nq x b; theta_out: b + 1; mask_p_out: b; mask_out: the 48 mask slots as the launch left them. */
+int scs_debug_small_rr(scs_ctx *ctx, const double *tm, int32_t nparts, int32_t nq, int32_t b, const int32_t *mask,
+                       double drop_tol, int32_t exact_from, int32_t start, double *c_out, double *d_out,
+                       double *theta_out, int32_t *mask_p_out, int32_t *mask_out);
+
+/* The projected SVQB (small_orth_core) on nparts (1 ... 1024) partials of 3 b^2 + b doubles each ([x p]^T r, r^T r,
+ * u^T r).  layout 0: k_small_orth (b <= 8: its working set holds no wider block); layout 1 (b = 4 or 8): a debug
+ * kernel that declares the compact orth_small_lds<b> and calls small_orth_core on it as k_symm_tri_tf does.
+ * theta: b + 1 values for the report.  coef_out: (3b + 4) x b; mask_out: b; report_out: 41 doubles of ordinary
+ * device memory, written with a sequence number of 7 (slots [0, b), [16, 16 + b] and [40]). */
+int scs_debug_small_orth(scs_ctx *ctx, const double *partial, int32_t nparts, int32_t b, double drop_tol,
+                         const double *theta, int32_t layout, double *coef_out, int32_t *mask_out,
+                         double *report_out);
+
+/* One launch of one tall kernel on the panels q, aq ((n + SCS_DEBUG_PANEL_PAD) x 3b, row-major; the rows past n
+ * are the caller's sentinels and travel both ways, as do the columns the kernel leaves alone).  which:
+ *   0 k_panel_rr<b>: coef_a = c, coef_b = d (3b x b each), theta (b); partial_out: blocks x (3 b^2 + b);
+ *   1 k_panel_tf<b, Gram>: coef_a ((3b + 4) x b); partial_out as 0;
+ *   2 k_panel_tf<b, writes Z>: coef_a, dinv; zt_out (b x (n + pad), k-major, leading dimension n + pad) goes in
+ *     with the caller's sentinels and comes back with the launch's stores;
+ *   3 k_gram_qaq<b, 0>: partial_out: blocks x (3b x 3b);
+ *   4 k_gram_qaq<b, 1>: ypart ((nseg x n + pad) x b, nseg in 1 ... 4), dinv; aq_out gets AR; partial_out as 3;
+ *   5 k_rr_update on q with nq = 3b: coef_a = c, coef_b = d; its own grid ((n + 15) / 16 workgroups);
+ *   6 k_residual: theta (b); partial_out: (n + 255) / 256 x b squared norms, one row per workgroup.
+ * 0 ... 4 take b = 4, 8 and blocks in 1 ... 128 (the grid); 5 and 6 take b = 4, 8, 12, 16.  u, dinv: n + pad
+ * entries; u may be null (unconstrained).  The per-workgroup partials come back unsummed.  q_out, aq_out (may be
+ * null): the panels after the launch. */
+#define SCS_DEBUG_PANEL_PAD 16
+int scs_debug_panel(scs_ctx *ctx, int32_t which, int32_t b, int32_t n, const double *q, const double *aq,
+                    const double *u, const double *coef_a, const double *coef_b, const double *theta,
+                    const double *dinv, const double *ypart, int32_t nseg, int32_t blocks, double *q_out,
+                    double *aq_out, double *partial_out, double *zt_out);
+
 /* One grouped round of ncclSend + ncclRecv from this rank to itself through the wrapper the
  * shared build's tile exchange uses (ncclGroupStart ... ncclGroupEnd, ncclFloat64, the
  * context's stream): host_out receives host_in (count doubles).  Needs a context created

@@ -198,6 +198,12 @@ SIGNATURES = {
     "scs_debug_gram_ex": (C.c_int, [_P, _DP, _I32, _I32, _I32, _DP, _I32, _I32, _I32, _I32, _I32, _I32, _DP]),
     "scs_debug_update": (C.c_int, [_P, _DP, _I32, _I32, _I32, C.c_double, _DP, _I32, _I32, _I32, _DP, _I32,
                                    C.c_double, _I32]),
+    "scs_debug_small_svqb": (C.c_int, [_P, _DP, _I32, C.c_double, _DP, _IP]),
+    "scs_debug_small_rr": (C.c_int, [_P, _DP, _I32, _I32, _I32, _IP, C.c_double, _I32, _I32, _DP, _DP, _DP, _IP,
+                                     _IP]),
+    "scs_debug_small_orth": (C.c_int, [_P, _DP, _I32, _I32, C.c_double, _DP, _I32, _DP, _IP, _DP]),
+    "scs_debug_panel": (C.c_int, [_P, _I32, _I32, _I32, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _I32, _I32, _DP,
+                                  _DP, _DP, _DP]),
     "scs_debug_comm_selftest": (C.c_int, [_P, _I32, _DP, _DP]),
     "scs_debug_copy_bandwidth": (C.c_int, [_P, C.c_int64, _I32, _DP]),
     "scs_debug_scan": (C.c_int, [_P, _I32, _I32, C.c_int64, _IP, _IP]),

@@ -495,6 +495,73 @@ class Device:
                                             nv.dptr(a), a.shape[1], a_col0, ka, nv.dptr(c), c.shape[1],
                                             float(sign), y.shape[0]))
 
+    def debug_small_svqb(self, g: np.ndarray, drop_tol: float):
+        """One ``k_small_svqb`` launch on ``g`` (k x k): ``(t, mask)`` (``scs_debug_small_svqb``)."""
+        assert g.dtype == np.float64 and g.flags.c_contiguous and g.ndim == 2 and g.shape[0] == g.shape[1]
+        k = g.shape[0]
+        t = np.empty((k, k))
+        mask = np.empty(k, dtype=np.int32)
+        nv.check(self._lib.scs_debug_small_svqb(self._ctx, nv.dptr(g), k, float(drop_tol), nv.dptr(t), nv.iptr(mask)))
+        return t, mask
+
+    def debug_small_rr(self, tm: np.ndarray, nq: int, b: int, mask, drop_tol: float, exact_from: int = -1,
+                       start: int = 0):
+        """The Rayleigh-Ritz solve through the product kernels (``scs_debug_small_rr``): ``tm`` is nq x nq, or
+        nparts x nq x nq partials that the kernel sums.  ``(c, d, theta, mask_p, mask48)``."""
+        assert tm.dtype == np.float64 and tm.flags.c_contiguous and tm.shape[-2:] == (nq, nq)
+        nparts = tm.shape[0] if tm.ndim == 3 else 0
+        c, d = np.empty((nq, b)), np.empty((nq, b))
+        theta = np.empty(b + 1)
+        mask_p, mask48 = np.empty(b, dtype=np.int32), np.empty(48, dtype=np.int32)
+        mk = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        assert mk is None or mk.shape == (nq,)
+        nv.check(self._lib.scs_debug_small_rr(self._ctx, nv.dptr(tm), nparts, nq, b, None if mk is None else nv.iptr(mk),
+                                              float(drop_tol), int(exact_from), int(start), nv.dptr(c), nv.dptr(d),
+                                              nv.dptr(theta), nv.iptr(mask_p), nv.iptr(mask48)))
+        return c, d, theta, mask_p, mask48
+
+    def debug_small_orth(self, partial: np.ndarray, b: int, drop_tol: float, theta: np.ndarray, layout: int = 0):
+        """The projected SVQB on ``partial`` (nparts x (3 b^2 + b)) (``scs_debug_small_orth``): ``(coef, mask,
+        report)``; ``layout`` 1 runs it on the compact working set of one width."""
+        assert partial.dtype == np.float64 and partial.flags.c_contiguous and partial.ndim == 2
+        assert partial.shape[1] == 3 * b * b + b and theta.dtype == np.float64 and theta.shape == (b + 1,)
+        coef = np.empty((3 * b + 4, b))
+        mask = np.empty(b, dtype=np.int32)
+        report = np.empty(41)
+        nv.check(self._lib.scs_debug_small_orth(self._ctx, nv.dptr(partial), partial.shape[0], b, float(drop_tol),
+                                                nv.dptr(theta), int(layout), nv.dptr(coef), nv.iptr(mask),
+                                                nv.dptr(report)))
+        return coef, mask, report
+
+    PANEL_PAD = 16  # SCS_DEBUG_PANEL_PAD: rows the panels of debug_panel carry past n
+
+    def debug_panel(self, which: int, b: int, n: int, q: np.ndarray, aq: np.ndarray, u=None, coef_a=None,
+                    coef_b=None, theta=None, dinv=None, ypart=None, nseg: int = 0, blocks: int = 1, zt=None):
+        """One launch of one tall kernel of the loop on the panels ``q``, ``aq`` ((n + PANEL_PAD) x 3b)
+        (``scs_debug_panel``; ``which`` as the header lists them): ``(q_out, aq_out, partials)``; ``zt`` (kernel 2)
+        is updated in place."""
+        rows = n + self.PANEL_PAD
+        for m in (q, aq):
+            assert m.dtype == np.float64 and m.flags.c_contiguous and m.shape == (rows, 3 * b)
+        for m in (u, dinv):
+            assert m is None or (m.dtype == np.float64 and m.flags.c_contiguous and m.shape == (rows,))
+        for m in (coef_a, coef_b):
+            assert m is None or (m.dtype == np.float64 and m.flags.c_contiguous
+                                 and m.shape == ((3 * b + 4 if which in (1, 2) else 3 * b), b))
+        assert theta is None or (theta.dtype == np.float64 and theta.flags.c_contiguous and len(theta) >= b)
+        assert ypart is None or (ypart.dtype == np.float64 and ypart.flags.c_contiguous
+                                 and ypart.size == (nseg * n + self.PANEL_PAD) * b)
+        assert zt is None or (zt.dtype == np.float64 and zt.flags.c_contiguous and zt.shape == (b, rows))
+        nb = (n + 15) // 16 if which == 5 else ((n + 255) // 256 if which == 6 else blocks)
+        nper = 3 * b * b + b if which <= 1 else (b if which == 6 else 9 * b * b)
+        part = np.empty((nb, nper))
+        q_out, aq_out = np.empty_like(q), np.empty_like(aq)
+        ptr = lambda m: None if m is None else nv.dptr(m)  # noqa: E731
+        nv.check(self._lib.scs_debug_panel(self._ctx, int(which), b, n, nv.dptr(q), nv.dptr(aq), ptr(u), ptr(coef_a),
+                                           ptr(coef_b), ptr(theta), ptr(dinv), ptr(ypart), int(nseg), int(blocks),
+                                           nv.dptr(q_out), nv.dptr(aq_out), nv.dptr(part), ptr(zt)))
+        return q_out, aq_out, part
+
     def debug_scan(self, op: int, rows: np.ndarray) -> np.ndarray:
         """The exclusive scan of every row of ``rows`` (int32 ``[n_parts, n]``; ``op`` 0 sum, 1 max) through the
         multi-block scan of the forest split (``scs_debug_scan``): ``[n_parts, n + 1]``, the last entry the total."""

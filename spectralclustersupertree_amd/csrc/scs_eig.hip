@@ -1247,7 +1247,7 @@ __device__ void rr_directions_wave(const jacobi_lds &s, int nq, double drop_tol,
 // two search directions keep the mean: their entries are O(||S||).
 __device__ __forceinline__ void small_rr_body(const double *__restrict__ tm, int nparts, int nq, int b,
                               const int *mask, double *c, double *d, double *theta, int *mask_p,
-                              double drop_tol, int exact_from = -1) {
+                              double drop_tol, int exact_from = -1, bool wave_path = true) {
     __shared__ jacobi_lds s;
     __shared__ double cc[3 * MAXB][MAXB];
     __shared__ double dd[3 * MAXB][MAXB];
@@ -1281,7 +1281,9 @@ __device__ __forceinline__ void small_rr_body(const double *__restrict__ tm, int
     if (tid <= b && tid < nq) theta[tid] = s.w[tid];
     __syncthreads();
     if (nq == b) return;  // plain rotation of X (start-up / refresh): no search directions
-    if (nq == 3 * b && (b == 4 || b == 8)) {
+    // (wave_path = false: the debug hook's general path at these sizes, DESIGN.md section 35 -- a constant
+    // in every kernel, so the product kernels compile as before)
+    if (wave_path && nq == 3 * b && (b == 4 || b == 8)) {
         if (tid < 64) {
             if (b == 4) rr_directions_wave<4>(s, nq, drop_tol, d, mask_p);
             else rr_directions_wave<8>(s, nq, drop_tol, d, mask_p);
@@ -1343,8 +1345,9 @@ __global__ __launch_bounds__(256) void k_small_rr(const double *__restrict__ tm,
                                                    int nq, int b, const int *__restrict__ mask,
                                                    double *__restrict__ c, double *__restrict__ d,
                                                    double *__restrict__ theta,
-                                                   int *__restrict__ mask_p, double drop_tol) {
-    small_rr_body(tm, nparts, nq, b, mask, c, d, theta, mask_p, drop_tol);
+                                                   int *__restrict__ mask_p, double drop_tol,
+                                                   int exact_from = -1) {
+    small_rr_body(tm, nparts, nq, b, mask, c, d, theta, mask_p, drop_tol, exact_from);
 }
 
 // The b x b rotation of X that closes start-up and a confirmation, with the masks it needs and leaves set
@@ -4255,6 +4258,222 @@ extern "C" int scs_debug_update(scs_ctx *ctx, double *y, int32_t ldy, int32_t y_
     SCS_TRY(sv.update(dy.d() + y_col0, ldy, kc, alpha, (same ? dy.d() : da.d()) + a_col0, lda, ka, dc.d(), ldc, sign));
     SCS_HIP_CHECK(hipMemcpyAsync(y, dy.p, (size_t)n * ldy * 8, hipMemcpyDeviceToHost, ctx->stream));
     SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return SCS_OK;
+}
+
+// ---- the loop's small solves and tall panel kernels, one launch each
+// Every output and every scratch buffer starts as 0xFF bytes (NaN, -1): what the launch did not write shows.
+static int debug_upload(dbuf &d, const void *host, size_t bytes, hipStream_t s) {
+    SCS_TRY(d.alloc(bytes));
+    SCS_HIP_CHECK(hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, s));
+    return SCS_OK;
+}
+static int debug_blank(dbuf &d, size_t bytes, hipStream_t s) {
+    SCS_TRY(d.alloc(bytes));
+    SCS_HIP_CHECK(hipMemsetAsync(d.p, 0xFF, bytes, s));
+    return SCS_OK;
+}
+static int debug_download(void *host, const dbuf &d, size_t bytes, hipStream_t s) {
+    if (host) SCS_HIP_CHECK(hipMemcpyAsync(host, d.p, bytes, hipMemcpyDeviceToHost, s));
+    return SCS_OK;
+}
+
+// small_rr_body with the register-and-shuffle path switched off: nq = 3b at b = 4, 8 on the general path
+__global__ __launch_bounds__(256) void k_debug_small_rr_general(const double *__restrict__ tm, int nparts, int nq,
+                                                                 int b, const int *__restrict__ mask,
+                                                                 double *__restrict__ c, double *__restrict__ d,
+                                                                 double *__restrict__ theta,
+                                                                 int *__restrict__ mask_p, double drop_tol,
+                                                                 int exact_from) {
+    small_rr_body(tm, nparts, nq, b, mask, c, d, theta, mask_p, drop_tol, exact_from, false);
+}
+
+// the projected SVQB on the compact layout of one width, declared and called as k_symm_tri_tf does
+template <int B>
+__global__ __launch_bounds__(256) void k_debug_small_orth_compact(const double *__restrict__ partial, int nparts,
+                                                                   double drop_tol, double *__restrict__ coef,
+                                                                   int *__restrict__ mask,
+                                                                   const double *__restrict__ theta, double *report,
+                                                                   double seq) {
+    __shared__ orth_small_lds<B> L;
+    small_orth_core(L, partial, nparts, B, drop_tol, L.coef, mask, theta, report, seq);
+    __syncthreads();
+    for (int e = threadIdx.x; e < PANEL_COEF_ROWS<B> * B; e += 256) coef[e] = L.coef[e];
+}
+
+extern "C" int scs_debug_small_svqb(scs_ctx *ctx, const double *g, int32_t k, double drop_tol, double *t_out,
+                                    int32_t *mask_out) {
+    SCS_REQUIRE(ctx && g && t_out && mask_out, "scs_debug_small_svqb: null argument");
+    SCS_REQUIRE(k >= 1 && k <= MAXS, "scs_debug_small_svqb: k must be in [1, %d]", MAXS);
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    hipStream_t s = ctx->stream;
+    dbuf dg, dt, dm;
+    SCS_TRY(debug_upload(dg, g, (size_t)k * k * 8, s));
+    SCS_TRY(debug_blank(dt, (size_t)k * k * 8, s));
+    SCS_TRY(debug_blank(dm, (size_t)k * 4, s));
+    k_small_svqb<<<1, 256, 0, s>>>(dg.d(), k, drop_tol, dt.d(), (int *)dm.p);
+    SCS_HIP_CHECK(hipGetLastError());
+    SCS_TRY(debug_download(t_out, dt, (size_t)k * k * 8, s));
+    SCS_TRY(debug_download(mask_out, dm, (size_t)k * 4, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
+    return SCS_OK;
+}
+
+extern "C" int scs_debug_small_rr(scs_ctx *ctx, const double *tm, int32_t nparts, int32_t nq, int32_t b,
+                                  const int32_t *mask, double drop_tol, int32_t exact_from, int32_t start,
+                                  double *c_out, double *d_out, double *theta_out, int32_t *mask_p_out,
+                                  int32_t *mask_out) {
+    SCS_REQUIRE(ctx && tm && c_out && d_out && theta_out && mask_p_out && mask_out,
+                "scs_debug_small_rr: null argument");
+    SCS_REQUIRE(start >= 0 && start <= 2, "scs_debug_small_rr: start must be 0 (k_small_rr), 1 (k_small_rr_start) "
+                                          "or 2 (k_small_rr's body on the general path)");
+    SCS_REQUIRE(b >= 1 && b <= MAXB && nq >= b && nq <= 3 * b, "scs_debug_small_rr: need 1 <= b <= %d, b <= nq <= 3b",
+                MAXB);
+    SCS_REQUIRE(nparts >= 0 && nparts <= 1024, "scs_debug_small_rr: nparts must be in [0, 1024]");
+    SCS_REQUIRE(nparts == 0 || nq <= 24, "scs_debug_small_rr: partials are summed for nq <= 24 only (asked: %d)", nq);
+    SCS_REQUIRE(exact_from >= -1 && exact_from <= nq, "scs_debug_small_rr: exact_from must be in [-1, nq]");
+    SCS_REQUIRE(start != 1 || (nq == b && nparts == 0 && exact_from < 0),
+                "scs_debug_small_rr: k_small_rr_start solves nq = b on one matrix");
+    SCS_REQUIRE(start == 1 || mask, "scs_debug_small_rr: null mask");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    hipStream_t s = ctx->stream;
+    const size_t nt = (size_t)std::max(1, nparts) * nq * nq;
+    dbuf dtm, dmask, dc, dd, dth, dmp;
+    SCS_TRY(debug_upload(dtm, tm, nt * 8, s));
+    SCS_TRY(debug_blank(dmask, 48 * 4, s));
+    SCS_TRY(debug_blank(dc, (size_t)nq * b * 8, s));
+    SCS_TRY(debug_blank(dd, (size_t)nq * b * 8, s));
+    SCS_TRY(debug_blank(dth, (size_t)(b + 1) * 8, s));
+    SCS_TRY(debug_blank(dmp, (size_t)b * 4, s));
+    if (start != 1) SCS_HIP_CHECK(hipMemcpyAsync(dmask.p, mask, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    int *mk = (int *)dmask.p, *mp = (int *)dmp.p;
+    if (start == 1)
+        k_small_rr_start<<<1, 256, 0, s>>>(dtm.d(), b, mk, dc.d(), dd.d(), dth.d(), drop_tol);
+    else if (start == 2)
+        k_debug_small_rr_general<<<1, 256, 0, s>>>(dtm.d(), nparts, nq, b, mk, dc.d(), dd.d(), dth.d(), mp, drop_tol,
+                                                   exact_from);
+    else
+        k_small_rr<<<1, 256, 0, s>>>(dtm.d(), nparts, nq, b, mk, dc.d(), dd.d(), dth.d(), mp, drop_tol, exact_from);
+    SCS_HIP_CHECK(hipGetLastError());
+    SCS_TRY(debug_download(c_out, dc, (size_t)nq * b * 8, s));
+    SCS_TRY(debug_download(d_out, dd, (size_t)nq * b * 8, s));
+    SCS_TRY(debug_download(theta_out, dth, (size_t)(b + 1) * 8, s));
+    SCS_TRY(debug_download(mask_p_out, dmp, (size_t)b * 4, s));
+    SCS_TRY(debug_download(mask_out, dmask, 48 * 4, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
+    return SCS_OK;
+}
+
+extern "C" int scs_debug_small_orth(scs_ctx *ctx, const double *partial, int32_t nparts, int32_t b, double drop_tol,
+                                    const double *theta, int32_t layout, double *coef_out, int32_t *mask_out,
+                                    double *report_out) {
+    SCS_REQUIRE(ctx && partial && theta && coef_out && mask_out && report_out, "scs_debug_small_orth: null argument");
+    SCS_REQUIRE(layout == 0 || layout == 1, "scs_debug_small_orth: layout must be 0 (general) or 1 (compact)");
+    // (orth_lds holds cxp[16][8], gm[9][8]: the projected SVQB exists for the fused loop's widths only)
+    SCS_REQUIRE(b >= 1 && b <= 8, "scs_debug_small_orth: the projected SVQB takes block widths up to 8 (asked: %d)", b);
+    SCS_REQUIRE(layout == 0 || b == 4 || b == 8, "scs_debug_small_orth: the compact layout is built for widths 4 and 8");
+    SCS_REQUIRE(nparts >= 1 && nparts <= 1024, "scs_debug_small_orth: nparts must be in [1, 1024]");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    hipStream_t s = ctx->stream;
+    const size_t nout = (size_t)3 * b * b + b, ncoef = (size_t)(3 * b + 4) * b;
+    const double seq = 7.0;
+    dbuf dp, dth, dco, dm, drep;
+    SCS_TRY(debug_upload(dp, partial, (size_t)nparts * nout * 8, s));
+    SCS_TRY(debug_upload(dth, theta, (size_t)(b + 1) * 8, s));
+    SCS_TRY(debug_blank(dco, ncoef * 8, s));
+    SCS_TRY(debug_blank(dm, (size_t)b * 4, s));
+    SCS_TRY(debug_blank(drep, 41 * 8, s));
+    if (layout == 0)
+        k_small_orth<<<1, 256, 0, s>>>(dp.d(), nparts, b, drop_tol, dco.d(), (int *)dm.p, dth.d(), drep.d(), seq);
+    else if (b == 4)
+        k_debug_small_orth_compact<4><<<1, 256, 0, s>>>(dp.d(), nparts, drop_tol, dco.d(), (int *)dm.p, dth.d(),
+                                                         drep.d(), seq);
+    else
+        k_debug_small_orth_compact<8><<<1, 256, 0, s>>>(dp.d(), nparts, drop_tol, dco.d(), (int *)dm.p, dth.d(),
+                                                         drep.d(), seq);
+    SCS_HIP_CHECK(hipGetLastError());
+    SCS_TRY(debug_download(coef_out, dco, ncoef * 8, s));
+    SCS_TRY(debug_download(mask_out, dm, (size_t)b * 4, s));
+    SCS_TRY(debug_download(report_out, drep, 41 * 8, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
+    return SCS_OK;
+}
+
+template <int B>
+static int debug_panel_fused(int which, int n, int nb, double *q, double *aq, const double *u, const double *ca,
+                             const double *cb, const double *theta, const double *dinv, const double *ypart,
+                             int nseg, double *part, double *zt, int64_t ldz, hipStream_t s) {
+    switch (which) {
+    case 0: k_panel_rr<B><<<nb, 256, 0, s>>>(q, aq, u, ca, cb, theta, n, part); break;
+    case 1: k_panel_tf<B, true, false><<<nb, 256, 0, s>>>(q, u, ca, n, part, nullptr, nullptr, 0); break;
+    case 2: k_panel_tf<B, false, true><<<nb, 256, 0, s>>>(q, u, ca, n, nullptr, dinv, zt, ldz); break;
+    case 3: k_gram_qaq<B, 0><<<nb, 256, 0, s>>>(q, aq, n, nullptr, 0, nullptr, part); break;
+    default: k_gram_qaq<B, 1><<<nb, 256, 0, s>>>(q, aq, n, ypart, nseg, dinv, part); break;
+    }
+    SCS_HIP_CHECK(hipGetLastError());
+    return SCS_OK;
+}
+
+extern "C" int scs_debug_panel(scs_ctx *ctx, int32_t which, int32_t b, int32_t n, const double *q, const double *aq,
+                               const double *u, const double *coef_a, const double *coef_b, const double *theta,
+                               const double *dinv, const double *ypart, int32_t nseg, int32_t blocks, double *q_out,
+                               double *aq_out, double *partial_out, double *zt_out) {
+    SCS_REQUIRE(ctx && q && aq, "scs_debug_panel: null panel");
+    SCS_REQUIRE(which >= 0 && which <= 6, "scs_debug_panel: which must be in [0, 6]");
+    const bool fused = which <= 4;
+    SCS_REQUIRE(fused ? (b == 4 || b == 8) : (b == 4 || b == 8 || b == 12 || b == 16),
+                "scs_debug_panel: kernel %d does not take block width %d", which, b);
+    SCS_REQUIRE(n >= 1 && n <= (1 << 24), "scs_debug_panel: n must be in [1, 2^24]");
+    SCS_REQUIRE(!fused || (blocks >= 1 && blocks <= PANEL_BLOCKS_MAX), "scs_debug_panel: blocks must be in [1, %d]",
+                PANEL_BLOCKS_MAX);
+    SCS_REQUIRE((which != 0 && which != 1 && which != 2 && which != 5) || coef_a, "scs_debug_panel: null coefficients");
+    SCS_REQUIRE((which != 0 && which != 5) || coef_b, "scs_debug_panel: null coefficients");
+    SCS_REQUIRE((which != 0 && which != 6) || theta, "scs_debug_panel: null theta");
+    SCS_REQUIRE((which != 2 && which != 4) || dinv, "scs_debug_panel: null dinv");
+    SCS_REQUIRE(which != 2 || zt_out, "scs_debug_panel: null zt_out");
+    SCS_REQUIRE(which != 4 || (ypart && nseg >= 1 && nseg <= 4), "scs_debug_panel: FINISH 1 sums 1 ... 4 segments");
+    SCS_REQUIRE(which == 2 || which == 5 || partial_out, "scs_debug_panel: null partial_out");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    t_ctx = ctx;
+    hipStream_t s = ctx->stream;
+    const int pad = SCS_DEBUG_PANEL_PAD;
+    const size_t rows = (size_t)n + pad, ld = (size_t)3 * b;
+    const size_t ncoef = which == 1 || which == 2 ? (size_t)(3 * b + 4) * b : ld * b;
+    const int nb = which == 5 ? (n + 15) / 16 : (which == 6 ? (n + 255) / 256 : blocks);
+    const size_t nper = which <= 1 ? (size_t)3 * b * b + b : (which == 6 ? (size_t)b : ld * ld);
+    dbuf dq, daq, du, dca, dcb, dth, ddi, dyp, dpart, dzt;
+    SCS_TRY(debug_upload(dq, q, rows * ld * 8, s));
+    SCS_TRY(debug_upload(daq, aq, rows * ld * 8, s));
+    if (u) SCS_TRY(debug_upload(du, u, rows * 8, s));
+    if (coef_a) SCS_TRY(debug_upload(dca, coef_a, ncoef * 8, s));
+    if (coef_b) SCS_TRY(debug_upload(dcb, coef_b, ncoef * 8, s));
+    if (theta) SCS_TRY(debug_upload(dth, theta, (size_t)b * 8, s));
+    if (dinv) SCS_TRY(debug_upload(ddi, dinv, rows * 8, s));
+    if (which == 4) SCS_TRY(debug_upload(dyp, ypart, ((size_t)nseg * n + pad) * b * 8, s));
+    SCS_TRY(debug_blank(dpart, (size_t)nb * nper * 8, s));
+    if (which == 2) SCS_TRY(debug_upload(dzt, zt_out, (size_t)b * rows * 8, s));
+    const double *up = u ? du.d() : nullptr;
+    if (which == 5) {
+        k_rr_update<<<nb, 256, 0, s>>>(dq.d(), b, 3 * b, dca.d(), dcb.d(), n);
+        SCS_HIP_CHECK(hipGetLastError());
+    } else if (which == 6) {
+        k_residual<<<nb, 256, 0, s>>>(dq.d(), daq.d(), b, dth.d(), n, dpart.d());
+        SCS_HIP_CHECK(hipGetLastError());
+    } else if (b == 4) {
+        SCS_TRY(debug_panel_fused<4>(which, n, nb, dq.d(), daq.d(), up, dca.d(), dcb.d(), dth.d(), ddi.d(), dyp.d(),
+                                     nseg, dpart.d(), dzt.d(), (int64_t)rows, s));
+    } else {
+        SCS_TRY(debug_panel_fused<8>(which, n, nb, dq.d(), daq.d(), up, dca.d(), dcb.d(), dth.d(), ddi.d(), dyp.d(),
+                                     nseg, dpart.d(), dzt.d(), (int64_t)rows, s));
+    }
+    SCS_TRY(debug_download(q_out, dq, rows * ld * 8, s));
+    SCS_TRY(debug_download(aq_out, daq, rows * ld * 8, s));
+    if (which != 2 && which != 5) SCS_TRY(debug_download(partial_out, dpart, (size_t)nb * nper * 8, s));
+    if (which == 2) SCS_TRY(debug_download(zt_out, dzt, (size_t)b * rows * 8, s));
+    SCS_HIP_CHECK(hipStreamSynchronize(s));
     return SCS_OK;
 }
 

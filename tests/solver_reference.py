@@ -39,7 +39,7 @@ PANEL_ROWS = (1, 3, 4, 5, 63, 64, 65, 255, 257, 4099, 100003)
 SENTINEL = 1e300  # fills the columns of a panel that a kernel must neither read nor write
 GRAM_PATTERNS = ("x_ax", "q_r", "q_aq", "u_y")
 UPDATE_PATTERNS = ("u", "in_place", "q_r")
-JACOBI_SIZES = (2, 3, 12, 24, 36, 48, 64)
+JACOBI_SIZES = (2, 3, 4, 5, 7, 8, 12, 16, 23, 24, 36, 48, 64)
 JACOBI_FAMILIES = ("zero", "identity", "rank_one", "repeated", "cluster", "graded", "ritz", "gauss_1e+150",
                    "gauss_1e-150", "ritz_separated")
 # scs_fiedler sets `gram_blocks = 256` for every n (csrc/scs_eig.hip, "sv.gram_blocks = 256"): the product's value
