@@ -370,6 +370,30 @@ int scs_score_source_pairs(scs_ctx *ctx, const scs_tables *sources, int32_t n_ro
                            int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *common, int32_t *clusters,
                            int32_t *clusters_other, int32_t *shared);
 
+/* Triple coverage of the sources: which taxa are ever seen together.
+ * `sources` are tables as for scs_score_source_pairs.  Only `tree_off` and `leaf_taxon` are read.  n = the tables'
+ * `n_taxa`.
+ *   M[x] is the set of trees that hold taxon x.
+ *   cov(a, b, c) = |M[a] ∩ M[b] ∩ M[c]|.
+ *   A triple of three distinct taxa is *covered* when cov >= k, with k = `min_trees` >= 1.
+ * For the row taxa r, given as `rows` (ids in any order, repeats allowed; NULL means every taxon, and then `n_rows`
+ * must be n):
+ *   `occurs[x]`, int32, n entries, always for all taxa: |M[x]|.
+ *   `pair_trees[r][b]`, int32, n_rows x n, row-major: |M[a] ∩ M[b]|.  The diagonal is `occurs[a]`.
+ *   `pair_covered[r][b]`, int32, n_rows x n: #{c ∉ {a, b} : cov(a, b, c) >= k}.  The diagonal is 0.
+ *   `taxon_covered[r]`, int64, n_rows: the covered triples that contain a.  This equals Σ_b `pair_covered[r][b]` / 2.
+ * Any output may be null.  With both matrices null no device buffer of n_rows x n entries is allocated: taxon_covered
+ * comes from sums kept on the device.  The rows are batched by workspace; max_batch_rows > 0 caps a row batch (tests).
+ * max_reg_words > 0 lowers the words of a taxon's membership row a lane holds in registers (64 at most: up to 2 048
+ * trees; tests) -- a row of more words is streamed from memory instead, so no number of trees is refused.  No size is
+ * refused: the cost is O(n_rows · n² · ⌈trees/32⌉) word operations, every count exact.
+ * SCS_EINVAL: null ctx or tables, min_trees < 1, a row id out of range, n_rows < 0, rows NULL with n_rows != n, a
+ * negative knob, or (checked on the device before any sweep kernel runs) a source taxon out of range or twice in one
+ * tree. */
+int scs_score_coverage(scs_ctx *ctx, const scs_tables *sources, int32_t n_rows, const int32_t *rows, int32_t min_trees,
+                       int32_t max_batch_rows, int32_t max_reg_words, int32_t *occurs, int32_t *pair_trees,
+                       int32_t *pair_covered, int64_t *taxon_covered);
+
 /* Rooted triplet terms per source tree, same inputs and SCS_EINVAL cases as
  * scs_score_supertree.  For a source tree T on the leaf set L and S' = S|L, a triple {a, b, c} of L is resolved
  * ab|c in a tree when one of its clusters holds a and b but not c, and a fan when no cluster separates one pair:
@@ -990,6 +1014,27 @@ int scs_debug_parsimony_plan(const scs_tables *sources, int32_t n_trees, const i
 int scs_debug_source_pairs_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
                                 int32_t n_rows, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *n_batches_out,
                                 int32_t *bstart_out, int64_t *info_out, int64_t *tile_out);
+
+/* The plan of one scs_score_coverage call on the host, by the functions the export calls.  `sources` or, when it is
+ * NULL, n_trees and n_taxa (tree_off is not read: the plan depends on the tree count alone).  n_rows < 0 stands for
+ * rows NULL (every taxon); min_trees, max_batch_rows and max_reg_words as for the export; matrices_wanted: how many
+ * of pair_trees / pair_covered are asked for (0, 1 or 2).
+ * info_out[12] = {words per taxon (⌈trees/32⌉, at least 1),
+ *   the sweep variant: words a lane holds in registers (4, 8, 16, 32 or 64), or 0 for the streaming kernel,
+ *   stride of a taxon-major membership row in words, stride of a word-major row in taxa (n rounded up to 64),
+ *   tiles of 64 column taxa per row (one workgroup each),
+ *   bytes a row adds to the call's block (8 and its cells of the matrices wanted),
+ *   bytes of the block without the matrices,
+ *   row batches,
+ *   the workgroups one launch may have (2^30, and no more work-items than a dispatch counts in 32 bits),
+ *   the rows one launch takes under that limit (at least 1: a longer row is strided over),
+ *   1 when only pairs a < b are swept and both cells written (rows NULL, and the matrices, if wanted, hold every row
+ *   at once), 1 when the lanes count trees (min_trees > 1) instead of testing for one}.
+ * batches_out (may be NULL; room for 4 x the batches, which a first call with NULL returns in info_out[7]):
+ *   {first row, rows, bytes of the call's block, workgroups of the batch's first launch}. */
+int scs_debug_coverage_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
+                            int32_t n_rows, int32_t min_trees, int32_t max_batch_rows, int32_t max_reg_words,
+                            int32_t matrices_wanted, int64_t *info_out, int64_t *batches_out);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,37 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_coverage(self, sources, rows=None, min_trees: int = 1, pairs: bool = False, batch_rows: int = 0,
+                       reg_words: int = 0, outputs=("occurs", "taxon_covered")) -> dict:
+        """``scs_score_coverage``: the triple coverage of the sources.  ``sources`` as for ``score`` (only their trees'
+        taxa are read); ``rows``: the taxon ids of the rows wanted (any order, repeats allowed; None: every taxon);
+        a triple counts as covered when ``min_trees`` trees hold all three.  Returns ``occurs`` (int32, taxa),
+        ``taxon_covered`` (int64, rows) and, with ``pairs``, ``pair_trees`` and ``pair_covered`` (int32, rows x taxa;
+        None otherwise) -- ``outputs`` names the ones wanted beside the matrices, the others are None.
+        ``batch_rows`` > 0 caps a row batch, ``reg_words`` > 0 the words of a membership row a lane holds in registers
+        (tests).  The cost is O(rows x taxa^2 x ceil(trees / 32))."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        n = tabs.n_taxa
+        if rows is None:
+            n_rows, row_ptr = n, None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.ndim != 1:
+                msg = "rows must be a list of taxon ids"
+                raise ValueError(msg)
+            n_rows, row_ptr = len(rows), nv.iptr(rows)
+        want = set(outputs) | ({"pair_trees", "pair_covered"} if pairs else set())
+        shapes = {"occurs": ((n,), np.int32), "pair_trees": ((n_rows, n), np.int32),
+                  "pair_covered": ((n_rows, n), np.int32), "taxon_covered": ((n_rows,), np.int64)}
+        out = {k: np.zeros(shape, dtype=dt) if k in want else None for k, (shape, dt) in shapes.items()}
+        rc = self._lib.scs_score_coverage(self._ctx, tabs._h, n_rows, row_ptr, int(min_trees), int(batch_rows),
+                                          int(reg_words), *(None if v is None else v.ctypes.data for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_coverage: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.
@@ -897,6 +928,29 @@ def debug_source_pairs_plan(sources, n_taxa: int = 0, n_rows: int | None = None,
             "width": tiles[:, :, 0].copy(), "lds": tiles[:, :, 1].copy(), "slab": tiles[:, :, 2].copy(),
             "need": tiles[:, :, 3].copy(), "threads": tiles[:, :, 4].copy(), "grid_limit": tiles[:, :, 5].copy(),
             "rows_per_launch": tiles[:, :, 6].copy()}
+
+
+def debug_coverage_plan(sources, n_taxa: int = 0, n_rows: int | None = None, min_trees: int = 1, batch_rows: int = 0,
+                        reg_words: int = 0, matrices: int = 0) -> dict:
+    """``scs_debug_coverage_plan``: the plan of ``scs_score_coverage`` for ``sources`` (device tables, or the number
+    of trees with ``n_taxa``), ``n_rows`` rows (None: rows None, every taxon) and ``matrices`` of the two matrices
+    wanted -- once ``words`` (per taxon), ``variant`` (words a lane holds in registers; 0: the streaming kernel),
+    ``bits_stride``, ``taxa_stride``, ``tiles`` (workgroups of a row), ``row_bytes``, ``fixed_bytes``, ``n_batches``,
+    ``grid_limit``, ``rows_per_launch``, ``mirror``, ``count`` (``min_trees`` > 1); per batch ``first_row``, ``rows``,
+    ``bytes`` (of the call's block) and ``grid`` (workgroups of its first launch).  The library's own arithmetic, on
+    the host."""
+    handle, m = (sources._h, sources.n_trees) if isinstance(sources, DeviceTables) else (None, int(sources))
+    lib = nv.load_library()
+    info = np.zeros(12, dtype=np.int64)
+    args = (handle, m, None, int(n_taxa), -1 if n_rows is None else int(n_rows), int(min_trees), int(batch_rows),
+            int(reg_words), int(matrices), nv.lptr(info))
+    nv.check(lib.scs_debug_coverage_plan(*args, None))  # (the number of batches first)
+    batches = np.zeros((int(info[7]), 4), dtype=np.int64)
+    nv.check(lib.scs_debug_coverage_plan(*args, nv.lptr(batches) if len(batches) else None))
+    keys = ("words", "variant", "bits_stride", "taxa_stride", "tiles", "row_bytes", "fixed_bytes", "n_batches",
+            "grid_limit", "rows_per_launch", "mirror", "count")
+    return {**{key: int(info[i]) for i, key in enumerate(keys)}, "first_row": batches[:, 0].copy(),
+            "rows": batches[:, 1].copy(), "bytes": batches[:, 2].copy(), "grid": batches[:, 3].copy()}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

@@ -121,6 +121,12 @@ from spectralclustersupertree_amd import __version__
 @click.option("--min-common", default=3, type=click.IntRange(min=3), show_default=True,
               help="The fewest shared taxa of a pair --source-distances-out lists (3: every pair that has a cluster to "
                    "compare; the library's mean_distance and outlier_sources start at 4, where two trees can differ).")
+@click.option("--coverage-out", default=None,
+              help="Also write a TSV with one row per taxon (taxon, occurs, covered, triples, coverage): of the rooted "
+                   "triples that hold the taxon, how many some source tree holds whole -- whether the sources overlap "
+                   "enough to determine a tree at all.")
+@click.option("--coverage-min-trees", default=1, type=click.IntRange(min=1), show_default=True, metavar="K",
+              help="The source trees that must hold a triple for --coverage-out to count it as covered.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
@@ -133,7 +139,7 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         resolve_first: bool = False, branch_resample: int = 0, resample_seed: int = 0, jackknife: bool = False,
         branch_support_out: str | None = None, parsimony: bool = False,
         source_clades_out: str | None = None, source_distances_out: str | None = None,
-        min_common: int = 3) -> None:
+        min_common: int = 3, coverage_out: str | None = None, coverage_min_trees: int = 1) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if branch_resample and not (branches_out or branch_support_out):
         msg = "--branch-resample needs --branches-out or --branch-support-out"
@@ -236,6 +242,10 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
             from spectralclustersupertree_amd.score import source_distances
 
             Path(source_distances_out).write_text(source_distances(sources).table(min_common))
+        if coverage_out:
+            from spectralclustersupertree_amd.score import source_coverage
+
+            Path(coverage_out).write_text(source_coverage(sources, min_trees=coverage_min_trees).table())
         if resolved_out:
             from spectralclustersupertree_amd.resolve import resolve_polytomies
 

@@ -160,6 +160,8 @@ Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_sco
 
 ``source_distances`` measures the sources against one another instead: the same RF terms between every two source
 trees, each pair restricted to the taxa both hold (``scs_score_source_pairs``).
+``source_coverage`` asks the earlier question, whether the sources overlap enough to determine a tree at all: the
+rooted triples of taxa that some source tree holds whole (``scs_score_coverage``).
 """
 
 from __future__ import annotations
@@ -1903,3 +1905,151 @@ def source_distances(trees, rows=None, device=None) -> SourceDistances:
             timings["pairs"] = time.perf_counter() - t1
     timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
     return SourceDistances(rows=given, n_leaves=np.asarray(src.n_leaves, dtype=np.int64), timings=timings, **out)
+
+
+# ------------------------------------------------------------------------------------- the triple coverage of the sources
+@dataclass
+class SourceCoverage:
+    """Which taxa the sources ever show together (``source_coverage``).  M[x] is the set of
+    trees that hold taxon x; cov(a, b, c) = |M[a] ∩ M[b] ∩ M[c]|; a triple of three distinct taxa is *covered* when
+    cov >= k, with k = ``min_trees`` >= 1.  Row i is taxon ``rows[i]``; taxon ids index ``taxa``.
+
+    ``occurs[x]`` = |M[x]| for all taxa; ``taxon_covered[i]`` the covered triples that contain the row's taxon,
+    ``taxon_triples`` = C(n - 1, 2) the triples that do, ``taxon_coverage`` their ratio (NaN for n < 3).  With every
+    taxon a row (``rows`` None): ``triples_total`` = C(n, 3), ``triples_covered``, ``coverage`` and ``decisive`` (every
+    triple covered: the taxon sets alone leave no rooted tree undetermined); None otherwise.  With ``pairs``:
+    ``pair_trees[i][b]`` = |M[a] ∩ M[b]| (the diagonal is ``occurs[a]``) and ``pair_covered[i][b]`` =
+    #{c ∉ {a, b} : cov(a, b, c) >= k} (the diagonal is 0), int32, rows x taxa; None otherwise."""
+
+    taxa: list
+    rows: np.ndarray
+    min_trees: int
+    occurs: np.ndarray
+    taxon_covered: np.ndarray
+    taxon_triples: int
+    triples_total: int | None = None
+    triples_covered: int | None = None
+    pair_trees: np.ndarray | None = None
+    pair_covered: np.ndarray | None = None
+    timings: dict = field(default_factory=dict)
+
+    @property
+    def taxon_coverage(self) -> np.ndarray:
+        """``taxon_covered`` / ``taxon_triples``; NaN with fewer than three taxa."""
+        return _normalized(self.taxon_covered.astype(np.float64),
+                           np.full(len(self.rows), float(self.taxon_triples)))
+
+    @property
+    def coverage(self) -> float | None:
+        """``triples_covered`` / ``triples_total`` (NaN with fewer than three taxa); None unless every taxon is a row."""
+        if self.triples_total is None:
+            return None
+        return self.triples_covered / self.triples_total if self.triples_total else float("nan")
+
+    @property
+    def decisive(self) -> bool | None:
+        """Every triple is covered (None unless every taxon is a row)."""
+        return None if self.triples_total is None else self.triples_covered == self.triples_total
+
+    def least_covered_taxa(self, n: int | None = None, min_occurs: int = 1) -> list[dict]:
+        """The rows by ``taxon_covered``, the worst first (ties by taxon id; each taxon once; taxa in fewer than
+        ``min_occurs`` trees left out): dicts ``taxon``, ``name``, ``occurs``, ``covered``, ``coverage``; the first
+        ``n`` of them."""
+        first: dict = {}
+        for i, r in enumerate(self.rows.tolist()):
+            first.setdefault(r, i)
+        ratio = self.taxon_coverage
+        order = sorted((i for r, i in first.items() if self.occurs[r] >= int(min_occurs)),
+                       key=lambda i: (int(self.taxon_covered[i]), int(self.rows[i])))
+        out = [{"taxon": int(self.rows[i]), "name": self.taxa[int(self.rows[i])],
+                "occurs": int(self.occurs[self.rows[i]]), "covered": int(self.taxon_covered[i]),
+                "coverage": float(ratio[i])} for i in order]
+        return out if n is None else out[: max(int(n), 0)]
+
+    def never_together(self) -> list[tuple]:
+        """The pairs (a, b) of taxon ids, a < b, that no tree holds together (``pair_trees`` == 0), each once, among
+        the pairs a row of the matrices holds.  It needs ``pairs=True``."""
+        if self.pair_trees is None:
+            msg = "never_together needs the pair matrices: source_coverage(..., pairs=True)"
+            raise ValueError(msg)
+        i, b = np.nonzero(self.pair_trees == 0)
+        a = self.rows[i]
+        keep = a != b
+        pairs = np.unique(np.stack([np.minimum(a, b)[keep], np.maximum(a, b)[keep]], axis=1), axis=0)
+        return [(int(x), int(y)) for x, y in pairs.tolist()]
+
+    def table(self) -> str:
+        """TSV, one row per row taxon: taxon, occurs, covered, triples, coverage."""
+        lines = ["taxon\toccurs\tcovered\ttriples\tcoverage"]
+        ratio = self.taxon_coverage
+        for i, r in enumerate(self.rows.tolist()):
+            cov = "nan" if np.isnan(ratio[i]) else f"{ratio[i]:.4f}"
+            lines.append(f"{self.taxa[r]}\t{self.occurs[r]}\t{self.taxon_covered[i]}\t{self.taxon_triples}\t{cov}")
+        return "\n".join(lines) + "\n"
+
+
+def _one_leaf_occurrences(trees, index: dict, n: int) -> np.ndarray:
+    """Per taxon id of ``index`` the one-leaf trees of a ``TreeArrays`` that hold it: such trees have no tables."""
+    extra = np.zeros(n, dtype=np.int32)
+    if isinstance(trees, TreeArrays):
+        counts = trees.leaf_counts()
+        taxon, node_off = np.asarray(trees.taxon), np.asarray(trees.node_off)
+        for t in np.flatnonzero(counts == 1).tolist():
+            ids = taxon[node_off[t]:node_off[t + 1]]
+            extra[index[trees.name(int(ids[ids >= 0][0]))]] += 1
+    return extra
+
+
+def source_coverage(trees, min_trees: int = 1, rows=None, pairs: bool = False, device=None) -> SourceCoverage:
+    """The triple coverage of the sources: do they overlap enough to determine a tree at all (``SourceCoverage``)?
+    A rooted triple that no source tree holds whole can only be resolved by inference through other taxa; the share
+    of covered triples is the partial decisiveness of the taxon sampling.
+
+    ``trees``: a list of tree objects (``NotCompleted`` entries dropped) or a ``TreeArrays``, as for
+    ``source_distances``; the taxon ids number the union of their names (a list: in order of first appearance; a
+    ``TreeArrays``: in the order of its own ids) and are listed in ``taxa``.  A triple counts
+    as covered when at least ``min_trees`` trees hold all three taxa.  ``rows``: the taxa (names or ids) whose rows are
+    wanted, in any order; None: all of them, which also gives the totals.  ``pairs``: the two rows x taxa matrices as
+    well.  Every count is exact and comes from ``scs_score_coverage``, whose cost is
+    O(rows x taxa^2 x ceil(trees / 32)); one-leaf trees of a ``TreeArrays`` have no tables and are added to ``occurs``
+    (and the diagonal of ``pair_trees``) here, so both inputs give the same numbers."""
+    t0 = time.perf_counter()
+    if int(min_trees) < 1:
+        msg = f"min_trees = {min_trees} is less than 1"
+        raise ValueError(msg)
+    names = _source_names(trees)
+    index = {name: i for i, name in enumerate(names)}
+    n = len(names)
+    if rows is None:
+        given = np.arange(n, dtype=np.int64)
+    else:
+        rows = list(rows)
+        bad = [r for r in rows if (isinstance(r, str) and r not in index)
+               or (not isinstance(r, str) and not 0 <= int(r) < n)]
+        if bad:
+            msg = f"rows must be names or ids of the {n} taxa of the sources, not {bad[0]!r}"
+            raise ValueError(msg)
+        given = np.array([index[r] if isinstance(r, str) else int(r) for r in rows], dtype=np.int64)
+    with _resident_tables(device, trees, names, index) as src:
+        timings = {"prepare": 0.0, "tables": src.seconds, "coverage": 0.0}
+        out = {"occurs": np.zeros(n, dtype=np.int32), "taxon_covered": np.zeros(len(given), dtype=np.int64),
+               "pair_trees": np.zeros((len(given), n), dtype=np.int32) if pairs else None,
+               "pair_covered": np.zeros((len(given), n), dtype=np.int32) if pairs else None}
+        if src.tabs is not None:
+            t1 = time.perf_counter()
+            out = src.dev.score_coverage(src.tabs, None if rows is None else given.astype(np.int32),
+                                         min_trees=int(min_trees), pairs=pairs)
+            timings["coverage"] = time.perf_counter() - t1
+    extra = _one_leaf_occurrences(trees, index, n)
+    if extra.any():
+        out["occurs"] = out["occurs"] + extra
+        if pairs:
+            out["pair_trees"][np.arange(len(given)), given] += extra[given]
+    total = covered = None
+    if rows is None:
+        total, covered = n * (n - 1) * (n - 2) // 6, int(out["taxon_covered"].sum()) // 3
+    timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
+    return SourceCoverage(taxa=names, rows=given, min_trees=int(min_trees), occurs=out["occurs"],
+                          taxon_covered=out["taxon_covered"], taxon_triples=(n - 1) * (n - 2) // 2 if n >= 3 else 0,
+                          triples_total=total, triples_covered=covered, pair_trees=out["pair_trees"],
+                          pair_covered=out["pair_covered"], timings=timings)

@@ -27,6 +27,10 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
                                                      # beside scs_score_supertree and scs_score_triplets on the same
                                                      # tables and the host reference on a sample of the pairs
                                                      # 
+    python tools/score_bench.py --coverage --size 10000x500   # scs_score_coverage for min_trees 1 and 2, with and
+                                                     # without the two matrices, beside the numpy reference on a sample
+                                                     # of rows and the word operations the sweep needs (DESIGN.md
+                                                     # section 36)
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -547,6 +551,76 @@ def run_source_pairs(dev: Device, size: str, repeats: int = 7, sample: int = 40)
     return out
 
 
+# vector lanes of the device per second: 256 CUs x 4 SIMDs x 32 lanes at 2.4 GHz (one 32-bit operation each)
+LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9
+
+
+def run_coverage(dev: Device, size: str, repeats: int = 5, sample: int = 64) -> dict:
+    """``scs_score_coverage`` for every taxon on resident tables, min_trees 1 and 2, with and without the two
+    matrices: a warm-up and ``repeats`` timed calls each.  Beside them the numpy reference
+    (``tests/coverage_reference.py``, ``by_matmul``) on ``sample`` rows, which must give the device's numbers and whose
+    time is scaled to all rows, and the word operations the sweep's lanes need at the device's rate."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import coverage_reference as cr
+
+    from spectralclustersupertree_amd.backend import debug_coverage_plan
+
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    tips = [arrays.name(i) for i in range(n_taxa)]
+    index = {x: i for i, x in enumerate(tips)}
+    out = {"size": size, "coverage": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    res = {}
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        for k in (1, 2):
+            out[f"k{k}_s_min_median_max"], res[k, False] = timed(lambda: dev.score_coverage(tabs, min_trees=k))
+            out[f"k{k}_matrices_s_min_median_max"], res[k, True] = timed(
+                lambda: dev.score_coverage(tabs, min_trees=k, pairs=True))
+        plan = debug_coverage_plan(tabs, matrices=2)
+        off, leaf = (np.array(x) for x in src.forest.tables()[:2])
+    sets = [leaf[off[t]:off[t + 1]].tolist() for t in range(len(off) - 1)]
+    rows = np.random.RandomState(3).choice(n_taxa, size=min(sample, n_taxa), replace=False)
+    same = True
+    for k in (1, 2):
+        t0 = time.perf_counter()
+        want = cr.by_matmul(sets, n_taxa, k, rows)
+        out[f"k{k}_host_reference_s_all_rows"] = round((time.perf_counter() - t0) / len(rows) * n_taxa, 1)
+        same = same and np.array_equal(want["occurs"], res[k, True]["occurs"])
+        for key in ("pair_trees", "pair_covered", "taxon_covered"):
+            same = same and np.array_equal(want[key], res[k, True][key][rows])
+        same = same and np.array_equal(res[k, False]["taxon_covered"], res[k, True]["taxon_covered"])
+        # the model: every pair a < b that takes part meets every taxon in k trees or more, `variant` words each (one
+        # and-or a word, or an and and a popcount); a streamed row has its own words
+        pt = res[k, True]["pair_trees"]
+        pairs = (int((pt >= k).sum()) - int((np.diagonal(pt) >= k).sum())) // 2
+        nc = int((res[k, True]["occurs"] >= k).sum())
+        ops = pairs * nc * (plan["variant"] or plan["words"]) * (1 if k == 1 else 2)
+        covered = int(res[k, True]["taxon_covered"].sum()) // 3
+        med = out[f"k{k}_s_min_median_max"][1]
+        out.update({f"k{k}_pairs_swept": pairs, f"k{k}_taxa_walked": nc, f"k{k}_lane_ops": ops,
+                    f"k{k}_model_s": round(ops / LANE_OPS_PER_S, 4), f"k{k}_over_model": round(med * LANE_OPS_PER_S / ops, 2)
+                    if ops else None, f"k{k}_triples_covered": covered,
+                    f"k{k}_coverage": round(covered / (n_taxa * (n_taxa - 1) * (n_taxa - 2) / 6), 6),
+                    f"k{k}_host_over_device": round(out[f"k{k}_host_reference_s_all_rows"] / med, 1)})
+    out.update({"words": plan["words"], "variant": plan["variant"], "batches_with_matrices": plan["n_batches"],
+                "mirror_with_matrices": plan["mirror"], "block_bytes_with_matrices": int(plan["bytes"].max()),
+                "host_reference_rows": len(rows), "host_reference_agrees": bool(same)})
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -588,6 +662,10 @@ def main() -> None:
                     help="time scs_score_parsimony instead, without and with the per-clade lengths")
     ap.add_argument("--source-pairs", action="store_true",
                     help="time scs_score_source_pairs instead: every pair of the synthetic sources")
+    ap.add_argument("--coverage", action="store_true",
+                    help="time scs_score_coverage instead: the triple coverage of the synthetic sources")
+    ap.add_argument("--coverage-sample", type=int, default=64, metavar="ROWS",
+                    help="the rows --coverage checks against the numpy reference")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -610,6 +688,12 @@ def main() -> None:
             run_source_pairs(dev, "200x6", repeats=1, sample=4)  # warm-up
             for size in args.size or SIZES[:1]:
                 print(json.dumps(run_source_pairs(dev, size, args.repeats)), flush=True)
+        return
+    if args.coverage:
+        with Device(0) as dev:
+            run_coverage(dev, "200x6", repeats=1, sample=4)  # warm-up
+            for size in args.size or ("10000x500", "20000x2000x500"):
+                print(json.dumps(run_coverage(dev, size, max(args.repeats, 3), args.coverage_sample)), flush=True)
         return
     if args.polytomies:
         with Device(0) as dev:
