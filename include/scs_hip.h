@@ -763,6 +763,21 @@ int scs_small_solve_end(scs_ctx *ctx, int32_t ticket, double *maps_out, double *
 
 /* ---- diagnostics used by the parity tests ------------------------------ */
 
+/* The packed input arrays of a begun batch (a ticket of any of the three _begin entries that has not been
+ * ended; it stays begun), copied from the batch's DEVICE block exactly as the solve's first kernel reads
+ * them: tree_off [sum (n_trees[k] + 1)] (every node's offsets start at 0), leaf_taxon / adj_depth / adj_val
+ * [sum of the nodes' leaves], tree_w [sum n_trees[k]].  Any pointer may be null.  Waits for the batch.  What
+ * scs_small_solve_begin_forest and _level pack on the device is held against the host's packing with it. */
+int scs_debug_small_inputs(scs_ctx *ctx, int32_t ticket, int32_t *tree_off, int32_t *leaf_taxon,
+                           int32_t *adj_depth, double *adj_val, double *tree_w);
+
+/* The five device arrays of a tables handle to the host -- tree_off [n_trees + 1], leaf_taxon / adj_depth /
+ * adj_val [n_leaves], tree_w [n_trees]; any pointer may be null -- and info = {n_taxa, n_trees, n_leaves,
+ * max_leaves} (may be null; a first call with null arrays gives the sizes).  Waits for an upload that is
+ * still on its way.  What scs_tables_from_forest and _from_forest_range leave in a handle is read with it. */
+int scs_debug_tables_download(scs_ctx *ctx, const scs_tables *tables, int64_t *tree_off, int32_t *leaf_taxon,
+                              int32_t *adj_depth, double *adj_val, double *tree_w, int64_t *info);
+
 /* The stop / renew / confirm rules of scs_fiedler's loop (csrc/scs_policy.h; what stands in for ARPACK's
  * tol = 0 behind scs.py:252) on a scripted sequence of residuals, no device involved: actions_out[i] = 0 go
  * on, 1 stop for the confirmation (the next residual of the script is the one measured through W), 2 renew

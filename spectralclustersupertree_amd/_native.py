@@ -190,6 +190,8 @@ SIGNATURES = {
                                         C.POINTER(C.c_int32)]),
     "scs_small_solve_begin_forest": (C.c_int, [_P, _P, _IP, _I32, _I32, _IP, _I32, _P]),
     "scs_small_solve_end": (C.c_int, [_P, _I32, _DP, _DP, _DP]),
+    "scs_debug_small_inputs": (C.c_int, [_P, _I32, _IP, _IP, _IP, _DP, _DP]),
+    "scs_debug_tables_download": (C.c_int, [_P, _P, _LP, _IP, _IP, _DP, _DP, _LP]),
     "scs_debug_loop_policy": (C.c_int, [C.c_double, _I32, C.c_double, C.c_double, _I32, _I32, _DP, _IP]),
     "scs_debug_jacobi": (C.c_int, [_P, _DP, _I32, _DP, _DP]),
     "scs_debug_gram": (C.c_int, [_P, _DP, _DP, _I32, _I32, _I32, _I32, _DP]),

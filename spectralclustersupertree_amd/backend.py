@@ -408,7 +408,10 @@ class Device:
                 nv.check(self._lib.scs_small_solve_begin_forest(
                     self._ctx, forest._h, nv.iptr(rl) if rl is not None else None, int(tables.n_taxa), len(gs) - 1,
                     nv.iptr(gs), int(want_w), C.byref(ticket)))
-                return SmallTicket(self, ticket.value, np.asarray([len(gs) - 1], dtype=np.int32), want_w, list(nodes))
+                return SmallTicket(self, ticket.value, np.asarray([len(gs) - 1], dtype=np.int32), want_w, list(nodes),
+                                   # (a slice does not know its leaf count here: no counts, no read-back)
+                                   None if getattr(forest, "_base", None) is not None
+                                   else (forest.n_trees + 1, forest.n_leaves, forest.n_trees))
         n_taxa = np.empty(k, dtype=np.int32)
         n_trees = np.empty(k, dtype=np.int32)
         n_groups = np.empty(k, dtype=np.int32)
@@ -439,13 +442,14 @@ class Device:
             self._ctx, k, nv.iptr(n_taxa), nv.iptr(n_trees), nv.iptr(n_groups), nv.iptr(toff_a),
             nv.iptr(lt_a), nv.iptr(ad_a), nv.dptr(av_a), nv.dptr(tw_a), nv.iptr(gs_a), int(want_w),
             C.byref(ticket)))
-        return SmallTicket(self, ticket.value, n_groups, want_w, list(nodes))
+        return SmallTicket(self, ticket.value, n_groups, want_w, list(nodes), (len(toff_a), len(lt_a), len(tw_a)))
 
     def small_solve_begin_level(self, forest: "DeviceForest", t_begin, n_trees, n_leaves, u_base, u_size, relabel,
-                                n_taxa, n_groups, group_start) -> "SmallTicket":
+                                n_taxa, n_groups, group_start, want_w: bool = False) -> "SmallTicket":
         """``scs_small_solve_begin_level``: the K small nodes of one level of the recursion from the level
         forest's resident tables (``levels.Engine``; reference: scs.py:110-134 for every node of the level).
-        All arguments are arrays over the K nodes (``relabel`` / ``group_start`` concatenated)."""
+        All arguments are arrays over the K nodes (``relabel`` / ``group_start`` concatenated).  ``want_w``: the
+        ticket's ``result()`` carries every node's contracted W as well."""
         k = len(t_begin)
         as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
         t_begin, n_trees, u_base, u_size = as32(t_begin), as32(n_trees), as32(u_base), as32(u_size)
@@ -454,9 +458,22 @@ class Device:
         ticket = C.c_int32(-1)
         nv.check(self._lib.scs_small_solve_begin_level(
             self._ctx, forest._h, k, nv.iptr(t_begin), nv.iptr(n_trees), nv.lptr(n_leaves), nv.iptr(u_base),
-            nv.iptr(u_size), nv.iptr(relabel), nv.iptr(n_taxa), nv.iptr(n_groups), nv.iptr(group_start), 0,
+            nv.iptr(u_size), nv.iptr(relabel), nv.iptr(n_taxa), nv.iptr(n_groups), nv.iptr(group_start), int(want_w),
             C.byref(ticket)))
-        return SmallTicket(self, ticket.value, n_groups, False, None)
+        return SmallTicket(self, ticket.value, n_groups, bool(want_w), None,
+                           (int(n_trees.sum()) + k, int(n_leaves.sum()), int(n_trees.sum())))
+
+    def debug_small_inputs(self, ticket: int, n_toff: int, n_leaf: int, n_tree: int):
+        """``scs_debug_small_inputs`` of the begun batch ``ticket`` (``SmallTicket.debug_inputs``, which knows the
+        counts: the library copies what the batch holds, whatever the buffers here are sized for)."""
+        tree_off = np.full(int(n_toff), -1, dtype=np.int32)
+        leaf_taxon = np.full(int(n_leaf), -1, dtype=np.int32)
+        adj_depth = np.full(int(n_leaf), -1, dtype=np.int32)
+        adj_val = np.full(int(n_leaf), np.nan)
+        tree_w = np.full(int(n_tree), np.nan)
+        nv.check(self._lib.scs_debug_small_inputs(self._ctx, int(ticket), nv.iptr(tree_off), nv.iptr(leaf_taxon),
+                                                  nv.iptr(adj_depth), nv.dptr(adj_val), nv.dptr(tree_w)))
+        return tree_off, leaf_taxon, adj_depth, adj_val, tree_w
 
     def upload_range(self, forest: "DeviceForest", t_begin: int, t_end: int, u_base: int, u_size: int,
                      relabel: np.ndarray, n_taxa: int, monotone: bool) -> "DeviceTables":
@@ -974,9 +991,10 @@ class SmallTicket:
     """An ``scs_small_solve_begin`` that has not been ended: ``result()`` waits and returns one
     ``(maps, lambdas[, W])`` per node (once; kept).  Dropped unasked-for, it releases its slot."""
 
-    def __init__(self, dev: Device, ticket: int, n_groups: np.ndarray, want_w: bool, nodes=None) -> None:
+    def __init__(self, dev: Device, ticket: int, n_groups: np.ndarray, want_w: bool, nodes=None, counts=None) -> None:
         self.dev, self._ticket, self._n_groups, self._want_w = dev, ticket, n_groups, want_w
         self._nodes = nodes
+        self._counts = counts  # (offset entries, leaves, trees) of the batch's packed input arrays
         self._out = None
 
     def _general_path(self, i: int):
@@ -1007,6 +1025,15 @@ class SmallTicket:
             raise RuntimeError(msg)
         finally:
             graph.free()
+
+    def debug_inputs(self):
+        """``scs_debug_small_inputs``: ``(tree_off, leaf_taxon, adj_depth, adj_val, tree_w)`` of this batch as its
+        first kernel reads them from the device block -- trees + 1 over the nodes, leaves, leaves, leaves and trees
+        entries, the counts the batch was begun with.  Waits for the batch; the ticket stays begun."""
+        if self._counts is None:
+            msg = "this batch's array sizes are not known here"
+            raise ValueError(msg)
+        return self.dev.debug_small_inputs(self._ticket, *self._counts)
 
     def raw(self):
         """Waits and returns ``(maps [sum n_groups, 2], lambdas [K, 3])``, nothing re-solved: a node whose one-sided
@@ -1087,6 +1114,25 @@ class DeviceTables:
             self.free()
         except Exception:  # noqa: BLE001
             pass
+
+    def debug_download(self):
+        """``scs_debug_tables_download``: ``(tree_off, leaf_taxon, adj_depth, adj_val, tree_w, info)`` -- host copies
+        of the handle's five device arrays, ``info`` = ``{n_taxa, n_trees, n_leaves, max_leaves}`` as the handle
+        holds them."""
+        four = np.zeros(4, dtype=np.int64)
+        nv.check(self.dev._lib.scs_debug_tables_download(self.dev._ctx, self._h, None, None, None, None, None,
+                                                         nv.lptr(four)))
+        m, l = int(four[1]), int(four[2])
+        tree_off = np.full(m + 1, -1, dtype=np.int64)
+        leaf_taxon = np.full(l, -1, dtype=np.int32)
+        adj_depth = np.full(l, -1, dtype=np.int32)
+        adj_val = np.full(l, np.nan)
+        tree_w = np.full(m, np.nan)
+        nv.check(self.dev._lib.scs_debug_tables_download(self.dev._ctx, self._h, nv.lptr(tree_off), nv.iptr(leaf_taxon),
+                                                         nv.iptr(adj_depth), nv.dptr(adj_val), nv.dptr(tree_w),
+                                                         nv.lptr(four)))
+        info = dict(zip(("n_taxa", "n_trees", "n_leaves", "max_leaves"), (int(x) for x in four)))
+        return tree_off, leaf_taxon, adj_depth, adj_val, tree_w, info
 
     def build(self, row_begin: int = 0, row_end: int | None = None,
               shared: bool | None = None, upper: bool = False, scatter: bool = False) -> "DeviceGraph":

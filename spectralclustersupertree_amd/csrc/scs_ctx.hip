@@ -1130,6 +1130,30 @@ extern "C" int scs_tables_from_forest_range(scs_ctx *ctx, const scs_forest *f, i
     return SCS_OK;
 }
 
+// The five device arrays of a tables handle to the host (n_trees + 1, n_leaves, n_leaves, n_leaves and n_trees
+// entries; any pointer may be null), whichever entry made the handle; info = {n_taxa, n_trees, n_leaves,
+// max_leaves}.  A first call with null arrays gives the sizes.
+extern "C" int scs_debug_tables_download(scs_ctx *ctx, const scs_tables *t, int64_t *tree_off, int32_t *leaf_taxon,
+                                         int32_t *adj_depth, double *adj_val, double *tree_w, int64_t *info) {
+    SCS_REQUIRE(ctx && t, "scs_debug_tables_download: null argument");
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    SCS_TRY(scs_tables_finish(ctx, t));
+    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const size_t m = (size_t)t->n_trees, l = (size_t)t->n_leaves;
+    if (tree_off) SCS_HIP_CHECK(hipMemcpy(tree_off, t->d_tree_off, (m + 1) * 8, hipMemcpyDeviceToHost));
+    if (leaf_taxon && l) SCS_HIP_CHECK(hipMemcpy(leaf_taxon, t->d_leaf_taxon, l * 4, hipMemcpyDeviceToHost));
+    if (adj_depth && l) SCS_HIP_CHECK(hipMemcpy(adj_depth, t->d_adj_depth, l * 4, hipMemcpyDeviceToHost));
+    if (adj_val && l) SCS_HIP_CHECK(hipMemcpy(adj_val, t->d_adj_val, l * 8, hipMemcpyDeviceToHost));
+    if (tree_w && m) SCS_HIP_CHECK(hipMemcpy(tree_w, t->d_tree_w, m * 8, hipMemcpyDeviceToHost));
+    if (info) {
+        info[0] = t->n_taxa;
+        info[1] = t->n_trees;
+        info[2] = t->n_leaves;
+        info[3] = t->max_leaves;
+    }
+    return SCS_OK;
+}
+
 extern "C" int scs_tables_upload(scs_ctx *ctx, int32_t n_taxa, int32_t n_trees,
                                  const int64_t *tree_off, const int32_t *leaf_taxon,
                                  const int32_t *adj_depth, const double *adj_val,

@@ -3903,7 +3903,37 @@ static int small_solve_begin_impl(scs_ctx *ctx, int32_t n_nodes, const int32_t *
     slot.lam_bytes = (size_t)K * 24;
     slot.o_w = o_w;
     slot.w_bytes = w_out ? (size_t)w_ptr[K] * 8 : 0;
+    slot.o_to = o_to;
+    slot.o_lt = o_lt;
+    slot.o_ad = o_ad;
+    slot.o_av = o_av;
+    slot.o_tw = o_tw;
+    slot.n_toff = n_toff;
+    slot.n_leaf = n_leaf;
+    slot.n_tree = n_tree;
     *ticket_out = pick;
+    return SCS_OK;
+}
+
+// The packed input arrays of a begun batch, copied from the slot's DEVICE block as k_small_addends reads them
+// (n_toff, n_leaf, n_leaf, n_leaf and n_tree entries; any pointer may be null) -- whichever entry began the
+// batch: packed on the host, by k_small_pack or by k_small_pack_level.  The ticket stays begun.
+extern "C" int scs_debug_small_inputs(scs_ctx *ctx, int32_t ticket, int32_t *tree_off, int32_t *leaf_taxon,
+                                      int32_t *adj_depth, double *adj_val, double *tree_w) {
+    SCS_REQUIRE(ctx != nullptr, "scs_debug_small_inputs: null context");
+    SCS_REQUIRE(ticket >= 0 && (size_t)ticket < ctx->small_slots.size() && ctx->small_slots[ticket].busy,
+                "scs_small_solve_end: no such ticket (%d)", ticket);
+    SCS_HIP_CHECK(hipSetDevice(ctx->device));
+    const scs_ctx::small_slot &slot = ctx->small_slots[ticket];
+    // (the batch's kernels and its copy back have run: nothing of the slot's is in flight behind the event)
+    SCS_HIP_CHECK(hipEventSynchronize(slot.done));
+    const unsigned char *d = slot.dev;
+    const size_t nl = (size_t)slot.n_leaf;
+    if (tree_off && slot.n_toff) SCS_HIP_CHECK(hipMemcpy(tree_off, d + slot.o_to, (size_t)slot.n_toff * 4, hipMemcpyDeviceToHost));
+    if (leaf_taxon && nl) SCS_HIP_CHECK(hipMemcpy(leaf_taxon, d + slot.o_lt, nl * 4, hipMemcpyDeviceToHost));
+    if (adj_depth && nl) SCS_HIP_CHECK(hipMemcpy(adj_depth, d + slot.o_ad, nl * 4, hipMemcpyDeviceToHost));
+    if (adj_val && nl) SCS_HIP_CHECK(hipMemcpy(adj_val, d + slot.o_av, nl * 8, hipMemcpyDeviceToHost));
+    if (tree_w && slot.n_tree) SCS_HIP_CHECK(hipMemcpy(tree_w, d + slot.o_tw, (size_t)slot.n_tree * 8, hipMemcpyDeviceToHost));
     return SCS_OK;
 }
 

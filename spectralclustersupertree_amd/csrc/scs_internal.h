@@ -178,6 +178,10 @@ struct scs_ctx {
         hipEvent_t done = nullptr;
         bool busy = false;
         size_t o_maps = 0, maps_bytes = 0, o_lam = 0, lam_bytes = 0, o_w = 0, w_bytes = 0;
+        // where the batch's packed input arrays sit in the device block and how long they are
+        // (scs_debug_small_inputs reads them back as k_small_addends reads them)
+        size_t o_to = 0, o_lt = 0, o_ad = 0, o_av = 0, o_tw = 0;
+        int64_t n_toff = 0, n_leaf = 0, n_tree = 0;
         // the batch's device scratch (addends, uncontracted weights): owned by the slot until the
         // ticket is ended -- the batch runs on small_stream, beside whatever the main stream does
         unsigned char *scratch = nullptr;
