@@ -2843,20 +2843,36 @@ extern "C" int scs_fiedler(scs_ctx *ctx, scs_graph *g, const double *x_init, dou
             sv.use32 = false;  // the confirmation, and whatever follows it, through W
             // confirm against a freshly applied operator (AX drifts by linear updates)
             if (policy.begin_confirmation()) {
-                SCS_TRY(sv.apply(Q, 0, AQ, 0));
-                SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
-                // (the kernel leaves the P slots dead: the search directions restart after the refresh)
-                k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
-                SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
-                k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
-                k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
-                SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
-                SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8,
-                                             hipMemcpyDeviceToHost, s));
-                SCS_HIP_CHECK(hipStreamSynchronize(s));
                 double w2 = 0.0;
-                for (int j = 0; j < want; ++j) w2 = std::max(w2, std::sqrt(h_rn[j]));
-                for (int j = 0; j < want; ++j) final_res[constrained ? 1 : j] = std::sqrt(h_rn[j]);
+                auto measure = [&]() -> int {
+                    SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
+                    // (the kernel leaves the P slots dead: the search directions restart after the refresh)
+                    k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
+                    SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
+                    k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
+                    k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
+                    SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
+                    SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8,
+                                                 hipMemcpyDeviceToHost, s));
+                    SCS_HIP_CHECK(hipStreamSynchronize(s));
+                    w2 = 0.0;
+                    for (int j = 0; j < want; ++j) w2 = std::max(w2, std::sqrt(h_rn[j]));
+                    for (int j = 0; j < want; ++j) final_res[constrained ? 1 : j] = std::sqrt(h_rn[j]);
+                    return SCS_OK;
+                };
+                SCS_TRY(sv.apply(Q, 0, AQ, 0));
+                SCS_TRY(measure());
+                if (!(w2 <= tol)) {
+                    // X is carried by linear updates and never normalised again: after hundreds of iterations
+                    // ||x||^2 = 1 + 2 eps, the Ritz value x^T S x is off by 2 eps lambda, and no residual
+                    // S x - theta x can fall below that error however good x is (the path on 257 vertices:
+                    // theta off by 2.4e-13 / 1.8e-13 / 7.3e-13 at widths 4 / 8 / 16, the residuals flat at
+                    // exactly those values).  So a confirmation that misses the target
+                    // orthonormalises X, takes the fresh S X through the same transform (no further
+                    // application) and measures once more.
+                    SCS_TRY(svqb(X, AX, MASK));
+                    SCS_TRY(measure());
+                }
                 bool conv = false;
                 if (policy.confirm(w2, &conv)) {
                     converged = conv;

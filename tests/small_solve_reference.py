@@ -91,8 +91,13 @@ def _sign_ok(col: np.ndarray) -> bool:
     return len(col) > 1 and mags[order[0]] - mags[order[1]] <= TIE_REL * mags[order[0]]
 
 
-def node_errors(w: np.ndarray, maps: np.ndarray, lam: np.ndarray) -> dict:
-    """The figures ``check_node`` judges: finite, norm, orth, residual, lambda, tail, sign."""
+def node_errors(w: np.ndarray, maps: np.ndarray, lam: np.ndarray, exact: int = 3) -> dict:
+    """The figures ``check_node`` judges: finite, norm, orth, residual, lambda, tail, sign.  ``exact``: how many
+    leading entries of ``lam`` are eigenvalues (3: the dense solves).  With 2 (the iterative per-graph solve,
+    ``fiedler_reference``) ``lam[2]`` is an unconverged Ritz value of a block orthogonal to what has converged: by
+    Cauchy interlacing at most lambda_3, and at most ``lam[1]`` (the Ritz values come in order); ``lambda_next`` is
+    how far it exceeds either, and it has no lower bar."""
+    assert exact in (2, 3), exact
     v = w.shape[0]
     maps = np.asarray(maps, dtype=np.float64)
     lam = np.asarray(lam, dtype=np.float64)
@@ -106,21 +111,28 @@ def node_errors(w: np.ndarray, maps: np.ndarray, lam: np.ndarray) -> dict:
     out["orth"] = float(abs((x[:, 0] * x[:, 1]).sum()))
     out["residual"] = float(max(np.max(np.abs(s @ x[:, c] - LD(lam[c]) * x[:, c])) for c in range(2)))
     ev = np.linalg.eigvalsh(s.astype(np.float64))[::-1]
-    k = min(3, v)
+    k = min(exact, v)
     out["lambda"] = float(np.max(np.abs(lam[:k] - ev[:k])))
+    if exact == 2 and v > 2:
+        out["lambda_next"] = float(max(lam[2] - ev[2], lam[2] - lam[1]))
     out["tail"] = bool(np.all(lam[v:] == 0))
     out["sign"] = bool(_sign_ok(maps[:, 0]) and _sign_ok(maps[:, 1]))
     return out
 
 
-def check_node(w: np.ndarray, maps: np.ndarray, lam: np.ndarray) -> dict:
-    """Holds one node's ``(maps, lambda)`` to the reference of its W, whatever its spectrum; returns the figures."""
-    e = node_errors(w, maps, lam)
+def check_node(w: np.ndarray, maps: np.ndarray, lam: np.ndarray, exact: int = 3) -> dict:
+    """Holds one node's ``(maps, lambda)`` to the reference of its W, whatever its spectrum; returns the figures.
+    ``exact``: see ``node_errors``."""
+    e = node_errors(w, maps, lam, exact)
     assert e["finite"], f"non-finite output: maps {maps!r} lambda {lam!r}"
     assert e["norm"] <= ORTH_BAR, f"| ||x_c|| - 1 | = {e['norm']:.3e} > {ORTH_BAR}"
     assert e["orth"] <= ORTH_BAR, f"|x_0^T x_1| = {e['orth']:.3e} > {ORTH_BAR}"
     assert e["residual"] <= RESIDUAL_BAR, f"max|S x - lambda x| = {e['residual']:.3e} > {RESIDUAL_BAR}"
     assert e["lambda"] <= LAMBDA_BAR, f"|lambda - LAPACK| = {e['lambda']:.3e} > {LAMBDA_BAR} ({lam!r})"
+    if "lambda_next" in e:
+        # (against lambda_3 with the eigenvalue bar; against lam[1] exactly: both are the solver's own numbers)
+        assert e["lambda_next"] <= LAMBDA_BAR and lam[2] <= lam[1], (
+            f"lambda_next {lam[2]!r} above lambda_3 + {LAMBDA_BAR} or above lambda[1] {lam[1]!r}")
     assert e["tail"], f"lambda beyond the vertex count is not 0: {lam!r}"
     assert e["sign"], "the entry of largest magnitude of a column is negative (and no tie)"
     return e
@@ -371,14 +383,16 @@ def two_squares():
 PATH_TAXA = (3, 8, 64, 65, 128)
 
 
+def path_tables(n: int):
+    """The path t0 - t1 - ... - t(n-1): one two-leaf tree an edge, weight 1 under strategy ``one``."""
+    names = _names(n)
+    trees = [_unary(TreeNode("", [_leaf(names[i]), _leaf(names[i + 1])], 1.0, 100.0)) for i in range(n - 1)]
+    return fl.flatten_trees(trees, [1.0] * (n - 1), "one", names)
+
+
 @functools.lru_cache(maxsize=None)
 def path():
-    out = []
-    for n in PATH_TAXA:
-        names = _names(n)
-        trees = [_unary(TreeNode("", [_leaf(names[i]), _leaf(names[i + 1])], 1.0, 100.0)) for i in range(n - 1)]
-        out.append((f"path-n{n}", fl.flatten_trees(trees, [1.0] * (n - 1), "one", names), None, True))
-    return out
+    return [(f"path-n{n}", path_tables(n), None, True) for n in PATH_TAXA]
 
 
 ISOLATED_TAXA = (40, 64, 65, 128)
@@ -413,20 +427,21 @@ def isolated():
 TWO_COMPONENT_TAXA = (10, 64, 90)
 
 
+def two_component_tables(n: int):
+    """Two groups of n / 2 - 1 and n / 2 + 1 taxa that no tree joins: two random trees over either."""
+    rng = random.Random(7 * n)
+    names = _names(n)
+    half = n // 2 - 1
+    trees = []
+    for side in (names[:half], names[half:], names[:half], names[half:]):
+        leaves = [_leaf(x, rng.expovariate(10.0)) for x in side]
+        trees.append(_unary(_join(rng, leaves, lambda: rng.expovariate(10.0))))
+    return fl.flatten_trees(trees, [1.0, 1.5, 0.75, 2.0], "branch", names)
+
+
 @functools.lru_cache(maxsize=None)
 def two_components():
-    out = []
-    for n in TWO_COMPONENT_TAXA:
-        rng = random.Random(7 * n)
-        names = _names(n)
-        half = n // 2 - 1
-        trees = []
-        for side in (names[:half], names[half:], names[:half], names[half:]):
-            leaves = [_leaf(x, rng.expovariate(10.0)) for x in side]
-            trees.append(_unary(_join(rng, leaves, lambda: rng.expovariate(10.0))))
-        out.append((f"two_components-n{n}", fl.flatten_trees(trees, [1.0, 1.5, 0.75, 2.0], "branch", names), None,
-                    False))
-    return out
+    return [(f"two_components-n{n}", two_component_tables(n), None, False) for n in TWO_COMPONENT_TAXA]
 
 
 SCALES = (1e150, 1e-150)

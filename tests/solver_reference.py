@@ -259,3 +259,44 @@ def jacobi_errors(a: np.ndarray, w: np.ndarray, v: np.ndarray, normalise: bool):
     scale = max(1.0, float(np.abs(w_ref).max()))
     return (float(np.max(np.abs(w - w_ref))), float(np.max(np.abs(a @ v - v * w))),
             float(np.max(np.abs(v.T @ v - np.eye(len(w))))), scale)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# a whole solve: the reported residual against the extended-precision operator
+# ---------------------------------------------------------------------------------------------------------------
+def check_against_reference(w, dinv, maps, stats, case: str, image: bool = False):
+    """The residual norms ``scs_fiedler`` reports against S x - lambda x in extended precision, formed on the host
+    from the downloaded W and the returned pair.  With x = maps / d^-1/2 scaled to unit length the two differ by at most
+
+    * the budget of one application, ``(2 V + 16) u (|S| |x|)`` entrywise (``apply_reference``), 2-norm;
+    * what recovering x from the embedding adds: every entry carries the device's d^-1/2 (relative error
+      (V / 2 + 4) u, the same terms the apply budget counts) and one product, and ``||S - lambda|| <= 2``:
+      ``(V + 8) u``;
+    * the residual norm itself, a Gram product over V rows: ``(V + 2) u`` relative;
+    * the rotation that closes start-up and confirmation (``X <- X T``, ``S X <- (S X) T``, sums of b + 1 terms,
+      b <= 8, on both sides): ``4 (b + 3) u <= 44 u``.
+
+    ``image``: the product the report rests on streamed the single-precision image (start-up of the image loop; a
+    confirmed solve always reports through W), so the reference multiplies the image's entries, as ``apply_reference``
+    provides."""
+    v = w.shape[0]
+    assert np.isfinite(maps).all() and np.isfinite(stats["lambda"]).all() and np.isfinite(stats["resid"]).all(), case
+    cols = (1,) if stats["used_constraint"] else (0, 1)
+    x = maps[:, cols].astype(LD) / dinv[:, None]
+    norm = np.sqrt((x * x).sum(axis=0))
+    assert (norm > 0).all(), case
+    x64 = (x / norm).astype(np.float64)  # (what the reference is given; its own rounding, u, is inside 44 u)
+    sx, budget = apply_reference(w, x64, w_op=image_model(w) if image else None)
+    b = stats["block"]
+    for k, col in enumerate(cols):
+        lam = LD(stats["lambda"][col])
+        r = sx[:, k] - lam * x64[:, k].astype(LD)
+        want = float(np.sqrt((r * r).sum()))
+        got = float(stats["resid"][col])
+        slack = (float(np.sqrt((budget[:, k] ** 2).sum())) + (v + 8) * U + (v + 2) * U * max(got, want)
+                 + 4 * (b + 3) * U)
+        print(f"[chain] {case} column {col}: reported {got:.3e}, reference {want:.3e}, slack {slack:.3e}, "
+              f"{stats['iterations']} iterations")
+        assert abs(got - want) <= slack, (f"{case} column {col}: reported {got:.6e}, reference {want:.6e}, "
+                                          f"slack {slack:.3e}")
+    return cols

@@ -88,31 +88,7 @@ def _solve(g, monkeypatch, env=None, **kw):
     return maps, stats
 
 
-def _check_against_reference(w, dinv, maps, stats, case: str, image: bool = False):
-    """The reported residual norms against S x - lambda x in extended precision (module docstring).  ``image``: the
-    product the report rests on streamed the single-precision image (start-up of the image loop; a confirmed solve
-    always reports through W), so the reference multiplies the image's entries, as ``apply_reference`` provides."""
-    v = w.shape[0]
-    assert np.isfinite(maps).all() and np.isfinite(stats["lambda"]).all() and np.isfinite(stats["resid"]).all(), case
-    cols = (1,) if stats["used_constraint"] else (0, 1)
-    x = maps[:, cols].astype(ref.LD) / dinv[:, None]
-    norm = np.sqrt((x * x).sum(axis=0))
-    assert (norm > 0).all(), case
-    x64 = (x / norm).astype(np.float64)  # (what the reference is given; its own rounding, u, is inside 44 u)
-    sx, budget = ref.apply_reference(w, x64, w_op=ref.image_model(w) if image else None)
-    b = stats["block"]
-    for k, col in enumerate(cols):
-        lam = ref.LD(stats["lambda"][col])
-        r = sx[:, k] - lam * x64[:, k].astype(ref.LD)
-        want = float(np.sqrt((r * r).sum()))
-        got = float(stats["resid"][col])
-        slack = (float(np.sqrt((budget[:, k] ** 2).sum())) + (v + 8) * ref.U + (v + 2) * ref.U * max(got, want)
-                 + 4 * (b + 3) * ref.U)
-        print(f"[chain] {case} column {col}: reported {got:.3e}, reference {want:.3e}, slack {slack:.3e}, "
-              f"{stats['iterations']} iterations")
-        assert abs(got - want) <= slack, (f"{case} column {col}: reported {got:.6e}, reference {want:.6e}, "
-                                          f"slack {slack:.3e}")
-    return cols
+_check_against_reference = ref.check_against_reference  # (host code, shared with tests/test_gpu_fiedler_edges.py)
 
 
 def _same_pair(maps_a, stats_a, maps_b, stats_b, case: str):
