@@ -1947,6 +1947,50 @@ struct solver {
 
     double *small_at(int off) const { return small.d() + off; }
 
+    // ---- set-up.  The local part is `bind` and then alloc_symm_buffers; the team part is team_splits
+    // (COLLECTIVE: scs_fiedler and scs_debug_team_apply only) and then team_buffers.  The callers allocate
+    // their own panels and yloc in between, each in the order it always had.
+    // (`g` stays null for the exports that only reach gram / update)
+    void bind(scs_ctx *c, int n_, int b_ = 0, scs_graph *g_ = nullptr) {
+        ctx = c;
+        g = g_;
+        s = c->stream;
+        n = n_;
+        b = b_;
+        rows = g ? g->row_end - g->row_begin : 0;
+        world = c->comm.world;
+        gram_blocks = 256;
+    }
+    int team_splits() {
+        SCS_TRY(scs_gather_row_splits(ctx, g->row_begin, g->row_end, g->n, splits));
+        int max_rows = 0;
+        for (int r = 0; r < world; ++r) max_rows = std::max(max_rows, splits[r + 1] - splits[r]);
+        chunk = g->upper ? (int64_t)n * b : (int64_t)max_rows * b;  // (upper: whole partial products travel)
+        return SCS_OK;
+    }
+    // (after alloc_symm_buffers, which decides part_mode)
+    int team_buffers() {
+        if (world == 1 || part_mode) return SCS_OK;
+        SCS_TRY(yfull.alloc((size_t)n * b * 8));
+        SCS_TRY(recv.alloc((size_t)chunk * world * 8));
+        SCS_TRY(splits_d.alloc((size_t)(world + 1) * 4));
+        SCS_HIP_CHECK(hipMemcpyAsync(splits_d.p, splits.data(), (size_t)(world + 1) * 4, hipMemcpyHostToDevice, s));
+        return SCS_OK;
+    }
+
+    // Where the loop may stream the single-precision image, as far as the graph's layout and the width say:
+    // whole rows of W at width 4, either all of them on one rank (alloc_symm_buffers then picks the symmetric
+    // schedule, whose 256-column tiles -- tri_ct == 2, the only width it sets -- the image's own tile list
+    // sits behind) or a row-partitioned rank's (k_symm).  Asked before the solver is set up (the width choice
+    // and the degree pass depend on it), so it reads the graph and not the solver.  scs_fiedler adds its
+    // switches and the byte cap; the debug exports add nothing.
+    static bool image_layout(const scs_ctx *ctx, const scs_graph *g, int b) {
+        const int world = ctx->comm.world;
+        const bool one = world == 1 && !g->upper && g->row_begin == 0 && g->row_end == g->n;
+        const bool row_ranks = world > 1 && !g->upper;  // (part_mode is g->upper)
+        return !g->mf && g->n >= 4096 && b == 4 && (one || row_ranks);
+    }
+
     // the all-gather of an iteration, timed with its own event pair when fused_back times the launch
     int gather(const double *send, double *recvb, size_t count) {
         hipEvent_t a = nullptr, b = nullptr;
@@ -2185,21 +2229,29 @@ struct solver {
         return SCS_OK;
     }
 
+    // one application, counted; `timed`: between an event pair of its own (kept in `ev`, read by the statistics)
+    int timed_symm(bool timed, const double *zin, double *yout) {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (timed) {
+            SCS_TRY(new_event(&e0));
+            SCS_TRY(new_event(&e1));
+            ev.push_back(e0);
+            ev.push_back(e1);
+            ev32.push_back(use32 ? 1 : 0);
+            SCS_HIP_CHECK(hipEventRecord(e0, s));
+        }
+        SCS_TRY(launch_symm(zin, yout));
+        if (timed) SCS_HIP_CHECK(hipEventRecord(e1, s));
+        ++n_apply;
+        return SCS_OK;
+    }
+
     // dst_panel[:, c0:c0+b] = S * src_panel[:, c0s:c0s+b]   (panels have ld 3b)
     int apply(const double *src, int c0s, double *dst, int c0d) {
         const int nb = n * b;
         k_scale_rows<<<(nb + 255) / 256, 256, 0, s>>>(src, 3 * b, c0s, b, n, g->d_dinv, z.d(),
                                                       ldz);
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        SCS_TRY(new_event(&e0));
-        SCS_TRY(new_event(&e1));
-        ev.push_back(e0);
-        ev.push_back(e1);
-        ev32.push_back(use32 ? 1 : 0);
-        SCS_HIP_CHECK(hipEventRecord(e0, s));
-        SCS_TRY(launch_symm(z.d(), yloc.d()));
-        SCS_HIP_CHECK(hipEventRecord(e1, s));
-        ++n_apply;
+        SCS_TRY(timed_symm(true, z.d(), yloc.d()));
         const double *yf = yloc.d();
         if (part_mode) {
             // (launch_symm_tri gathered the ranks' partial products and yloc holds their scaled
@@ -2335,59 +2387,39 @@ struct solver {
     int fused_back(int *nparts, double *pout) {
         // k_symm is timed with HIP events on every fourth launch only: recording an event costs
         // the device a ~6 us bubble
-        hipEvent_t e0 = nullptr, e1 = nullptr;
         const bool timed = (n_apply & 3) == 0;
         time_ag = timed && world > 1;
-        if (timed) {
-            SCS_TRY(new_event(&e0));
-            SCS_TRY(new_event(&e1));
-            ev.push_back(e0);
-            ev.push_back(e1);
-            ev32.push_back(use32 ? 1 : 0);
-        }
         gram_from32 = use32;
         const int nb = fold_pass2 ? panel_blocks16() : panel_blocks4();
         const int nb16 = panel_blocks16();  // partials of pass 1's Gram products (k_panel_tf_solve)
         *nparts = nb;
-        if (part_mode) {
-            // the gathered partial products (world x V x b, unscaled) are added in rank order and
-            // scaled inside the Gram kernel
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e0, s));
-            SCS_TRY(launch_symm(z.d(), nullptr));
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e1, s));
-            ++n_apply;
-            if (fold_pass2)
-                k_panel_gram_tf_solve<B, 3><<<nb, 256, 0, s>>>(q.d(), aq.d(), fold_u, part2.d(), nb16, fold_mask_r,
-                                                               fold_theta, n, recv.d(), world, g->d_dinv, pout);
-            else
-                k_gram_qaq<B, 3><<<nb, 256, 0, s>>>(q.d(), aq.d(), n, recv.d(), world, g->d_dinv, pout);
-        } else if (world == 1) {
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e0, s));
-            SCS_TRY(launch_symm(z.d(), nullptr));
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e1, s));
-            ++n_apply;
-            if (fold_pass2)
-                k_panel_gram_tf_solve<B, 1><<<nb, 256, 0, s>>>(q.d(), aq.d(), fold_u, part2.d(), nb16, fold_mask_r,
-                                                               fold_theta, n, ypart.d(), last_nseg, g->d_dinv, pout,
-                                                               0, nullptr, overlap_pass1 ? coef1.d() : nullptr);
-            else
-                k_gram_qaq<B, 1><<<nb, 256, 0, s>>>(q.d(), aq.d(), n, ypart.d(), last_nseg,
-                                                       g->d_dinv, pout);
+        // What the Gram kernel sums into AQ's R slot (its FINISH), scaling as it goes:
+        //   3  the ranks' gathered partial products (world x V x b), added in rank order (launch_symm_tri gathers);
+        //   1  this device's column segments, left unscaled in ypart;
+        //   2  the ranks' gathered slices, scaled by launch_symm, placed by `chunk` and the row splits.
+        const int finish = part_mode ? 3 : (world == 1 ? 1 : 2);
+        SCS_TRY(timed_symm(timed, z.d(), finish == 2 ? yloc.d() : nullptr));
+        if (finish == 2) SCS_TRY(gather(yloc.d(), recv.d(), (size_t)chunk));
+        const double *seg = finish == 1 ? ypart.d() : recv.d();
+        const int nseg = finish == 1 ? last_nseg : world;
+        const int64_t ch = finish == 2 ? chunk : 0;
+        const int32_t *sp = finish == 2 ? (const int32_t *)splits_d.p : nullptr;
+        // (overlap_pass1 is a one-device loop: FINISH 1)
+#define GRAM_BACK(F_)                                                                                             \
+    if (fold_pass2)                                                                                               \
+        k_panel_gram_tf_solve<B, F_><<<nb, 256, 0, s>>>(q.d(), aq.d(), fold_u, part2.d(), nb16, fold_mask_r,      \
+                                                        fold_theta, n, seg, nseg, g->d_dinv, pout, ch, sp,        \
+                                                        overlap_pass1 ? coef1.d() : nullptr);                     \
+    else                                                                                                          \
+        k_gram_qaq<B, F_><<<nb, 256, 0, s>>>(q.d(), aq.d(), n, seg, nseg, g->d_dinv, pout, ch, sp)
+        if (finish == 3) {
+            GRAM_BACK(3);
+        } else if (finish == 1) {
+            GRAM_BACK(1);
         } else {
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e0, s));
-            SCS_TRY(launch_symm(z.d(), yloc.d()));
-            if (timed) SCS_HIP_CHECK(hipEventRecord(e1, s));
-            ++n_apply;
-            SCS_TRY(gather(yloc.d(), recv.d(), (size_t)chunk));
-            // (the gathered slices go straight into AQ's R slot inside the Gram kernel)
-            if (fold_pass2)
-                k_panel_gram_tf_solve<B, 2><<<nb, 256, 0, s>>>(q.d(), aq.d(), fold_u, part2.d(), nb16, fold_mask_r,
-                                                               fold_theta, n, recv.d(), world, g->d_dinv, pout,
-                                                               (int64_t)chunk, (const int32_t *)splits_d.p);
-            else
-                k_gram_qaq<B, 2><<<nb, 256, 0, s>>>(q.d(), aq.d(), n, recv.d(), world, g->d_dinv, pout,
-                                                    (int64_t)chunk, (const int32_t *)splits_d.p);
+            GRAM_BACK(2);
         }
+#undef GRAM_BACK
         time_ag = false;
         SCS_HIP_CHECK(hipGetLastError());
         return SCS_OK;
@@ -2421,11 +2453,480 @@ void sign_flip_and_store(const std::vector<double> &col0, const std::vector<doub
     }
 }
 
-}  // namespace
-
-static int gather_full_rows(scs_ctx *ctx, scs_graph *g, std::vector<int32_t> &splits) {
-    return scs_gather_row_splits(ctx, g->row_begin, g->row_end, g->n, splits);
+// the two readings of a probe switch (scs_dbg: unset unless SCS_DEBUG=1 at load)
+bool dbg_on(const char *name) {  // off unless set to non-zero
+    const char *e = scs_dbg(name);
+    return e && atoi(e);
 }
+bool dbg_not_off(const char *name) {  // on unless set to 0
+    const char *e = scs_dbg(name);
+    return !(e && !atoi(e));
+}
+
+// Every switch of a solve, read once (scs_fiedler makes one plan per call), and what follows from them.  The image decision
+// (made before the width is chosen) and the loop (set up after it) ask the same plan: a loop that was not built
+// for the image cannot be handed it.
+struct loop_plan {
+    // ---- mixed precision (round 5; SCS_LOWP=0 off, 1, 2 = default).  The loop applies the operator to
+    // its SEARCH DIRECTIONS only (S X and S P are carried by linear updates), and a search direction does
+    // not need S to sixteen digits: with the symmetric schedule at width 4 the SYMM streams a single-
+    // precision image of W -- half the bytes, products and sums still in double precision -- that the
+    // degree pass writes on its way through W.  What the image's rounding leaves in S X and S P is removed
+    // by renewing both through W itself (two applications) when the residual passes 1e-8, and
+    // once more should it stop halving; mode 1 goes on in double precision after the first renewal, mode 2
+    // stays with the image.  The confirmation at the end always applies W, and a solve it sends back into the loop
+    // continues without the image.
+    const int lowp_mode = getenv("SCS_LOWP") ? atoi(getenv("SCS_LOWP")) : 2;
+    // (an image above SCS_LOWP_MAX_BYTES, default 16 GiB -- about 65 000 vertices -- is not made: what it
+    // saves a solve of that size, some 80 ms, is less than what an allocation of tens of GB can cost)
+    const double lowp_max_bytes = getenv("SCS_LOWP_MAX_BYTES") ? atof(getenv("SCS_LOWP_MAX_BYTES")) : 16.0 * (1u << 30);
+    // SCS_LEGACY_LOOP=1: the one-kernel-per-step formulation at widths 4 and 8 too
+    const bool legacy_loop = dbg_on("SCS_LEGACY_LOOP");
+    // SCS_SPLIT_SMALL=1: the small solves as one-workgroup kernels of their own (the round-3 loop)
+    const bool split_small = dbg_on("SCS_SPLIT_SMALL");
+    const bool fold_pass2_on = dbg_not_off("SCS_FOLD_PASS2"), overlap_pass1_on = dbg_not_off("SCS_OVERLAP_PASS1");
+    const bool use_mfma = !dbg_on("SCS_NO_MFMA");
+
+    // Fused iteration (scs_panel.h) for the default block widths; the unfused loop is the only one for widths 12 and 16.
+    bool fused(int b) const { return (b == 4 || b == 8) && !legacy_loop; }
+    // round 5: the second orthonormalisation pass of R rides the Gram kernel behind the SYMM stream.
+    // (Only this, the default loop, hands its Rayleigh-Ritz solve the one-sided entries -- small_rr_body -- so
+    // only it is given the image.)
+    bool fold_pass2(int b) const { return fused(b) && !split_small && fold_pass2_on; }
+    // ... and the first pass rides the SYMM launch itself (k_symm_tri_tf: one device, symmetric schedule)
+    bool overlap_pass1(int b, bool tri, bool part_mode, int world) const {
+        return fold_pass2(b) && tri && !part_mode && world == 1 && overlap_pass1_on;
+    }
+};
+
+// The block width of a solve, and (want32) whether its loop will stream the image: the degree pass, begun
+// right after, then writes it.
+int choose_width(const scs_ctx *ctx, const scs_graph *g, int block, const loop_plan &plan, bool *want32) {
+    const int n = g->n;
+    // (round 6: a row-partitioned job -- whole rows on every rank, k_symm -- keeps the image of each rank's rows:
+    // the first real multi-GPU run streams per rank what the one-GPU run streams, not twice that)
+    const bool image_ok = solver::image_layout(ctx, g, 4) && plan.lowp_mode > 0 && plan.fold_pass2(4) &&
+                          (g->have_w32 ||
+                           4.0 * (double)(g->row_end - g->row_begin) * (double)g->ld <= plan.lowp_max_bytes);
+    // default width: 4 while the panel kernels and the 3b x 3b Rayleigh-Ritz solve weigh
+    // against the SYMM stream, 8 once streaming W dominates (measured crossover ~ 16k) -- unless the
+    // loop can stream the single-precision image, which exists at width 4: half the bytes an
+    // application outweigh the iterations width 8 saves (configs[3], 50 000 vertices: 48 iterations and
+    // 78 ms against 35 and 101)
+    int b = block ? block : ((n >= 16384 && !image_ok) ? 8 : 4);
+    if (g->upper && b > 8) b = 8;  // the symmetric SYMM kernel comes in widths 4 and 8
+    if (g->mf) b = std::min(b <= 4 ? 4 : 8, g->mf->b_cap);  // (the sweep kernel likewise)
+    {
+        const int allowed[] = {16, 12, 8, 4};
+        const int cap = (n - 2) / 3;  // 3b basis vectors + the constraint must fit in V
+        int pick = 4;
+        for (int a : allowed)
+            if (a <= b && a <= cap) {
+                pick = a;
+                break;
+            }
+        b = pick;  // (>= 4: more than the one or two pairs wanted)
+    }
+    *want32 = image_ok && b == 4;
+    return b;
+}
+
+// One LOBPCG solve: the solver's buffers and launches, the loop's pointers into them and what the host keeps
+// between iterations.  scs_fiedler drives it step by step; every step only enqueues, unless it says that it waits.
+struct lobpcg {
+    scs_ctx *const ctx;
+    scs_graph *const g;
+    const hipStream_t s;
+    const int n, b, q3;
+    const loop_plan &plan;
+    const bool fused;
+    solver sv;
+    scs_loop_policy policy;  // the stop / renew / confirm rules (scs_policy.h)
+    static constexpr double drop_tol = 1e-13;
+    // panel layout [X | P | R]: the blocks R is projected against are contiguous
+    double *Q = nullptr, *AQ = nullptr, *X = nullptr, *R = nullptr, *AX = nullptr;
+    double *G = nullptr, *T = nullptr, *C = nullptr, *D = nullptr, *TH = nullptr, *RN = nullptr;
+    int *MASK = nullptr;
+    bool constrained = false;
+    int want = 0;
+    const double *uvec = nullptr;
+    dbuf x0d, res_part;
+    int res_blocks = 0;
+    std::vector<double> h_rn, h_th;  // the residual norms^2 and Ritz values of the block the host last saw
+    double final_res[2] = {0.0, 0.0};
+    // fused loop: where the Gram partials go, and what the next iteration's opening Rayleigh-Ritz solve is told
+    double *qaq_out = nullptr;
+    int rr_solve = 0, rr_parts = 0, mpar = 0;
+    int *maskp[2] = {nullptr, nullptr};
+
+    lobpcg(scs_ctx *ctx_, scs_graph *g_, int b_, const loop_plan &plan_)
+        : ctx(ctx_), g(g_), s(ctx_->stream), n(g_->n), b(b_), q3(3 * b_), plan(plan_), fused(plan_.fused(b_)) {}
+
+    // the solver and every buffer of the loop but three small ones of `start`; ends by WAITING for the degrees
+    int setup(double tol, bool want32) {
+        sv.bind(ctx, n, b, g);
+        sv.use_mfma = plan.use_mfma;
+        SCS_TRY(sv.team_splits());
+        SCS_TRY(sv.q.alloc((size_t)n * q3 * 8));
+        SCS_TRY(sv.aq.alloc((size_t)n * q3 * 8));
+        SCS_TRY(sv.alloc_symm_buffers());
+        SCS_TRY(sv.yloc.alloc((size_t)sv.chunk * 8));
+        SCS_TRY(sv.u.alloc((size_t)n * 8));
+        SCS_TRY(sv.part.alloc((size_t)1024 * q3 * q3 * 8));
+        SCS_TRY(sv.part2.alloc((size_t)1024 * q3 * q3 * 8));
+        SCS_TRY(sv.part3.alloc((size_t)1024 * q3 * q3 * 8));
+        SCS_TRY(sv.small.alloc((size_t)SM_TOTAL * 8));
+        SCS_TRY(sv.team_buffers());
+        SCS_HIP_CHECK(hipMemsetAsync(sv.q.p, 0, (size_t)n * q3 * 8, s));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.aq.p, 0, (size_t)n * q3 * 8, s));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0, (size_t)sv.chunk * 8, s));
+        SCS_HIP_CHECK(hipMemsetAsync(sv.small.p, 0, (size_t)SM_TOTAL * 8, s));
+        sv.fold_pass2 = plan.fold_pass2(b);
+        sv.overlap_pass1 = plan.overlap_pass1(b, sv.tri, sv.part_mode, sv.world);
+
+        Q = sv.q.d(), AQ = sv.aq.d();
+        X = Q, R = Q + 2 * b;
+        AX = AQ;
+        G = sv.small_at(SM_G), T = sv.small_at(SM_T), C = sv.small_at(SM_C);
+        D = sv.small_at(SM_D);
+        TH = sv.small_at(SM_THETA), RN = sv.small_at(SM_RN);
+        MASK = (int *)sv.small_at(SM_MASK);
+        h_rn.resize(b);
+        h_th.resize(b + 1);
+
+        SCS_TRY(scs_graph_prepare_degrees(ctx, g));  // (begun by the caller: the degrees are needed from here on)
+        sv.use32 = want32 && g->have_w32;
+        policy.tol = tol;
+        policy.lowp_mode = plan.lowp_mode;
+        policy.lowp_tol = 1e-8;
+        policy.lowp_tol2 = 0.0;
+        policy.lowp_state = sv.use32 ? 1 : 0;  // image in use: 1 + the renewals of S X / S P made so far; 0: off
+        constrained = g->n_isolated == 0;
+        want = constrained ? 1 : 2;
+        return SCS_OK;
+    }
+
+    // project the constraint out of a panel block (`passes` times)
+    int project_u(double *Y, int passes) {
+        if (!constrained) return SCS_OK;
+        for (int pass = 0; pass < passes; ++pass) {
+            SCS_TRY(sv.gram(sv.u.d(), 1, 1, Y, q3, b, C, false));
+            SCS_TRY(sv.update(Y, q3, b, 1.0, sv.u.d(), 1, 1, C, b, -1.0));
+        }
+        return SCS_OK;
+    }
+    // SVQB-orthonormalise a panel block; the companion AY (may be null) receives the same column transform.
+    // mask handling: pass 2 would overwrite mask with all-live for surviving columns and 0
+    // for dead ones (their Gram diagonal is 0 -> dsc 0 -> eigenvalue 0 -> dropped since
+    // 0 > 0 is false), so the mask of the second pass is the final one.
+    int svqb(double *Y, double *AY, int *mask_out) {
+        for (int pass = 0; pass < 2; ++pass) {
+            SCS_TRY(sv.gram(Y, q3, b, Y, q3, b, G, sv.use_mfma));
+            k_small_svqb<<<1, 256, 0, s>>>(G, b, pass == 0 ? drop_tol : 0.0, T, mask_out);
+            // second pass: every surviving direction is kept (dead columns stay dead: dsc = 0)
+            SCS_TRY(sv.update(Y, q3, b, 0.0, Y, q3, b, T, b, 1.0));
+            if (AY) SCS_TRY(sv.update(AY, q3, b, 0.0, AY, q3, b, T, b, 1.0));
+        }
+        return SCS_OK;
+    }
+    // rotate X so that X^T A X is diagonal
+    // (masks: all live going in, no search directions coming out -- set by the kernel itself, which leaves the
+    // P slots dead; X and S X rotated in one launch)
+    int rotate_x() {
+        SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
+        k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
+        return sv.rotate2(X, AX, q3, b, T, b);
+    }
+
+    // the start block: constraint vector, init, projection, SVQB, first application, the rotating Rayleigh-Ritz
+    int start(const double *x_init) {
+        if (x_init) {
+            SCS_TRY(x0d.alloc((size_t)n * 8));
+            SCS_HIP_CHECK(hipMemcpyAsync(x0d.p, x_init, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        }
+        if (constrained)
+            k_trivial<<<(n + 255) / 256, 256, 0, s>>>(g->d_deg, 1.0 / g->dd_norm, n, sv.u.d());
+        k_init_block<<<(n * b + 255) / 256, 256, 0, s>>>(Q, b, n, x_init ? x0d.d() : nullptr);
+        SCS_TRY(project_u(X, 2));
+        SCS_TRY(svqb(X, nullptr, MASK));
+        SCS_TRY(sv.apply(Q, 0, AQ, 0));
+        SCS_TRY(rotate_x());
+
+        res_blocks = (n + 255) / 256;
+        SCS_TRY(res_part.alloc((size_t)res_blocks * b * 8));
+        if (fused) {
+            if (!ctx->h_report) {
+                SCS_HIP_CHECK(hipHostMalloc((void **)&ctx->h_report, 64 * sizeof(double),
+                                            hipHostMallocMapped | hipHostMallocCoherent));
+                SCS_HIP_CHECK(hipHostGetDevicePointer((void **)&ctx->d_report, ctx->h_report, 0));
+                memset(ctx->h_report, 0, 64 * sizeof(double));
+            }
+            k_unit_coeffs<<<(3 * b * b + 255) / 256, 256, 0, s>>>(T, D, b);
+        }
+        uvec = constrained ? sv.u.d() : nullptr;
+        if (sv.overlap_pass1) SCS_TRY(sv.coef1.alloc((size_t)(3 * 8 + 4) * 8 * 8));
+        sv.fold_u = uvec;
+        sv.fold_mask_r = MASK + 2 * b;
+        sv.fold_theta = TH;
+        qaq_out = sv.fold_pass2 ? sv.part3.d() : sv.part2.d();
+        maskp[0] = MASK + b;
+        maskp[1] = MASK + 32;
+        return SCS_OK;
+    }
+
+    template <int B>
+    int enqueue_fused_b(double seq) {
+        int nparts = 0;
+        if (!plan.split_small) {
+            // (the Rayleigh-Ritz solve on the previous iteration's Gram partials opens the
+            // first launch)
+            SCS_TRY(sv.fused_front_solve<B>(uvec, rr_parts, rr_solve, TH, maskp[mpar], MASK + 2 * b, maskp[mpar ^ 1],
+                                            drop_tol, ctx->d_report, seq));
+            SCS_TRY(sv.fused_back<B>(&nparts, qaq_out));
+            rr_parts = nparts;
+            rr_solve = 1;
+            mpar ^= 1;
+        } else {
+            SCS_TRY(sv.fused_front<B>(uvec, T, D, TH, C, MASK + 2 * b, drop_tol, ctx->d_report, seq));
+            SCS_TRY(sv.fused_back<B>(&nparts, sv.part.d()));
+            k_small_rr<<<1, 256, 0, s>>>(sv.part.d(), nparts, q3, b, MASK, T, D, TH, MASK + b, drop_tol);
+        }
+        SCS_HIP_CHECK(hipGetLastError());
+        return SCS_OK;
+    }
+    // One fused iteration, all of it enqueued before the host looks at the residual norms the
+    // first small kernel reports under `seq`: the device never waits for the host.  Nothing
+    // after that kernel touches X, so on a stop X is the block the norms belong to.
+    int enqueue_fused(double *seq) {
+        *seq = (double)(++ctx->report_seq);
+        return b == 4 ? enqueue_fused_b<4>(*seq) : enqueue_fused_b<8>(*seq);
+    }
+
+    // WAITS for the report of the iteration enqueued under `seq` (the device is already working on the rest
+    // of the iteration) and takes its norms and Ritz values; gives up if the stream died
+    int await_report(double seq, int iter) {
+        volatile double *hr = (volatile double *)ctx->h_report;
+        const auto t_wait = std::chrono::steady_clock::now();
+        unsigned spins = 0;
+        while (hr[40] != seq) {
+            __builtin_ia32_pause();
+            // (a report normally arrives within a few microseconds; a host thread that has
+            // waited much longer lets others run -- eight ranks may share the cores)
+            if (spins > (1u << 18) && (spins & 0x3FF) == 0) sched_yield();
+            if ((++spins & 0xFFFF) == 0) {
+                const hipError_t qe = hipStreamQuery(s);
+                if (qe != hipSuccess && qe != hipErrorNotReady) {
+                    scs_set_error("scs_fiedler: stream failed: %s", hipGetErrorString(qe));
+                    return SCS_EHIP;
+                }
+                if (qe == hipSuccess && hr[40] != seq) {
+                    // everything ran and the report never arrived
+                    if (std::chrono::steady_clock::now() - t_wait > std::chrono::seconds(5)) {
+                        scs_set_error("scs_fiedler: residual report lost at iteration %d", iter);
+                        return SCS_EHIP;
+                    }
+                }
+            }
+        }
+        for (int j = 0; j < b; ++j) h_rn[j] = hr[j];
+        for (int j = 0; j <= b; ++j) h_th[j] = hr[16 + j];
+        return SCS_OK;
+    }
+
+    // the residual block of X and its norms, read back (WAITS): an unfused iteration's front, and the confirmation's measurement
+    int read_residual() {
+        k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
+        k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
+        SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
+        SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8, hipMemcpyDeviceToHost, s));
+        SCS_HIP_CHECK(hipStreamSynchronize(s));
+        return SCS_OK;
+    }
+    // the worst residual of the wanted columns in h_rn; they are what the solve reports should it end here
+    double worst_residual() {
+        double worst = 0.0;
+        for (int j = 0; j < want; ++j) worst = std::max(worst, std::sqrt(h_rn[j]));
+        for (int j = 0; j < want; ++j) final_res[constrained ? 1 : j] = std::sqrt(h_rn[j]);
+        return worst;
+    }
+
+    // the back of an unfused iteration: projection, SVQB, application, Rayleigh-Ritz
+    int unfused_back() {
+        // R <- orthonormal complement of [u, X, P] within span(R); P is orthonormal and
+        // orthogonal to X by construction (k_small_rr), dead P columns are zero vectors
+        // S u = u exactly, so R = S X - X theta inherits X's orthogonality to u; one
+        // pass keeps rounding drift from accumulating
+        SCS_TRY(project_u(R, 1));
+        for (int pass = 0; pass < 2; ++pass) {
+            SCS_TRY(sv.gram(Q, q3, 2 * b, R, q3, b, C, sv.use_mfma));
+            SCS_TRY(sv.update(R, q3, b, 1.0, Q, q3, 2 * b, C, b, -1.0));
+        }
+        SCS_TRY(svqb(R, nullptr, MASK + 2 * b));
+        SCS_TRY(sv.apply(Q, 2 * b, AQ, 2 * b));
+
+        // Rayleigh-Ritz on the orthonormal basis [X P R]; new X and new P in one pass each
+        SCS_TRY(sv.gram(Q, q3, q3, AQ, q3, q3, G, sv.use_mfma));
+        k_small_rr<<<1, 256, 0, s>>>(G, 0, q3, b, MASK, T, D, TH, MASK + b, drop_tol);
+        k_rr_update<<<(n + 15) / 16, 256, 0, s>>>(Q, b, q3, T, D, n);
+        k_rr_update<<<(n + 15) / 16, 256, 0, s>>>(AQ, b, q3, T, D, n);
+        SCS_HIP_CHECK(hipGetLastError());
+        return SCS_OK;
+    }
+
+    // S X and S P anew through W itself, behind the iteration already enqueued (its Gram matrix,
+    // formed with the old products, steers one more Rayleigh-Ritz step: coefficients only).
+    // What the image adds to S X afterwards is its rounding (~1e-10 ||S||) times the steps still
+    // to be taken, which are of the size of the residual over the spectral gap: one renewal clears
+    // what the long early steps left (measured: without it 15 more iterations); a second one is
+    // made when the residual stops halving (four iterations) (a second threshold on the residual itself exists and is off).
+    // After the FIRST renewal a loop that has not halved its residual in eight iterations stops for the
+    // confirmation (the image's rounding has become the floor); before it LOBPCG has plateaus of its own
+    // -- ten iterations at 4e-5 on the `bootstrap` workload -- five orders above the image's rounding.
+    int renew() {
+        sv.use32 = false;
+        SCS_TRY(sv.apply(Q, 0, AQ, 0));
+        SCS_TRY(sv.apply(Q, b, AQ, b));
+        sv.use32 = policy.image_in_use();
+        return SCS_OK;
+    }
+
+    // The confirmation: the residual of X against a freshly applied operator (AX drifts by linear updates),
+    // into *w2 (WAITS).  The search directions are dead afterwards: a loop that goes on calls restart_directions.
+    int confirm(double tol, double *w2) {
+        sv.use32 = false;  // the confirmation, and whatever follows it, through W
+        SCS_TRY(sv.apply(Q, 0, AQ, 0));
+        SCS_TRY(rotate_x());
+        SCS_TRY(read_residual());
+        *w2 = worst_residual();
+        if (!(*w2 <= tol)) {
+            // X is carried by linear updates and never normalised again: after hundreds of iterations
+            // ||x||^2 = 1 + 2 eps, the Ritz value x^T S x is off by 2 eps lambda, and no residual
+            // S x - theta x can fall below that error however good x is (the path on 257 vertices:
+            // theta off by 2.4e-13 / 1.8e-13 / 7.3e-13 at widths 4 / 8 / 16, the residuals flat at
+            // exactly those values).  So a confirmation that misses the target
+            // orthonormalises X, takes the fresh S X through the same transform (no further
+            // application) and measures once more.
+            SCS_TRY(svqb(X, AX, MASK));
+            SCS_TRY(rotate_x());
+            SCS_TRY(read_residual());
+            *w2 = worst_residual();
+        }
+        return SCS_OK;
+    }
+    int restart_directions() {
+        if (fused) k_unit_coeffs<<<(3 * b * b + 255) / 256, 256, 0, s>>>(T, D, b);
+        rr_solve = 0;
+        return SCS_OK;
+    }
+
+    // the two wanted columns, scaled, from the device (not the whole panel), sign-fixed into maps_out, and the
+    // Ritz values into st; records ev_b behind the solve's last copy and WAITS
+    int extract(hipEvent_t ev_b, double *maps_out, scs_stats *st) {
+        // what an event pair around a launch adds to the launch's own time on this stream (the pair's two records
+        // back to back, the stream busy with the solve's last kernels): reported beside the timed launches
+        hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
+        if (sv.new_event(&ev_c0) == SCS_OK && sv.new_event(&ev_c1) == SCS_OK) {
+            sv.ev_cal[0] = ev_c0;
+            sv.ev_cal[1] = ev_c1;
+            hipEventRecord(ev_c0, s);
+            hipEventRecord(ev_c1, s);
+        }
+        dbuf maps_d;
+        SCS_TRY(maps_d.alloc((size_t)n * 2 * 8));
+        k_extract_maps<<<(n + 255) / 256, 256, 0, s>>>(Q, q3, n, g->d_dinv, 1.0 / g->dd_norm, constrained ? 1 : 0,
+                                                      maps_d.d());
+        // (page-locked staging: a pageable destination goes through the runtime's own bounce buffers)
+        struct pinned_buf {
+            scs_ctx *ctx;
+            void *p = nullptr;
+            ~pinned_buf() {
+                if (p) scs_pinned_release(ctx, p);
+            }
+        } cols_h{ctx};
+        SCS_TRY(scs_pinned_get(ctx, (size_t)n * 2 * 8, &cols_h.p));
+        const double *cols = (const double *)cols_h.p;
+        SCS_HIP_CHECK(hipMemcpyAsync(cols_h.p, maps_d.p, (size_t)n * 2 * 8, hipMemcpyDeviceToHost, s));
+        // (fused loop: TH already holds the next iteration's Ritz values; h_th has X's)
+        if (!fused)
+            SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8, hipMemcpyDeviceToHost, s));
+        SCS_HIP_CHECK(hipEventRecord(ev_b, s));
+        SCS_HIP_CHECK(hipStreamSynchronize(s));
+        std::vector<double> c0(n), c1(n);
+        for (int i = 0; i < n; ++i) {
+            c0[i] = cols[(size_t)i * 2];
+            c1[i] = cols[(size_t)i * 2 + 1];
+        }
+        if (constrained) {
+            st->lambda[0] = 1.0;
+            st->lambda[1] = h_th[0];
+            st->lambda_next = b > 1 ? h_th[1] : 0.0;
+        } else {
+            st->lambda[0] = h_th[0];
+            st->lambda[1] = h_th[1];
+            st->lambda_next = b > 2 ? h_th[2] : 0.0;
+        }
+        sign_flip_and_store(c0, c1, n, maps_out);
+        return SCS_OK;
+    }
+
+    // the counts and the event arithmetic (after `extract`: every event has been reached)
+    void fill_stats(scs_stats *st) const {
+        st->block = b;
+        st->n_apply = sv.n_apply;
+        st->n_apply32 = sv.n_apply32;
+        st->used_constraint = constrained ? 1 : 0;
+        st->resid[0] = final_res[0];
+        st->resid[1] = final_res[1];
+        double tot = 0.0, mn = 1e300, tot32 = 0.0;
+        int n_timed = 0, n_timed32 = 0;
+        for (size_t i = 0; i + 1 < sv.ev.size(); i += 2) {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, sv.ev[i], sv.ev[i + 1]) == hipSuccess) {
+                if (i / 2 < sv.ev32.size() && sv.ev32[i / 2]) {
+                    tot32 += t;
+                    ++n_timed32;
+                    continue;
+                }
+                tot += t;
+                mn = std::min(mn, (double)t);
+                ++n_timed;
+            }
+        }
+        // the fused loop times every fourth launch: scale the sample to all launches (of its kind: the
+        // launches that streamed the single-precision image are reported on their own)
+        if (n_timed > 0) tot *= (double)(sv.n_apply - sv.n_apply32) / n_timed;
+        if (n_timed32 > 0) tot32 *= (double)sv.n_apply32 / n_timed32;
+        st->apply_ms_total = tot;
+        st->apply32_ms_total = tot32;
+        st->apply32_bytes = sv.n_apply32 ? sv.w32_bytes_per_apply + 8.0 * (double)n * b + 8.0 * (double)sv.rows * b : 0.0;
+        st->apply_ms_min = n_timed ? mn : 0.0;
+        {
+            float t = 0.f;
+            st->event_pair_ms = (sv.ev_cal[1] && hipEventElapsedTime(&t, sv.ev_cal[0], sv.ev_cal[1]) == hipSuccess) ? t : 0.0;
+        }
+        // W bytes one application streams (all of this rank's rows, or the upper tiles of the
+        // symmetric schedule) + the block in and out
+        st->apply_bytes = sv.w_bytes_per_apply + 8.0 * (double)n * b + 8.0 * (double)sv.rows * b;
+        {
+            // the timed all-gathers (every fourth iteration of the fused loop), scaled to all of them
+            double ag = 0.0;
+            int n_ag = 0;
+            for (size_t i = 0; i + 1 < sv.ev_ag.size(); i += 2) {
+                float t = 0.f;
+                if (hipEventElapsedTime(&t, sv.ev_ag[i], sv.ev_ag[i + 1]) == hipSuccess) {
+                    ag += t;
+                    ++n_ag;
+                }
+            }
+            st->n_allgather = sv.n_allgather;
+            st->allgather_ms_total = n_ag ? ag * (double)sv.n_allgather / n_ag : 0.0;
+            // bytes one all-gather delivers to this rank: `world` chunks of `chunk` doubles
+            st->allgather_bytes = sv.world > 1 ? 8.0 * (double)sv.chunk * sv.world : 0.0;
+        }
+    }
+};
+
+}  // namespace
 
 // small-V path: dense S on the device, full Jacobi, top two eigenvectors
 // 65 .. 128 vertices: dense S on the device, one-sided Jacobi in LDS (k_dense_onesided)
@@ -2532,17 +3033,11 @@ extern "C" int scs_fiedler(scs_ctx *ctx, scs_graph *g, const double *x_init, dou
     // against 3.0 ms for LOBPCG, 4.5 against 3.5 ms at 120 -- the crossover is near 100.
     // An asked-for block width keeps the iterative path.
     static const int dense_max = 96;
-    if (n > MAXS && n <= dense_max && block == 0 && ctx->comm.world == 1 && !g->upper) {
-        SCS_TRY(fiedler_dense_onesided(ctx, g, maps_out, st));
-        SCS_HIP_CHECK(hipEventRecord(ev_b, s));
-        SCS_HIP_CHECK(hipEventSynchronize(ev_b));
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, ev_a, ev_b);
-        st->solve_ms = ms;
-        return SCS_OK;
-    }
-    if (n <= MAXS) {
-        SCS_TRY(fiedler_dense(ctx, g, maps_out, st));
+    int (*dense)(scs_ctx *, scs_graph *, double *, scs_stats *) = nullptr;
+    if (n > MAXS && n <= dense_max && block == 0 && ctx->comm.world == 1 && !g->upper) dense = fiedler_dense_onesided;
+    if (n <= MAXS) dense = fiedler_dense;
+    if (dense) {
+        SCS_TRY(dense(ctx, g, maps_out, st));
         SCS_HIP_CHECK(hipEventRecord(ev_b, s));
         SCS_HIP_CHECK(hipEventSynchronize(ev_b));
         float ms = 0.f;
@@ -2551,2014 +3046,77 @@ extern "C" int scs_fiedler(scs_ctx *ctx, scs_graph *g, const double *x_init, dou
         return SCS_OK;
     }
 
-    // ---- mixed precision (round 5; SCS_LOWP=0 off, 1, 2 = default).  The loop applies the operator to
-    // its SEARCH DIRECTIONS only (S X and S P are carried by linear updates), and a search direction does
-    // not need S to sixteen digits: with the symmetric schedule at width 4 the SYMM streams a single-
-    // precision image of W -- half the bytes, products and sums still in double precision -- that the
-    // degree pass writes on its way through W.  What the image's rounding leaves in S X and S P is removed
-    // by renewing both through W itself (two applications) when the residual passes 1e-8, and
-    // once more should it stop halving; mode 1 goes on in double precision after the first renewal, mode 2
-    // stays with the image.  The confirmation at the end always applies W, and a solve it sends back into the loop
-    // continues without the image.
-    const int lowp_mode = getenv("SCS_LOWP") ? atoi(getenv("SCS_LOWP")) : 2;
-    const double lowp_tol = 1e-8, lowp_tol2 = 0.0;
-    // (only the default loop hands its Rayleigh-Ritz solve the one-sided entries: small_rr_body)
-    const bool loop_fused = !(scs_dbg("SCS_LEGACY_LOOP") && atoi(scs_dbg("SCS_LEGACY_LOOP"))) &&
-                            !(scs_dbg("SCS_SPLIT_SMALL") && atoi(scs_dbg("SCS_SPLIT_SMALL"))) &&
-                            !(scs_dbg("SCS_FOLD_PASS2") && !atoi(scs_dbg("SCS_FOLD_PASS2")));
-    // (an image above SCS_LOWP_MAX_BYTES, default 16 GiB -- about 65 000 vertices -- is not made: what it
-    // saves a solve of that size, some 80 ms, is less than what an allocation of tens of GB can cost)
-    const double lowp_max_bytes = getenv("SCS_LOWP_MAX_BYTES") ? atof(getenv("SCS_LOWP_MAX_BYTES")) : 16.0 * (1u << 30);
-    // (round 6: a row-partitioned job -- whole rows on every rank, k_symm -- keeps the image of each rank's rows:
-    // the first real multi-GPU run streams per rank what the one-GPU run streams, not twice that)
-    const bool image_rows = ctx->comm.world > 1 && !g->upper;
-    const bool image_one = ctx->comm.world == 1 && !g->upper && g->row_begin == 0 && g->row_end == n;
-    const bool image_ok = !g->mf && lowp_mode > 0 && n >= 4096 && loop_fused && (image_one || image_rows) &&
-                          (g->have_w32 || 4.0 * (double)(g->row_end - g->row_begin) * (double)g->ld <= lowp_max_bytes);
-    // default width: 4 while the panel kernels and the 3b x 3b Rayleigh-Ritz solve weigh
-    // against the SYMM stream, 8 once streaming W dominates (measured crossover ~ 16k) -- unless the
-    // loop can stream the single-precision image, which exists at width 4: half the bytes an
-    // application outweigh the iterations width 8 saves (configs[3], 50 000 vertices: 48 iterations and
-    // 78 ms against 35 and 101)
-    int b = block ? block : ((n >= 16384 && !image_ok) ? 8 : 4);
-    if (g->upper && b > 8) b = 8;  // the symmetric SYMM kernel comes in widths 4 and 8
-    if (g->mf) b = std::min(b <= 4 ? 4 : 8, g->mf->b_cap);  // (the sweep kernel likewise)
-    {
-        const int allowed[] = {16, 12, 8, 4};
-        const int cap = (n - 2) / 3;  // 3b basis vectors + the constraint must fit in V
-        int pick = 4;
-        for (int a : allowed)
-            if (a <= b && a <= cap) {
-                pick = a;
-                break;
-            }
-        b = pick;  // (>= 4: more than the one or two pairs wanted)
-    }
-    const int q3 = 3 * b;
-
-    const bool want32 = image_ok && b == 4;
+    const loop_plan plan{};
+    bool want32 = false;
+    const int b = choose_width(ctx, g, block, plan, &want32);
     // (the iterative path allocates and clears its buffers while k_degrees streams W, and only then waits
     // for the degrees)
     SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, want32));
+    lobpcg L(ctx, g, b, plan);
+    SCS_TRY(L.setup(tol, want32));
+    SCS_TRY(L.start(x_init));
 
-    solver sv;
-    sv.ctx = ctx;
-    sv.g = g;
-    sv.s = s;
-    sv.n = n;
-    sv.b = b;
-    sv.rows = g->row_end - g->row_begin;
-    sv.world = ctx->comm.world;
-    sv.use_mfma = !(scs_dbg("SCS_NO_MFMA") && atoi(scs_dbg("SCS_NO_MFMA")));
-    sv.gram_blocks = 256;
-    SCS_TRY(gather_full_rows(ctx, g, sv.splits));
-    int max_rows = 0;
-    for (int r = 0; r < sv.world; ++r)
-        max_rows = std::max(max_rows, sv.splits[r + 1] - sv.splits[r]);
-    sv.chunk = g->upper ? (int64_t)n * b : (int64_t)max_rows * b;  // (upper: whole partial products travel)
-
-    SCS_TRY(sv.q.alloc((size_t)n * q3 * 8));
-    SCS_TRY(sv.aq.alloc((size_t)n * q3 * 8));
-    SCS_TRY(sv.alloc_symm_buffers());
-    SCS_TRY(sv.yloc.alloc((size_t)sv.chunk * 8));
-    SCS_TRY(sv.u.alloc((size_t)n * 8));
-    SCS_TRY(sv.part.alloc((size_t)1024 * q3 * q3 * 8));
-    SCS_TRY(sv.part2.alloc((size_t)1024 * q3 * q3 * 8));
-    SCS_TRY(sv.part3.alloc((size_t)1024 * q3 * q3 * 8));
-    SCS_TRY(sv.small.alloc((size_t)SM_TOTAL * 8));
-    if (sv.world > 1 && !sv.part_mode) {
-        SCS_TRY(sv.yfull.alloc((size_t)n * b * 8));
-        SCS_TRY(sv.recv.alloc((size_t)sv.chunk * sv.world * 8));
-        SCS_TRY(sv.splits_d.alloc((size_t)(sv.world + 1) * 4));
-        SCS_HIP_CHECK(hipMemcpyAsync(sv.splits_d.p, sv.splits.data(), (size_t)(sv.world + 1) * 4,
-                                     hipMemcpyHostToDevice, s));
-    }
-    SCS_HIP_CHECK(hipMemsetAsync(sv.q.p, 0, (size_t)n * q3 * 8, s));
-    SCS_HIP_CHECK(hipMemsetAsync(sv.aq.p, 0, (size_t)n * q3 * 8, s));
-    SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0, (size_t)sv.chunk * 8, s));
-    SCS_HIP_CHECK(hipMemsetAsync(sv.small.p, 0, (size_t)SM_TOTAL * 8, s));
-
-    double *Q = sv.q.d(), *AQ = sv.aq.d();
-    // panel layout [X | P | R]: the blocks R is projected against are contiguous
-    double *X = Q, *R = Q + 2 * b;
-    double *AX = AQ;
-    double *G = sv.small_at(SM_G), *T = sv.small_at(SM_T), *C = sv.small_at(SM_C);
-    double *D = sv.small_at(SM_D);
-    double *TH = sv.small_at(SM_THETA), *RN = sv.small_at(SM_RN);
-    int *MASK = (int *)sv.small_at(SM_MASK);
-    const double drop_tol = 1e-13;
-
-    SCS_TRY(scs_graph_prepare_degrees(ctx, g));  // (begun at the top: the degrees are needed from here on)
-    sv.use32 = want32 && g->have_w32 && (sv.tri ? sv.tri_ct == 2 : (image_rows && !sv.part_mode));
-    scs_loop_policy policy;  // the stop / renew / confirm rules (scs_policy.h)
-    policy.tol = tol;
-    policy.lowp_mode = lowp_mode;
-    policy.lowp_tol = lowp_tol;
-    policy.lowp_tol2 = lowp_tol2;
-    policy.lowp_state = sv.use32 ? 1 : 0;  // image in use: 1 + the renewals of S X / S P made so far; 0: off
-    const bool constrained = g->n_isolated == 0;
-    const int want = constrained ? 1 : 2;
-
-    // constraint vector
-    dbuf x0d;
-    if (x_init) {
-        SCS_TRY(x0d.alloc((size_t)n * 8));
-        SCS_HIP_CHECK(hipMemcpyAsync(x0d.p, x_init, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    }
-    if (constrained)
-        k_trivial<<<(n + 255) / 256, 256, 0, s>>>(g->d_deg, 1.0 / g->dd_norm, n, sv.u.d());
-
-    // project the constraint out of a panel block (twice) and SVQB-orthonormalise it;
-    // companion (may be null) receives the same column transform
-    auto project_u = [&](double *Y, int passes) -> int {
-        if (!constrained) return SCS_OK;
-        for (int pass = 0; pass < passes; ++pass) {
-            SCS_TRY(sv.gram(sv.u.d(), 1, 1, Y, q3, b, C, false));
-            SCS_TRY(sv.update(Y, q3, b, 1.0, sv.u.d(), 1, 1, C, b, -1.0));
-        }
-        return SCS_OK;
-    };
-    auto svqb = [&](double *Y, double *AY, int *mask_out) -> int {
-        for (int pass = 0; pass < 2; ++pass) {
-            SCS_TRY(sv.gram(Y, q3, b, Y, q3, b, G, sv.use_mfma));
-            k_small_svqb<<<1, 256, 0, s>>>(G, b, pass == 0 ? drop_tol : 0.0, T, mask_out);
-            // second pass: every surviving direction is kept (dead columns stay dead: dsc = 0)
-            SCS_TRY(sv.update(Y, q3, b, 0.0, Y, q3, b, T, b, 1.0));
-            if (AY) SCS_TRY(sv.update(AY, q3, b, 0.0, AY, q3, b, T, b, 1.0));
-        }
-        return SCS_OK;
-    };
-    // mask handling: pass 2 would overwrite mask with all-live for surviving columns and 0
-    // for dead ones (their Gram diagonal is 0 -> dsc 0 -> eigenvalue 0 -> dropped since
-    // 0 > 0 is false), so the mask of the second pass is the final one.
-
-    // ---- start block
-    k_init_block<<<(n * b + 255) / 256, 256, 0, s>>>(Q, b, n, x_init ? x0d.d() : nullptr);
-    SCS_TRY(project_u(X, 2));
-    SCS_TRY(svqb(X, nullptr, MASK));
-    SCS_TRY(sv.apply(Q, 0, AQ, 0));
-    // rotate X so that X^T A X is diagonal
-    SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
-    {
-        // (masks: all live going in, no search directions yet coming out -- set by the kernel itself;
-        // X and S X rotated in one launch)
-        k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
-        SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
-    }
-
-    const int res_blocks = (n + 255) / 256;
-    dbuf res_part;
-    SCS_TRY(res_part.alloc((size_t)res_blocks * b * 8));
-    std::vector<double> h_rn(b), h_th(b + 1);
     int iter = 0;
     bool converged = false;
-    double final_res[2] = {0.0, 0.0};
-
-    // Fused iteration (scs_panel.h) for the default block widths; SCS_LEGACY_LOOP=1 keeps
-    // the one-kernel-per-step formulation (also used for widths 12 and 16).
-    const bool fused = (b == 4 || b == 8) &&
-                       !(scs_dbg("SCS_LEGACY_LOOP") && atoi(scs_dbg("SCS_LEGACY_LOOP")));
-    if (fused) {
-        if (!ctx->h_report) {
-            SCS_HIP_CHECK(hipHostMalloc((void **)&ctx->h_report, 64 * sizeof(double),
-                                        hipHostMallocMapped | hipHostMallocCoherent));
-            SCS_HIP_CHECK(hipHostGetDevicePointer((void **)&ctx->d_report, ctx->h_report, 0));
-            memset(ctx->h_report, 0, 64 * sizeof(double));
-        }
-        k_unit_coeffs<<<(3 * b * b + 255) / 256, 256, 0, s>>>(T, D, b);
-    }
-    const double *uvec = constrained ? sv.u.d() : nullptr;
-    // SCS_SPLIT_SMALL=1: the small solves as one-workgroup kernels of their own (the round-3 loop)
-    const bool split_small = scs_dbg("SCS_SPLIT_SMALL") && atoi(scs_dbg("SCS_SPLIT_SMALL"));
-    sv.fold_pass2 = fused && !split_small && !(scs_dbg("SCS_FOLD_PASS2") && !atoi(scs_dbg("SCS_FOLD_PASS2")));
-    sv.overlap_pass1 = sv.fold_pass2 && sv.tri && !sv.part_mode && sv.world == 1 &&
-                       !(scs_dbg("SCS_OVERLAP_PASS1") && !atoi(scs_dbg("SCS_OVERLAP_PASS1")));
-    if (sv.overlap_pass1) SCS_TRY(sv.coef1.alloc((size_t)(3 * 8 + 4) * 8 * 8));
-    sv.fold_u = uvec;
-    sv.fold_mask_r = MASK + 2 * b;
-    sv.fold_theta = TH;
-    double *qaq_out = sv.fold_pass2 ? sv.part3.d() : sv.part2.d();
-    int rr_solve = 0, rr_parts = 0, mpar = 0;
-    int *maskp[2] = {MASK + b, MASK + 32};
-
     for (iter = 0; iter < max_iter; ++iter) {
-        if (fused) {
-            // The whole iteration is enqueued before the host looks at the residual norms the
-            // first small kernel reported: the device never waits for the host.  Nothing
-            // after that kernel touches X, so on a stop X is the block the norms belong to.
-            int nparts = 0;
-            const double seq = (double)(++ctx->report_seq);
-            if (!split_small) {
-                // (the Rayleigh-Ritz solve on the previous iteration's Gram partials opens the
-                // first launch)
-                if (b == 4) {
-                    SCS_TRY(sv.fused_front_solve<4>(uvec, rr_parts, rr_solve, TH, maskp[mpar], MASK + 2 * b,
-                                                    maskp[mpar ^ 1], drop_tol, ctx->d_report, seq));
-                    SCS_TRY(sv.fused_back<4>(&nparts, qaq_out));
-                } else {
-                    SCS_TRY(sv.fused_front_solve<8>(uvec, rr_parts, rr_solve, TH, maskp[mpar], MASK + 2 * b,
-                                                    maskp[mpar ^ 1], drop_tol, ctx->d_report, seq));
-                    SCS_TRY(sv.fused_back<8>(&nparts, qaq_out));
-                }
-                rr_parts = nparts;
-                rr_solve = 1;
-                mpar ^= 1;
-            } else {
-                if (b == 4) {
-                    SCS_TRY(sv.fused_front<4>(uvec, T, D, TH, C, MASK + 2 * b, drop_tol, ctx->d_report, seq));
-                    SCS_TRY(sv.fused_back<4>(&nparts, sv.part.d()));
-                } else {
-                    SCS_TRY(sv.fused_front<8>(uvec, T, D, TH, C, MASK + 2 * b, drop_tol, ctx->d_report, seq));
-                    SCS_TRY(sv.fused_back<8>(&nparts, sv.part.d()));
-                }
-                k_small_rr<<<1, 256, 0, s>>>(sv.part.d(), nparts, q3, b, MASK, T, D, TH, MASK + b,
-                                             drop_tol);
-            }
-            SCS_HIP_CHECK(hipGetLastError());
-            {
-                // wait for this iteration's report (the device is already working on the rest of
-                // the iteration); give up if the stream died
-                volatile double *hr = (volatile double *)ctx->h_report;
-                const auto t_wait = std::chrono::steady_clock::now();
-                unsigned spins = 0;
-                while (hr[40] != seq) {
-                    __builtin_ia32_pause();
-                    // (a report normally arrives within a few microseconds; a host thread that has
-                    // waited much longer lets others run -- eight ranks may share the cores)
-                    if (spins > (1u << 18) && (spins & 0x3FF) == 0) sched_yield();
-                    if ((++spins & 0xFFFF) == 0) {
-                        const hipError_t qe = hipStreamQuery(s);
-                        if (qe != hipSuccess && qe != hipErrorNotReady) {
-                            scs_set_error("scs_fiedler: stream failed: %s", hipGetErrorString(qe));
-                            return SCS_EHIP;
-                        }
-                        if (qe == hipSuccess && hr[40] != seq) {
-                            // everything ran and the report never arrived
-                            if (std::chrono::steady_clock::now() - t_wait > std::chrono::seconds(5)) {
-                                scs_set_error("scs_fiedler: residual report lost at iteration %d", iter);
-                                return SCS_EHIP;
-                            }
-                        }
-                    }
-                }
-            }
-            for (int j = 0; j < b; ++j) h_rn[j] = ((volatile double *)ctx->h_report)[j];
-            for (int j = 0; j <= b; ++j) h_th[j] = ((volatile double *)ctx->h_report)[16 + j];
+        if (L.fused) {
+            double seq = 0.0;
+            SCS_TRY(L.enqueue_fused(&seq));
+            SCS_TRY(L.await_report(seq, iter));
         } else {
-            // residual block and its norms
-            k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
-            k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
-            SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
-            SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8, hipMemcpyDeviceToHost, s));
-            SCS_HIP_CHECK(hipStreamSynchronize(s));
+            SCS_TRY(L.read_residual());
         }
-        double worst = 0.0;
-        for (int j = 0; j < want; ++j) worst = std::max(worst, std::sqrt(h_rn[j]));
-        for (int j = 0; j < want; ++j) final_res[constrained ? 1 : j] = std::sqrt(h_rn[j]);
-        static const bool trace_res = scs_dbg("SCS_TRACE_RESIDUAL") && atoi(scs_dbg("SCS_TRACE_RESIDUAL"));
-        if (trace_res) fprintf(stderr, "[lobpcg] it %3d  residual %.3e  theta %.12g %.12g\n", iter, worst, h_th[0], h_th[1]);
+        const double worst = L.worst_residual();
+        static const bool trace_res = dbg_on("SCS_TRACE_RESIDUAL");
+        if (trace_res) fprintf(stderr, "[lobpcg] it %3d  residual %.3e  theta %.12g %.12g\n", iter, worst, L.h_th[0], L.h_th[1]);
         if (!(worst == worst)) {
             scs_set_error("scs_fiedler: NaN residual at iteration %d", iter);
             return SCS_EHIP;
         }
-        const int action = policy.step(worst);
-        const bool stop = action == scs_loop_policy::STOP;
+        const int action = L.policy.step(worst);
         if (action == scs_loop_policy::RENEW) {
-            // S X and S P anew through W itself, behind the iteration already enqueued (its Gram matrix,
-            // formed with the old products, steers one more Rayleigh-Ritz step: coefficients only).
-            // What the image adds to S X afterwards is its rounding (~1e-10 ||S||) times the steps still
-            // to be taken, which are of the size of the residual over the spectral gap: one renewal clears
-            // what the long early steps left (measured: without it 15 more iterations); a second one is
-            // made when the residual stops halving (four iterations) (a second threshold on the residual itself exists and is off).
-            // After the FIRST renewal a loop that has not halved its residual in eight iterations stops for the
-            // confirmation (the image's rounding has become the floor); before it LOBPCG has plateaus of its own
-            // -- ten iterations at 4e-5 on the `bootstrap` workload -- five orders above the image's rounding.
-            sv.use32 = false;
-            SCS_TRY(sv.apply(Q, 0, AQ, 0));
-            SCS_TRY(sv.apply(Q, b, AQ, b));
-            sv.use32 = policy.image_in_use();
+            SCS_TRY(L.renew());
             ++st->lowp_renewals;
         }
-        if (stop) {
-            sv.use32 = false;  // the confirmation, and whatever follows it, through W
-            // confirm against a freshly applied operator (AX drifts by linear updates)
-            if (policy.begin_confirmation()) {
-                double w2 = 0.0;
-                auto measure = [&]() -> int {
-                    SCS_TRY(sv.gram(X, q3, b, AX, q3, b, G, sv.use_mfma));
-                    // (the kernel leaves the P slots dead: the search directions restart after the refresh)
-                    k_small_rr_start<<<1, 256, 0, s>>>(G, b, MASK, T, D, TH, drop_tol);
-                    SCS_TRY(sv.rotate2(X, AX, q3, b, T, b));
-                    k_residual<<<res_blocks, 256, 0, s>>>(Q, AQ, b, TH, n, res_part.d());
-                    k_reduce_partials<<<(b + 3) / 4, 256, 0, s>>>(res_part.d(), res_blocks, b, RN);
-                    SCS_HIP_CHECK(hipMemcpyAsync(h_rn.data(), RN, (size_t)b * 8, hipMemcpyDeviceToHost, s));
-                    SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8,
-                                                 hipMemcpyDeviceToHost, s));
-                    SCS_HIP_CHECK(hipStreamSynchronize(s));
-                    w2 = 0.0;
-                    for (int j = 0; j < want; ++j) w2 = std::max(w2, std::sqrt(h_rn[j]));
-                    for (int j = 0; j < want; ++j) final_res[constrained ? 1 : j] = std::sqrt(h_rn[j]);
-                    return SCS_OK;
-                };
-                SCS_TRY(sv.apply(Q, 0, AQ, 0));
-                SCS_TRY(measure());
-                if (!(w2 <= tol)) {
-                    // X is carried by linear updates and never normalised again: after hundreds of iterations
-                    // ||x||^2 = 1 + 2 eps, the Ritz value x^T S x is off by 2 eps lambda, and no residual
-                    // S x - theta x can fall below that error however good x is (the path on 257 vertices:
-                    // theta off by 2.4e-13 / 1.8e-13 / 7.3e-13 at widths 4 / 8 / 16, the residuals flat at
-                    // exactly those values).  So a confirmation that misses the target
-                    // orthonormalises X, takes the fresh S X through the same transform (no further
-                    // application) and measures once more.
-                    SCS_TRY(svqb(X, AX, MASK));
-                    SCS_TRY(measure());
-                }
-                bool conv = false;
-                if (policy.confirm(w2, &conv)) {
-                    converged = conv;
-                    break;
-                }
-                if (fused) k_unit_coeffs<<<(3 * b * b + 255) / 256, 256, 0, s>>>(T, D, b);
-                rr_solve = 0;
-            } else {
+        if (action == scs_loop_policy::STOP) {
+            if (!L.policy.begin_confirmation()) {
                 converged = worst <= tol;
                 break;
             }
+            double w2 = 0.0;
+            SCS_TRY(L.confirm(tol, &w2));
+            bool conv = false;
+            if (L.policy.confirm(w2, &conv)) {
+                converged = conv;
+                break;
+            }
+            SCS_TRY(L.restart_directions());
         }
-
-        if (fused) continue;
-        // R <- orthonormal complement of [u, X, P] within span(R); P is orthonormal and
-        // orthogonal to X by construction (k_small_rr), dead P columns are zero vectors
-        // S u = u exactly, so R = S X - X theta inherits X's orthogonality to u; one
-        // pass keeps rounding drift from accumulating
-        SCS_TRY(project_u(R, 1));
-        for (int pass = 0; pass < 2; ++pass) {
-            SCS_TRY(sv.gram(Q, q3, 2 * b, R, q3, b, C, sv.use_mfma));
-            SCS_TRY(sv.update(R, q3, b, 1.0, Q, q3, 2 * b, C, b, -1.0));
-        }
-        SCS_TRY(svqb(R, nullptr, MASK + 2 * b));
-        SCS_TRY(sv.apply(Q, 2 * b, AQ, 2 * b));
-
-        // Rayleigh-Ritz on the orthonormal basis [X P R]; new X and new P in one pass each
-        SCS_TRY(sv.gram(Q, q3, q3, AQ, q3, q3, G, sv.use_mfma));
-        k_small_rr<<<1, 256, 0, s>>>(G, 0, q3, b, MASK, T, D, TH, MASK + b, drop_tol);
-        k_rr_update<<<(n + 15) / 16, 256, 0, s>>>(Q, b, q3, T, D, n);
-        k_rr_update<<<(n + 15) / 16, 256, 0, s>>>(AQ, b, q3, T, D, n);
-        SCS_HIP_CHECK(hipGetLastError());
+        if (!L.fused) SCS_TRY(L.unfused_back());
     }
 
-    // what an event pair around a launch adds to the launch's own time on this stream (the pair's two records
-    // back to back, the stream busy with the solve's last kernels): reported beside the timed launches
-    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
-    if (sv.new_event(&ev_c0) == SCS_OK && sv.new_event(&ev_c1) == SCS_OK) {
-        sv.ev_cal[0] = ev_c0;
-        sv.ev_cal[1] = ev_c1;
-        hipEventRecord(ev_c0, s);
-        hipEventRecord(ev_c1, s);
-    }
-
-    // ---- results: the two wanted columns, scaled, from the device (not the whole panel)
-    dbuf maps_d;
-    SCS_TRY(maps_d.alloc((size_t)n * 2 * 8));
-    k_extract_maps<<<(n + 255) / 256, 256, 0, s>>>(Q, q3, n, g->d_dinv, 1.0 / g->dd_norm, constrained ? 1 : 0,
-                                                  maps_d.d());
-    // (page-locked staging: a pageable destination goes through the runtime's own bounce buffers)
-    struct pinned_buf {
-        scs_ctx *ctx;
-        void *p = nullptr;
-        ~pinned_buf() {
-            if (p) scs_pinned_release(ctx, p);
-        }
-    } cols_h{ctx};
-    SCS_TRY(scs_pinned_get(ctx, (size_t)n * 2 * 8, &cols_h.p));
-    const double *cols = (const double *)cols_h.p;
-    SCS_HIP_CHECK(hipMemcpyAsync(cols_h.p, maps_d.p, (size_t)n * 2 * 8, hipMemcpyDeviceToHost, s));
-    // (fused loop: TH already holds the next iteration's Ritz values; h_th has X's)
-    if (!fused)
-        SCS_HIP_CHECK(hipMemcpyAsync(h_th.data(), TH, (size_t)(b + 1) * 8, hipMemcpyDeviceToHost, s));
-    SCS_HIP_CHECK(hipEventRecord(ev_b, s));
-    SCS_HIP_CHECK(hipStreamSynchronize(s));
-    std::vector<double> c0(n), c1(n);
-    for (int i = 0; i < n; ++i) {
-        c0[i] = cols[(size_t)i * 2];
-        c1[i] = cols[(size_t)i * 2 + 1];
-    }
-    if (constrained) {
-        st->lambda[0] = 1.0;
-        st->lambda[1] = h_th[0];
-        st->lambda_next = b > 1 ? h_th[1] : 0.0;
-    } else {
-        st->lambda[0] = h_th[0];
-        st->lambda[1] = h_th[1];
-        st->lambda_next = b > 2 ? h_th[2] : 0.0;
-    }
-    sign_flip_and_store(c0, c1, n, maps_out);
-
-    st->block = b;
-    st->iterations = iter;
-    st->n_apply = sv.n_apply;
-    st->n_apply32 = sv.n_apply32;
-    st->converged = converged ? 1 : 0;
-    st->used_constraint = constrained ? 1 : 0;
-    st->resid[0] = final_res[0];
-    st->resid[1] = final_res[1];
+    SCS_TRY(L.extract(ev_b, maps_out, st));
     float ms = 0.f;
     hipEventElapsedTime(&ms, ev_a, ev_b);
     st->solve_ms = ms;
-    double tot = 0.0, mn = 1e300, tot32 = 0.0;
-    int n_timed = 0, n_timed32 = 0;
-    for (size_t i = 0; i + 1 < sv.ev.size(); i += 2) {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, sv.ev[i], sv.ev[i + 1]) == hipSuccess) {
-            if (i / 2 < sv.ev32.size() && sv.ev32[i / 2]) {
-                tot32 += t;
-                ++n_timed32;
-                continue;
-            }
-            tot += t;
-            mn = std::min(mn, (double)t);
-            ++n_timed;
-        }
-    }
-    // the fused loop times every fourth launch: scale the sample to all launches (of its kind: the
-    // launches that streamed the single-precision image are reported on their own)
-    if (n_timed > 0) tot *= (double)(sv.n_apply - sv.n_apply32) / n_timed;
-    if (n_timed32 > 0) tot32 *= (double)sv.n_apply32 / n_timed32;
-    st->apply_ms_total = tot;
-    st->apply32_ms_total = tot32;
-    st->apply32_bytes = sv.n_apply32 ? sv.w32_bytes_per_apply + 8.0 * (double)n * b + 8.0 * (double)sv.rows * b : 0.0;
-    st->apply_ms_min = n_timed ? mn : 0.0;
-    {
-        float t = 0.f;
-        st->event_pair_ms = (sv.ev_cal[1] && hipEventElapsedTime(&t, sv.ev_cal[0], sv.ev_cal[1]) == hipSuccess) ? t : 0.0;
-    }
-    // W bytes one application streams (all of this rank's rows, or the upper tiles of the
-    // symmetric schedule) + the block in and out
-    st->apply_bytes = sv.w_bytes_per_apply + 8.0 * (double)n * b + 8.0 * (double)sv.rows * b;
-    {
-        // the timed all-gathers (every fourth iteration of the fused loop), scaled to all of them
-        double ag = 0.0;
-        int n_ag = 0;
-        for (size_t i = 0; i + 1 < sv.ev_ag.size(); i += 2) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, sv.ev_ag[i], sv.ev_ag[i + 1]) == hipSuccess) {
-                ag += t;
-                ++n_ag;
-            }
-        }
-        st->n_allgather = sv.n_allgather;
-        st->allgather_ms_total = n_ag ? ag * (double)sv.n_allgather / n_ag : 0.0;
-        // bytes one all-gather delivers to this rank: `world` chunks of `chunk` doubles
-        st->allgather_bytes = sv.world > 1 ? 8.0 * (double)sv.chunk * sv.world : 0.0;
-    }
-    if (n >= 4096 && scs_dbg("SCS_TRACE_SOLVES") && atoi(scs_dbg("SCS_TRACE_SOLVES")))
+    st->iterations = iter;
+    st->converged = converged ? 1 : 0;
+    L.fill_stats(st);
+    const double res = std::max(L.final_res[0], L.final_res[1]);
+    if (n >= 4096 && dbg_on("SCS_TRACE_SOLVES"))
         fprintf(stderr, "[solve] V %d block %d iterations %d applies %d image %d renewals %d refreshes %d solve_ms %.3f "
-                        "wall_ms %.3f residual %.3e gap %.3e\n", n, b, iter, sv.n_apply, sv.n_apply32, st->lowp_renewals,
-                policy.confirmations, st->solve_ms,
+                        "wall_ms %.3f residual %.3e gap %.3e\n", n, b, iter, st->n_apply, st->n_apply32, st->lowp_renewals,
+                L.policy.confirmations, st->solve_ms,
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count(),
-                std::max(final_res[0], final_res[1]), st->lambda[1] - st->lambda_next);
+                res, st->lambda[1] - st->lambda_next);
     if (!converged) {
         // maps_out and stats are filled: the caller decides whether the block is usable
-        scs_set_error("scs_fiedler: residual %.3e above tol %.3e after %d iterations (V = %d, block %d)",
-                      std::max(final_res[0], final_res[1]), tol, iter, n, b);
+        scs_set_error("scs_fiedler: residual %.3e above tol %.3e after %d iterations (V = %d, block %d)", res, tol,
+                      iter, n, b);
         return SCS_ENOCONV;
     }
     return SCS_OK;
 }
 
-// ---------------------------------------------------------------------------
-// batched small nodes: tables -> W -> contraction -> S -> Jacobi -> maps
-// ---------------------------------------------------------------------------
-// Deep levels of the recursion are thousands of nodes of a few to a few dozen taxa
-// (reference: scs.py:110-134 at depth; 47 spectral calls with V <= 100 in the reference's
-// supertriplets fixture), each with up to thousands of trees, and at any moment the recursion
-// knows only a handful of them (the children of the node it has just split).  A launch per
-// node with one workgroup walking the node's trees one after the other left the other 255
-// CUs idle for milliseconds (round 2: 3.2 us per tree, 16 ms for a 60-taxon node of 5 000
-// trees).  Round 3 spreads ONE node over the chip without giving up the tree-ordered sums:
-//   k_small_addends  the trees of a node are dealt to workgroups in runs; a workgroup stages
-//                    four trees at a time (one per wave: sparse table over the gaps' depths by
-//                    wave shuffles) and every thread writes, for its cells (x, y) and each
-//                    tree, the ADDEND value(LCA) * weight -- rounded on its own, 0 when the
-//                    tree does not join the two taxa -- to addends[tree][cell];
-//   k_small_sum      one thread per cell adds its addends in tree order: the reference's sum
-//                    (scs.py:644-658; x + 0.0 == x, so the zeros change nothing), bit-identical
-//                    to scs_pcg_build's W; the dependent chain is one fp64 add per tree;
-//   k_small_finish   one workgroup per node, in LDS: contraction max-reduce over consecutive id
-//                    ranges, scipy's degree scaling, the full Jacobi eigen-decomposition and
-//                    scikit-learn's embedding conventions.
-// K nodes = three launches, one upload, one download.
-struct small_batch {
-    const int32_t *n_taxa;      // [K] taxa of the node (<= MAXS)
-    const int32_t *n_trees;     // [K]
-    const int32_t *n_groups;    // [K] vertices after contraction (>= 2)
-    const int32_t *tree_ptr;    // [K+1] first tree of node k in tree_w; its tree_off starts at tree_ptr[k] + k
-    const int64_t *leaf_ptr;    // [K+1] first leaf slot of node k
-    const int32_t *vertex_ptr;  // [K+1] first vertex of node k in maps; its group_start at vertex_ptr[k] + k
-    const int32_t *tree_off;    // per node: n_trees + 1 leaf offsets relative to the node's first slot
-    const int32_t *leaf_taxon;
-    const int32_t *adj_depth;
-    const double *adj_val;
-    const double *tree_w;
-    const int32_t *group_start;  // per node: n_groups + 1 entries, 0 .. n_taxa
-    double *maps;                // [total vertices][2]
-    double *lambda;              // [K][3]
-    double *w_out;               // per node n_groups^2 doubles at w_ptr[k], or null
-    const int64_t *w_ptr;
-    // work items of k_small_addends: (node, first tree, end tree); of k_small_sum: (node, first cell)
-    const int32_t *item_node, *item_t0, *item_t1;
-    const int32_t *sum_node, *sum_e0;
-    // [K] first addend of node k.  Nodes of at most SMALL_TR_MAX taxa: addends[add_ptr[k] + (x * v0 + y) * ms +
-    // tree], ms = trees rounded up to even -- a cell's addends lie in tree order in ONE piece, which the one
-    // thread of that cell streams with 16-byte loads (a node of 8 taxa has 28 cells: with the trees outermost
-    // its few threads fetched a line per tree).  Larger nodes: addends[add_ptr[k] + tree * v0^2 + x * v0 + y]
-    // -- hundreds of cells, neighbouring threads read neighbouring addresses (measured both ways:
-    // tools/small_solve_bench.py).  The space reserved is v0^2 * ms either way.
-    const int64_t *add_ptr;
-    double *addends;
-    const int64_t *w0_ptr;   // [K] the node's v0 x v0 uncontracted weights in w0
-    double *w0;
-};
-
-constexpr int SMALL_Q = MAXS * MAXS / 256;  // cells of a thread at the largest node of the one-wave form
-constexpr int SMALL_MAXS = 128;             // largest node of the batched path (round 4: was MAXS)
-constexpr int SMALL_TR_MAX = 24;            // up to here a cell's addends are stored contiguously (small_batch::add_ptr)
-
-// A node of 65 .. 128 taxa (round 4; SURVEY.md 8f rank 3 asks for V <= 128): the same three
-// launches.  A tree restricted to such a node has up to 128 leaves -- two per lane while a wave
-// stages it, the sparse table built level by level in LDS (seven levels, keys (depth << 7 | gap));
-// a thread owns the cells of one column y and every other row x < y.
-__device__ void small_addends_big(const small_batch &p, int k, int t0, int t1, unsigned (*s_sp)[7][SMALL_MAXS],
-                                  double (*s_val)[SMALL_MAXS], int (*s_pos)[SMALL_MAXS]) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int v0 = p.n_taxa[k];
-    const int ncell = v0 * v0;
-    const int32_t *toff = p.tree_off + p.tree_ptr[k] + k;
-    const int64_t lbase = p.leaf_ptr[k];
-    double *out = p.addends + p.add_ptr[k];
-    const bool tr = v0 <= SMALL_TR_MAX;  // (never here: the big path starts above 64 taxa; kept for symmetry)
-    const int64_t cs = tr ? (p.n_trees[k] + 1) & ~1 : 1;  // stride between two cells of a tree (small_batch::add_ptr)
-    const int y = tid & 127, x0 = tid >> 7;
-    for (int g = t0; g < t1; g += 4) {
-        __syncthreads();  // the cells of the previous four trees are done with the buffers
-        const int ts = g + wave;
-        if (ts < t1) {
-            const int off = toff[ts], n = toff[ts + 1] - off;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int i = lane + 64 * h;
-                int f_dep = 0;
-                double f_val = 0.0;
-                if (i < n) {
-                    f_dep = p.adj_depth[lbase + off + i];
-                    f_val = p.adj_val[lbase + off + i];
-                }
-                // gap i = the LCA of leaves i and i + 1 (adj_* of leaf i), i < n - 1
-                s_sp[wave][0][i] = i + 1 < n ? ((unsigned)f_dep << 7) | (unsigned)i : 0xFFFFFFFFu;
-                s_val[wave][i] = f_val;
-                s_pos[wave][i] = -1;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations are performed in order)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int i = lane + 64 * h;
-                if (i < n) s_pos[wave][p.leaf_taxon[lbase + off + i]] = i;
-            }
-            for (int j = 1; j < 7; ++j) {
-                if ((1 << j) >= n) break;  // (uniform) no pair of this tree is 2^j gaps apart
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                unsigned nk[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int i = lane + 64 * h, i2 = i + (1 << (j - 1));
-                    const unsigned a = s_sp[wave][j - 1][i];
-                    const unsigned b = i2 < SMALL_MAXS ? s_sp[wave][j - 1][i2] : 0xFFFFFFFFu;
-                    nk[h] = b < a ? b : a;
-                }
-#pragma unroll
-                for (int h = 0; h < 2; ++h) s_sp[wave][j][lane + 64 * h] = nk[h];
-            }
-        }
-        __syncthreads();
-        for (int j = 0; j < 4; ++j) {
-            const int t = g + j;
-            if (t >= t1) break;
-            const double wt = p.tree_w[p.tree_ptr[k] + t];
-            double *row = tr ? out + t : out + (int64_t)t * ncell;
-            const int py = y < v0 ? s_pos[j][y] : -1;
-            for (int x = x0; x < y && y < v0; x += 2) {
-                const int px = s_pos[j][x];
-                const bool live = px >= 0 && py >= 0;
-                const int lo = live ? (px < py ? px : py) : 0, hi = live ? (px < py ? py : px) : 1;
-                const int lv = 31 - __clz(hi - lo);
-                const unsigned ka = s_sp[j][lv][lo], kb = s_sp[j][lv][hi - (1 << lv)];
-                // (leftmost on ties, as a left-to-right sweep finds it)
-                const unsigned key = kb < ka ? kb : ka;
-                const double mv = s_val[j][key & 127u];
-                double add = 0.0;
-                // the root (depth 0) separates the two: nothing to add
-                if (live && (key >> 7) != 0) {
-#pragma clang fp contract(off)
-                    add = mv * wt;  // rounded on its own, never fused into the sum
-                }
-                row[(int64_t)(x * v0 + y) * cs] = add;
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_small_addends(small_batch p) {
-    // per wave one staged tree: sparse table over the gaps' (depth << 6 | gap) keys, the gaps'
-    // values, the position of every taxon (-1: absent)
-    __shared__ unsigned s_sp[4][7][SMALL_MAXS];
-    __shared__ double s_val[4][SMALL_MAXS];
-    __shared__ int s_pos[4][SMALL_MAXS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int k = p.item_node[blockIdx.x];
-    const int t0 = p.item_t0[blockIdx.x], t1 = p.item_t1[blockIdx.x];
-    const int v0 = p.n_taxa[k];
-    if (v0 > MAXS) {
-        small_addends_big(p, k, t0, t1, s_sp, s_val, s_pos);
-        return;
-    }
-    const int ncell = v0 * v0;
-    const int32_t *toff = p.tree_off + p.tree_ptr[k] + k;
-    const int64_t lbase = p.leaf_ptr[k];
-    double *out = p.addends + p.add_ptr[k];
-    const bool tr = v0 <= SMALL_TR_MAX;
-    const int64_t cs = tr ? (p.n_trees[k] + 1) & ~1 : 1;
-    const int nq = (ncell + 255) / 256;
-    int cx[SMALL_Q], cy[SMALL_Q];
-#pragma unroll
-    for (int q = 0; q < SMALL_Q; ++q) {
-        const int e = tid + 256 * q;
-        cx[q] = e / v0;
-        cy[q] = e - cx[q] * v0;
-        if (e >= ncell || cx[q] >= cy[q]) cx[q] = -1;  // not a cell of the upper triangle
-    }
-    for (int g = t0; g < t1; g += 4) {
-        __syncthreads();  // the cells of the previous four trees are done with the buffers
-        const int ts = g + wave;
-        if (ts < t1) {
-            const int off = toff[ts], n = toff[ts + 1] - off;
-            int f_tax = 0, f_dep = 0;
-            double f_val = 0.0;
-            if (lane < n) {
-                f_tax = p.leaf_taxon[lbase + off + lane];
-                f_dep = p.adj_depth[lbase + off + lane];
-                f_val = p.adj_val[lbase + off + lane];
-            }
-            // gap i = the LCA of leaves i and i + 1 (adj_* of leaf i), i < n - 1
-            unsigned key = lane + 1 < n ? ((unsigned)f_dep << 6) | (unsigned)lane : 0xFFFFFFFFu;
-            s_sp[wave][0][lane] = key;
-#pragma unroll
-            for (int j = 1; j < 6; ++j) {
-                if ((1 << j) >= n) break;  // (uniform) no pair of this tree is 2^j gaps apart
-                const unsigned other = __shfl_down(key, 1 << (j - 1), 64);
-                if (lane + (1 << (j - 1)) < 64) key = other < key ? other : key;
-                s_sp[wave][j][lane] = key;
-            }
-            s_val[wave][lane] = f_val;
-            s_pos[wave][lane] = -1;
-            if (lane < n) s_pos[wave][f_tax] = lane;  // (same wave: after the clearing store)
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int t = g + j;
-            if (t >= t1) break;
-            const double wt = p.tree_w[p.tree_ptr[k] + t];
-            double *row = tr ? out + t : out + (int64_t)t * ncell;
-#pragma unroll
-            for (int q = 0; q < SMALL_Q; ++q) {
-                if (q >= nq) break;  // (uniform) most nodes are tiny
-                if (cx[q] < 0) continue;
-                const int px = s_pos[j][cx[q]], py = s_pos[j][cy[q]];
-                const bool live = px >= 0 && py >= 0;
-                const int lo = live ? (px < py ? px : py) : 0, hi = live ? (px < py ? py : px) : 1;
-                const int lv = 31 - __clz(hi - lo);
-                const unsigned ka = s_sp[j][lv][lo], kb = s_sp[j][lv][hi - (1 << lv)];
-                // (leftmost on ties, as a left-to-right sweep finds it)
-                const unsigned key = kb < ka ? kb : ka;
-                const double mv = s_val[j][key & 63u];
-                double add = 0.0;
-                // the root (depth 0) separates the two: nothing to add
-                if (live && (key >> 6) != 0) {
-#pragma clang fp contract(off)
-                    add = mv * wt;  // rounded on its own, never fused into the sum
-                }
-                row[(int64_t)(tid + 256 * q) * cs] = add;
-            }
-        }
-    }
-}
-
-// thread = one cell (x < y) of one node: its addends in tree order (reference: scs.py:655-657)
-__global__ __launch_bounds__(256) void k_small_sum(small_batch p) {
-    const int k = p.sum_node[blockIdx.x];
-    const int e = p.sum_e0[blockIdx.x] + threadIdx.x;
-    const int v0 = p.n_taxa[k], m = p.n_trees[k];
-    const int ncell = v0 * v0;
-    if (e >= ncell) return;
-    const int x = e / v0, y = e - x * v0;
-    double *w0 = p.w0 + p.w0_ptr[k];
-    if (x == y) w0[e] = 0.0;
-    if (x >= y) return;
-    double acc = 0.0;
-    int t = 0;
-    // (the adds are one chain in tree order -- the reference's order, scs.py:656 -- but the LOADS need not wait
-    // for it.  With 8 loads in flight the kernel took 190 us for 5 000 trees whatever the node's size, 625 round
-    // trips, and a recursion runs it tens of thousands of times; tools/small_solve_bench.py)
-    if (v0 <= SMALL_TR_MAX) {
-        const int64_t ms = (m + 1) & ~1;
-        const double *in = p.addends + p.add_ptr[k] + (int64_t)e * ms;  // 16-byte aligned: add_ptr and ms are even
-        // two batches of 64 addends in flight: the next one's loads are issued before this one's adds
-        if (t + 64 <= m) {
-            double2 a[32], b[32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) a[j] = *(const double2 *)(in + t + 2 * j);
-            for (; t + 128 <= m; t += 64) {
-#pragma unroll
-                for (int j = 0; j < 32; ++j) b[j] = *(const double2 *)(in + t + 64 + 2 * j);
-#pragma unroll
-                for (int j = 0; j < 32; ++j) {
-                    acc = acc + a[j].x;
-                    acc = acc + a[j].y;
-                }
-#pragma unroll
-                for (int j = 0; j < 32; ++j) a[j] = b[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 32; ++j) {
-                acc = acc + a[j].x;
-                acc = acc + a[j].y;
-            }
-            t += 64;
-        }
-        for (; t + 8 <= m; t += 8) {
-            double2 a[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) a[j] = *(const double2 *)(in + t + 2 * j);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc = acc + a[j].x;
-                acc = acc + a[j].y;
-            }
-        }
-        for (; t < m; ++t) acc = acc + in[t];
-    } else {
-        const double *in = p.addends + p.add_ptr[k] + e;
-        for (; t + 32 <= m; t += 32) {
-            double a[32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) a[j] = in[(int64_t)(t + j) * ncell];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) acc = acc + a[j];
-        }
-        for (; t < m; ++t) acc = acc + in[(int64_t)t * ncell];
-    }
-    w0[e] = acc;
-    w0[y * v0 + x] = acc;
-}
-
-// NT = 256: the nodes of up to 24 vertices (the Jacobi variants written for 256 threads).  NT = 1 024 (round 5, late):
-// the nodes of 25 .. 64 vertices -- everything up to the eigen-solve is done by the first 256 threads as it
-// always was, the Jacobi sweeps spread their independent work items over all 1 024 (jacobi_eig_generic): the same
-// bits, a solve of 64 vertices 1.5 -> 0.7 ms.  The host launches the instance(s) a batch needs.
-template <int NT>
-__global__ __launch_bounds__(NT) void k_small_finish(small_batch p) {
-    __shared__ jacobi_lds s;
-    __shared__ double s_dd[MAXS];
-    __shared__ int s_gs[MAXS + 1];
-    const int tid = threadIdx.x;
-    const int k = blockIdx.x;
-    const int v = p.n_groups[k], v0 = p.n_taxa[k];
-    if (v0 > MAXS) return;  // k_small_finish_big's
-    if ((v > 24) != (NT > 256)) return;  // the other instance's
-    const bool first = tid < 256;  // the threads of the 256-thread form: every strided loop below is theirs
-    double(*w0)[SLD] = s.e;  // the uncontracted weights live where Jacobi later keeps its vectors
-    if (first && tid <= v) s_gs[tid] = p.group_start[p.vertex_ptr[k] + k + tid];
-    {
-        const double *src = p.w0 + p.w0_ptr[k];
-        for (int e = tid; e < v0 * v0 && first; e += 256) w0[e / v0][e % v0] = src[e];
-    }
-    __syncthreads();
-    // ---- contraction: vertex g = taxa [gs[g], gs[g+1]); weight = max over member pairs
-    // (reference: scs.py:336-387), diagonal 0
-    for (int e = tid; e < v * v && first; e += 256) {
-        const int g = e / v, h = e - g * v;
-        double best = 0.0;
-        if (g != h) {
-            best = w0[s_gs[g]][s_gs[h]];
-            for (int r = s_gs[g]; r < s_gs[g + 1]; ++r)
-                for (int c = s_gs[h]; c < s_gs[h + 1]; ++c) best = w0[r][c] > best ? w0[r][c] : best;
-        }
-        s.a[g][h] = best;
-    }
-    __syncthreads();
-    if (p.w_out)
-        for (int e = tid; e < v * v && first; e += 256) p.w_out[p.w_ptr[k] + e] = s.a[e / v][e % v];
-    // ---- degrees as scipy takes them (column sums, rows in order; isolated -> 1)
-    if (tid < v) {
-        double d = 0.0;
-        for (int i = 0; i < v; ++i) d = d + s.a[i][tid];
-        s_dd[tid] = d == 0.0 ? 1.0 : sqrt(d);
-    }
-    __syncthreads();
-    // S = (W / dd) / dd^T: two successive divisions (scipy/sparse/csgraph/_laplacian.py:552-557),
-    // then the symmetric part (the two orders of division may differ in the last bit)
-    double keep[(MAXS * MAXS + 255) / 256];
-    {
-        int q = 0;
-        for (int e = tid; e < v * v && first; e += 256, ++q) {
-            const int g = e / v, h = e - g * v;
-            const double x = (s.a[g][h] / s_dd[h]) / s_dd[g];
-            const double y = (s.a[h][g] / s_dd[g]) / s_dd[h];
-            keep[q] = g == h ? 0.0 : 0.5 * (x + y);
-        }
-        __syncthreads();
-        q = 0;
-        for (int e = tid; e < v * v && first; e += 256, ++q) s.a[e / v][e % v] = keep[q];
-    }
-    __syncthreads();
-    if (NT > 256) jacobi_eig_generic<NT>(s, v);
-    else jacobi_eig(s, v);
-    // ---- embedding: unit eigenvectors / dd, largest |entry| of each column positive, column 0
-    // <-> the largest eigenvalue (sklearn/manifold/_spectral_embedding.py:373-376, 463)
-    if (tid < 2) {
-        const int col = s.perm[tid];
-        int arg = 0;
-        double best = -1.0;
-        for (int i = 0; i < v; ++i) {
-            const double x = fabs(s.e[i][col] / s_dd[i]);
-            if (x > best) {
-                best = x;
-                arg = i;
-            }
-        }
-        const double sg = s.e[arg][col] < 0.0 ? -1.0 : 1.0;
-        double *out = p.maps + (int64_t)p.vertex_ptr[k] * 2 + tid;
-        for (int i = 0; i < v; ++i) out[2 * i] = sg * (s.e[i][col] / s_dd[i]);
-    }
-    if (tid < 3) p.lambda[k * 3 + tid] = tid < v ? s.w[tid] : 0.0;
-}
-
-// The nodes of 65 .. 128 taxa of a batch, one workgroup each: contraction straight from the
-// uncontracted weights in device memory into the one LDS array the one-sided Jacobi works in
-// (dense path of scs_fiedler: (V + 1) x V doubles, 132 KB at 128), scipy's degree scaling in
-// place (the contracted matrix is symmetric bit for bit, so every cell's two orders of division
-// need only the cell itself), A = S + I, the sweeps, scikit-learn's embedding conventions.  A
-// batch's workgroups of this kind run side by side on as many CUs: what the recursion's walk
-// used to solve one node after the other with ~35 latency-bound LOBPCG iterations each.
-__global__ __launch_bounds__(256) void k_small_finish_big(small_batch p) {
-    extern __shared__ double dyn_lds[];
-    double(*a)[DENSE2_LD] = (double(*)[DENSE2_LD])dyn_lds;
-    __shared__ double s_dd[SMALL_MAXS], s_norm[SMALL_MAXS];
-    __shared__ int s_gs[SMALL_MAXS + 1];
-    __shared__ int s_rot, s_top[3];
-    const int tid = threadIdx.x;
-    const int k = blockIdx.x;
-    const int v = p.n_groups[k], v0 = p.n_taxa[k];
-    if (v0 <= MAXS) return;  // k_small_finish's
-    const int m = v + (v & 1);
-    if (tid <= v) s_gs[tid] = p.group_start[p.vertex_ptr[k] + k + tid];
-    __syncthreads();
-    // ---- contraction: vertex g = taxa [gs[g], gs[g+1]); weight = max over member pairs
-    // (reference: scs.py:336-387), diagonal 0; the padding row / column of an odd V is zero
-    const double *w0 = p.w0 + p.w0_ptr[k];
-    for (int e = tid; e < m * m; e += 256) {
-        const int g = e / m, h = e - g * m;
-        double best = 0.0;
-        if (g != h && g < v && h < v) {
-            best = w0[s_gs[g] * v0 + s_gs[h]];
-            for (int r = s_gs[g]; r < s_gs[g + 1]; ++r)
-                for (int c = s_gs[h]; c < s_gs[h + 1]; ++c) {
-                    const double x = w0[r * v0 + c];
-                    best = x > best ? x : best;
-                }
-        }
-        a[g][h] = best;
-    }
-    __syncthreads();
-    if (p.w_out)
-        for (int e = tid; e < v * v; e += 256) p.w_out[p.w_ptr[k] + e] = a[e / v][e % v];
-    // ---- degrees as scipy takes them (column sums, rows in order; isolated -> 1)
-    if (tid < v) {
-        double d = 0.0;
-        for (int i = 0; i < v; ++i) d = d + a[i][tid];
-        s_dd[tid] = d == 0.0 ? 1.0 : sqrt(d);
-    }
-    __syncthreads();
-    // S = (W / dd) / dd^T: two successive divisions (scipy/sparse/csgraph/_laplacian.py:552-557),
-    // then the symmetric part (the two orders of division may differ in the last bit); + I
-    for (int e = tid; e < v * v; e += 256) {
-        const int g = e / v, h = e - g * v;
-        const double w = a[g][h];  // == a[h][g]
-        const double x = (w / s_dd[h]) / s_dd[g];
-        const double y = (w / s_dd[g]) / s_dd[h];
-        a[g][h] = g == h ? 1.0 : 0.5 * (x + y);
-    }
-    __syncthreads();
-    // Two vertices that share an edge: S = [[0, s], [s, 0]] with s = 1 up to its last bit, lambda = (s, -s), and
-    // the second eigenvalue is the null direction of A = S + I -- a WANTED column whose norm is 0 (s == 1 exactly:
-    // contracted weights 1, 4, 9, ...) or rounding noise, and the division by that norm below is 0 / 0.  Every other
-    // wanted column is safe: with three vertices or more the trace of S is 0 and lambda_2 >= -1 / (V - 1), a norm
-    // of at least 1 / 2; without an edge A = I.  So this one case is written down in closed form -- eigenvectors
-    // (1, 1) / sqrt(2) and (1, -1) / sqrt(2) -- with the conventions of the general case below.
-    // (the branch is uniform; a NaN weight takes it too and comes back as NaN eigenvalues, which the host refuses)
-    if (v == 2 && a[0][1] != 0.0) {
-        if (tid == 0) {
-            const double s01 = a[0][1], r = 0.70710678118654752440;
-            const double x0 = r / s_dd[0], x1 = r / s_dd[1];
-            // the largest |entry| of a column positive, the first one on a tie
-            const double sg = x1 > x0 ? -1.0 : 1.0;
-            double *out = p.maps + (int64_t)p.vertex_ptr[k] * 2;
-            out[0] = x0;
-            out[2] = x1;
-            out[1] = sg * x0;
-            out[3] = -sg * x1;
-            p.lambda[k * 3 + 0] = s01;
-            p.lambda[k * 3 + 1] = -s01;
-            p.lambda[k * 3 + 2] = 0.0;
-        }
-        return;
-    }
-    const bool ok = onesided_sweeps(a, m, &s_rot);
-    // eigenvalues of S: column norms - 1 (the padding column of an odd V has norm 0: last)
-    if (tid < v) {
-        double s2 = 0.0;
-        for (int r = 0; r < v; ++r) s2 = fma(a[r][tid], a[r][tid], s2);
-        s_norm[tid] = sqrt(s2);
-    }
-    __syncthreads();
-    if (tid < v) {
-        const double mine = s_norm[tid];
-        int rank = 0;
-        for (int j = 0; j < v; ++j) {
-            const double o = s_norm[j];
-            if (o > mine || (o == mine && j < tid)) ++rank;
-        }
-        if (rank < 3) s_top[rank] = tid;
-    }
-    __syncthreads();
-    // ---- embedding: unit eigenvectors / dd, largest |entry| of each column positive, column 0
-    // <-> the largest eigenvalue (sklearn/manifold/_spectral_embedding.py:373-376, 463)
-    if (tid < 2) {
-        const int col = s_top[tid];
-        const double nrm = s_norm[col];
-        int arg = 0;
-        double best = -1.0;
-        for (int i = 0; i < v; ++i) {
-            const double x = fabs((a[i][col] / nrm) / s_dd[i]);
-            if (x > best) {
-                best = x;
-                arg = i;
-            }
-        }
-        const double sg = a[arg][col] < 0.0 ? -1.0 : 1.0;
-        double *out = p.maps + (int64_t)p.vertex_ptr[k] * 2 + tid;
-        for (int i = 0; i < v; ++i) out[2 * i] = sg * ((a[i][col] / nrm) / s_dd[i]);
-    }
-    // (sweeps that did not converge: NaN eigenvalues -- the host refuses the node)
-    if (tid < 3) p.lambda[k * 3 + tid] = !ok ? __longlong_as_double(0x7FF8000000000000ll)
-                                             : (tid < v ? s_norm[s_top[tid]] - 1.0 : 0.0);
-}
-
-// leaf arrays of ONE node straight from a forest's device tables into the batch's device block
-// (taxa renumbered through `relabel` when the node numbers them differently -- present taxa only,
-// contraction groups made consecutive), offsets narrowed to 32 bits
-__global__ void k_small_pack(const int64_t *__restrict__ tree_off64, const int32_t *__restrict__ leaf_taxon,
-                             const int32_t *__restrict__ adj_depth, const double *__restrict__ adj_val,
-                             const double *__restrict__ tree_w, const int32_t *__restrict__ relabel,
-                             int32_t n_trees, int64_t n_leaves, int32_t *__restrict__ to, int32_t *__restrict__ lt,
-                             int32_t *__restrict__ ad, double *__restrict__ av, double *__restrict__ tw) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_leaves) {
-        const int32_t x = leaf_taxon[i];
-        lt[i] = relabel ? relabel[x] : x;
-        ad[i] = adj_depth[i];
-        av[i] = adj_val[i];
-    }
-    if (i <= n_trees) to[i] = (int32_t)tree_off64[i];
-    if (i < n_trees) tw[i] = tree_w[i];
-}
-
-// the same for the K nodes of a level (scs_small_solve_begin_level): node k owns the trees [t_begin[k],
-// t_begin[k] + n_trees[k]) of the level forest and the taxon ids [u_base[k], u_base[k] + u_size[k]) of its
-// universe; relabel (all nodes' maps, concatenated: rl_ptr[k] is node k's first entry) sends an id of that
-// range to the node's own numbering
-struct level_pack {
-    const int32_t *t_begin, *u_base, *rl_ptr;  // device [K]
-    const int32_t *relabel;                    // device, concatenated
-    const int32_t *tree_ptr;                   // device [K + 1] first tree of node k in the batch
-    const int64_t *leaf_ptr;                   // device [K + 1] first leaf slot of node k in the batch
-};
-
-__global__ void k_small_pack_level(const int64_t *__restrict__ tree_off64, const int32_t *__restrict__ leaf_taxon,
-                                   const int32_t *__restrict__ adj_depth, const double *__restrict__ adj_val,
-                                   const double *__restrict__ tree_w, level_pack lp, int32_t n_nodes, int64_t n_leaves,
-                                   int32_t n_trees, int32_t *__restrict__ to, int32_t *__restrict__ lt,
-                                   int32_t *__restrict__ ad, double *__restrict__ av, double *__restrict__ tw) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_leaves) {
-        int32_t lo = 0, hi = n_nodes - 1;  // last k with leaf_ptr[k] <= i
-        while (lo < hi) {
-            const int32_t mid = (lo + hi + 1) >> 1;
-            if (lp.leaf_ptr[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        const int64_t src = tree_off64[lp.t_begin[lo]] + (i - lp.leaf_ptr[lo]);
-        lt[i] = lp.relabel[lp.rl_ptr[lo] + (leaf_taxon[src] - lp.u_base[lo])];
-        ad[i] = adj_depth[src];
-        av[i] = adj_val[src];
-    }
-    if (i < n_trees + n_nodes) {
-        // node k's offsets sit at tree_ptr[k] + k .. tree_ptr[k + 1] + k (its trees + 1 entries)
-        int32_t lo = 0, hi = n_nodes - 1;  // last k with tree_ptr[k] + k <= i
-        while (lo < hi) {
-            const int32_t mid = (lo + hi + 1) >> 1;
-            if (lp.tree_ptr[mid] + mid <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        const int32_t j = (int32_t)i - (lp.tree_ptr[lo] + lo);  // 0 .. trees of the node
-        const int32_t t0 = lp.t_begin[lo];
-        to[i] = (int32_t)(tree_off64[t0 + j] - tree_off64[t0]);
-        if (j < lp.tree_ptr[lo + 1] - lp.tree_ptr[lo]) tw[lp.tree_ptr[lo] + j] = tree_w[t0 + j];
-    }
-}
-
-struct level_src {
-    const scs_forest *forest;
-    const int32_t *t_begin, *u_base, *u_size;  // host [K]
-    const int64_t *n_leaves;                   // host [K]
-    const int32_t *relabel;                    // host, concatenated (sum of u_size entries)
-};
-
-static int small_solve_begin_impl(scs_ctx *ctx, int32_t n_nodes, const int32_t *n_taxa,
-                                  const int32_t *n_trees, const int32_t *n_groups,
-                                  const int32_t *tree_off, const int32_t *leaf_taxon,
-                                  const int32_t *adj_depth, const double *adj_val,
-                                  const double *tree_w, const int32_t *group_start, int32_t want_w,
-                                  int32_t *ticket_out, const scs_forest *src, const int32_t *relabel,
-                                  const level_src *lvl = nullptr);
-
-// The K small nodes of one level of the recursion straight from the level forest's resident tables
-// (scs_forest_split_level): nothing but the renumbering and the group boundaries travels.
-extern "C" int scs_small_solve_begin_level(scs_ctx *ctx, const scs_forest *forest, int32_t n_nodes,
-                                           const int32_t *t_begin, const int32_t *n_trees, const int64_t *n_leaves,
-                                           const int32_t *u_base, const int32_t *u_size, const int32_t *relabel,
-                                           const int32_t *n_taxa, const int32_t *n_groups,
-                                           const int32_t *group_start, int32_t want_w, int32_t *ticket_out) {
-    SCS_REQUIRE(ctx && forest && t_begin && n_trees && n_leaves && u_base && u_size && relabel && n_taxa && n_groups &&
-                    group_start && ticket_out,
-                "scs_small_solve_begin_level: null argument");
-    SCS_REQUIRE(forest->has_tables, "scs_small_solve_begin_level: the forest carries no tables");
-    for (int32_t k = 0; k < n_nodes; ++k) {
-        SCS_REQUIRE(t_begin[k] >= 0 && n_trees[k] >= 1 && (int64_t)t_begin[k] + n_trees[k] <= forest->n_trees,
-                    "scs_small_solve_begin_level: node %d: bad tree range", k);
-        SCS_REQUIRE(u_base[k] >= 0 && u_size[k] >= 1 && (int64_t)u_base[k] + u_size[k] <= forest->n_taxa,
-                    "scs_small_solve_begin_level: node %d: bad taxon range", k);
-        SCS_REQUIRE(n_leaves[k] >= 2 * (int64_t)n_trees[k] && n_leaves[k] <= (int64_t)n_trees[k] * n_taxa[k],
-                    "scs_small_solve_begin_level: node %d: bad leaf count", k);
-    }
-    level_src lvl{forest, t_begin, u_base, u_size, n_leaves, relabel};
-    return small_solve_begin_impl(ctx, n_nodes, n_taxa, n_trees, n_groups, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  group_start, want_w, ticket_out, nullptr, nullptr, &lvl);
-}
-
-extern "C" int scs_small_solve_begin(scs_ctx *ctx, int32_t n_nodes, const int32_t *n_taxa,
-                                     const int32_t *n_trees, const int32_t *n_groups,
-                                     const int32_t *tree_off, const int32_t *leaf_taxon,
-                                     const int32_t *adj_depth, const double *adj_val,
-                                     const double *tree_w, const int32_t *group_start, int32_t want_w,
-                                     int32_t *ticket_out) {
-    SCS_REQUIRE(ctx && n_taxa && n_trees && n_groups && tree_off && leaf_taxon && adj_depth &&
-                    adj_val && tree_w && group_start && ticket_out,
-                "scs_small_solve: null argument");
-    return small_solve_begin_impl(ctx, n_nodes, n_taxa, n_trees, n_groups, tree_off, leaf_taxon, adj_depth, adj_val,
-                                  tree_w, group_start, want_w, ticket_out, nullptr, nullptr);
-}
-
-// ONE node whose tables are resident (a child of scs_forest_split): nothing but the group boundaries
-// and the renumbering travels; the leaf arrays are packed on the device (k_small_pack)
-extern "C" int scs_small_solve_begin_forest(scs_ctx *ctx, const scs_forest *forest, const int32_t *relabel,
-                                            int32_t n_taxa, int32_t n_groups, const int32_t *group_start,
-                                            int32_t want_w, int32_t *ticket_out) {
-    SCS_REQUIRE(ctx && forest && group_start && ticket_out, "scs_small_solve_begin_forest: null argument");
-    SCS_REQUIRE(forest->has_tables, "scs_small_solve_begin_forest: the forest carries no tables (not a child of scs_forest_split)");
-    SCS_REQUIRE(forest->n_leaves <= INT32_MAX, "scs_small_solve_begin_forest: too many leaves");
-    const int32_t n_trees = forest->n_trees;
-    return small_solve_begin_impl(ctx, 1, &n_taxa, &n_trees, &n_groups, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  group_start, want_w, ticket_out, forest, relabel);
-}
-
-static int small_solve_begin_impl(scs_ctx *ctx, int32_t n_nodes, const int32_t *n_taxa,
-                                  const int32_t *n_trees, const int32_t *n_groups,
-                                  const int32_t *tree_off, const int32_t *leaf_taxon,
-                                  const int32_t *adj_depth, const double *adj_val,
-                                  const double *tree_w, const int32_t *group_start, int32_t want_w,
-                                  int32_t *ticket_out, const scs_forest *src, const int32_t *relabel,
-                                  const level_src *lvl) {
-    const bool w_out = want_w != 0;
-    SCS_REQUIRE(n_nodes >= 1, "scs_small_solve: need at least one node");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    // (a stream of its own: scs_internal.h)
-    const bool own_stream = true;
-    if (own_stream && !ctx->small_stream)
-        SCS_HIP_CHECK(hipStreamCreateWithFlags(&ctx->small_stream, hipStreamNonBlocking));
-    hipStream_t s = own_stream ? ctx->small_stream : ctx->stream;
-    const int K = n_nodes;
-    // ---- layout of the one staging block: [pointers | tree_off | group_start | leaf arrays |
-    // tree_w], 8-byte aligned pieces
-    std::vector<int32_t> tree_ptr(K + 1, 0), vertex_ptr(K + 1, 0);
-    std::vector<int64_t> leaf_ptr(K + 1, 0), w_ptr(K + 1, 0);
-    int64_t toff_at = 0;
-    bool any_big = false;  // nodes of more than MAXS taxa: k_small_finish_big
-    for (int k = 0; k < K; ++k) {
-        SCS_REQUIRE(n_taxa[k] >= 2 && n_taxa[k] <= SMALL_MAXS, "scs_small_solve: node %d has %d taxa (2..%d)",
-                    k, n_taxa[k], SMALL_MAXS);
-        any_big = any_big || n_taxa[k] > MAXS;
-        SCS_REQUIRE(n_groups[k] >= 2 && n_groups[k] <= n_taxa[k], "scs_small_solve: node %d: bad group count %d",
-                    k, n_groups[k]);
-        SCS_REQUIRE(n_trees[k] >= 1, "scs_small_solve: node %d has no tree", k);
-        const int32_t *to = (src || lvl) ? nullptr : tree_off + toff_at;
-        if (!src && !lvl) {
-            SCS_REQUIRE(to[0] == 0, "scs_small_solve: node %d: tree_off must start at 0", k);
-            for (int t = 0; t < n_trees[k]; ++t)
-                SCS_REQUIRE(to[t + 1] >= to[t] && to[t + 1] - to[t] <= n_taxa[k],
-                            "scs_small_solve: node %d tree %d: bad leaf range", k, t);
-        }
-        const int32_t *gs = group_start + vertex_ptr[k] + k;
-        SCS_REQUIRE(gs[0] == 0 && gs[n_groups[k]] == n_taxa[k], "scs_small_solve: node %d: group_start must span the taxa", k);
-        for (int g = 0; g < n_groups[k]; ++g)
-            SCS_REQUIRE(gs[g] < gs[g + 1], "scs_small_solve: node %d: empty group %d", k, g);
-        tree_ptr[k + 1] = tree_ptr[k] + n_trees[k];
-        leaf_ptr[k + 1] = leaf_ptr[k] + (lvl ? lvl->n_leaves[k] : src ? src->n_leaves : (int64_t)to[n_trees[k]]);
-        vertex_ptr[k + 1] = vertex_ptr[k] + n_groups[k];
-        w_ptr[k + 1] = w_ptr[k] + (int64_t)n_groups[k] * n_groups[k];
-        toff_at += n_trees[k] + 1;
-    }
-    const int64_t n_toff = toff_at, n_gs = vertex_ptr[K] + K, n_leaf = leaf_ptr[K], n_tree = tree_ptr[K];
-    // ---- work items: runs of trees for k_small_addends (enough runs to fill the chip, at
-    // least 16 trees each, whole groups of four), 256-cell pieces for k_small_sum
-    int per_item = (int)std::max<int64_t>(16, (n_tree + 1023) / 1024);
-    per_item = (per_item + 3) / 4 * 4;
-    std::vector<int32_t> item_node, item_t0, item_t1, sum_node, sum_e0;
-    std::vector<int64_t> add_ptr(K + 1, 0), w0_ptr(K + 1, 0);
-    for (int k = 0; k < K; ++k) {
-        const int64_t ncell = (int64_t)n_taxa[k] * n_taxa[k];
-        add_ptr[k + 1] = add_ptr[k] + ncell * (((int64_t)n_trees[k] + 1) & ~(int64_t)1);
-        w0_ptr[k + 1] = w0_ptr[k] + ncell;
-        for (int t = 0; t < n_trees[k]; t += per_item) {
-            item_node.push_back(k);
-            item_t0.push_back(t);
-            item_t1.push_back(std::min(n_trees[k], t + per_item));
-        }
-        for (int e = 0; e < ncell; e += 256) {
-            sum_node.push_back(k);
-            sum_e0.push_back(e);
-        }
-    }
-    const size_t n_items = item_node.size(), n_sums = sum_node.size();
-    SCS_REQUIRE((uint64_t)add_ptr[K] * 8 <= ((uint64_t)48 << 30),
-                "scs_small_solve: batch too large (%lld addends): pass fewer nodes per call",
-                (long long)add_ptr[K]);
-    auto up8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
-    size_t at = 0;
-    const size_t o_nt = at; at += up8((size_t)K * 4);
-    const size_t o_nm = at; at += up8((size_t)K * 4);
-    const size_t o_ng = at; at += up8((size_t)K * 4);
-    const size_t o_tp = at; at += up8((size_t)(K + 1) * 4);
-    const size_t o_vp = at; at += up8((size_t)(K + 1) * 4);
-    const size_t o_lp = at; at += (size_t)(K + 1) * 8;
-    const size_t o_wp = at; at += (size_t)(K + 1) * 8;
-    const size_t o_ap = at; at += (size_t)(K + 1) * 8;
-    const size_t o_w0p = at; at += (size_t)(K + 1) * 8;
-    const size_t o_in = at; at += up8(n_items * 4);
-    const size_t o_i0 = at; at += up8(n_items * 4);
-    const size_t o_i1 = at; at += up8(n_items * 4);
-    const size_t o_sn = at; at += up8(n_sums * 4);
-    const size_t o_s0 = at; at += up8(n_sums * 4);
-    const size_t o_to = at; at += up8((size_t)n_toff * 4);
-    const size_t o_gs = at; at += up8((size_t)n_gs * 4);
-    const size_t o_lt = at; at += up8((size_t)n_leaf * 4);
-    const size_t o_ad = at; at += up8((size_t)n_leaf * 4);
-    const size_t o_av = at; at += (size_t)n_leaf * 8;
-    const size_t o_tw = at; at += (size_t)n_tree * 8;
-    // (a resident node: the leaf arrays above are filled on the device; only the header travels --
-    // up to o_to -- and the renumbering behind it)
-    const size_t o_rl = at; if (src && relabel) at += up8((size_t)src->n_taxa * 4);
-    // a level: t_begin | u_base | rl_ptr [K] each, then the concatenated renumbering
-    std::vector<int32_t> rl_ptr(lvl ? K + 1 : 0, 0);
-    for (int k = 0; lvl && k < K; ++k) rl_ptr[k + 1] = rl_ptr[k] + lvl->u_size[k];
-    const size_t o_ltb = at; if (lvl) at += up8((size_t)K * 4);
-    const size_t o_lub = at; if (lvl) at += up8((size_t)K * 4);
-    const size_t o_lrp = at; if (lvl) at += up8((size_t)K * 4);
-    const size_t o_lrl = at; if (lvl) at += up8((size_t)rl_ptr[K] * 4);
-    const size_t in_bytes = at;
-    const size_t o_maps = at; at += (size_t)vertex_ptr[K] * 16;
-    const size_t o_lam = at; at += (size_t)K * 24;
-    const size_t o_w = at; if (w_out) at += (size_t)w_ptr[K] * 8;
-    const size_t total = at;
-    // a free slot that is large enough (the smallest such), else the largest free one (grown), else
-    // a new one
-    int pick = -1;
-    for (size_t i = 0; i < ctx->small_slots.size(); ++i) {
-        const auto &c = ctx->small_slots[i];
-        if (c.busy) continue;
-        if (pick < 0) {
-            pick = (int)i;
-            continue;
-        }
-        const auto &p = ctx->small_slots[pick];
-        const bool c_fits = c.cap >= total, p_fits = p.cap >= total;
-        if ((c_fits && (!p_fits || c.cap < p.cap)) || (!c_fits && !p_fits && c.cap > p.cap)) pick = (int)i;
-    }
-    if (pick < 0) {
-        ctx->small_slots.emplace_back();
-        pick = (int)ctx->small_slots.size() - 1;
-    }
-    scs_ctx::small_slot &slot = ctx->small_slots[pick];
-    if (slot.cap < total) {
-        if (slot.dev) scs_dev_free(slot.dev);
-        if (slot.host) hipHostFree(slot.host);
-        slot.dev = nullptr;
-        slot.host = nullptr;
-        slot.cap = 0;
-        const size_t cap = std::max<size_t>(total * 2, (size_t)1 << 20);
-        SCS_HIP_CHECK(scs_dev_malloc(ctx, (void **)&slot.dev, cap));
-        SCS_HIP_CHECK(hipHostMalloc((void **)&slot.host, cap, hipHostMallocDefault));
-        slot.cap = cap;
-    }
-    if (!slot.done) SCS_HIP_CHECK(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-    // device scratch: the addends (trees x cells per node) and the uncontracted weights
-    t_ctx = ctx;
-    const size_t add_bytes = ((size_t)std::max<int64_t>(add_ptr[K], 1) * 8 + 255) / 256 * 256;
-    const size_t w0_bytes = (size_t)std::max<int64_t>(w0_ptr[K], 1) * 8;
-    if (slot.scratch_cap < add_bytes + w0_bytes) {
-        if (slot.scratch) scs_dev_free(slot.scratch);
-        slot.scratch = nullptr;
-        slot.scratch_cap = 0;
-        const size_t cap = std::max<size_t>((add_bytes + w0_bytes) * 3 / 2, (size_t)1 << 20);
-        SCS_HIP_CHECK(scs_dev_malloc(ctx, (void **)&slot.scratch, cap));
-        slot.scratch_cap = cap;
-    }
-    unsigned char *h = slot.host, *d = slot.dev;
-    memcpy(h + o_nt, n_taxa, (size_t)K * 4);
-    memcpy(h + o_nm, n_trees, (size_t)K * 4);
-    memcpy(h + o_ng, n_groups, (size_t)K * 4);
-    memcpy(h + o_tp, tree_ptr.data(), (size_t)(K + 1) * 4);
-    memcpy(h + o_vp, vertex_ptr.data(), (size_t)(K + 1) * 4);
-    memcpy(h + o_lp, leaf_ptr.data(), (size_t)(K + 1) * 8);
-    memcpy(h + o_wp, w_ptr.data(), (size_t)(K + 1) * 8);
-    memcpy(h + o_ap, add_ptr.data(), (size_t)(K + 1) * 8);
-    memcpy(h + o_w0p, w0_ptr.data(), (size_t)(K + 1) * 8);
-    memcpy(h + o_in, item_node.data(), n_items * 4);
-    memcpy(h + o_i0, item_t0.data(), n_items * 4);
-    memcpy(h + o_i1, item_t1.data(), n_items * 4);
-    memcpy(h + o_sn, sum_node.data(), n_sums * 4);
-    memcpy(h + o_s0, sum_e0.data(), n_sums * 4);
-    memcpy(h + o_gs, group_start, (size_t)n_gs * 4);
-    if (lvl) {
-        // header and group boundaries, the level's per-node ranges and renumbering; the leaf arrays are
-        // packed on the device from the level forest's tables
-        memcpy(h + o_ltb, lvl->t_begin, (size_t)K * 4);
-        memcpy(h + o_lub, lvl->u_base, (size_t)K * 4);
-        memcpy(h + o_lrp, rl_ptr.data(), (size_t)K * 4);
-        memcpy(h + o_lrl, lvl->relabel, (size_t)rl_ptr[K] * 4);
-        SCS_HIP_CHECK(hipMemcpyAsync(d, h, o_to, hipMemcpyHostToDevice, s));
-        SCS_HIP_CHECK(hipMemcpyAsync(d + o_gs, h + o_gs, up8((size_t)n_gs * 4), hipMemcpyHostToDevice, s));
-        SCS_HIP_CHECK(hipMemcpyAsync(d + o_ltb, h + o_ltb, in_bytes - o_ltb, hipMemcpyHostToDevice, s));
-        level_pack lp;
-        lp.t_begin = (const int32_t *)(d + o_ltb);
-        lp.u_base = (const int32_t *)(d + o_lub);
-        lp.rl_ptr = (const int32_t *)(d + o_lrp);
-        lp.relabel = (const int32_t *)(d + o_lrl);
-        lp.tree_ptr = (const int32_t *)(d + o_tp);
-        lp.leaf_ptr = (const int64_t *)(d + o_lp);
-        const scs_forest *lf = lvl->forest;
-        const int64_t work = std::max<int64_t>(n_leaf, n_tree + K);
-        k_small_pack_level<<<(unsigned)((work + 255) / 256), 256, 0, s>>>(
-            lf->tree_off, lf->leaf_taxon, lf->adj_depth, lf->adj_val, lf->weights, lp, K, n_leaf, (int32_t)n_tree,
-            (int32_t *)(d + o_to), (int32_t *)(d + o_lt), (int32_t *)(d + o_ad), (double *)(d + o_av),
-            (double *)(d + o_tw));
-    } else if (!src) {
-        memcpy(h + o_to, tree_off, (size_t)n_toff * 4);
-        memcpy(h + o_lt, leaf_taxon, (size_t)n_leaf * 4);
-        memcpy(h + o_ad, adj_depth, (size_t)n_leaf * 4);
-        memcpy(h + o_av, adj_val, (size_t)n_leaf * 8);
-        memcpy(h + o_tw, tree_w, (size_t)n_tree * 8);
-        SCS_HIP_CHECK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
-    } else {
-        // header and group boundaries (two small pieces around the leaf arrays), the renumbering
-        SCS_HIP_CHECK(hipMemcpyAsync(d, h, o_to, hipMemcpyHostToDevice, s));
-        SCS_HIP_CHECK(hipMemcpyAsync(d + o_gs, h + o_gs, up8((size_t)n_gs * 4), hipMemcpyHostToDevice, s));
-        const int32_t *d_rl = nullptr;
-        if (relabel) {
-            memcpy(h + o_rl, relabel, (size_t)src->n_taxa * 4);
-            SCS_HIP_CHECK(hipMemcpyAsync(d + o_rl, h + o_rl, (size_t)src->n_taxa * 4, hipMemcpyHostToDevice, s));
-            d_rl = (const int32_t *)(d + o_rl);
-        }
-        const int64_t work = std::max<int64_t>(n_leaf, n_tree + 1);
-        k_small_pack<<<(unsigned)((work + 255) / 256), 256, 0, s>>>(
-            src->tree_off, src->leaf_taxon, src->adj_depth, src->adj_val, src->weights, d_rl, (int32_t)n_tree, n_leaf,
-            (int32_t *)(d + o_to), (int32_t *)(d + o_lt), (int32_t *)(d + o_ad), (double *)(d + o_av),
-            (double *)(d + o_tw));
-    }
-    small_batch sb;
-    sb.n_taxa = (const int32_t *)(d + o_nt);
-    sb.n_trees = (const int32_t *)(d + o_nm);
-    sb.n_groups = (const int32_t *)(d + o_ng);
-    sb.tree_ptr = (const int32_t *)(d + o_tp);
-    sb.vertex_ptr = (const int32_t *)(d + o_vp);
-    sb.leaf_ptr = (const int64_t *)(d + o_lp);
-    sb.w_ptr = (const int64_t *)(d + o_wp);
-    sb.add_ptr = (const int64_t *)(d + o_ap);
-    sb.w0_ptr = (const int64_t *)(d + o_w0p);
-    sb.item_node = (const int32_t *)(d + o_in);
-    sb.item_t0 = (const int32_t *)(d + o_i0);
-    sb.item_t1 = (const int32_t *)(d + o_i1);
-    sb.sum_node = (const int32_t *)(d + o_sn);
-    sb.sum_e0 = (const int32_t *)(d + o_s0);
-    sb.tree_off = (const int32_t *)(d + o_to);
-    sb.group_start = (const int32_t *)(d + o_gs);
-    sb.leaf_taxon = (const int32_t *)(d + o_lt);
-    sb.adj_depth = (const int32_t *)(d + o_ad);
-    sb.adj_val = (const double *)(d + o_av);
-    sb.tree_w = (const double *)(d + o_tw);
-    sb.maps = (double *)(d + o_maps);
-    sb.lambda = (double *)(d + o_lam);
-    sb.w_out = w_out ? (double *)(d + o_w) : nullptr;
-    sb.addends = (double *)slot.scratch;
-    sb.w0 = (double *)(slot.scratch + add_bytes);
-    k_small_addends<<<(unsigned)n_items, 256, 0, s>>>(sb);
-    k_small_sum<<<(unsigned)n_sums, 256, 0, s>>>(sb);
-    {
-        bool any_small = false, any_mid = false;
-        for (int k = 0; k < K; ++k) {
-            if (n_taxa[k] > MAXS) continue;
-            if (n_groups[k] > 24) any_mid = true;
-            else any_small = true;
-        }
-        if (any_small) k_small_finish<256><<<K, 256, 0, s>>>(sb);
-        if (any_mid) k_small_finish<1024><<<K, 1024, 0, s>>>(sb);
-    }
-    if (any_big) {
-        // (every node gets a workgroup of either kind; the one that is not its own returns at once)
-        SCS_HIP_CHECK(hipFuncSetAttribute((const void *)k_small_finish_big, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          DENSE2_MAX * DENSE2_LD * (int)sizeof(double)));
-        k_small_finish_big<<<K, 256, (size_t)DENSE2_MAX * DENSE2_LD * sizeof(double), s>>>(sb);
-    }
-    SCS_HIP_CHECK(hipGetLastError());
-    SCS_HIP_CHECK(hipMemcpyAsync(h + o_maps, d + o_maps, total - o_maps, hipMemcpyDeviceToHost, s));
-    SCS_HIP_CHECK(hipEventRecord(slot.done, s));
-    slot.busy = true;
-    slot.o_maps = o_maps;
-    slot.maps_bytes = (size_t)vertex_ptr[K] * 16;
-    slot.o_lam = o_lam;
-    slot.lam_bytes = (size_t)K * 24;
-    slot.o_w = o_w;
-    slot.w_bytes = w_out ? (size_t)w_ptr[K] * 8 : 0;
-    slot.o_to = o_to;
-    slot.o_lt = o_lt;
-    slot.o_ad = o_ad;
-    slot.o_av = o_av;
-    slot.o_tw = o_tw;
-    slot.n_toff = n_toff;
-    slot.n_leaf = n_leaf;
-    slot.n_tree = n_tree;
-    *ticket_out = pick;
-    return SCS_OK;
-}
-
-// The packed input arrays of a begun batch, copied from the slot's DEVICE block as k_small_addends reads them
-// (n_toff, n_leaf, n_leaf, n_leaf and n_tree entries; any pointer may be null) -- whichever entry began the
-// batch: packed on the host, by k_small_pack or by k_small_pack_level.  The ticket stays begun.
-extern "C" int scs_debug_small_inputs(scs_ctx *ctx, int32_t ticket, int32_t *tree_off, int32_t *leaf_taxon,
-                                      int32_t *adj_depth, double *adj_val, double *tree_w) {
-    SCS_REQUIRE(ctx != nullptr, "scs_debug_small_inputs: null context");
-    SCS_REQUIRE(ticket >= 0 && (size_t)ticket < ctx->small_slots.size() && ctx->small_slots[ticket].busy,
-                "scs_small_solve_end: no such ticket (%d)", ticket);
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    const scs_ctx::small_slot &slot = ctx->small_slots[ticket];
-    // (the batch's kernels and its copy back have run: nothing of the slot's is in flight behind the event)
-    SCS_HIP_CHECK(hipEventSynchronize(slot.done));
-    const unsigned char *d = slot.dev;
-    const size_t nl = (size_t)slot.n_leaf;
-    if (tree_off && slot.n_toff) SCS_HIP_CHECK(hipMemcpy(tree_off, d + slot.o_to, (size_t)slot.n_toff * 4, hipMemcpyDeviceToHost));
-    if (leaf_taxon && nl) SCS_HIP_CHECK(hipMemcpy(leaf_taxon, d + slot.o_lt, nl * 4, hipMemcpyDeviceToHost));
-    if (adj_depth && nl) SCS_HIP_CHECK(hipMemcpy(adj_depth, d + slot.o_ad, nl * 4, hipMemcpyDeviceToHost));
-    if (adj_val && nl) SCS_HIP_CHECK(hipMemcpy(adj_val, d + slot.o_av, nl * 8, hipMemcpyDeviceToHost));
-    if (tree_w && slot.n_tree) SCS_HIP_CHECK(hipMemcpy(tree_w, d + slot.o_tw, (size_t)slot.n_tree * 8, hipMemcpyDeviceToHost));
-    return SCS_OK;
-}
-
-extern "C" int scs_small_solve_end(scs_ctx *ctx, int32_t ticket, double *maps_out, double *lambda_out,
-                                   double *w_out) {
-    SCS_REQUIRE(ctx != nullptr, "scs_small_solve_end: null context");
-    SCS_REQUIRE(ticket >= 0 && (size_t)ticket < ctx->small_slots.size() && ctx->small_slots[ticket].busy,
-                "scs_small_solve_end: no such ticket (%d)", ticket);
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    scs_ctx::small_slot &slot = ctx->small_slots[ticket];
-    const hipError_t e = hipEventSynchronize(slot.done);
-    slot.busy = false;  // (whatever happened: the slot is the caller's no longer)
-    if (e != hipSuccess) {
-        scs_set_error("scs_small_solve: %s", hipGetErrorString(e));
-        return SCS_EHIP;
-    }
-    if (maps_out) memcpy(maps_out, slot.host + slot.o_maps, slot.maps_bytes);
-    if (lambda_out) memcpy(lambda_out, slot.host + slot.o_lam, slot.lam_bytes);
-    if (w_out && slot.w_bytes) memcpy(w_out, slot.host + slot.o_w, slot.w_bytes);
-    return SCS_OK;
-}
-
-extern "C" int scs_small_solve(scs_ctx *ctx, int32_t n_nodes, const int32_t *n_taxa,
-                               const int32_t *n_trees, const int32_t *n_groups,
-                               const int32_t *tree_off, const int32_t *leaf_taxon,
-                               const int32_t *adj_depth, const double *adj_val,
-                               const double *tree_w, const int32_t *group_start, double *maps_out,
-                               double *lambda_out, double *w_out) {
-    SCS_REQUIRE(maps_out && lambda_out, "scs_small_solve: null output");
-    int32_t ticket = -1;
-    SCS_TRY(scs_small_solve_begin(ctx, n_nodes, n_taxa, n_trees, n_groups, tree_off, leaf_taxon, adj_depth,
-                                  adj_val, tree_w, group_start, w_out != nullptr, &ticket));
-    return scs_small_solve_end(ctx, ticket, maps_out, lambda_out, w_out);
-}
-
-// ---------------------------------------------------------------------------
-// debug entry points (parity tests of the building blocks)
-// ---------------------------------------------------------------------------
-extern "C" int scs_debug_jacobi(scs_ctx *ctx, const double *a, int32_t n, double *w, double *v) {
-    SCS_REQUIRE(ctx && a && w && v, "scs_debug_jacobi: null argument");
-    SCS_REQUIRE(n >= 1 && n <= MAXS, "scs_debug_jacobi: n must be in [1, %d]", MAXS);
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    dbuf da, dw, dv;
-    SCS_TRY(da.alloc((size_t)n * n * 8));
-    SCS_TRY(dw.alloc((size_t)n * 8));
-    SCS_TRY(dv.alloc((size_t)n * n * 8));
-    SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * n * 8, hipMemcpyHostToDevice, ctx->stream));
-    k_small_eig<<<1, 256, 0, ctx->stream>>>(da.d(), n, dw.d(), dv.d());
-    SCS_HIP_CHECK(hipMemcpyAsync(w, dw.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipMemcpyAsync(v, dv.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SCS_OK;
-}
-
-extern "C" int scs_debug_gram(scs_ctx *ctx, const double *a, const double *b, int32_t n,
-                              int32_t ka, int32_t kb, int32_t use_mfma, double *out) {
-    SCS_REQUIRE(ctx && a && b && out, "scs_debug_gram: null argument");
-    SCS_REQUIRE(n >= 1 && ka >= 1 && ka <= 48 && kb >= 1 && kb <= 48, "scs_debug_gram: bad shape");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    solver sv;
-    sv.ctx = ctx;
-    sv.s = ctx->stream;
-    sv.n = n;
-    sv.gram_blocks = 256;
-    dbuf da, db, dout;
-    SCS_TRY(da.alloc((size_t)n * ka * 8));
-    SCS_TRY(db.alloc((size_t)n * kb * 8));
-    SCS_TRY(dout.alloc((size_t)ka * kb * 8));
-    SCS_TRY(sv.part.alloc((size_t)1024 * 48 * 48 * 8));
-    SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * ka * 8, hipMemcpyHostToDevice, ctx->stream));
-    SCS_HIP_CHECK(hipMemcpyAsync(db.p, b, (size_t)n * kb * 8, hipMemcpyHostToDevice, ctx->stream));
-    SCS_TRY(sv.gram(da.d(), ka, ka, db.d(), kb, kb, dout.d(), use_mfma != 0));
-    SCS_HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)ka * kb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SCS_OK;
-}
-
-extern "C" int scs_debug_apply(scs_ctx *ctx, scs_graph *g, const double *x, int32_t b, double *y) {
-    SCS_REQUIRE(ctx && g && x && y, "scs_debug_apply: null argument");
-    SCS_REQUIRE(b == 4 || b == 8 || b == 12 || b == 16, "scs_debug_apply: b must be 4, 8, 12 or 16");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    SCS_TRY(scs_graph_prepare_degrees(ctx, g));
-    solver sv;
-    sv.ctx = ctx;
-    sv.g = g;
-    sv.s = ctx->stream;
-    sv.n = g->n;
-    sv.b = b;
-    sv.rows = g->row_end - g->row_begin;
-    sv.world = ctx->comm.world;
-    const int n = g->n;
-    dbuf dx;
-    SCS_TRY(dx.alloc((size_t)n * b * 8));
-    SCS_TRY(sv.alloc_symm_buffers());
-    // (an SCS_BUILD_UPPER graph: collective, the product comes back for all V rows and this
-    // rank's slice of it is returned)
-    SCS_TRY(sv.yloc.alloc((size_t)(g->upper ? n : sv.rows) * b * 8));
-    SCS_HIP_CHECK(hipMemcpyAsync(dx.p, x, (size_t)n * b * 8, hipMemcpyHostToDevice, ctx->stream));
-    k_scale_rows<<<(n * b + 255) / 256, 256, 0, ctx->stream>>>(dx.d(), b, 0, b, n, g->d_dinv,
-                                                               sv.z.d(), sv.ldz);
-    SCS_TRY(sv.launch_symm(sv.z.d(), sv.yloc.d()));
-    SCS_HIP_CHECK(hipMemcpyAsync(y, sv.yloc.d() + (g->upper ? (size_t)g->row_begin * b : 0),
-                                 (size_t)sv.rows * b * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SCS_OK;
-}
-
-// scs_debug_apply with ONE solver object for `reps` applications (the tile lists alternate as in the loop),
-// optionally on the single-precision image, and a report of what ran
-extern "C" int scs_debug_apply_ex(scs_ctx *ctx, scs_graph *g, const double *x, int32_t b, int32_t image,
-                                  int32_t reps, double *y_out, int32_t *info_out) {
-    SCS_REQUIRE(ctx && g && x && y_out && info_out, "scs_debug_apply_ex: null argument");
-    SCS_REQUIRE(b == 4 || b == 8 || b == 12 || b == 16, "scs_debug_apply_ex: b must be 4, 8, 12 or 16");
-    SCS_REQUIRE(reps >= 1 && reps <= 64, "scs_debug_apply_ex: reps must be in [1, 64]");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    if (image) {
-        SCS_REQUIRE(!g->mf, "scs_debug_apply_ex: a matrix-free graph has no image");
-        SCS_REQUIRE(b == 4, "scs_debug_apply_ex: the image is streamed at block width 4 (asked: %d)", b);
-        SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, true));
-    }
-    SCS_TRY(scs_graph_prepare_degrees(ctx, g));
-    solver sv;
-    sv.ctx = ctx;
-    sv.g = g;
-    sv.s = ctx->stream;
-    sv.n = g->n;
-    sv.b = b;
-    sv.rows = g->row_end - g->row_begin;
-    sv.world = ctx->comm.world;
-    const int n = g->n;
-    dbuf dx;
-    SCS_TRY(dx.alloc((size_t)n * b * 8));
-    SCS_TRY(sv.alloc_symm_buffers());
-    if (image) {
-        // scs_fiedler's own condition for streaming the image: nothing else is ever run on it
-        const bool usable = g->have_w32 && n >= 4096 &&
-                            (sv.tri ? sv.tri_ct == 2 : (sv.world > 1 && !g->upper && !sv.part_mode));
-        if (!usable) {
-            scs_set_error("scs_debug_apply_ex: no image for this graph (%s)",
-                          !g->have_w32 ? "it could not be made" : "the solver does not stream one at this size");
-            return SCS_EUNSUP;
-        }
-        sv.use32 = true;
-    }
-    const size_t out_rows = (size_t)(g->upper ? n : sv.rows);
-    SCS_TRY(sv.yloc.alloc(out_rows * b * 8));
-    SCS_HIP_CHECK(hipMemcpyAsync(dx.p, x, (size_t)n * b * 8, hipMemcpyHostToDevice, ctx->stream));
-    k_scale_rows<<<(n * b + 255) / 256, 256, 0, ctx->stream>>>(dx.d(), b, 0, b, n, g->d_dinv, sv.z.d(), sv.ldz);
-    int tiles = 0;
-    for (int r = 0; r < reps; ++r) {
-        // every application has to write every partial sum it adds up: what an earlier one left must not
-        // stand in for a tile that was dropped
-        if (sv.tri) {  // (the sizes alloc_symm_buffers gave them)
-            const size_t slab = (size_t)n * b * 8;
-            const size_t n_rb = g->upper ? (size_t)(sv.tri_rb_hi - sv.tri_rb_lo) : (size_t)((n + TRI_TH - 1) / TRI_TH);
-            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_pdir.p, 0xFF, (size_t)std::max(sv.tri_nct, sv.tri32_nct) * slab,
-                                         ctx->stream));
-            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_ptr.p, 0xFF, n_rb * slab, ctx->stream));
-        }
-        if (!g->mf) SCS_HIP_CHECK(hipMemsetAsync(sv.ypart.p, 0xFF, sv.ypart_cap * 8, ctx->stream));
-        SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0xFF, out_rows * b * 8, ctx->stream));
-        SCS_TRY(sv.launch_symm(sv.z.d(), sv.yloc.d()));
-        SCS_HIP_CHECK(hipMemcpyAsync(y_out + (size_t)r * sv.rows * b,
-                                     sv.yloc.d() + (g->upper ? (size_t)g->row_begin * b : 0),
-                                     (size_t)sv.rows * b * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (sv.tri) tiles = sv.use32 ? sv.tri32_ntiles : sv.tri_ntiles;
-    info_out[0] = sv.tri ? 1 : 0;
-    info_out[1] = sv.use32 ? 1 : 0;
-    info_out[2] = tiles;
-    info_out[3] = sv.last_nseg;
-    info_out[4] = sv.tri ? (sv.use32 ? 512 : sv.tri_ct * 128) : 0;
-    info_out[5] = sv.n_apply32;
-    info_out[6] = sv.part_mode ? 1 : 0;
-    info_out[7] = g->mf ? 1 : 0;
-    return SCS_OK;
-}
-
-// The operator as a multi-rank solve assembles it (collective): the solver is set up as scs_fiedler sets it up,
-// S is applied to the R block of the host panel q by solver::apply (path 0) or solver::fused_back with
-// fold_pass2 off (path 1), `reps` times on one solver object, and every application returns the R slot of AQ
-// -- all V rows, as THIS rank holds them after the gather
-extern "C" int scs_debug_team_apply(scs_ctx *ctx, scs_graph *g, const double *q, const double *aq, int32_t b,
-                                    int32_t path, int32_t image, int32_t reps, double *y_out, double *qaq_out,
-                                    double *part_out, int64_t *info_out) {
-    // (argument checks: the same verdict on every rank, before the first collective)
-    SCS_REQUIRE(ctx && g && q && aq && y_out && info_out, "scs_debug_team_apply: null argument");
-    SCS_REQUIRE(!g->mf, "scs_debug_team_apply: a matrix-free graph is solved on one rank");
-    SCS_REQUIRE(path == 0 || path == 1, "scs_debug_team_apply: path must be 0 (apply) or 1 (fused_back)");
-    SCS_REQUIRE(b == 4 || b == 8 || b == 12 || b == 16, "scs_debug_team_apply: b must be 4, 8, 12 or 16");
-    SCS_REQUIRE(path == 0 || b == 4 || b == 8, "scs_debug_team_apply: the fused loop takes block widths 4 and 8 (asked: %d)", b);
-    SCS_REQUIRE(path == 0 || qaq_out, "scs_debug_team_apply: path 1 returns Q^T AQ");
-    SCS_REQUIRE(!g->upper || part_out, "scs_debug_team_apply: an SCS_BUILD_UPPER graph returns its partial product");
-    SCS_REQUIRE(reps >= 1 && reps <= 64, "scs_debug_team_apply: reps must be in [1, 64]");
-    SCS_REQUIRE(!image || b == 4, "scs_debug_team_apply: the image is streamed at block width 4 (asked: %d)", b);
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    hipStream_t s = ctx->stream;
-    const int n = g->n, q3 = 3 * b;
-    // scs_fiedler's own condition for a row-partitioned rank to stream the image of its rows
-    const bool image_rows = ctx->comm.world > 1 && !g->upper && n >= 4096 && b == 4;
-    SCS_TRY(scs_graph_prepare_degrees_begin(ctx, g, image && image_rows));
-    SCS_TRY(scs_graph_prepare_degrees(ctx, g));
-
-    solver sv;
-    sv.ctx = ctx;
-    sv.g = g;
-    sv.s = s;
-    sv.n = n;
-    sv.b = b;
-    sv.rows = g->row_end - g->row_begin;
-    sv.world = ctx->comm.world;
-    sv.gram_blocks = 256;
-    SCS_TRY(gather_full_rows(ctx, g, sv.splits));
-    int max_rows = 0;
-    for (int r = 0; r < sv.world; ++r) max_rows = std::max(max_rows, sv.splits[r + 1] - sv.splits[r]);
-    sv.chunk = g->upper ? (int64_t)n * b : (int64_t)max_rows * b;
-    // (from here on every refusal is the same on all ranks and no collective lies behind it)
-    SCS_TRY(sv.alloc_symm_buffers());
-    if (image) {
-        if (!image_rows || !g->have_w32) {
-            scs_set_error("scs_debug_team_apply: no image for this graph (%s)",
-                          image_rows ? "it could not be made" : "the solver does not stream one in this layout or at this size");
-            return SCS_EUNSUP;
-        }
-        sv.use32 = true;
-    }
-    SCS_TRY(sv.q.alloc((size_t)n * q3 * 8));
-    SCS_TRY(sv.aq.alloc((size_t)n * q3 * 8));
-    SCS_TRY(sv.yloc.alloc((size_t)sv.chunk * 8));
-    SCS_TRY(sv.part2.alloc((size_t)1024 * q3 * q3 * 8));
-    SCS_TRY(sv.small.alloc((size_t)SM_TOTAL * 8));
-    const bool rows_mode = sv.world > 1 && !sv.part_mode;
-    if (rows_mode) {
-        SCS_TRY(sv.yfull.alloc((size_t)n * b * 8));
-        SCS_TRY(sv.recv.alloc((size_t)sv.chunk * sv.world * 8));
-        SCS_TRY(sv.splits_d.alloc((size_t)(sv.world + 1) * 4));
-        SCS_HIP_CHECK(hipMemcpyAsync(sv.splits_d.p, sv.splits.data(), (size_t)(sv.world + 1) * 4,
-                                     hipMemcpyHostToDevice, s));
-    }
-    SCS_HIP_CHECK(hipMemcpyAsync(sv.q.p, q, (size_t)n * q3 * 8, hipMemcpyHostToDevice, s));
-    SCS_HIP_CHECK(hipMemcpyAsync(sv.aq.p, aq, (size_t)n * q3 * 8, hipMemcpyHostToDevice, s));
-    double *G = sv.small_at(SM_G);
-    const size_t slab = (size_t)n * b * 8;
-    for (int r = 0; r < reps; ++r) {
-        // whatever an application adds up or unpacks it has to have written itself: a tail of a chunk, a slab or
-        // a row that nobody wrote is NaN in the product, not what the application before left there
-        if (sv.tri) {  // (the sizes alloc_symm_buffers gave them)
-            const size_t n_rb = sv.part_mode ? (size_t)(sv.tri_rb_hi - sv.tri_rb_lo) : (size_t)((n + TRI_TH - 1) / TRI_TH);
-            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_pdir.p, 0xFF, (size_t)std::max(sv.tri_nct, sv.tri32_nct) * slab, s));
-            SCS_HIP_CHECK(hipMemsetAsync(sv.tri_ptr.p, 0xFF, n_rb * slab, s));
-        }
-        if (sv.ysend.p) SCS_HIP_CHECK(hipMemsetAsync(sv.ysend.p, 0xFF, slab, s));
-        if (sv.recv.p) SCS_HIP_CHECK(hipMemsetAsync(sv.recv.p, 0xFF, (size_t)sv.chunk * sv.world * 8, s));
-        if (sv.yfull.p) SCS_HIP_CHECK(hipMemsetAsync(sv.yfull.p, 0xFF, slab, s));
-        SCS_HIP_CHECK(hipMemsetAsync(sv.ypart.p, 0xFF, sv.ypart_cap * 8, s));
-        SCS_HIP_CHECK(hipMemsetAsync(sv.yloc.p, 0xFF, (size_t)sv.chunk * 8, s));
-        SCS_HIP_CHECK(hipMemset2DAsync(sv.aq.d() + 2 * b, (size_t)q3 * 8, 0xFF, (size_t)b * 8, (size_t)n, s));
-        if (path == 0) {
-            SCS_TRY(sv.apply(sv.q.d(), 2 * b, sv.aq.d(), 2 * b));
-        } else {
-            int nparts = 0;
-            k_scale_rows<<<(n * b + 255) / 256, 256, 0, s>>>(sv.q.d(), q3, 2 * b, b, n, g->d_dinv, sv.z.d(), sv.ldz);
-            if (b == 4) {
-                SCS_TRY(sv.fused_back<4>(&nparts, sv.part2.d()));
-            } else {
-                SCS_TRY(sv.fused_back<8>(&nparts, sv.part2.d()));
-            }
-            k_reduce_partials<<<(q3 * q3 + 3) / 4, 256, 0, s>>>(sv.part2.d(), nparts, q3 * q3, G);
-            SCS_HIP_CHECK(hipGetLastError());
-            SCS_HIP_CHECK(hipMemcpyAsync(qaq_out + (size_t)r * q3 * q3, G, (size_t)q3 * q3 * 8,
-                                         hipMemcpyDeviceToHost, s));
-        }
-        SCS_HIP_CHECK(hipGetLastError());
-        SCS_HIP_CHECK(hipMemcpy2DAsync(y_out + (size_t)r * n * b, (size_t)b * 8, sv.aq.d() + 2 * b, (size_t)q3 * 8,
-                                       (size_t)b * 8, (size_t)n, hipMemcpyDeviceToHost, s));
-        if (sv.part_mode)
-            SCS_HIP_CHECK(hipMemcpyAsync(part_out + (size_t)r * n * b, sv.ysend.p, slab, hipMemcpyDeviceToHost, s));
-        // (a peer reads this rank's send buffer inside the gather: nothing is refilled before all have met there,
-        // and the in-process gather ends with such a meeting)
-        SCS_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    info_out[0] = sv.part_mode ? 1 : 0;
-    info_out[1] = path;
-    info_out[2] = sv.world;
-    info_out[3] = sv.chunk;
-    info_out[4] = sv.last_nseg;
-    info_out[5] = sv.tri ? sv.tri_ntiles : 0;
-    info_out[6] = sv.n_apply32;
-    info_out[7] = sv.n_allgather;
-    return SCS_OK;
-}
-
-// scs_debug_gram on column sub-blocks of wider host panels, with the caller's count of partials
-extern "C" int scs_debug_gram_ex(scs_ctx *ctx, const double *a, int32_t lda, int32_t a_col0, int32_t ka,
-                                 const double *b, int32_t ldb, int32_t b_col0, int32_t kb, int32_t n,
-                                 int32_t use_mfma, int32_t gram_blocks, double *out) {
-    SCS_REQUIRE(ctx && a && b && out, "scs_debug_gram_ex: null argument");
-    SCS_REQUIRE(n >= 1 && ka >= 1 && ka <= 48 && kb >= 1 && kb <= 48, "scs_debug_gram_ex: bad shape");
-    SCS_REQUIRE(a_col0 >= 0 && a_col0 + ka <= lda && b_col0 >= 0 && b_col0 + kb <= ldb,
-                "scs_debug_gram_ex: the column block leaves the panel");
-    SCS_REQUIRE(gram_blocks >= 1 && gram_blocks <= 1024, "scs_debug_gram_ex: gram_blocks must be in [1, 1024]");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    solver sv;
-    sv.ctx = ctx;
-    sv.s = ctx->stream;
-    sv.n = n;
-    sv.gram_blocks = gram_blocks;
-    const bool same = a == b && lda == ldb;  // two blocks of one panel, as gram(Q, 3b, 2b, R, 3b, b)
-    dbuf da, db, dout;
-    SCS_TRY(da.alloc((size_t)n * lda * 8));
-    if (!same) SCS_TRY(db.alloc((size_t)n * ldb * 8));
-    SCS_TRY(dout.alloc((size_t)ka * kb * 8));
-    SCS_TRY(sv.part.alloc((size_t)1024 * 48 * 48 * 8));
-    SCS_HIP_CHECK(hipMemsetAsync(sv.part.p, 0xFF, (size_t)1024 * 48 * 48 * 8, ctx->stream));
-    SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * lda * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (!same) SCS_HIP_CHECK(hipMemcpyAsync(db.p, b, (size_t)n * ldb * 8, hipMemcpyHostToDevice, ctx->stream));
-    SCS_TRY(sv.gram(da.d() + a_col0, lda, ka, (same ? da.d() : db.d()) + b_col0, ldb, kb, dout.d(), use_mfma != 0));
-    SCS_HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)ka * kb * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SCS_OK;
-}
-
-// one k_update launch on host operands; the whole y panel travels both ways
-extern "C" int scs_debug_update(scs_ctx *ctx, double *y, int32_t ldy, int32_t y_col0, int32_t kc, double alpha,
-                                const double *a, int32_t lda, int32_t a_col0, int32_t ka, const double *c,
-                                int32_t ldc, double sign, int32_t n) {
-    SCS_REQUIRE(ctx && y && a && c, "scs_debug_update: null argument");
-    SCS_REQUIRE(n >= 1 && kc >= 1 && kc <= MAXB && ka >= 1 && ka <= 3 * MAXB, "scs_debug_update: bad shape");
-    SCS_REQUIRE(y_col0 >= 0 && y_col0 + kc <= ldy && a_col0 >= 0 && a_col0 + ka <= lda && ldc >= kc,
-                "scs_debug_update: the column block leaves the panel");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    solver sv;
-    sv.ctx = ctx;
-    sv.s = ctx->stream;
-    sv.n = n;
-    const bool same = a == y && lda == ldy;  // in place, or two blocks of one panel
-    dbuf dy, da, dc;
-    SCS_TRY(dy.alloc((size_t)n * ldy * 8));
-    if (!same) SCS_TRY(da.alloc((size_t)n * lda * 8));
-    SCS_TRY(dc.alloc((size_t)ka * ldc * 8));
-    SCS_HIP_CHECK(hipMemcpyAsync(dy.p, y, (size_t)n * ldy * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (!same) SCS_HIP_CHECK(hipMemcpyAsync(da.p, a, (size_t)n * lda * 8, hipMemcpyHostToDevice, ctx->stream));
-    SCS_HIP_CHECK(hipMemcpyAsync(dc.p, c, (size_t)ka * ldc * 8, hipMemcpyHostToDevice, ctx->stream));
-    SCS_TRY(sv.update(dy.d() + y_col0, ldy, kc, alpha, (same ? dy.d() : da.d()) + a_col0, lda, ka, dc.d(), ldc, sign));
-    SCS_HIP_CHECK(hipMemcpyAsync(y, dy.p, (size_t)n * ldy * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SCS_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return SCS_OK;
-}
-
-// ---- the loop's small solves and tall panel kernels, one launch each
-// Every output and every scratch buffer starts as 0xFF bytes (NaN, -1): what the launch did not write shows.
-static int debug_upload(dbuf &d, const void *host, size_t bytes, hipStream_t s) {
-    SCS_TRY(d.alloc(bytes));
-    SCS_HIP_CHECK(hipMemcpyAsync(d.p, host, bytes, hipMemcpyHostToDevice, s));
-    return SCS_OK;
-}
-static int debug_blank(dbuf &d, size_t bytes, hipStream_t s) {
-    SCS_TRY(d.alloc(bytes));
-    SCS_HIP_CHECK(hipMemsetAsync(d.p, 0xFF, bytes, s));
-    return SCS_OK;
-}
-static int debug_download(void *host, const dbuf &d, size_t bytes, hipStream_t s) {
-    if (host) SCS_HIP_CHECK(hipMemcpyAsync(host, d.p, bytes, hipMemcpyDeviceToHost, s));
-    return SCS_OK;
-}
-
-// small_rr_body with the register-and-shuffle path switched off: nq = 3b at b = 4, 8 on the general path
-__global__ __launch_bounds__(256) void k_debug_small_rr_general(const double *__restrict__ tm, int nparts, int nq,
-                                                                 int b, const int *__restrict__ mask,
-                                                                 double *__restrict__ c, double *__restrict__ d,
-                                                                 double *__restrict__ theta,
-                                                                 int *__restrict__ mask_p, double drop_tol,
-                                                                 int exact_from) {
-    small_rr_body(tm, nparts, nq, b, mask, c, d, theta, mask_p, drop_tol, exact_from, false);
-}
-
-// the projected SVQB on the compact layout of one width, declared and called as k_symm_tri_tf does
-template <int B>
-__global__ __launch_bounds__(256) void k_debug_small_orth_compact(const double *__restrict__ partial, int nparts,
-                                                                   double drop_tol, double *__restrict__ coef,
-                                                                   int *__restrict__ mask,
-                                                                   const double *__restrict__ theta, double *report,
-                                                                   double seq) {
-    __shared__ orth_small_lds<B> L;
-    small_orth_core(L, partial, nparts, B, drop_tol, L.coef, mask, theta, report, seq);
-    __syncthreads();
-    for (int e = threadIdx.x; e < PANEL_COEF_ROWS<B> * B; e += 256) coef[e] = L.coef[e];
-}
-
-extern "C" int scs_debug_small_svqb(scs_ctx *ctx, const double *g, int32_t k, double drop_tol, double *t_out,
-                                    int32_t *mask_out) {
-    SCS_REQUIRE(ctx && g && t_out && mask_out, "scs_debug_small_svqb: null argument");
-    SCS_REQUIRE(k >= 1 && k <= MAXS, "scs_debug_small_svqb: k must be in [1, %d]", MAXS);
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    hipStream_t s = ctx->stream;
-    dbuf dg, dt, dm;
-    SCS_TRY(debug_upload(dg, g, (size_t)k * k * 8, s));
-    SCS_TRY(debug_blank(dt, (size_t)k * k * 8, s));
-    SCS_TRY(debug_blank(dm, (size_t)k * 4, s));
-    k_small_svqb<<<1, 256, 0, s>>>(dg.d(), k, drop_tol, dt.d(), (int *)dm.p);
-    SCS_HIP_CHECK(hipGetLastError());
-    SCS_TRY(debug_download(t_out, dt, (size_t)k * k * 8, s));
-    SCS_TRY(debug_download(mask_out, dm, (size_t)k * 4, s));
-    SCS_HIP_CHECK(hipStreamSynchronize(s));
-    return SCS_OK;
-}
-
-extern "C" int scs_debug_small_rr(scs_ctx *ctx, const double *tm, int32_t nparts, int32_t nq, int32_t b,
-                                  const int32_t *mask, double drop_tol, int32_t exact_from, int32_t start,
-                                  double *c_out, double *d_out, double *theta_out, int32_t *mask_p_out,
-                                  int32_t *mask_out) {
-    SCS_REQUIRE(ctx && tm && c_out && d_out && theta_out && mask_p_out && mask_out,
-                "scs_debug_small_rr: null argument");
-    SCS_REQUIRE(start >= 0 && start <= 2, "scs_debug_small_rr: start must be 0 (k_small_rr), 1 (k_small_rr_start) "
-                                          "or 2 (k_small_rr's body on the general path)");
-    SCS_REQUIRE(b >= 1 && b <= MAXB && nq >= b && nq <= 3 * b, "scs_debug_small_rr: need 1 <= b <= %d, b <= nq <= 3b",
-                MAXB);
-    SCS_REQUIRE(nparts >= 0 && nparts <= 1024, "scs_debug_small_rr: nparts must be in [0, 1024]");
-    SCS_REQUIRE(nparts == 0 || nq <= 24, "scs_debug_small_rr: partials are summed for nq <= 24 only (asked: %d)", nq);
-    SCS_REQUIRE(exact_from >= -1 && exact_from <= nq, "scs_debug_small_rr: exact_from must be in [-1, nq]");
-    SCS_REQUIRE(start != 1 || (nq == b && nparts == 0 && exact_from < 0),
-                "scs_debug_small_rr: k_small_rr_start solves nq = b on one matrix");
-    SCS_REQUIRE(start == 1 || mask, "scs_debug_small_rr: null mask");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    hipStream_t s = ctx->stream;
-    const size_t nt = (size_t)std::max(1, nparts) * nq * nq;
-    dbuf dtm, dmask, dc, dd, dth, dmp;
-    SCS_TRY(debug_upload(dtm, tm, nt * 8, s));
-    SCS_TRY(debug_blank(dmask, 48 * 4, s));
-    SCS_TRY(debug_blank(dc, (size_t)nq * b * 8, s));
-    SCS_TRY(debug_blank(dd, (size_t)nq * b * 8, s));
-    SCS_TRY(debug_blank(dth, (size_t)(b + 1) * 8, s));
-    SCS_TRY(debug_blank(dmp, (size_t)b * 4, s));
-    if (start != 1) SCS_HIP_CHECK(hipMemcpyAsync(dmask.p, mask, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    int *mk = (int *)dmask.p, *mp = (int *)dmp.p;
-    if (start == 1)
-        k_small_rr_start<<<1, 256, 0, s>>>(dtm.d(), b, mk, dc.d(), dd.d(), dth.d(), drop_tol);
-    else if (start == 2)
-        k_debug_small_rr_general<<<1, 256, 0, s>>>(dtm.d(), nparts, nq, b, mk, dc.d(), dd.d(), dth.d(), mp, drop_tol,
-                                                   exact_from);
-    else
-        k_small_rr<<<1, 256, 0, s>>>(dtm.d(), nparts, nq, b, mk, dc.d(), dd.d(), dth.d(), mp, drop_tol, exact_from);
-    SCS_HIP_CHECK(hipGetLastError());
-    SCS_TRY(debug_download(c_out, dc, (size_t)nq * b * 8, s));
-    SCS_TRY(debug_download(d_out, dd, (size_t)nq * b * 8, s));
-    SCS_TRY(debug_download(theta_out, dth, (size_t)(b + 1) * 8, s));
-    SCS_TRY(debug_download(mask_p_out, dmp, (size_t)b * 4, s));
-    SCS_TRY(debug_download(mask_out, dmask, 48 * 4, s));
-    SCS_HIP_CHECK(hipStreamSynchronize(s));
-    return SCS_OK;
-}
-
-extern "C" int scs_debug_small_orth(scs_ctx *ctx, const double *partial, int32_t nparts, int32_t b, double drop_tol,
-                                    const double *theta, int32_t layout, double *coef_out, int32_t *mask_out,
-                                    double *report_out) {
-    SCS_REQUIRE(ctx && partial && theta && coef_out && mask_out && report_out, "scs_debug_small_orth: null argument");
-    SCS_REQUIRE(layout == 0 || layout == 1, "scs_debug_small_orth: layout must be 0 (general) or 1 (compact)");
-    // (orth_lds holds cxp[16][8], gm[9][8]: the projected SVQB exists for the fused loop's widths only)
-    SCS_REQUIRE(b >= 1 && b <= 8, "scs_debug_small_orth: the projected SVQB takes block widths up to 8 (asked: %d)", b);
-    SCS_REQUIRE(layout == 0 || b == 4 || b == 8, "scs_debug_small_orth: the compact layout is built for widths 4 and 8");
-    SCS_REQUIRE(nparts >= 1 && nparts <= 1024, "scs_debug_small_orth: nparts must be in [1, 1024]");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    hipStream_t s = ctx->stream;
-    const size_t nout = (size_t)3 * b * b + b, ncoef = (size_t)(3 * b + 4) * b;
-    const double seq = 7.0;
-    dbuf dp, dth, dco, dm, drep;
-    SCS_TRY(debug_upload(dp, partial, (size_t)nparts * nout * 8, s));
-    SCS_TRY(debug_upload(dth, theta, (size_t)(b + 1) * 8, s));
-    SCS_TRY(debug_blank(dco, ncoef * 8, s));
-    SCS_TRY(debug_blank(dm, (size_t)b * 4, s));
-    SCS_TRY(debug_blank(drep, 41 * 8, s));
-    if (layout == 0)
-        k_small_orth<<<1, 256, 0, s>>>(dp.d(), nparts, b, drop_tol, dco.d(), (int *)dm.p, dth.d(), drep.d(), seq);
-    else if (b == 4)
-        k_debug_small_orth_compact<4><<<1, 256, 0, s>>>(dp.d(), nparts, drop_tol, dco.d(), (int *)dm.p, dth.d(),
-                                                         drep.d(), seq);
-    else
-        k_debug_small_orth_compact<8><<<1, 256, 0, s>>>(dp.d(), nparts, drop_tol, dco.d(), (int *)dm.p, dth.d(),
-                                                         drep.d(), seq);
-    SCS_HIP_CHECK(hipGetLastError());
-    SCS_TRY(debug_download(coef_out, dco, ncoef * 8, s));
-    SCS_TRY(debug_download(mask_out, dm, (size_t)b * 4, s));
-    SCS_TRY(debug_download(report_out, drep, 41 * 8, s));
-    SCS_HIP_CHECK(hipStreamSynchronize(s));
-    return SCS_OK;
-}
-
-template <int B>
-static int debug_panel_fused(int which, int n, int nb, double *q, double *aq, const double *u, const double *ca,
-                             const double *cb, const double *theta, const double *dinv, const double *ypart,
-                             int nseg, double *part, double *zt, int64_t ldz, hipStream_t s) {
-    switch (which) {
-    case 0: k_panel_rr<B><<<nb, 256, 0, s>>>(q, aq, u, ca, cb, theta, n, part); break;
-    case 1: k_panel_tf<B, true, false><<<nb, 256, 0, s>>>(q, u, ca, n, part, nullptr, nullptr, 0); break;
-    case 2: k_panel_tf<B, false, true><<<nb, 256, 0, s>>>(q, u, ca, n, nullptr, dinv, zt, ldz); break;
-    case 3: k_gram_qaq<B, 0><<<nb, 256, 0, s>>>(q, aq, n, nullptr, 0, nullptr, part); break;
-    default: k_gram_qaq<B, 1><<<nb, 256, 0, s>>>(q, aq, n, ypart, nseg, dinv, part); break;
-    }
-    SCS_HIP_CHECK(hipGetLastError());
-    return SCS_OK;
-}
-
-extern "C" int scs_debug_panel(scs_ctx *ctx, int32_t which, int32_t b, int32_t n, const double *q, const double *aq,
-                               const double *u, const double *coef_a, const double *coef_b, const double *theta,
-                               const double *dinv, const double *ypart, int32_t nseg, int32_t blocks, double *q_out,
-                               double *aq_out, double *partial_out, double *zt_out) {
-    SCS_REQUIRE(ctx && q && aq, "scs_debug_panel: null panel");
-    SCS_REQUIRE(which >= 0 && which <= 6, "scs_debug_panel: which must be in [0, 6]");
-    const bool fused = which <= 4;
-    SCS_REQUIRE(fused ? (b == 4 || b == 8) : (b == 4 || b == 8 || b == 12 || b == 16),
-                "scs_debug_panel: kernel %d does not take block width %d", which, b);
-    SCS_REQUIRE(n >= 1 && n <= (1 << 24), "scs_debug_panel: n must be in [1, 2^24]");
-    SCS_REQUIRE(!fused || (blocks >= 1 && blocks <= PANEL_BLOCKS_MAX), "scs_debug_panel: blocks must be in [1, %d]",
-                PANEL_BLOCKS_MAX);
-    SCS_REQUIRE((which != 0 && which != 1 && which != 2 && which != 5) || coef_a, "scs_debug_panel: null coefficients");
-    SCS_REQUIRE((which != 0 && which != 5) || coef_b, "scs_debug_panel: null coefficients");
-    SCS_REQUIRE((which != 0 && which != 6) || theta, "scs_debug_panel: null theta");
-    SCS_REQUIRE((which != 2 && which != 4) || dinv, "scs_debug_panel: null dinv");
-    SCS_REQUIRE(which != 2 || zt_out, "scs_debug_panel: null zt_out");
-    SCS_REQUIRE(which != 4 || (ypart && nseg >= 1 && nseg <= 4), "scs_debug_panel: FINISH 1 sums 1 ... 4 segments");
-    SCS_REQUIRE(which == 2 || which == 5 || partial_out, "scs_debug_panel: null partial_out");
-    SCS_HIP_CHECK(hipSetDevice(ctx->device));
-    t_ctx = ctx;
-    hipStream_t s = ctx->stream;
-    const int pad = SCS_DEBUG_PANEL_PAD;
-    const size_t rows = (size_t)n + pad, ld = (size_t)3 * b;
-    const size_t ncoef = which == 1 || which == 2 ? (size_t)(3 * b + 4) * b : ld * b;
-    const int nb = which == 5 ? (n + 15) / 16 : (which == 6 ? (n + 255) / 256 : blocks);
-    const size_t nper = which <= 1 ? (size_t)3 * b * b + b : (which == 6 ? (size_t)b : ld * ld);
-    dbuf dq, daq, du, dca, dcb, dth, ddi, dyp, dpart, dzt;
-    SCS_TRY(debug_upload(dq, q, rows * ld * 8, s));
-    SCS_TRY(debug_upload(daq, aq, rows * ld * 8, s));
-    if (u) SCS_TRY(debug_upload(du, u, rows * 8, s));
-    if (coef_a) SCS_TRY(debug_upload(dca, coef_a, ncoef * 8, s));
-    if (coef_b) SCS_TRY(debug_upload(dcb, coef_b, ncoef * 8, s));
-    if (theta) SCS_TRY(debug_upload(dth, theta, (size_t)b * 8, s));
-    if (dinv) SCS_TRY(debug_upload(ddi, dinv, rows * 8, s));
-    if (which == 4) SCS_TRY(debug_upload(dyp, ypart, ((size_t)nseg * n + pad) * b * 8, s));
-    SCS_TRY(debug_blank(dpart, (size_t)nb * nper * 8, s));
-    if (which == 2) SCS_TRY(debug_upload(dzt, zt_out, (size_t)b * rows * 8, s));
-    const double *up = u ? du.d() : nullptr;
-    if (which == 5) {
-        k_rr_update<<<nb, 256, 0, s>>>(dq.d(), b, 3 * b, dca.d(), dcb.d(), n);
-        SCS_HIP_CHECK(hipGetLastError());
-    } else if (which == 6) {
-        k_residual<<<nb, 256, 0, s>>>(dq.d(), daq.d(), b, dth.d(), n, dpart.d());
-        SCS_HIP_CHECK(hipGetLastError());
-    } else if (b == 4) {
-        SCS_TRY(debug_panel_fused<4>(which, n, nb, dq.d(), daq.d(), up, dca.d(), dcb.d(), dth.d(), ddi.d(), dyp.d(),
-                                     nseg, dpart.d(), dzt.d(), (int64_t)rows, s));
-    } else {
-        SCS_TRY(debug_panel_fused<8>(which, n, nb, dq.d(), daq.d(), up, dca.d(), dcb.d(), dth.d(), ddi.d(), dyp.d(),
-                                     nseg, dpart.d(), dzt.d(), (int64_t)rows, s));
-    }
-    SCS_TRY(debug_download(q_out, dq, rows * ld * 8, s));
-    SCS_TRY(debug_download(aq_out, daq, rows * ld * 8, s));
-    if (which != 2 && which != 5) SCS_TRY(debug_download(partial_out, dpart, (size_t)nb * nper * 8, s));
-    if (which == 2) SCS_TRY(debug_download(zt_out, dzt, (size_t)b * rows * 8, s));
-    SCS_HIP_CHECK(hipStreamSynchronize(s));
-    return SCS_OK;
-}
-
-
-// The loop's decision rules on a scripted sequence of residuals (no device): actions_out[i] = 0 go on, 1 stop
-// (the NEXT residual of the script is then taken as the confirmation's: the loop ends there or goes on in double
-// precision), 2 renew, 3 = ended converged, 4 = ended not converged; entries behind the end are -1.
-extern "C" int scs_debug_loop_policy(double tol, int32_t lowp_mode, double lowp_tol, double lowp_tol2,
-                                     int32_t image, int32_t n, const double *residuals, int32_t *actions_out) {
-    SCS_REQUIRE(residuals && actions_out && n >= 0, "scs_debug_loop_policy: bad arguments");
-    scs_loop_policy p;
-    p.tol = tol;
-    p.lowp_mode = lowp_mode;
-    p.lowp_tol = lowp_tol;
-    p.lowp_tol2 = lowp_tol2;
-    p.lowp_state = image ? 1 : 0;
-    bool ended = false;
-    for (int32_t i = 0; i < n; ++i) {
-        if (ended) {
-            actions_out[i] = -1;
-            continue;
-        }
-        const int a = p.step(residuals[i]);
-        actions_out[i] = a;
-        if (a == scs_loop_policy::STOP) {
-            if (!p.begin_confirmation()) {
-                actions_out[i] = residuals[i] <= tol ? 3 : 4;
-                ended = true;
-            } else if (i + 1 < n) {
-                bool conv = false;
-                ++i;
-                if (p.confirm(residuals[i], &conv)) {
-                    actions_out[i] = conv ? 3 : 4;
-                    ended = true;
-                } else {
-                    actions_out[i] = 0;
-                }
-            }
-        }
-    }
-    return SCS_OK;
-}
+#include "scs_eig_small.h"
+#include "scs_eig_debug.h"

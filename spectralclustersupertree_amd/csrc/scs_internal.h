@@ -269,7 +269,7 @@ struct scs_graph {
     double dd_norm = 0.0;  // ||sqrt(deg)||_2 with isolated rows counted as 1
 };
 
-// ---- source forests in HBM (scs_forest.hip; scs_eig.hip packs a small node's tables from one) ----
+// ---- source forests in HBM (scs_forest.hip; scs_eig_small.h packs a small node's tables from one) ----
 #include <memory>
 // device arrays a split leaves behind for ALL children: one allocation each, children are slices
 struct forest_region {
@@ -322,6 +322,6 @@ void scs_matfree_release(scs_graph *g);
 int scs_gather_row_splits(scs_ctx *ctx, int32_t row_begin, int32_t row_end, int32_t n,
                           std::vector<int32_t> &splits);
 
-// eig.hip helpers used by debug entry points are declared in scs_hip.h
+// (the eigen-solver's debug entry points, scs_eig_debug.h, are declared in scs_hip.h)
 
 static inline int64_t scs_round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }

@@ -9,7 +9,8 @@
 #include <algorithm>
 
 struct scs_loop_policy {
-    // ---- the rules' constants (scs_fiedler reads SCS_LOWP* into the three lowp_* fields)
+    // ---- the rules' constants (lobpcg::setup fills the three lowp_* fields: SCS_LOWP from the solve's loop_plan, the two
+    // thresholds as written there)
     double tol = 1e-13;        // ||S x - lambda x|| target of the wanted pair(s)
     int lowp_mode = 2;         // 0 no image, 1 image up to the first renewal, 2 image throughout
     double lowp_tol = 1e-8;    // residual at which S X / S P are renewed through W (first renewal)

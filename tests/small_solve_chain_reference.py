@@ -31,7 +31,7 @@ from __future__ import annotations
 import numpy as np
 from solver_reference import LD, SENTINEL, U, require_extended_precision, worst  # noqa: F401
 
-DROP_TOL = 1e-13  # scs_fiedler's drop_tol (csrc/scs_eig.hip)
+DROP_TOL = 1e-13  # the loop's drop_tol (csrc/scs_eig.hip, lobpcg::drop_tol)
 PAD = 16  # SCS_DEBUG_PANEL_PAD
 
 SVQB_SIZES = (1, 2, 4, 8, 12, 16, 24, 64)

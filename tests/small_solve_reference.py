@@ -1,5 +1,5 @@
 """Reference, checks and cases for the batched small-node solve (``scs_small_solve*``: ``k_small_addends`` ->
-``k_small_sum`` -> ``k_small_finish<256|1024>`` / ``k_small_finish_big`` in ``csrc/scs_eig.hip``).  A helper module:
+``k_small_sum`` -> ``k_small_finish<256|1024>`` / ``k_small_finish_big`` in ``csrc/scs_eig_small.h``).  A helper module:
 pytest collects nothing here, and nothing here needs a device.  DESIGN.md section 21.
 
 The reference of a node is built from its contracted W (fp64: the kernel's ``w_out``, bit for bit the oracle's) in
@@ -34,7 +34,7 @@ FIEDLER_TOL = 1e-10
 TIE_REL = 1e-9
 GAP = 1e-6  # below this distance of lambda_1, lambda_2, lambda_3 the eigenvectors are not compared entry by entry
 
-SMALL_TR_MAX = 24  # csrc/scs_eig.hip: the addend layout changes above this many TAXA (and k_small_finish<256> gives
+SMALL_TR_MAX = 24  # csrc/scs_eig_small.h: the addend layout changes above this many TAXA (and k_small_finish<256> gives
 #                    way to <1024> above as many VERTICES)
 TWO_SIDED_MAX = 64  # ... and k_small_finish to k_small_finish_big above this many TAXA
 STRATEGIES = ("one", "depth", "branch", "bootstrap")

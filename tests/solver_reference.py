@@ -42,7 +42,7 @@ UPDATE_PATTERNS = ("u", "in_place", "q_r")
 JACOBI_SIZES = (2, 3, 4, 5, 7, 8, 12, 16, 23, 24, 36, 48, 64)
 JACOBI_FAMILIES = ("zero", "identity", "rank_one", "repeated", "cluster", "graded", "ritz", "gauss_1e+150",
                    "gauss_1e-150", "ritz_separated")
-# scs_fiedler sets `gram_blocks = 256` for every n (csrc/scs_eig.hip, "sv.gram_blocks = 256"): the product's value
+# scs_fiedler sets `gram_blocks = 256` for every n (csrc/scs_eig.hip, solver::bind: "gram_blocks = 256"): the product's value
 # and the old hook's coincide.  The others: one partial, the panel kernels' cap, and what the partials buffer holds.
 FIEDLER_GRAM_BLOCKS = 256
 GRAM_BLOCKS = (FIEDLER_GRAM_BLOCKS, 1, 128, 1024)

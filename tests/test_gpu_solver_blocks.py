@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import solver_reference as ref
 
+from spectralclustersupertree_amd import _native as nv
 from spectralclustersupertree_amd import synthetic
 from spectralclustersupertree_amd.backend import Device
 
@@ -127,12 +128,33 @@ def test_symmetric_schedule_with_graded_columns(dev, mode):
     _tri_case(dev, "full", 4607, mode, graded=True)
 
 
-def test_the_image_is_refused_where_the_solver_streams_none(dev):
+def _default_solve(g, monkeypatch, block: int) -> dict:
+    for name in ("SCS_LOWP", "SCS_LOWP_MAX_BYTES", "SCS_SPLIT_SMALL", "SCS_FOLD_PASS2", "SCS_LEGACY_LOOP"):
+        monkeypatch.delenv(name, raising=False)
+    try:
+        return g.fiedler(None, block=block)[1]
+    except nv.ConvergenceError as e:
+        return e.stats
+
+
+def test_the_image_is_refused_where_the_solver_streams_none(dev, monkeypatch):
     g, _ = _graph(dev, "full", 513)
     with pytest.raises(RuntimeError, match="scs_debug_apply_ex"):
         g.apply_ex(ref.apply_vectors(513, 4, 1), image=True)
     with pytest.raises(RuntimeError, match="block width 4"):
         g.apply_ex(ref.apply_vectors(513, 8, 1), image=True)
+    # one predicate (solver::image_layout) answers the export and scs_fiedler: held where it switches, by both
+    g, _ = _graph(dev, "full", 4095)
+    with pytest.raises(RuntimeError, match="no image"):
+        g.apply_ex(ref.apply_vectors(4095, 4, 1), image=True)
+    assert _default_solve(g, monkeypatch, 4)["n_apply32"] == 0
+    g, _ = _graph(dev, "full", 4096)
+    _, info = g.apply_ex(ref.apply_vectors(4096, 4, 1), image=True)
+    assert info["image"] == 1, info
+    assert _default_solve(g, monkeypatch, 4)["n_apply32"] > 0
+    with pytest.raises(RuntimeError, match="block width 4"):
+        g.apply_ex(ref.apply_vectors(4096, 8, 1), image=True)
+    assert _default_solve(g, monkeypatch, 8)["n_apply32"] == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------
