@@ -370,6 +370,28 @@ int scs_score_source_pairs(scs_ctx *ctx, const scs_tables *sources, int32_t n_ro
                            int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *common, int32_t *clusters,
                            int32_t *clusters_other, int32_t *shared);
 
+/* Pairwise rooted-triplet terms of the source trees on shared taxa: the two-sided restriction of
+ * scs_score_source_pairs joined to the node-pair sum of scs_score_triplets.  `sources`, `rows`, `n_rows` and
+ * max_batch_trees as for scs_score_source_pairs.  For a row tree A and a column tree B, with L = L(A) ∩ L(B) and
+ * c = |L|, a triple {a, b, d} of L is resolved ab|d in a tree when one of its clusters holds a and b but not d:
+ *   common[A][B] = c (int32),
+ *   triplets[A][B] = the triples of L that A resolves, triplets_other[A][B] = those that B resolves,
+ *   triplets_shared[A][B] = those both resolve the same way (int64; the total is C(c, 3)).
+ *   c < 3: the three counts are 0.  A against itself: all three are equal.  Every count is exact and unweighted.
+ * Outputs: n_rows x n_trees, row-major; any of them may be null (without triplets_shared no node pair is swept).
+ * With rows NULL only the pairs A <= B are computed and the cell (B, A) gets the cell (A, B) with triplets and
+ * triplets_other swapped.
+ * max_lds_bytes > 0 caps the LDS of a workgroup (tests): the sweep takes fewer nodes of B a workgroup, down to one,
+ * and a pair whose restriction needs more runs from its region of the call's block.  max_chunk_pairs > 0 caps the
+ * pairs whose restricted trees lie in the workspace at once (tests); 0: sized by bytes.
+ * SCS_EINVAL: the cases of scs_score_source_pairs, a negative knob, a pair of trees whose smaller one has more than
+ * 327 679 leaves (the two bitset rows of one node of B must fit the 160 KiB of a workgroup) or, with max_lds_bytes,
+ * more than its rows hold -- both decided on the host before any kernel runs. */
+int scs_score_source_pair_triplets(scs_ctx *ctx, const scs_tables *sources, int32_t n_rows, const int32_t *rows,
+                                   int32_t max_batch_trees, int32_t max_lds_bytes, int32_t max_chunk_pairs,
+                                   int32_t *common, int64_t *triplets, int64_t *triplets_other,
+                                   int64_t *triplets_shared);
+
 /* Triple coverage of the sources: which taxa are ever seen together.
  * `sources` are tables as for scs_score_source_pairs.  Only `tree_off` and `leaf_taxon` are read.  n = the tables'
  * `n_taxa`.
@@ -1029,6 +1051,29 @@ int scs_debug_parsimony_plan(const scs_tables *sources, int32_t n_trees, const i
 int scs_debug_source_pairs_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
                                 int32_t n_rows, int32_t max_batch_trees, int32_t max_lds_bytes, int32_t *n_batches_out,
                                 int32_t *bstart_out, int64_t *info_out, int64_t *tile_out);
+
+/* The plan of one scs_score_source_pair_triplets call on the host, by the functions the export calls.  Trees as for
+ * scs_debug_source_pairs_plan; n_rows, rows and the three knobs as for the export (the chunks depend on which trees
+ * the rows are).  Batches as scs_debug_source_pairs_plan reports them without an LDS cap.
+ * info_out[8] = {levels of the per-tree min tables, stride of a dense position row in entries, the LDS bytes a
+ * workgroup may take, the common taxa up to which a pair is finished in the restrict kernel (64), workspace bytes of
+ * the call with all four outputs asked for, of which the regions of a chunk, the workgroups one launch may have, the
+ * chunks of the call}.
+ * tile_out (may be NULL; room for n_batches x n_batches x 12), per row batch I and column batch J (zeros: no launch):
+ *   {rows of the tile, the common taxa a pair of it may have (the smaller of its largest row and column tree),
+ *    words of a bitset row, nodes of B a sweep workgroup takes (zb), dynamic LDS bytes of the sweep launch,
+ *    dynamic LDS bytes of the restrict launch, 1 when the tile also launches the restrict kernel over the regions,
+ *    the LDS bytes its largest pair's restriction needs, bytes of a pair's region, pairs of a chunk at most,
+ *    pairs of the tile (rows x column trees), chunks of the tile}.
+ * chunk_out (may be NULL; room for 8 x the chunks, which a first call returns in info_out[7]), in launch order:
+ *   {I, J, first pair of the tile (row-major), pairs (= workgroups of the restrict launch), of which pairs the host
+ *    knows to finish in the restrict kernel (the smaller tree has at most 64 leaves), of which pairs the mirror
+ *    leaves out, workgroups of the sweep launch, rows of the tile the chunk touches}.
+ * SCS_EINVAL also for the sizes the export refuses, with its message. */
+int scs_debug_source_pair_triplets_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off,
+                                        int32_t n_taxa, int32_t n_rows, const int32_t *rows, int32_t max_batch_trees,
+                                        int32_t max_lds_bytes, int32_t max_chunk_pairs, int32_t *n_batches_out,
+                                        int32_t *bstart_out, int64_t *info_out, int64_t *tile_out, int64_t *chunk_out);
 
 /* The plan of one scs_score_coverage call on the host, by the functions the export calls.  `sources` or, when it is
  * NULL, n_trees and n_taxa (tree_off is not read: the plan depends on the tree count alone).  n_rows < 0 stands for

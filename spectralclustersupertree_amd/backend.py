@@ -346,6 +346,36 @@ class Device:
         nv.check(rc)
         return out
 
+    def score_source_pair_triplets(self, sources, rows=None, batch_trees: int = 0, lds_bytes: int = 0,
+                                   chunk_pairs: int = 0,
+                                   outputs=("common", "triplets", "triplets_other", "triplets_shared")) -> dict:
+        """``scs_score_source_pair_triplets``: the rooted-triplet terms between every two source trees, each pair
+        restricted to the taxa both hold.  ``sources`` and ``rows`` as for ``score_source_pairs``.  Returns ``common``
+        (int32) and ``triplets``, ``triplets_other``, ``triplets_shared`` (int64), rows x trees (None for a name
+        ``outputs`` leaves out).  ``batch_trees`` > 0 caps the trees of a row and of a column batch, ``lds_bytes`` > 0
+        the LDS of a workgroup, ``chunk_pairs`` > 0 the pairs restricted at once (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        m = tabs.n_trees
+        if rows is None:
+            n_rows, row_ptr = m, None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.ndim != 1:
+                msg = "rows must be a list of tree ids"
+                raise ValueError(msg)
+            n_rows, row_ptr = len(rows), nv.iptr(rows)
+        names = ("common", "triplets", "triplets_other", "triplets_shared")
+        out = {k: np.zeros((n_rows, m), dtype=np.int32 if k == "common" else np.int64) if k in outputs else None
+               for k in names}
+        rc = self._lib.scs_score_source_pair_triplets(self._ctx, tabs._h, n_rows, row_ptr, int(batch_trees),
+                                                      int(lds_bytes), int(chunk_pairs),
+                                                      *(None if v is None else v.ctypes.data for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_source_pair_triplets: invalid input")
+        nv.check(rc)
+        return out
+
     def score_coverage(self, sources, rows=None, min_trees: int = 1, pairs: bool = False, batch_rows: int = 0,
                        reg_words: int = 0, outputs=("occurs", "taxon_covered")) -> dict:
         """``scs_score_coverage``: the triple coverage of the sources.  ``sources`` as for ``score`` (only their trees'
@@ -945,6 +975,43 @@ def debug_source_pairs_plan(sources, n_taxa: int = 0, n_rows: int | None = None,
             "width": tiles[:, :, 0].copy(), "lds": tiles[:, :, 1].copy(), "slab": tiles[:, :, 2].copy(),
             "need": tiles[:, :, 3].copy(), "threads": tiles[:, :, 4].copy(), "grid_limit": tiles[:, :, 5].copy(),
             "rows_per_launch": tiles[:, :, 6].copy()}
+
+
+def debug_source_pair_triplets_plan(sources, n_taxa: int = 0, rows=None, batch_trees: int = 0, lds_bytes: int = 0,
+                                    chunk_pairs: int = 0) -> dict:
+    """``scs_debug_source_pair_triplets_plan``: the plan of ``scs_score_source_pair_triplets`` for ``sources`` (as for
+    ``debug_source_pairs_plan``) and ``rows`` (tree ids; None: every tree) -- ``bstart``; per tile (row batch x column
+    batch; zeros: no launch) ``tile_rows``, ``max_common``, ``words``, ``zb``, ``lds_pairs``, ``lds_restrict``,
+    ``slab``, ``need``, ``pair_bytes``, ``chunk_cap``, ``pairs``, ``n_chunks``; ``chunks``, one row per chunk in launch
+    order: I, J, first pair, pairs, small pairs, mirrored pairs, sweep workgroups, rows; once ``levels``,
+    ``row_stride``, ``lds_cap``, ``small_common``, ``workspace``, ``region_bytes``, ``grid_limit``.  The library's own
+    arithmetic, on the host; ``ValueError`` for the sizes the export refuses."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+    lib = nv.load_library()
+    nb = C.c_int32(0)
+    bstart = np.zeros(m + 1, dtype=np.int32)
+    info = np.zeros(8, dtype=np.int64)
+    args = (handle, m, None if off is None else nv.lptr(off), int(n_taxa), m if rows is None else len(rows),
+            None if rows is None else nv.iptr(rows), int(batch_trees), int(lds_bytes), int(chunk_pairs), C.byref(nb),
+            nv.iptr(bstart), nv.lptr(info))
+    rc = lib.scs_debug_source_pair_triplets_plan(*args, None, None)  # (the batches and the chunk count first)
+    if rc == nv.EINVAL:
+        raise ValueError(lib.scs_last_error().decode())
+    nv.check(rc)
+    k = int(nb.value)
+    tiles = np.zeros((k, k, 12), dtype=np.int64)
+    chunks = np.zeros((int(info[7]), 8), dtype=np.int64)
+    nv.check(lib.scs_debug_source_pair_triplets_plan(*args, nv.lptr(tiles), nv.lptr(chunks)))
+    keys = ("levels", "row_stride", "lds_cap", "small_common", "workspace", "region_bytes", "grid_limit")
+    names = ("tile_rows", "max_common", "words", "zb", "lds_pairs", "lds_restrict", "slab", "need", "pair_bytes",
+             "chunk_cap", "pairs", "n_chunks")
+    return {"bstart": bstart[: k + 1].astype(np.int64), **{key: int(info[i]) for i, key in enumerate(keys)},
+            **{name: tiles[:, :, i].copy() for i, name in enumerate(names)}, "chunks": chunks}
 
 
 def debug_coverage_plan(sources, n_taxa: int = 0, n_rows: int | None = None, min_trees: int = 1, batch_rows: int = 0,

@@ -118,6 +118,9 @@ from spectralclustersupertree_amd import __version__
               help="Also write a TSV with one row per pair of source trees that share 3 taxa or more (tree_a, tree_b, "
                    "common, clusters_a, clusters_b, shared, rf, normalized_rf): the Robinson-Foulds terms between the "
                    "two trees restricted to the taxa both hold.")
+@click.option("--source-triplets", is_flag=True,
+              help="With --source-distances-out: also the rooted-triplet terms of every pair (triplets_a, triplets_b, "
+                   "triplets_shared, triplet_distance, normalized_triplet_distance), the graded measure beside RF.")
 @click.option("--min-common", default=3, type=click.IntRange(min=3), show_default=True,
               help="The fewest shared taxa of a pair --source-distances-out lists (3: every pair that has a cluster to "
                    "compare; the library's mean_distance and outlier_sources start at 4, where two trees can differ).")
@@ -139,7 +142,8 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         resolve_first: bool = False, branch_resample: int = 0, resample_seed: int = 0, jackknife: bool = False,
         branch_support_out: str | None = None, parsimony: bool = False,
         source_clades_out: str | None = None, source_distances_out: str | None = None,
-        min_common: int = 3, coverage_out: str | None = None, coverage_min_trees: int = 1) -> None:
+        source_triplets: bool = False, min_common: int = 3, coverage_out: str | None = None,
+        coverage_min_trees: int = 1) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
     if branch_resample and not (branches_out or branch_support_out):
         msg = "--branch-resample needs --branches-out or --branch-support-out"
@@ -152,6 +156,9 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         raise click.UsageError(msg)
     if refine_log and not refined_out:
         msg = "--refine-log needs --refined-out"
+        raise click.UsageError(msg)
+    if source_triplets and not source_distances_out:
+        msg = "--source-triplets needs --source-distances-out"
         raise click.UsageError(msg)
     if triplets and not scores_out:
         msg = "--triplets needs --scores-out"
@@ -241,7 +248,8 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         if source_distances_out:
             from spectralclustersupertree_amd.score import source_distances
 
-            Path(source_distances_out).write_text(source_distances(sources).table(min_common))
+            distances = source_distances(sources, triplets=source_triplets)
+            Path(source_distances_out).write_text(distances.table(min_common))
         if coverage_out:
             from spectralclustersupertree_amd.score import source_coverage
 

@@ -4584,4 +4584,5 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
 
 #include "scs_score_parsimony.h"
 #include "scs_score_pairs.h"
+#include "scs_score_pair_triplets.h"
 #include "scs_score_coverage.h"

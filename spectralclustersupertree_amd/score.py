@@ -159,7 +159,9 @@ Every count comes from the HIP kernels behind ``scs_score_supertree``, ``scs_sco
 ``scs_score_parsimony`` and (for ``refine_supertree``) ``scs_score_clade_moves``; the host only validates and lays out.
 
 ``source_distances`` measures the sources against one another instead: the same RF terms between every two source
-trees, each pair restricted to the taxa both hold (``scs_score_source_pairs``).
+trees, each pair restricted to the taxa both hold (``scs_score_source_pairs``), and with
+``triplets=True`` the rooted-triplet terms of every pair, the graded measure beside RF
+(``scs_score_source_pair_triplets``).
 ``source_coverage`` asks the earlier question, whether the sources overlap enough to determine a tree at all: the
 rooted triples of taxa that some source tree holds whole (``scs_score_coverage``).
 """
@@ -1788,7 +1790,11 @@ class SourceDistances:
     (``source_distances``).  Row i is tree ``rows[i]`` of the trees as given, column j tree j.
     With L the taxa both trees hold and C(X|L) the distinct sets cl(v) ∩ L of 2 <= size < |L| over the nodes v of X:
     ``common`` = |L|, ``clusters`` = |C(row|L)|, ``clusters_other`` = |C(column|L)|, ``shared`` = the sets in both
-    (int32, rows x trees; fewer than 3 common taxa: zeros beside ``common``)."""
+    (int32, rows x trees; fewer than 3 common taxa: zeros beside ``common``).
+
+    With ``triplets=True`` also the rooted-triplet terms of every pair (int64, rows x trees, None
+    otherwise): ``triplets`` / ``triplets_other`` = the triples of L that the row / column tree resolves,
+    ``triplets_shared`` = those both resolve the same way."""
 
     common: np.ndarray
     clusters: np.ndarray
@@ -1797,6 +1803,9 @@ class SourceDistances:
     rows: np.ndarray
     n_leaves: np.ndarray
     timings: dict = field(default_factory=dict)
+    triplets: np.ndarray | None = None
+    triplets_other: np.ndarray | None = None
+    triplets_shared: np.ndarray | None = None
 
     @property
     def rf(self) -> np.ndarray:
@@ -1808,23 +1817,57 @@ class SourceDistances:
         """``rf`` / (``clusters`` + ``clusters_other``); NaN where neither restricted tree has a cluster."""
         return _normalized(self.rf, self.clusters.astype(np.int64) + self.clusters_other)
 
-    def _comparable(self, min_common: int) -> np.ndarray:
-        ok = (self.common >= int(min_common)) & ~np.isnan(self.normalized_rf)
+    def _need_triplets(self) -> None:
+        if self.triplets is None or self.triplets_other is None or self.triplets_shared is None:
+            msg = "the triplet matrices are not there: ask source_distances for triplets=True"
+            raise ValueError(msg)
+
+    @property
+    def triples_total(self) -> np.ndarray:
+        """C(``common``, 3): the triples of every pair's common taxa (int64)."""
+        c = self.common.astype(np.int64)
+        return c * (c - 1) * (c - 2) // 6
+
+    @property
+    def triplet_distance(self) -> np.ndarray:
+        """The triples of every pair's common taxa that one tree resolves and the other does not resolve that way
+        (int64): ``triplets`` + ``triplets_other`` - 2 ``triplets_shared``."""
+        self._need_triplets()
+        return self.triplets + self.triplets_other - 2 * self.triplets_shared
+
+    @property
+    def normalized_triplet_distance(self) -> np.ndarray:
+        """``triplet_distance`` / (``triplets`` + ``triplets_other``); NaN where neither restricted tree resolves a
+        triple."""
+        return _normalized(self.triplet_distance, self.triplets + self.triplets_other)
+
+    def _normalized_by(self, by: str) -> np.ndarray:
+        if by == "rf":
+            return self.normalized_rf
+        if by == "triplets":
+            self._need_triplets()
+            return self.normalized_triplet_distance
+        msg = f"by must be 'rf' or 'triplets', not {by!r}"
+        raise ValueError(msg)
+
+    def _comparable(self, min_common: int, by: str = "rf") -> np.ndarray:
+        ok = (self.common >= int(min_common)) & ~np.isnan(self._normalized_by(by))
         ok[np.arange(len(self.rows)), self.rows] = False  # (a tree is not compared with itself)
         return ok
 
-    def mean_distance(self, min_common: int = 4) -> tuple[np.ndarray, np.ndarray]:
-        """``(mean, comparable)`` per row: the mean normalized RF to the other trees that share at least
-        ``min_common`` taxa with it (and have a cluster to compare; NaN when there is none) and how many those are."""
-        ok = self._comparable(min_common)
+    def mean_distance(self, min_common: int = 4, by: str = "rf") -> tuple[np.ndarray, np.ndarray]:
+        """``(mean, comparable)`` per row: the mean normalized RF (``by="triplets"``: the mean normalized triplet
+        distance) to the other trees that share at least ``min_common`` taxa with it (and have a cluster, or a
+        resolved triple, to compare; NaN when there is none) and how many those are."""
+        ok = self._comparable(min_common, by)
         comparable = ok.sum(axis=1).astype(np.int64)
-        total = np.where(ok, np.nan_to_num(self.normalized_rf), 0.0).sum(axis=1)
+        total = np.where(ok, np.nan_to_num(self._normalized_by(by)), 0.0).sum(axis=1)
         return _normalized(total, comparable), comparable
 
-    def outlier_sources(self, n: int | None = None, min_common: int = 4) -> list[dict]:
-        """The rows by ``mean_distance``, the worst first (ties by tree; trees with nothing to compare left out):
-        dicts ``tree``, ``mean_distance``, ``comparable``; the first ``n`` of them."""
-        mean, comparable = self.mean_distance(min_common)
+    def outlier_sources(self, n: int | None = None, min_common: int = 4, by: str = "rf") -> list[dict]:
+        """The rows by ``mean_distance`` (of ``by``), the worst first (ties by tree; trees with nothing to compare
+        left out): dicts ``tree``, ``mean_distance``, ``comparable``; the first ``n`` of them."""
+        mean, comparable = self.mean_distance(min_common, by)
         order = sorted((i for i in range(len(self.rows)) if comparable[i] > 0),
                        key=lambda i: (-mean[i], int(self.rows[i])))
         out = [{"tree": int(self.rows[i]), "mean_distance": float(mean[i]), "comparable": int(comparable[i])}
@@ -1833,9 +1876,15 @@ class SourceDistances:
 
     def table(self, min_common: int = 3) -> str:
         """TSV, one row per unordered pair of trees a < b with at least ``min_common`` (>= 3) common taxa that a row
-        of the matrices holds: tree_a, tree_b, common, clusters_a, clusters_b, shared, rf, normalized_rf."""
+        of the matrices holds: tree_a, tree_b, common, clusters_a, clusters_b, shared, rf, normalized_rf -- and, when
+        the triplet matrices are there, triplets_a, triplets_b, triplets_shared, triplet_distance,
+        normalized_triplet_distance."""
         floor = max(int(min_common), 3)
+        trip = self.triplets is not None
         lines = ["tree_a\ttree_b\tcommon\tclusters_a\tclusters_b\tshared\trf\tnormalized_rf"]
+        if trip:
+            self._need_triplets()
+            lines[0] += "\ttriplets_a\ttriplets_b\ttriplets_shared\ttriplet_distance\tnormalized_triplet_distance"
         first = {}
         for i, r in enumerate(self.rows.tolist()):
             first.setdefault(r, i)
@@ -1847,10 +1896,18 @@ class SourceDistances:
                 mine, other = int(self.clusters[i, j]), int(self.clusters_other[i, j])
                 a, b, ca, cb = (r, j, mine, other) if r < j else (j, r, other, mine)
                 found[(a, b)] = (int(self.common[i, j]), ca, cb, int(self.shared[i, j]))
-        for (a, b), (c, ca, cb, sh) in sorted(found.items()):
+                if trip:
+                    mine, other = int(self.triplets[i, j]), int(self.triplets_other[i, j])
+                    found[(a, b)] += (*((mine, other) if r < j else (other, mine)), int(self.triplets_shared[i, j]))
+        for (a, b), (c, ca, cb, sh, *more) in sorted(found.items()):
             rf = ca + cb - 2 * sh
             nrf = f"{rf / (ca + cb):.4f}" if ca + cb else "nan"
             lines.append(f"{a}\t{b}\t{c}\t{ca}\t{cb}\t{sh}\t{rf}\t{nrf}")
+            if trip:
+                ta, tb, ts = more
+                td = ta + tb - 2 * ts
+                ntd = f"{td / (ta + tb):.4f}" if ta + tb else "nan"
+                lines[-1] += f"\t{ta}\t{tb}\t{ts}\t{td}\t{ntd}"
         return "\n".join(lines) + "\n"
 
 
@@ -1866,18 +1923,21 @@ def _source_names(trees) -> list[str]:
     return list(seen)
 
 
-def source_distances(trees, rows=None, device=None) -> SourceDistances:
+def source_distances(trees, rows=None, device=None, triplets: bool = False) -> SourceDistances:
     """The Robinson-Foulds terms between every two source trees, each pair restricted to the taxa both trees hold:
     which sources disagree with the rest, which pairs overlap too little to say anything (``SourceDistances``).
 
     ``trees``: a list of tree objects (``NotCompleted`` entries dropped) or a ``TreeArrays``, as for
     ``score_supertree``; the taxon ids are the union of their names.  ``rows``: the trees (indices into ``trees`` as
     given) whose rows are wanted, in any order; None: all of them.  Trees of fewer than two leaves of a ``TreeArrays``
-    have no tables: their rows and columns are zeros.  Every count comes from ``scs_score_source_pairs``."""
+    have no tables: their rows and columns are zeros.  Every count comes from ``scs_score_source_pairs``; with
+    ``triplets`` the rooted-triplet terms of every pair come from ``scs_score_source_pair_triplets`` as well (the
+    graded measure: one misplaced taxon breaks every cluster on its path, but only the triples it is in)."""
     t0 = time.perf_counter()
     names = _source_names(trees)
     index = {name: i for i, name in enumerate(names)}
     keys = ("common", "clusters", "clusters_other", "shared")
+    tkeys = ("triplets", "triplets_other", "triplets_shared") if triplets else ()
     with _resident_tables(device, trees, names, index) as src:
         m = len(src.n_leaves)
         given = np.arange(m, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64)
@@ -1885,13 +1945,21 @@ def source_distances(trees, rows=None, device=None) -> SourceDistances:
             msg = f"rows must be indices of the {m} source trees"
             raise ValueError(msg)
         out = {k: np.zeros((len(given), m), dtype=np.int32) for k in keys}
+        out.update({k: np.zeros((len(given), m), dtype=np.int64) for k in tkeys})
         timings = {"prepare": 0.0, "tables": src.seconds, "pairs": 0.0}
+        if triplets:
+            timings["triplets"] = 0.0
         if src.tabs is not None and len(given):
             tree_index = src.tree_index()
             t1 = time.perf_counter()
             if tree_index is None:
-                res = src.dev.score_source_pairs(src.tabs, None if rows is None else given.astype(np.int32))
-                out = {k: res[k] for k in keys}
+                ask = None if rows is None else given.astype(np.int32)
+                res = src.dev.score_source_pairs(src.tabs, ask)
+                out.update({k: res[k] for k in keys})
+                timings["pairs"] = time.perf_counter() - t1
+                if triplets:
+                    res = src.dev.score_source_pair_triplets(src.tabs, ask, outputs=tkeys)
+                    out.update({k: res[k] for k in tkeys})
             else:
                 at = np.full(m, -1, dtype=np.int64)
                 at[tree_index] = np.arange(len(tree_index))
@@ -1902,7 +1970,13 @@ def source_distances(trees, rows=None, device=None) -> SourceDistances:
                     res = src.dev.score_source_pairs(src.tabs, None if everything else ask)
                     for k in keys:
                         out[k][np.ix_(have, tree_index)] = res[k]
-            timings["pairs"] = time.perf_counter() - t1
+                timings["pairs"] = time.perf_counter() - t1
+                if triplets and len(ask):
+                    res = src.dev.score_source_pair_triplets(src.tabs, None if everything else ask, outputs=tkeys)
+                    for k in tkeys:
+                        out[k][np.ix_(have, tree_index)] = res[k]
+            if triplets:
+                timings["triplets"] = time.perf_counter() - t1 - timings["pairs"]
     timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
     return SourceDistances(rows=given, n_leaves=np.asarray(src.n_leaves, dtype=np.int64), timings=timings, **out)
 

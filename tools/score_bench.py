@@ -27,6 +27,10 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
                                                      # beside scs_score_supertree and scs_score_triplets on the same
                                                      # tables and the host reference on a sample of the pairs
                                                      # 
+    python tools/score_bench.py --source-triplets    # scs_score_source_pair_triplets: one row and 16 rows of 10000x500,
+                                                     # every pair of 20000x2000x500, beside scs_score_source_pairs and
+                                                     # scs_score_triplets on the same tables and the host reference on
+                                                     # sampled cells
     python tools/score_bench.py --coverage --size 10000x500   # scs_score_coverage for min_trees 1 and 2, with and
                                                      # without the two matrices, beside the numpy reference on a sample
                                                      # of rows and the word operations the sweep needs (DESIGN.md
@@ -551,6 +555,87 @@ def run_source_pairs(dev: Device, size: str, repeats: int = 7, sample: int = 40)
     return out
 
 
+def run_source_triplets(dev: Device, size: str, repeats: int = 5, sample: int = 40) -> dict:
+    """``scs_score_source_pair_triplets`` on resident tables by the scheme of ``run_source_pairs``: a warm-up and
+    ``repeats`` timed calls.  Trees of more than 2 000 leaves: rows = one tree and 16 rows (every pair would take as
+    long as the node pairs of 125 250 such pairs do); smaller trees: every pair.  For scale ``scs_score_source_pairs``
+    with the same rows and ``scs_score_triplets`` on the same tables; sampled cells (one, for the large trees) against
+    the host's node-pair reference (``tests/source_triplets_reference.py``), which must give the device's numbers."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import source_triplets_reference as st
+
+    from spectralclustersupertree_amd.backend import debug_source_pair_triplets_plan
+
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    sup = random_binary_tree(2, n_taxa)
+    parent, taxon, tips = supertree_arrays(sup)
+    index = {x: i for i, x in enumerate(tips)}
+    large = int(arrays.leaf_counts().max()) > 2000
+    out = {"size": size, "source_triplets": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    def node_pairs(common, mirror):
+        c = np.maximum((np.triu(common) if mirror else common).astype(np.int64) - 2, 0)
+        return int((c * c).sum())
+
+    runs = {}
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        m = tabs.n_trees
+        out["triplets_s_min_median_max"], _ = timed(lambda: dev.score_triplets(tabs, parent, taxon))
+        asks = {"one_row": [m // 2], "rows_16": list(range(0, m, max(m // 16, 1)))[:16]} if large else {"all_pairs": None}
+        for name, rows in asks.items():
+            out[f"{name}_rf_s_min_median_max"], _ = timed(lambda: dev.score_source_pairs(tabs, rows))
+            out[f"{name}_s_min_median_max"], res = timed(lambda: dev.score_source_pair_triplets(tabs, rows))
+            out[f"{name}_unshared_s_min_median_max"], part = timed(lambda: dev.score_source_pair_triplets(
+                tabs, rows, outputs=("common", "triplets", "triplets_other")))
+            plan = debug_source_pair_triplets_plan(tabs, rows=rows)
+            med = out[f"{name}_s_min_median_max"][1]
+            pairs = node_pairs(res["common"], rows is None)
+            out.update({f"{name}_node_pairs": pairs, f"{name}_node_pairs_per_s": round(pairs / med),
+                        f"{name}_chunks": len(plan["chunks"]), f"{name}_sweep_workgroups": int(plan["chunks"][:, 6].sum()),
+                        f"{name}_restrict_workgroups": int(plan["chunks"][:, 3].sum()),
+                        f"{name}_workspace_bytes": plan["workspace"], f"{name}_zb": int(plan["zb"].max()),
+                        f"{name}_over_rf": round(med / out[f"{name}_rf_s_min_median_max"][1], 2),
+                        f"{name}_unshared_same": all(np.array_equal(part[k], res[k]) for k in st.KEYS[:3])})
+            runs[name] = (rows, res)
+        off, leaf, adj = (np.array(x) for x in src.forest.tables()[:3])
+    rows, res = next(iter(runs.values()))
+    ids = list(range(m)) if rows is None else rows
+    rs = np.random.RandomState(3)
+    cells = [(int(i), int(b)) for i, b in zip(rs.randint(0, len(ids), size=sample), rs.randint(0, m, size=sample))]
+    cells = cells[:1] if large else cells
+    t0 = time.perf_counter()
+    same = True
+    for i, b in cells:
+        a = ids[i]
+        want = st.pair_quadratic_tables(leaf[off[a]:off[a + 1]], adj[off[a]:off[a + 1]], leaf[off[b]:off[b + 1]],
+                                        adj[off[b]:off[b + 1]])
+        same = same and tuple(int(res[k][i, b]) for k in st.KEYS) == tuple(int(x) for x in want)
+    common = res["common"].astype(np.int64)
+    total = res["triplets"] + res["triplets_other"]
+    out.update({"tables_trees": m, "common_leaves_mean": round(float(common.mean()), 1),
+                "common_leaves_max": int(common.max()),
+                "mean_normalized_triplet_distance": round(float(np.nanmean(np.where(
+                    total > 0, (total - 2.0 * res["triplets_shared"]) / np.maximum(total, 1), np.nan))), 4),
+                "host_reference_sample": len(cells), "host_reference_agrees": bool(same),
+                "host_reference_s_per_cell": round((time.perf_counter() - t0) / max(len(cells), 1), 3)})
+    for name in runs:
+        out[f"{name}_over_triplets"] = round(out[f"{name}_s_min_median_max"][1] / out["triplets_s_min_median_max"][1], 2)
+    return out
+
+
 # vector lanes of the device per second: 256 CUs x 4 SIMDs x 32 lanes at 2.4 GHz (one 32-bit operation each)
 LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9
 
@@ -662,6 +747,9 @@ def main() -> None:
                     help="time scs_score_parsimony instead, without and with the per-clade lengths")
     ap.add_argument("--source-pairs", action="store_true",
                     help="time scs_score_source_pairs instead: every pair of the synthetic sources")
+    ap.add_argument("--source-triplets", action="store_true",
+                    help="time scs_score_source_pair_triplets instead: one row and 16 rows of 10000x500, every pair of "
+                         "20000x2000x500")
     ap.add_argument("--coverage", action="store_true",
                     help="time scs_score_coverage instead: the triple coverage of the synthetic sources")
     ap.add_argument("--coverage-sample", type=int, default=64, metavar="ROWS",
@@ -688,6 +776,12 @@ def main() -> None:
             run_source_pairs(dev, "200x6", repeats=1, sample=4)  # warm-up
             for size in args.size or SIZES[:1]:
                 print(json.dumps(run_source_pairs(dev, size, args.repeats)), flush=True)
+        return
+    if args.source_triplets:
+        with Device(0) as dev:
+            run_source_triplets(dev, "200x6", repeats=1, sample=4)  # warm-up
+            for size in args.size or ("10000x500", "20000x2000x500"):
+                print(json.dumps(run_source_triplets(dev, size, max(args.repeats, 5))), flush=True)
         return
     if args.coverage:
         with Device(0) as dev:
