@@ -404,6 +404,13 @@ extern "C" int scs_score_parsimony(scs_ctx *ctx, const scs_tables *src, int32_t 
     std::vector<int32_t> ccnt, stage;
     unsigned bad = 0;
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)M * 32, s);
+    // the frames in LDS take up to MP_LDS_MAX beside the static fdep (the attribute is per function and device: set
+    // on every call; the two variants with the frames in the block take no dynamic LDS)
+    if (!plan.in_block) {
+        const void *const fns[2] = {(const void *)k_mp_fold<false, false>, (const void *)k_mp_fold<true, false>};
+        for (int i = 0; i < 2 && e == hipSuccess; ++i)
+            e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, MP_LDS_MAX);
+    }
     for (size_t b = 0; b + 1 < c.bstart.size() && e == hipSuccess; ++b) {
         if (!sc_prepare_batch(src, s, c, b, e, bad)) break;
         const sc_bview v = sc_batch_of(src, c, b);
