@@ -416,6 +416,40 @@ int scs_score_coverage(scs_ctx *ctx, const scs_tables *sources, int32_t n_rows, 
                        int32_t max_batch_rows, int32_t max_reg_words, int32_t *occurs, int32_t *pair_trees,
                        int32_t *pair_covered, int64_t *taxon_covered);
 
+/* Internode distances of the sources, summed per pair of taxa: the input of ASTRID / NJst and
+ * of average-consensus supertrees.  `sources` are tables as for scs_score_source_pairs.  Only `tree_off`,
+ * `leaf_taxon` and `adj_depth` are read.  n = the tables' `n_taxa`.
+ *   T* is the tree of T's distinct clusters: gaps of equal adj_depth with no shallower gap between them are one node
+ *   (a polytomy is one node); a node with one child is merged away (the tables cannot see it).
+ *   r(gap) = the number of distinct nodes strictly above the gap's node.  The top node has r = 0 whatever its
+ *   adj_depth; the parent of a node is the node of the deeper of the two nearest strictly shallower gaps, left and
+ *   right.  A leaf's parent is the node of the deeper of its two neighbouring gaps (its only one at a tree's end), and
+ *   depth(leaf) = that r + 1.
+ *   d_T(a, b), a != b both in T, = depth(a) + depth(b) - 2 min r over the gaps between the two leaves: the number of
+ *   edges between them in T*.  A cherry gives 2; in ((a,b),c) d(a,c) = 3; every pair of a star gives 2.  d_T is taken
+ *   in T itself, not in a restriction (ASTRID's convention).
+ *   `tree_w`: a non-negative int64 per tree, NULL = 1.  A tree of weight w counts exactly like w copies of it; weight 0
+ *   counts as absent.
+ * For the row taxa r, given as `rows` (ids in any order, repeats allowed; NULL means every taxon, and then `n_rows`
+ * must be n), all int64 and exact, n_rows x n row-major with diagonal 0:
+ *   `pair_weight[r][b]` = Σ w_t over the trees that hold both taxa,
+ *   `dist_sum[r][b]` = Σ w_t d_t(a, b),   `sq_sum[r][b]` = Σ w_t d_t(a, b)²;
+ *   `taxon_weight[r]`, `taxon_sum[r]`, `taxon_sq[r]`: the row sums of the three;
+ *   `taxon_partners[r]`, int32: #{b : pair_weight > 0}.
+ * Any output may be null.  With the three matrices null no device buffer of n_rows x n entries is allocated: the
+ * per-taxon outputs come from sums kept on the device.  Rows and trees are batched by workspace; max_batch_rows /
+ * max_batch_trees > 0 cap a row / tree batch (tests).  Results do not depend on the batches.  No size is refused.
+ * Overflow: with h_t the largest leaf depth and m_t the leaves of tree t, B1 = Σ w_t (m_t - 1) 2h_t and, when sq_sum
+ * or taxon_sq is asked for, B2 = Σ w_t (m_t - 1) (2h_t)² bound every cell and row sum; one above 2^63 - 1 is
+ * SCS_EINVAL, decided after the depth pass and before any sweep kernel.
+ * SCS_EINVAL as well: null ctx or tables, a row id out of range, n_rows < 0, rows NULL with n_rows != n, a negative
+ * weight or knob, or (checked on the device before any sweep kernel runs) a source taxon out of range or twice in one
+ * tree. */
+int scs_score_internode(scs_ctx *ctx, const scs_tables *sources, int32_t n_rows, const int32_t *rows,
+                        const int64_t *tree_w, int32_t max_batch_rows, int32_t max_batch_trees,
+                        int64_t *pair_weight, int64_t *dist_sum, int64_t *sq_sum, int64_t *taxon_weight,
+                        int64_t *taxon_sum, int64_t *taxon_sq, int32_t *taxon_partners);
+
 /* Rooted triplet terms per source tree, same inputs and SCS_EINVAL cases as
  * scs_score_supertree.  For a source tree T on the leaf set L and S' = S|L, a triple {a, b, c} of L is resolved
  * ab|c in a tree when one of its clusters holds a and b but not c, and a fan when no cluster separates one pair:
@@ -1095,6 +1129,36 @@ int scs_debug_source_pair_triplets_plan(const scs_tables *sources, int32_t n_tre
 int scs_debug_coverage_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
                             int32_t n_rows, int32_t min_trees, int32_t max_batch_rows, int32_t max_reg_words,
                             int32_t matrices_wanted, int64_t *info_out, int64_t *batches_out);
+
+/* The plan of one scs_score_internode call on the host, by the functions the export calls.  `sources` or, when it is
+ * NULL, n_trees, tree_off[n_trees + 1] and n_taxa.  n_rows < 0 stands for rows NULL (every taxon); the two knobs as
+ * for the export; matrices_wanted: how many of pair_weight / dist_sum / sq_sum are asked for (0 ... 3).
+ * With `heights` (h_t per tree; `tree_w` per tree or NULL = 1; `squares` != 0 when a squared output is asked for) the
+ * export's overflow rule is applied too, and its SCS_EINVAL returned after the plan is written.
+ * info_out[16] = {levels of the min tables (2^levels > the largest tree), bytes of an entry of the table of r (4: the
+ *   one width there is), words per taxon (⌈trees/32⌉, at least 1), stride of a dense row in taxa (n rounded up to 64),
+ *   tiles of 256 column taxa per row, tiles of one work item, work items (workgroups) per row,
+ *   bytes of a row's cells in the matrices wanted, rows of a row batch at most,
+ *   bytes of the block without the matrices, bytes of the block with them,
+ *   row batches, tree batches,
+ *   the workgroups one launch may have (2^30, and no more work-items than a dispatch counts in 32 bits),
+ *   the rows one launch takes under that limit (at least 1: a longer row is strided over),
+ *   1 when only pairs a < b are swept and both cells written (rows NULL, and the matrices, if wanted, hold every row
+ *   at once)}.
+ * rows_out (may be NULL; 3 x the row batches): {first row, rows, workgroups of the batch's first launch}.
+ * trees_out (may be NULL; 3 x the tree batches): {first tree, trees, leaves}.  A first call with both NULL returns
+ * the two counts in info_out[11] and info_out[12]. */
+int scs_debug_internode_plan(const scs_tables *sources, int32_t n_trees, const int64_t *tree_off, int32_t n_taxa,
+                             int32_t n_rows, int32_t max_batch_rows, int32_t max_batch_trees, int32_t matrices_wanted,
+                             const int64_t *tree_w, const int32_t *heights, int32_t squares, int64_t *info_out,
+                             int64_t *rows_out, int64_t *trees_out);
+
+/* The depth pass of scs_score_internode alone, downloaded from the arrays its sweep reads: gap_r[leaves] (r of the gap
+ * after every leaf, by global leaf index; 0 at a tree's last leaf, which has no gap), leaf_depth[leaves] and
+ * tree_height[n_trees] (h_t, the largest leaf depth; 0 for a tree of one leaf).  Any output may be null.
+ * max_batch_trees as for the export.  SCS_EINVAL as the export's device check. */
+int scs_debug_internode_depths(scs_ctx *ctx, const scs_tables *sources, int32_t max_batch_trees, int32_t *gap_r,
+                               int32_t *leaf_depth, int32_t *tree_height);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,7 @@ SIGNATURES = {
     "scs_score_source_pairs": (C.c_int, [_P, _P, _I32, _IP, _I32, _I32, _IP, _IP, _IP, _IP]),
     "scs_score_source_pair_triplets": (C.c_int, [_P, _P, _I32, _IP, _I32, _I32, _I32, _IP, _LP, _LP, _LP]),
     "scs_score_coverage": (C.c_int, [_P, _P, _I32, _IP, _I32, _I32, _I32, _IP, _IP, _IP, _LP]),
+    "scs_score_internode": (C.c_int, [_P, _P, _I32, _IP, _LP, _I32, _I32, _LP, _LP, _LP, _LP, _LP, _LP, _IP]),
     "scs_pcg_build": (C.c_int, [_P, _P, _I32, _I32, _I32, _PP, C.POINTER(BuildStats)]),
     "scs_graph_contract": (C.c_int, [_P, _P, _IP, _I32, _PP]),
     "scs_graph_matrix_free": (C.c_int, [_P, _P, _I32, _PP]),
@@ -223,6 +224,9 @@ SIGNATURES = {
     "scs_debug_source_pair_triplets_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, _IP, _I32, _I32, _I32, _P, _IP, _LP,
                                                       _LP, _LP]),
     "scs_debug_coverage_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, _I32, _I32, _I32, _I32, _LP, _LP]),
+    "scs_debug_internode_plan": (C.c_int, [_P, _I32, _LP, _I32, _I32, _I32, _I32, _I32, _LP, _IP, _I32, _LP, _LP,
+                                           _LP]),
+    "scs_debug_internode_depths": (C.c_int, [_P, _P, _I32, _IP, _IP, _IP]),
 }
 
 _lib = None

@@ -407,6 +407,73 @@ class Device:
         nv.check(rc)
         return out
 
+    INTERNODE_OUTPUTS = ("pair_weight", "dist_sum", "sq_sum", "taxon_weight", "taxon_sum", "taxon_sq",
+                         "taxon_partners")
+
+    def score_internode(self, sources, rows=None, tree_weights=None, matrices: bool = True, squares: bool = False,
+                        batch_rows: int = 0, batch_trees: int = 0, outputs=None) -> dict:
+        """``scs_score_internode``: the internode distances of the sources, summed per pair of taxa.  ``sources`` as
+        for ``score`` (only their trees' taxa and ``adj_depth`` are read); ``rows``: the taxon ids of the rows wanted
+        (any order, repeats allowed; None: every taxon); ``tree_weights``: non-negative integers per tree (None: 1).
+        Returns ``pair_weight``, ``dist_sum``, ``sq_sum`` (int64, rows x taxa), ``taxon_weight``, ``taxon_sum``,
+        ``taxon_sq`` (int64, rows) and ``taxon_partners`` (int32, rows).  ``outputs`` names the ones wanted (the
+        others are None); by default all but the matrices without ``matrices`` and the squared ones without
+        ``squares``.  ``batch_rows`` / ``batch_trees`` > 0 cap a row / tree batch (tests)."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        n = tabs.n_taxa
+        if rows is None:
+            n_rows, row_ptr = n, None
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.ndim != 1:
+                msg = "rows must be a list of taxon ids"
+                raise ValueError(msg)
+            n_rows, row_ptr = len(rows), nv.iptr(rows)
+        w_ptr = None
+        if tree_weights is not None:
+            tree_weights = np.ascontiguousarray(tree_weights, dtype=np.int64)
+            if tree_weights.shape != (tabs.n_trees,):
+                msg = f"tree_weights must hold one weight per tree ({tabs.n_trees}), not {tree_weights.shape}"
+                raise ValueError(msg)
+            w_ptr = nv.lptr(tree_weights)
+        if outputs is None:
+            outputs = [k for k in self.INTERNODE_OUTPUTS
+                       if (matrices or k.startswith("taxon")) and (squares or k not in ("sq_sum", "taxon_sq"))]
+        unknown = set(outputs) - set(self.INTERNODE_OUTPUTS)
+        if unknown:
+            msg = f"unknown outputs {sorted(unknown)}"
+            raise ValueError(msg)
+        out = {}
+        for k in self.INTERNODE_OUTPUTS:
+            shape = (n_rows,) if k.startswith("taxon") else (n_rows, n)
+            out[k] = np.zeros(shape, dtype=np.int32 if k == "taxon_partners" else np.int64) if k in outputs else None
+        rc = self._lib.scs_score_internode(self._ctx, tabs._h, n_rows, row_ptr, w_ptr, int(batch_rows),
+                                           int(batch_trees),
+                                           *(None if v is None else v.ctypes.data for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_score_internode: invalid input")
+        nv.check(rc)
+        return out
+
+    def debug_internode_depths(self, sources, batch_trees: int = 0) -> dict:
+        """``scs_debug_internode_depths``: the depth pass of ``score_internode`` alone -- ``gap_r`` (r of the gap
+        after every leaf; 0 at a tree's last leaf), ``leaf_depth`` (both int32 by global leaf index) and
+        ``tree_height`` (int32 per tree), downloaded from the arrays the sweep reads."""
+        tabs = self.upload(sources) if isinstance(sources, TreeTables) else sources
+        four = np.zeros(4, dtype=np.int64)  # (n_taxa, n_trees, n_leaves, max_leaves as the handle holds them)
+        nv.check(self._lib.scs_debug_tables_download(self._ctx, tabs._h, None, None, None, None, None, nv.lptr(four)))
+        leaves = int(four[2])
+        out = {"gap_r": np.zeros(leaves, dtype=np.int32), "leaf_depth": np.zeros(leaves, dtype=np.int32),
+               "tree_height": np.zeros(tabs.n_trees, dtype=np.int32)}
+        rc = self._lib.scs_debug_internode_depths(self._ctx, tabs._h, int(batch_trees),
+                                                  *(nv.iptr(v) if len(v) else None for v in out.values()))
+        if rc == nv.EINVAL:
+            msg = self._lib.scs_last_error()
+            raise ValueError(msg.decode() if msg else "scs_debug_internode_depths: invalid input")
+        nv.check(rc)
+        return out
+
     # -- batched small nodes --------------------------------------------------
     # largest node of the batched path (SMALL_MAXS of libscs_hip: two-sided Jacobi in LDS up to 64
     # vertices, one-sided up to 128 -- SURVEY.md 8f rank 3).  SCS_SMALL_MAX_TAXA moves the limit down.
@@ -1035,6 +1102,46 @@ def debug_coverage_plan(sources, n_taxa: int = 0, n_rows: int | None = None, min
             "grid_limit", "rows_per_launch", "mirror", "count")
     return {**{key: int(info[i]) for i, key in enumerate(keys)}, "first_row": batches[:, 0].copy(),
             "rows": batches[:, 1].copy(), "bytes": batches[:, 2].copy(), "grid": batches[:, 3].copy()}
+
+
+def debug_internode_plan(sources, n_taxa: int = 0, n_rows: int | None = None, batch_rows: int = 0,
+                         batch_trees: int = 0, matrices: int = 0, tree_weights=None, heights=None,
+                         squares: bool = False) -> dict:
+    """``scs_debug_internode_plan``: the plan of ``scs_score_internode`` for ``sources`` (device tables, or a
+    ``tree_off`` array with ``n_taxa``), ``n_rows`` rows (None: rows None, every taxon) and ``matrices`` of the three
+    matrices wanted -- once ``levels``, ``width`` (bytes of an entry of the depth table), ``words``, ``taxa_stride``,
+    ``tiles``, ``tiles_per_item``, ``items_per_row``, ``row_bytes``, ``batch_rows``, ``fixed_bytes`` (the block without
+    matrices), ``bytes`` (with them), ``n_row_batches``, ``n_tree_batches``, ``grid_limit``, ``rows_per_launch``,
+    ``mirror``; per row batch ``first_row``, ``rows``, ``grid``; per tree batch ``first_tree``, ``trees``, ``leaves``.
+    With ``heights`` (h_t per tree) the export's overflow rule is applied to them and ``tree_weights`` (None: 1),
+    with B2 when ``squares``: ``ValueError`` with the library's message.  The library's own arithmetic, on the host."""
+    handle, off = (sources._h, None) if isinstance(sources, DeviceTables) else (None, sources)
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+    m = sources.n_trees if off is None else len(off) - 1
+    if tree_weights is not None:
+        tree_weights = np.ascontiguousarray(tree_weights, dtype=np.int64)
+    if heights is not None:
+        heights = np.ascontiguousarray(heights, dtype=np.int32)
+    lib = nv.load_library()
+    info = np.zeros(16, dtype=np.int64)
+    args = (handle, m, None if off is None else nv.lptr(off), int(n_taxa), -1 if n_rows is None else int(n_rows),
+            int(batch_rows), int(batch_trees), int(matrices), None if tree_weights is None else nv.lptr(tree_weights))
+    nv.check(lib.scs_debug_internode_plan(*args, None, 0, nv.lptr(info), None, None))  # (the batch counts first)
+    rows_b = np.zeros((int(info[11]), 3), dtype=np.int64)
+    trees_b = np.zeros((int(info[12]), 3), dtype=np.int64)
+    rc = lib.scs_debug_internode_plan(*args, None if heights is None else nv.iptr(heights), int(bool(squares)),
+                                      nv.lptr(info), nv.lptr(rows_b) if len(rows_b) else None,
+                                      nv.lptr(trees_b) if len(trees_b) else None)
+    if rc == nv.EINVAL:
+        raise ValueError(lib.scs_last_error().decode())
+    nv.check(rc)
+    keys = ("levels", "width", "words", "taxa_stride", "tiles", "tiles_per_item", "items_per_row", "row_bytes",
+            "batch_rows", "fixed_bytes", "bytes", "n_row_batches", "n_tree_batches", "grid_limit", "rows_per_launch",
+            "mirror")
+    return {**{key: int(info[i]) for i, key in enumerate(keys)}, "first_row": rows_b[:, 0].copy(),
+            "rows": rows_b[:, 1].copy(), "grid": rows_b[:, 2].copy(), "first_tree": trees_b[:, 0].copy(),
+            "trees": trees_b[:, 1].copy(), "leaves": trees_b[:, 2].copy()}
 
 
 # A module attribute only a test sets (never the environment: ADVICE r05): the batched path then reports the nodes of

@@ -130,6 +130,16 @@ from spectralclustersupertree_amd import __version__
                    "enough to determine a tree at all.")
 @click.option("--coverage-min-trees", default=1, type=click.IntRange(min=1), show_default=True, metavar="K",
               help="The source trees that must hold a triple for --coverage-out to count it as covered.")
+@click.option("--internode-out", default=None,
+              help="Also write the sources' average internode distance matrix as a square PHYLIP file: per pair of "
+                   "taxa the mean, over the source trees that hold both, of the number of edges between them (the "
+                   "input of ASTRID / NJst, FastME or any NJ program).")
+@click.option("--internode-missing", default=None, type=float, metavar="X",
+              help="The value --internode-out writes for a pair of taxa that no source tree holds together; without "
+                   "it such a pair is an error.")
+@click.option("--internode-taxa-out", default=None,
+              help="Also write a TSV with one row per taxon (taxon, partners, weight, sum, mean): how many taxa the "
+                   "sources relate it to, and its mean internode distance to them.")
 def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction: bool,
         scores_out: str | None = None, support_out: str | None = None, triplets: bool = False,
         conflicts: bool = False, conflict_out: str | None = None, concordance: bool = False,
@@ -143,8 +153,12 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
         branch_support_out: str | None = None, parsimony: bool = False,
         source_clades_out: str | None = None, source_distances_out: str | None = None,
         source_triplets: bool = False, min_common: int = 3, coverage_out: str | None = None,
-        coverage_min_trees: int = 1) -> None:
+        coverage_min_trees: int = 1, internode_out: str | None = None, internode_missing: float | None = None,
+        internode_taxa_out: str | None = None) -> None:
     """Spectral Cluster Supertree of the source trees in IN_FILE, on the MI355X core."""
+    if internode_missing is not None and not internode_out:
+        msg = "--internode-missing needs --internode-out"
+        raise click.UsageError(msg)
     if branch_resample and not (branches_out or branch_support_out):
         msg = "--branch-resample needs --branches-out or --branch-support-out"
         raise click.UsageError(msg)
@@ -254,6 +268,17 @@ def scs(in_file: str, out_file: str, pcg_weighting: str, *, disable_contraction:
             from spectralclustersupertree_amd.score import source_coverage
 
             Path(coverage_out).write_text(source_coverage(sources, min_trees=coverage_min_trees).table())
+        if internode_out or internode_taxa_out:
+            from spectralclustersupertree_amd.score import source_internode_distances
+
+            internode = source_internode_distances(sources, matrices=internode_out is not None)
+            if internode_taxa_out:
+                Path(internode_taxa_out).write_text(internode.table())
+            if internode_out:
+                try:
+                    internode.to_phylip(internode_out, missing=internode_missing)
+                except ValueError as err:
+                    raise click.ClickException(str(err)) from err
         if resolved_out:
             from spectralclustersupertree_amd.resolve import resolve_polytomies
 

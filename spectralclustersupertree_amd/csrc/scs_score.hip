@@ -4586,3 +4586,4 @@ extern "C" int scs_score_branch_resample(scs_ctx *ctx, const scs_tables *src, in
 #include "scs_score_pairs.h"
 #include "scs_score_pair_triplets.h"
 #include "scs_score_coverage.h"
+#include "scs_score_internode.h"

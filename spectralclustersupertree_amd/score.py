@@ -164,6 +164,9 @@ trees, each pair restricted to the taxa both hold (``scs_score_source_pairs``, D
 (``scs_score_source_pair_triplets``).
 ``source_coverage`` asks the earlier question, whether the sources overlap enough to determine a tree at all: the
 rooted triples of taxa that some source tree holds whole (``scs_score_coverage``).
+``source_internode_distances`` gives the sources' answer per pair of taxa: over the trees that hold both, the sum and
+the mean of the number of edges between them (``scs_score_internode``) -- the average internode
+distance matrix of ASTRID / NJst and of average-consensus supertrees, ready for FastME or any NJ program.
 """
 
 from __future__ import annotations
@@ -2127,3 +2130,187 @@ def source_coverage(trees, min_trees: int = 1, rows=None, pairs: bool = False, d
                           taxon_covered=out["taxon_covered"], taxon_triples=(n - 1) * (n - 2) // 2 if n >= 3 else 0,
                           triples_total=total, triples_covered=covered, pair_trees=out["pair_trees"],
                           pair_covered=out["pair_covered"], timings=timings)
+
+
+# ------------------------------------------------------------------------- the internode distances of the sources
+@dataclass
+class InternodeDistances:
+    """The internode distances of the sources, summed per pair of taxa (``source_internode_distances``; DESIGN.md
+    section 41).  For a tree T, T* is the tree of its distinct clusters (unary nodes merged away, a polytomy one
+    node); d_T(a, b) is the number of edges between the leaves a and b in T*, taken in T itself and not in a
+    restriction (ASTRID's convention): a cherry gives 2, in ((a,b),c) d(a,c) = 3, every pair of a star gives 2.  A
+    tree of weight w counts like w copies of it.  Row i is taxon ``rows[i]``; taxon ids index ``taxa``.
+
+    ``pair_weight[i][b]`` = Σ w_t over the trees that hold both taxa, ``dist_sum[i][b]`` = Σ w_t d_t(a, b),
+    ``sq_sum[i][b]`` = Σ w_t d_t(a, b)² (int64, rows x taxa, diagonal 0; None without ``matrices``, ``sq_sum`` also
+    without ``squares``); ``taxon_weight``, ``taxon_sum``, ``taxon_sq`` (None without ``squares``) their row sums and
+    ``taxon_partners[i]`` = #{b : pair_weight > 0}.  Every count is exact."""
+
+    taxa: list
+    rows: np.ndarray
+    taxon_weight: np.ndarray
+    taxon_sum: np.ndarray
+    taxon_partners: np.ndarray
+    taxon_sq: np.ndarray | None = None
+    pair_weight: np.ndarray | None = None
+    dist_sum: np.ndarray | None = None
+    sq_sum: np.ndarray | None = None
+    all_rows: bool = False
+    timings: dict = field(default_factory=dict)
+
+    def _need_matrices(self, what: str) -> None:
+        if self.pair_weight is None:
+            msg = f"{what} needs the matrices: source_internode_distances(..., matrices=True)"
+            raise ValueError(msg)
+
+    @property
+    def mean(self) -> np.ndarray:
+        """``dist_sum`` / ``pair_weight`` (float64): NaN where no tree holds both taxa, 0 on the diagonal."""
+        self._need_matrices("mean")
+        out = _normalized(self.dist_sum.astype(np.float64), self.pair_weight.astype(np.float64))
+        out[np.arange(len(self.rows)), self.rows] = 0.0
+        return out
+
+    @property
+    def variance(self) -> np.ndarray:
+        """The weighted variance of d over the trees of a pair, ``sq_sum`` / w - mean² (NaN where w = 0, diagonal
+        0).  It needs ``squares=True``."""
+        self._need_matrices("variance")
+        if self.sq_sum is None:
+            msg = "variance needs the squares: source_internode_distances(..., squares=True)"
+            raise ValueError(msg)
+        w = self.pair_weight.astype(np.float64)
+        mean = _normalized(self.dist_sum.astype(np.float64), w)
+        # (w Σwd² >= (Σwd)² by Cauchy-Schwarz: what falls below 0 is rounding)
+        out = np.maximum(_normalized(self.sq_sum.astype(np.float64), w) - mean * mean, 0.0)
+        out[w == 0] = np.nan
+        out[np.arange(len(self.rows)), self.rows] = 0.0
+        return out
+
+    @property
+    def taxon_mean(self) -> np.ndarray:
+        """``taxon_sum`` / ``taxon_weight``: the mean distance from the row's taxon to its partners (NaN with none)."""
+        return _normalized(self.taxon_sum.astype(np.float64), self.taxon_weight.astype(np.float64))
+
+    @property
+    def missing_pairs(self) -> int | None:
+        """The pairs of taxa that no tree holds together (None unless every taxon is a row)."""
+        if not self.all_rows:
+            return None
+        n = len(self.taxa)
+        return n * (n - 1) // 2 - int(self.taxon_partners.astype(np.int64).sum()) // 2
+
+    @property
+    def complete(self) -> bool | None:
+        """Every pair of taxa is in some tree: ``mean`` has no NaN (None unless every taxon is a row)."""
+        return None if not self.all_rows else self.missing_pairs == 0
+
+    def nearest(self, taxon, n: int | None = None) -> list[dict]:
+        """The partners of ``taxon`` (a name or an id; it must be a row) by mean distance, the nearest first (ties
+        by taxon id): dicts ``taxon``, ``name``, ``mean``, ``weight``; the first ``n`` of them."""
+        self._need_matrices("nearest")
+        x = self.taxa.index(taxon) if isinstance(taxon, str) else int(taxon)
+        at = np.flatnonzero(self.rows == x)
+        if len(at) == 0:
+            msg = f"taxon {taxon!r} is not a row of these distances"
+            raise ValueError(msg)
+        i = int(at[0])
+        w, d = self.pair_weight[i], self.dist_sum[i]
+        order = sorted(np.flatnonzero(w > 0).tolist(), key=lambda b: (int(d[b]) / int(w[b]), b))
+        out = [{"taxon": b, "name": self.taxa[b], "mean": int(d[b]) / int(w[b]), "weight": int(w[b])} for b in order]
+        return out if n is None else out[: max(int(n), 0)]
+
+    def table(self) -> str:
+        """TSV, one row per row taxon: taxon, partners, weight, sum, mean."""
+        lines = ["taxon\tpartners\tweight\tsum\tmean"]
+        mean = self.taxon_mean
+        for i, r in enumerate(self.rows.tolist()):
+            m = "nan" if np.isnan(mean[i]) else f"{mean[i]:.4f}"
+            lines.append(f"{self.taxa[r]}\t{self.taxon_partners[i]}\t{self.taxon_weight[i]}\t{self.taxon_sum[i]}\t{m}")
+        return "\n".join(lines) + "\n"
+
+    def to_phylip(self, path, missing: float | None = None) -> None:
+        """Write ``mean`` as a square PHYLIP distance matrix (every taxon must be a row, in order).  A pair that no
+        tree holds is written as ``missing``; without a fill value it is a ``ValueError``."""
+        self._need_matrices("to_phylip")
+        if not self.all_rows:
+            msg = "to_phylip needs every taxon as a row: source_internode_distances(..., rows=None)"
+            raise ValueError(msg)
+        mean = self.mean
+        gaps = np.isnan(mean)
+        if gaps.any():
+            if missing is None:
+                a, b = (int(v[0]) for v in np.nonzero(gaps))
+                msg = (f"{int(gaps.sum()) // 2} pairs of taxa are in no tree together (the first: {self.taxa[a]!r}, "
+                       f"{self.taxa[b]!r}): give a fill value, to_phylip(path, missing=...)")
+                raise ValueError(msg)
+            mean = np.where(gaps, float(missing), mean)
+        lines = [str(len(self.taxa))]
+        lines += [" ".join([str(name)] + [f"{v:.6f}" for v in row]) for name, row in zip(self.taxa, mean)]
+        with open(path, "w") as out:
+            out.write("\n".join(lines) + "\n")
+
+
+def source_internode_distances(trees, rows=None, tree_weights=None, squares: bool = False, matrices: bool = True,
+                               device=None) -> InternodeDistances:
+    """The internode distances of the sources, summed per pair of taxa (``InternodeDistances``): for every pair, how
+    many trees hold both taxa, and the sum and the mean over those trees of the number of edges between the two. This
+    is the average internode distance matrix of ASTRID / NJst and of average-consensus supertrees, and the input of
+    FastME or any NJ program for a second opinion on a spectral supertree; the mean and the variance per pair show
+    which taxa the sources place consistently and which pairs they never relate at all.
+
+    d_T(a, b) is counted in T*, the tree of T's distinct clusters: nodes with one child are merged away, a polytomy
+    is one node; a cherry gives 2, in ((a,b),c) d(a,c) = 3, every pair of a star gives 2.  It is taken in T itself, not
+    in T restricted to some taxon set (ASTRID's convention).
+
+    ``trees``: a list of tree objects (``NotCompleted`` entries dropped) or a ``TreeArrays``, as for
+    ``source_coverage``; its one-leaf trees have no pairs and change nothing.  ``rows``: the taxa (names or ids) whose
+    rows are wanted, in any order; None: all of them.  ``tree_weights``: non-negative integers, one per tree as given
+    (integral floats are accepted); a tree of weight w counts exactly like w copies, weight 0 as absent.  ``squares``:
+    the sums of squares as well (``variance``).  ``matrices`` False: only the per-taxon sums, and nothing of rows x
+    taxa is allocated anywhere.  Every count is exact and comes from ``scs_score_internode``; sums past 2^63 - 1 are
+    refused with a ``ValueError`` before anything is summed.
+
+    ``source_internode_distances([supertree])`` gives a supertree's own matrix, for a residual against the sources'
+    mean on the host."""
+    t0 = time.perf_counter()
+    names = _source_names(trees)
+    index = {name: i for i, name in enumerate(names)}
+    n = len(names)
+    if rows is None:
+        given = np.arange(n, dtype=np.int64)
+    else:
+        rows = list(rows)
+        bad = [r for r in rows if (isinstance(r, str) and r not in index)
+               or (not isinstance(r, str) and not 0 <= int(r) < n)]
+        if bad:
+            msg = f"rows must be names or ids of the {n} taxa of the sources, not {bad[0]!r}"
+            raise ValueError(msg)
+        given = np.array([index[r] if isinstance(r, str) else int(r) for r in rows], dtype=np.int64)
+    weights = None
+    if tree_weights is not None:
+        weights = _integers(tree_weights, "tree_weights")
+        m_given = trees.n_trees if isinstance(trees, TreeArrays) else len(trees)
+        if weights.shape != (m_given,):
+            msg = f"tree_weights must have one entry per source tree ({m_given}), not shape {weights.shape}"
+            raise ValueError(msg)
+        if not isinstance(trees, TreeArrays):
+            weights = weights[[i for i, t in enumerate(trees) if not is_not_completed(t)]]
+    keys = [k for k in ("pair_weight", "dist_sum", "sq_sum", "taxon_weight", "taxon_sum", "taxon_sq", "taxon_partners")
+            if (matrices or k.startswith("taxon")) and (squares or k not in ("sq_sum", "taxon_sq"))]
+    with _resident_tables(device, trees, names, index) as src:
+        timings = {"prepare": 0.0, "tables": src.seconds, "internode": 0.0}
+        out = {k: np.zeros(len(given) if k.startswith("taxon") else (len(given), n),
+                           dtype=np.int32 if k == "taxon_partners" else np.int64) for k in keys}
+        if src.tabs is not None:
+            tree_index = src.tree_index()
+            if weights is not None and tree_index is not None:
+                weights = weights[tree_index]
+            t1 = time.perf_counter()
+            out = src.dev.score_internode(src.tabs, None if rows is None else given.astype(np.int32),
+                                          tree_weights=weights, matrices=matrices, squares=squares)
+            timings["internode"] = time.perf_counter() - t1
+    timings["prepare"] = time.perf_counter() - t0 - sum(timings.values())
+    return InternodeDistances(taxa=names, rows=given, all_rows=rows is None, timings=timings,
+                              **{k: out.get(k) for k in ("pair_weight", "dist_sum", "sq_sum", "taxon_weight",
+                                                         "taxon_sum", "taxon_sq", "taxon_partners")})

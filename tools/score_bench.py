@@ -35,6 +35,10 @@ random binary supertree on all taxa: one JSON line per size with the host / devi
                                                      # without the two matrices, beside the numpy reference on a sample
                                                      # of rows and the word operations the sweep needs (DESIGN.md
                                                      # section 36)
+    python tools/score_bench.py --internode          # scs_score_internode on 10000x500 and 20000x2000x500 with and
+                                                     # without the matrices, beside the host reference on a sample of
+                                                     # rows and the (pair, tree) evaluations per second (DESIGN.md
+                                                     # section 41)
     python tools/score_bench.py --caterpillar        # supertree and sources caterpillars, sources reversed
     python tools/score_bench.py --caterpillar-supertree   # a caterpillar supertree against the synthetic sources
 """
@@ -706,6 +710,62 @@ def run_coverage(dev: Device, size: str, repeats: int = 5, sample: int = 64) -> 
     return out
 
 
+def run_internode(dev: Device, size: str, repeats: int = 3, sample: int = 16) -> dict:
+    """``scs_score_internode`` for every taxon on resident tables, without the matrices and with ``pair_weight`` and
+    ``dist_sum``: a warm-up and ``repeats`` timed calls each.  Beside them the host reference
+    (``tests/internode_reference.py``, ``by_tables``) on ``sample`` rows, which must give the device's numbers and whose
+    time is scaled to all rows, and the (pair, tree) evaluations a second: Σ m (m - 1) / 2 evaluations when only a < b
+    is swept (``mirror``), twice that otherwise."""
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tests"))
+    import internode_reference as ir
+
+    from spectralclustersupertree_amd.backend import debug_internode_plan
+
+    dims = [int(x) for x in size.split("x")]
+    n_taxa, n_trees = dims[0], dims[1]
+    per_tree = dims[2] if len(dims) > 2 else None
+    arrays = synthetic.tree_arrays(1, n_taxa, n_trees, leaves_per_tree=per_tree)
+    tips = [arrays.name(i) for i in range(n_taxa)]
+    index = {x: i for i, x in enumerate(tips)}
+    out = {"size": size, "internode": True, "n_taxa": n_taxa, "n_trees": n_trees,
+           "leaves": int(arrays.leaf_counts().sum()), "repeats": repeats}
+
+    def timed(call):
+        times = []
+        for _ in range(repeats + 1):
+            t0 = time.perf_counter()
+            res = call()
+            times.append(time.perf_counter() - t0)
+        return [round(x, 5) for x in _spread(times[1:])], res
+
+    with _resident_tables(dev, arrays, tips, index) as src:
+        tabs = src.tabs
+        out["s_min_median_max"], lean = timed(lambda: dev.score_internode(tabs, matrices=False))
+        out["matrices_s_min_median_max"], full = timed(lambda: dev.score_internode(tabs))
+        plans = {m: debug_internode_plan(tabs, matrices=m) for m in (0, 2)}
+        off, leaf, adj = (np.array(x) for x in src.forest.tables()[:3])
+    specs = [(leaf[off[t]:off[t + 1]].tolist(), adj[off[t]:off[t + 1] - 1].tolist()) for t in range(len(off) - 1)]
+    rows = np.random.RandomState(3).choice(n_taxa, size=min(sample, n_taxa), replace=False)
+    t0 = time.perf_counter()
+    want = ir.by_tables(specs, n_taxa, None, rows)
+    out["host_reference_s_all_rows"] = round((time.perf_counter() - t0) / len(rows) * n_taxa, 1)
+    same = all(np.array_equal(want[k], full[k][rows]) for k in ir.KEYS if full[k] is not None)
+    same = same and all(np.array_equal(lean[k], full[k]) for k in ir.KEYS if lean[k] is not None)
+    sizes = np.diff(off)
+    pairs = int((sizes * (sizes - 1) // 2).sum())
+    for name, key, m in (("", "s_min_median_max", 0), ("matrices_", "matrices_s_min_median_max", 2)):
+        evals = pairs * (1 if plans[m]["mirror"] else 2)
+        out.update({f"{name}evaluations": evals, f"{name}evaluations_per_s": round(evals / out[key][1]),
+                    f"{name}mirror": plans[m]["mirror"], f"{name}row_batches": plans[m]["n_row_batches"],
+                    f"{name}block_bytes": plans[m]["bytes"]})
+    out.update({"tree_batches": plans[0]["n_tree_batches"], "levels": plans[0]["levels"], "words": plans[0]["words"],
+                "tiles_per_item": plans[0]["tiles_per_item"], "pairs_in_trees": pairs,
+                "missing_pairs": n_taxa * (n_taxa - 1) // 2 - int(lean["taxon_partners"].astype(np.int64).sum()) // 2,
+                "host_over_device": round(out["host_reference_s_all_rows"] / out["s_min_median_max"][1], 1),
+                "host_reference_rows": len(rows), "host_reference_agrees": bool(same)})
+    return out
+
+
 def _queries(sup: TreeNode, n: int) -> list[str]:
     """``n`` tip names of the supertree, evenly spread over its leaf order (the same for every run)."""
     tips = sup.get_tip_names()
@@ -754,6 +814,9 @@ def main() -> None:
                     help="time scs_score_coverage instead: the triple coverage of the synthetic sources")
     ap.add_argument("--coverage-sample", type=int, default=64, metavar="ROWS",
                     help="the rows --coverage checks against the numpy reference")
+    ap.add_argument("--internode", action="store_true",
+                    help="time scs_score_internode instead: the summed internode distances of the synthetic sources, "
+                         "with and without the matrices")
     ap.add_argument("--caterpillar-supertree", action="store_true",
                     help="a caterpillar supertree on a random taxon order against the synthetic sources")
     ap.add_argument("--caterpillar", action="store_true",
@@ -788,6 +851,12 @@ def main() -> None:
             run_coverage(dev, "200x6", repeats=1, sample=4)  # warm-up
             for size in args.size or ("10000x500", "20000x2000x500"):
                 print(json.dumps(run_coverage(dev, size, max(args.repeats, 3), args.coverage_sample)), flush=True)
+        return
+    if args.internode:
+        with Device(0) as dev:
+            run_internode(dev, "200x6", repeats=1, sample=4)  # warm-up
+            for size in args.size or ("10000x500", "20000x2000x500"):
+                print(json.dumps(run_internode(dev, size, max(args.repeats, 3))), flush=True)
         return
     if args.polytomies:
         with Device(0) as dev:
